@@ -5,13 +5,19 @@
 * headline (`value`): inference, one "step" = one pass (`model(return_loss=False, rescale=True)`, the
   protocol of tools/analysis_tools/benchmark.py:98-131) of the UTDAC R50-PAFPN Boosting R-CNN over a
   batch of 8 synthetic 1333x800 images per GPU (BASELINE.json configs[1]), inputs resident in HBM,
-  results (boxes, labels, counts) copied to the host every step;
-* `train`: the other half of the metric ("inference+train"), timed in the same run: the full train step
+  results (boxes, labels, counts) copied to the host every step.  A plain run times this and nothing else;
+  `--full` adds everything below;
+* `--dump-outputs DIR`: after the timed steps, what the last timed step returned is written as DIR/<name>.npy
+  (inference: `detections`, float32 (batch, max_per_img, 6) = box, score and class of every detection of each image in
+  the order the caller receives them, zero rows past the image's count, and `num_detections` (batch,); the train leg,
+  where it runs: each logged loss as a float64 (1,) array); the inputs and weights are seeded, so two builds can be
+  compared output for output;
+* `train` (`--full`): the other half of the metric ("inference+train"), timed in the same run: the full train step
   of boosting_rcnn_r50_pafpn_1x_coco.py (BASELINE configs[2]/[3]: bf16 MFMA conv stack, fp32 master
   weights; forward_train with device-resident targets and losses, backward through the HIP dgrad /
   wgrad kernels, in-place all-reduce of the gradient arena over RCCL when N > 1 (brcnn/distributed.py), grad-clip, SGD);
-* `roofline` (dominant kernel: the MFMA implicit-GEMM conv, HIP-event timed) and `cpu_baseline` (the
-  oracle pipeline on the host cores, rank 0 at N=1 only).
+* `roofline` (dominant kernel: the MFMA implicit-GEMM conv, HIP-event timed), `stages_ms`, the batch-1 latency and
+  `cpu_baseline` (the oracle pipeline on the host cores, rank 0 at N=1 only): `--full` only.
 
 N > 1: launched by the driver as `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`
 (RANK / LOCAL_RANK / WORLD_SIZE in the environment); run plainly with `--gpus N`, this file starts that
@@ -68,13 +74,22 @@ def parse_args():
                          'and NMS stay fp32)')
     ap.add_argument('--train-dtype', choices=['f32', 'bf16', 'f16'], default='bf16',
                     help='conv-stack arithmetic of the train step (configs[2] names bf16)')
-    ap.add_argument('--mode', choices=['both', 'inference', 'train'], default='both',
-                    help="'both' (default): inference headline + the train step in the same JSON line")
+    ap.add_argument('--mode', choices=['both', 'inference', 'train'], default=None,
+                    help="'both': inference headline + the train step in the same JSON line (default with --full); "
+                         "'inference' (default otherwise); 'train'")
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the train leg (--mode both), the roofline / stage-breakdown / '
+                         'batch-1 latency passes and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (rank 0)')
     ap.add_argument('--train-steps', type=int, default=None, help='timed train steps (default: --steps)')
     ap.add_argument('--force-reducer', action='store_true',
                     help='N = 1 only: initialise a world-size-1 RCCL group and run the train step through the gradient '
                          'reducer of the N > 1 path (its overhead against the plain step)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.mode is None:
+        args.mode = 'both' if args.full else 'inference'
+    return args
 
 
 def launch_ranks(args):
@@ -201,7 +216,9 @@ def timed(step, steps, warmup, world, device, after_warmup=None):
 
 
 def train_bench(args, world, rank, device):
-    """full train step of boosting_rcnn_r50_pafpn_1x_coco.py (80 classes): SGD + clip, DDP when N > 1"""
+    """full train step of boosting_rcnn_r50_pafpn_1x_coco.py (80 classes): SGD + clip, DDP when N > 1.  Returns the
+    line and the logged losses of the last timed step"""
+    import numpy as np
     import torch
     model, cfg = build_model('boosting_rcnn_r50_pafpn_1x_coco.py', device)
     model = model.train()
@@ -281,6 +298,8 @@ def train_bench(args, world, rank, device):
     sync_wait = _rh.SYNC_WAIT
     _rh.SYNC_WAIT = None
     loss_last_timed = float(last['log_vars']['loss'])       # (the passes below run further steps)
+    log_vars = last['log_vars']
+    outputs = {f'train_{k}': np.asarray([float(log_vars[k])], dtype=np.float64) for k in list(log_vars.keys())}
     step_stats['host_slack_at_sync_ms'] = 1e3 * sync_wait[0] / max(1, sync_wait[1])
     from brcnn import lib as _lib
     _lib.handover_status()          # a lost stream-K hand-over inside the timed steps is an error, not a number
@@ -291,20 +310,22 @@ def train_bench(args, world, rank, device):
         tail = reduce_ev[-steps:]
         reduce_ms = sum(a.elapsed_time(b) for a, b in tail) / len(tail)
     grad_bytes = sum(p.numel() for p in params) * 4
-    from brcnn import profiling
-    # every rank runs the roofline pass: step() contains collectives (gradient all-reduce, the fused RPN normaliser,
-    # the log scalars), so a rank-0-only pass would pair them with nothing and hang at N > 1
     graphed = model.__dict__.get('_graphed_trunk')
     graph_info = None if graphed is None else {'captures': graphed.captures,
                                                'replays': sum(c.replays for c in graphed.caps.values()),
                                                'disabled': graphed.disabled_reason}
-    # where the MAIN stream's time goes (HIP events between the stages as they are queued; the weight-gradient stream and
-    # the proposal stream run beside it): backbone, neck, RPN tower, RPN loss + its backward pass (inside the forward pass),
-    # sampler (= the wait for proposals / assignment / the host's draw), RoIAlign, FC head, boosting loss, backward,
-    # reduce + optimizer
-    stages = profiling.stage_breakdown(step, cuda=True, iters=3, tail=None)
-    model.graph_trunk = False       # the roofline pass times every conv launch by its own pair of events: eager launches
-    roof = profiling.train_conv_roofline(step, dtype=args.train_dtype)
+    extra = {}
+    if args.full:
+        from brcnn import profiling
+        # every rank runs the roofline pass: step() contains collectives (gradient all-reduce, the fused RPN normaliser,
+        # the log scalars), so a rank-0-only pass would pair them with nothing and hang at N > 1.
+        # Where the MAIN stream's time goes (HIP events between the stages as they are queued; the weight-gradient stream
+        # and the proposal stream run beside it): backbone, neck, RPN tower, RPN loss + its backward pass (inside the
+        # forward pass), sampler (= the wait for proposals / assignment / the host's draw), RoIAlign, FC head, boosting
+        # loss, backward, reduce + optimizer
+        extra['stages_ms'] = profiling.stage_breakdown(step, cuda=True, iters=3, tail=None)
+        model.graph_trunk = False   # the roofline pass times every conv launch by its own pair of events: eager launches
+        extra['roofline'] = profiling.train_conv_roofline(step, dtype=args.train_dtype)
     return {
         'metric': 'images/sec (1333x800) Boosting R-CNN R50-PAFPN train step',
         'value': world * args.batch * steps / dt, 'unit': 'images/sec', 'ms_per_step': 1000.0 * dt / steps,
@@ -320,12 +341,12 @@ def train_bench(args, world, rank, device):
         'grad_bytes': grad_bytes, 'reduce_ms': reduce_ms,
         'grad_allreduce': None if reducer is None else reducer.describe(),
         'graph_trunk': graph_info,
-        'stages_ms': stages,
-        'roofline': roof,
-    }
+        **extra,
+    }, outputs
 
 
 def inference_bench(args, world, rank, device):
+    import numpy as np
     import torch
     model, cfg = build_model('boosting_rcnn_r50_pafpn_1x_utdac.py', device)
     model = model.eval().freeze_for_inference()
@@ -340,30 +361,47 @@ def inference_bench(args, world, rank, device):
             last['out'] = model(return_loss=False, rescale=True, img=[img], img_metas=[metas])
 
     dt, step_stats = timed(step, args.steps, args.warmup, world, device)
+    # what a caller of the timed pass receives (per image, per class, a (k, 5) array of boxes + scores), in fixed shapes:
+    # `detections` (batch, max_per_img, 6) = x1, y1, x2, y2, score, class in the caller's order (class by class), zero rows
+    # past each image's count; `num_detections` (batch,)
+    max_per_img = int(cfg.model.test_cfg.rcnn.max_per_img)
+    dets = np.zeros((len(last['out']), max_per_img, 6), dtype=np.float32)
+    counts = np.zeros(len(last['out']), dtype=np.float32)
+    for i, im in enumerate(last['out']):
+        rows = [np.concatenate([np.asarray(d, dtype=np.float32).reshape(-1, 5), np.full((len(d), 1), c, np.float32)], 1)
+                for c, d in enumerate(im)]
+        rows = np.concatenate(rows, 0)
+        assert len(rows) <= max_per_img, (len(rows), max_per_img)
+        dets[i, :len(rows)] = rows
+        counts[i] = len(rows)
+    outputs = {'detections': dets, 'num_detections': counts}
     from brcnn import lib as _lib
     _lib.handover_status()          # a lost stream-K hand-over inside the timed steps is an error, not a number
-    from brcnn import profiling
-    roof = profiling.conv_stack_roofline(model, img, metas, iters=5, dtype=args.dtype)
+    extra = {}
+    if args.full:
+        from brcnn import profiling
+        extra['roofline'] = profiling.conv_stack_roofline(model, img, metas, iters=5, dtype=args.dtype)
 
-    def device_pass():
-        with torch.no_grad():
-            det, lab, nd = model.simple_test_device(img, metas, rescale=True)
-        return det.cpu(), lab.cpu(), nd.cpu()
-    stages = profiling.stage_breakdown(device_pass, cuda=True)
-    # batch-1 latency (benchmark.py runs samples_per_gpu=1; the only published neighbours, BASELINE.md, are batch 1):
-    # synchronised passes over one image, mean of `steps`
-    img1, metas1 = img[:1].contiguous(), metas[:1]
-    lat1 = None
-    if not args.no_bs1:
-        with torch.no_grad():
-            for _ in range(max(2, args.warmup)):
-                model(return_loss=False, rescale=True, img=[img1], img_metas=[metas1])
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                model(return_loss=False, rescale=True, img=[img1], img_metas=[metas1])
-            torch.cuda.synchronize()
-            lat1 = (time.perf_counter() - t0) / args.steps * 1000.0
+        def device_pass():
+            with torch.no_grad():
+                det, lab, nd = model.simple_test_device(img, metas, rescale=True)
+            return det.cpu(), lab.cpu(), nd.cpu()
+        extra['stages_ms'] = profiling.stage_breakdown(device_pass, cuda=True)
+        # batch-1 latency (benchmark.py runs samples_per_gpu=1; the only published neighbours, BASELINE.md, are batch 1):
+        # synchronised passes over one image, mean of `steps`
+        img1, metas1 = img[:1].contiguous(), metas[:1]
+        lat1 = None
+        if not args.no_bs1:
+            with torch.no_grad():
+                for _ in range(max(2, args.warmup)):
+                    model(return_loss=False, rescale=True, img=[img1], img_metas=[metas1])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    model(return_loss=False, rescale=True, img=[img1], img_metas=[metas1])
+                torch.cuda.synchronize()
+                lat1 = (time.perf_counter() - t0) / args.steps * 1000.0
+        extra['latency_bs1_ms'], extra['fps_bs1'] = lat1, None if lat1 is None else 1000.0 / lat1
     line = {
         'metric': 'images/sec (1333x800) Boosting R-CNN R50-PAFPN inference',
         'value': world * args.batch * args.steps / dt, 'unit': 'images/sec',
@@ -374,12 +412,10 @@ def inference_bench(args, world, rank, device):
                                f'batch {args.batch} x 3x800x1344 per GPU, {args.dtype} MFMA conv stack, '
                                '1000 pre-NMS / 256 proposals per image, seeded synthetic weights',
                    'global_batch': world * args.batch, 'parallelism': f'dp{world}'},
-        'roofline': roof,
-        'stages_ms': stages,
-        'latency_bs1_ms': lat1, 'fps_bs1': None if lat1 is None else 1000.0 / lat1,
+        **extra,
         'detections_last_step': int(sum(len(c) for im in last['out'] for c in im)),
     }
-    return line, cfg, model
+    return line, cfg, model, outputs
 
 
 def main():
@@ -428,18 +464,25 @@ def main():
         del pool
     except RuntimeError:
         pass
-    line, cfg = None, None
+    line, cfg, outputs = None, None, {}
     if args.mode in ('both', 'inference'):
-        line, cfg, model = inference_bench(args, world, rank, device)
+        line, cfg, model, out = inference_bench(args, world, rank, device)
+        outputs.update(out)
         del model
     if args.mode in ('both', 'train'):
-        tr = train_bench(args, world, rank, device)
+        tr, out = train_bench(args, world, rank, device)
+        outputs.update(out)
         if line is None:
             line = dict(tr, higher_is_better=True, scaling='weak', vs_baseline=None, data='synthetic')
         else:
             line['train'] = tr
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline and cfg is not None:
+        if args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in outputs.items():
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
+        if args.full and world == 1 and not args.no_cpu_baseline and cfg is not None:
             from oracle import cpu_pipeline
             line['cpu_baseline'] = cpu_pipeline.timed_baseline(cfg, seed=0)
         # RCCL prints its version banner through C stdio, which would otherwise be flushed at exit -- AFTER the line

@@ -1261,6 +1261,9 @@ class ConvBnEvalActFunction(Function):
                                            ctx.needs_input_grad[0], ctx.needs_input_grad[1])
             if dskip is not None:
                 dx = dskip if dx is None else dx + dskip
+        # both tails are consumed: ctx.tail holds this layer's output, whose grad_fn is this node -- a cycle through the
+        # autograd graph that Python's collector cannot see, which kept every train step's activations alive
+        ctx.tail = ctx.in_tail = None
         return (dx, dw, dgamma.to(gdt), dbeta.to(bdt), None, None, None, dres) + (None,) * 8
 
 

@@ -133,7 +133,7 @@ def test_train_tool_two_ranks_keep_identical_replicas(tmp_path):
 
 def test_bench_under_the_launcher():
     r = _launch([os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '2',
-                 '--no-cpu-baseline'])
+                 '--full', '--no-cpu-baseline'])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     assert line['n_gpus'] == 1 and line['value'] > 0 and line['train']['value'] > 0 and 'roofline' in line
@@ -142,11 +142,33 @@ def test_bench_under_the_launcher():
     assert r.returncode != 0 and 'WORLD_SIZE' in (r.stdout + r.stderr)
 
 
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """a plain `bench.py --gpus 1`: the inference headline alone (none of the --full passes), exactly --steps timed
+    steps, and with --dump-outputs the last timed step's detections in fixed shapes, none of them empty"""
+    out = tmp_path / 'out'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--batch', '2', '--dump-outputs', str(out)], cwd=ROOT, capture_output=True, text=True, timeout=900,
+                       env=dict(os.environ, PYTHONPATH=ROOT))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0 and line['dtype'] == 'f32'
+    assert line['unit'] == 'images/sec' and line['higher_is_better'] is True and 'inference' in line['metric']
+    assert not {'train', 'roofline', 'stages_ms', 'latency_bs1_ms', 'cpu_baseline'} & set(line)
+    import numpy as np
+    assert sorted(os.listdir(out)) == ['detections.npy', 'num_detections.npy']
+    dets, counts = np.load(out / 'detections.npy'), np.load(out / 'num_detections.npy')
+    assert dets.dtype == np.float32 and dets.shape == (2, 100, 6) and counts.dtype == np.float32 and counts.shape == (2,)
+    assert counts.sum() == line['detections_last_step'] > 0
+    for d, n in zip(dets, counts.astype(int)):
+        assert (d[n:] == 0).all() and (d[:n, 4] > 0).all()              # zero padding past the count, real scores before
+        assert np.isin(d[:n, 5], np.arange(4)).all() and (np.diff(d[:n, 5]) >= 0).all()     # class by class
+
+
 def test_bench_two_ranks_prints_one_line_with_reduce_time():
     """`bench.py --gpus 2` as the driver launches it, both ranks on the one GPU (gloo): every rank runs the same
     collectives -- the roofline pass included -- and rank 0 prints ONE line carrying train.reduce_ms / grad_bytes"""
     r = _launch([os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2',
-                 '--no-cpu-baseline'], nproc=2, extra_env=TWO_ON_ONE, timeout=1500)
+                 '--full', '--no-cpu-baseline'], nproc=2, extra_env=TWO_ON_ONE, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1

@@ -13,7 +13,7 @@ for l in sys.stdin:
 done; done
 for v in 0 1; do
 echo "HIP_FORCE_DEV_KERNARG=$v"
-HIP_FORCE_DEV_KERNARG=$v python bench.py --mode inference --no-cpu-baseline 2>/dev/null | python -c "
+HIP_FORCE_DEV_KERNARG=$v python bench.py --full --mode inference --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

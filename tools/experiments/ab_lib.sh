@@ -4,7 +4,7 @@
 # usage (on the GPU box): bash tools/experiments/ab_lib.sh [rounds]
 R=${1:-2}
 one() {
-  python bench.py --no-cpu-baseline $2 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline $2 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

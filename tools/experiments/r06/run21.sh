@@ -1,7 +1,7 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out/r06
 timeout 1800 python -m pytest tests/ -x -q -m gpu > gpurun_out/r06/pytest_gpu_f.txt 2>&1; echo "rc=$?" >> gpurun_out/r06/pytest_gpu_f.txt
 tail -4 gpurun_out/r06/pytest_gpu_f.txt | cut -c1-200
-for i in 1 2; do python bench.py --mode train --steps 40 --warmup 8 --no-cpu-baseline 2>/dev/null | python -c "
+for i in 1 2; do python bench.py --full --mode train --steps 40 --warmup 8 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 l=[x for x in sys.stdin if x.startswith('{')][-1]; d=json.loads(l)
 s=d['stages_ms']

@@ -6,11 +6,11 @@ d = json.loads(sys.stdin.read())
 for k, v in d.items():
     if 'topk' in k or 'nms' in k or 'sort' in k: print(k, round(v['us'], 1))
 "
-python bench.py --mode inference --no-cpu-baseline 2>/dev/null | python -c "
+python bench.py --full --mode inference --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('inf', d['value'], d['ms_per_step'], d['stages_ms'])
 "
-python bench.py --mode inference --dtype bf16 --no-cpu-baseline 2>/dev/null | python -c "
+python bench.py --full --mode inference --dtype bf16 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('inf bf16', d['value'], d['ms_per_step'], d['stages_ms'])
 "
