@@ -1049,6 +1049,62 @@ def deform_im2col_autograd(x, om, stride, pad):
     return DeformIm2colFunction.apply(x, om, stride, pad)
 
 
+class DeformConvFunction(Function):
+    """modulated deformable 3x3 conv (DCNv2, deform_groups 1) in the 16-bit compute dtypes: x (N,H,W,Cp) bf16 / fp16,
+    om (N,Ho,Wo,27) fp32 raw conv_offset output, weight (Cout,Cp,3,3) in the parameter layout -> the raw conv output
+    (N,Ho,Wo,Cout) in x's dtype, from the fused kernel (the columns are never stored).  Backward: dcol = dY . W on the
+    16-bit GEMM with an fp32 result, dx / d_om from the 16-bit col2im (dx accumulated in fp32, rounded once), dW from the
+    recomputed 16-bit columns on the weight-gradient kernel.  (fp32 keeps DeformIm2colFunction + linear_autograd.)"""
+
+    @staticmethod
+    def forward(ctx, x, om, weight, stride, pad):
+        _require_gpu(x, om, weight)
+        if x.dtype not in (torch.bfloat16, torch.float16):
+            raise _L.BrcnnHipError(f'DeformConvFunction: bf16 / fp16 activations (got {x.dtype})')
+        x, om = x.contiguous(), om.contiguous()
+        assert om.shape[3] == 27 and om.dtype == torch.float32
+        w_p = weight.detach().permute(0, 2, 3, 1).to(x.dtype).contiguous()        # (Cout,3,3,Cp), K order (tap, c)
+        y = ops.deform_conv_nhwc(x, om, w_p, None, None, False, stride, pad)
+        ctx.save_for_backward(x, om)
+        ctx.w_p = w_p
+        ctx.cfg = (stride, pad)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, om = ctx.saved_tensors
+        stride, pad = ctx.cfg
+        w_p = ctx.w_p
+        n, h, w, cp = x.shape
+        _, ho, wo, cout = dy.shape
+        m = n * ho * wo
+        lib = _L.load()
+        dy = dy.to(x.dtype).contiguous().view(m, cout)
+        dx = dom = dw = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dcol = ops.linear_nhwc(dy, w_p.view(cout, 9 * cp).t().contiguous(), out_f32=True)      # (M, 9 Cp) fp32
+            dx32 = torch.zeros((n, h, w, cp), dtype=torch.float32, device=x.device)
+            dom = torch.empty_like(om)
+            st = lib.brcnn_deform_col2im_nhwc_ex(_ptr(x), _ptr(om), _ptr(dcol), _ptr(dx32), _ptr(dom), n, h, w, cp, 3, 3,
+                                                 int(stride), int(pad), 1, 27, cp, ops._dt(x), _stream())
+            _L.check(st, 'brcnn_deform_col2im_nhwc_ex')
+            dx = dx32.to(x.dtype)
+        if ctx.needs_input_grad[2]:
+            col, _ = ops.deform_im2col_nhwc(x, om, 3, stride, pad, 1)                 # recomputed, 16-bit
+            dwp = torch.zeros((cout, 1, 1, 9 * cp), dtype=torch.float32, device=x.device)
+            one = _ints([1])
+            st = lib.brcnn_conv2d_wgrad_nhwc_multi(_ptr(col), _ptr(dy), _ptr(dwp), m, 1, one, one, 9 * cp, cout, 1, 1, 1, 0,
+                                                   ops._dt(x), _conv_stream())
+            _L.check(st, 'brcnn_conv2d_wgrad_nhwc_multi')
+            dw = dwp.view(cout, 3, 3, cp).permute(0, 3, 1, 2)
+        return dx, dom, dw, None, None
+
+
+def deform_conv_autograd(x, om, weight, stride, pad):
+    return DeformConvFunction.apply(x, om, weight, stride, pad)
+
+
 class BnActFunction(Function):
     """out = [relu](z * scale + shift [+ res]) over NHWC rows, one kernel each way
     (`brcnn_bn_act_forward/backward`); scale / shift are the (C,) fp32 eval-BN affine."""

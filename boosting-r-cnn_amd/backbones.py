@@ -13,7 +13,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .blocks import PackedCache, build_norm_layer, conv_bn_act_nhwc, folded_conv_operands, to_nchw_view, to_nhwc
+from .blocks import (PackedCache, build_norm_layer, compute_dtype, conv_bn_act_nhwc, folded_conv_operands, to_nchw_view,
+                     to_nhwc)
 from .registry import BACKBONES
 
 
@@ -331,7 +332,8 @@ class Bottle2neck(nn.Module):
     wide; here every split is laid out padded to a multiple of 32 channels (zero filters / zero
     BN affine in the pad slots, so the pad channels stay exactly 0 through ReLU, the hierarchical
     adds and the concat), which keeps all convs on the vector (LDS-DMA) MFMA path; the packed,
-    padded weights are functions of the reference-layout parameters."""
+    padded weights are functions of the reference-layout parameters.  In the 16-bit compute dtypes the splits are padded to
+    a multiple of 64 instead (the Cin % 64 of the 16-bit conv kernels) and the DCN convs run on the fused kernel."""
     expansion = 4
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, style='pytorch', norm_cfg=dict(type='BN'),
@@ -361,6 +363,7 @@ class Bottle2neck(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self._cache = PackedCache()
+        self._cache16 = {}          # 16-bit compute dtype -> PackedCache of the 64-channel-padded layout
         self._c_down = PackedCache()
 
     # ---- padded, packed tensors (inference: cached; rebuilt when a parameter changes) --------
@@ -393,6 +396,48 @@ class Bottle2neck(nn.Module):
         srcs = [p for p in self.parameters()] + [b for b in self.buffers() if b.dtype.is_floating_point]
         return self._cache.get(srcs, builder)
 
+    def _packed16(self, dtype):
+        """the inference operands of the 16-bit compute dtypes: every split padded to a multiple of 64 channels
+        (26/52/104/208 -> 64/64/128/256: the 16-bit conv kernels take Cin % 64 == 0), weights in `dtype`, BN folded in
+        fp32, zero filters / zero affine in the pad slots as in the fp32 layout; conv_offset padded to 64 output rows
+        (its fp32 result is read in place by the fused DCN kernel, 27 live values per pixel)"""
+        from .blocks import fold_bn, pack_weight
+        F = torch.nn.functional
+        w, s, wp = self.width, self.scales, _pad_to(self.width, 64)
+
+        def builder():
+            d = {}
+            s1, b1 = fold_bn(self.bn1)
+            w1 = self.conv1.weight.detach().float().view(s, w, self.inplanes)
+            d['w1'] = F.pad(w1, (0, 0, 0, wp - w)).reshape(s * wp, 1, 1, self.inplanes).to(dtype).contiguous()
+            d['s1'] = F.pad(s1.view(s, w), (0, wp - w)).reshape(-1).contiguous()
+            d['b1'] = F.pad(b1.view(s, w), (0, wp - w)).reshape(-1).contiguous()
+            for i, (conv, bn) in enumerate(zip(self.convs, self.bns)):
+                si, bi = fold_bn(bn)
+                wi = pack_weight(conv.weight)                                   # (w, 3, 3, w)
+                d[f'cw{i}'] = F.pad(wi, (0, wp - w, 0, 0, 0, 0, 0, wp - w)).to(dtype).contiguous()
+                d[f'cs{i}'] = F.pad(si, (0, wp - w)).contiguous()
+                d[f'cb{i}'] = F.pad(bi, (0, wp - w)).contiguous()
+                if self.with_dcn:
+                    wo = pack_weight(conv.conv_offset.weight)                   # (27, 3, 3, w)
+                    d[f'wo{i}'] = F.pad(wo, (0, wp - w, 0, 0, 0, 0, 0, 64 - 27)).to(dtype).contiguous()
+                    d[f'bo{i}'] = F.pad(conv.conv_offset.bias.detach().float(), (0, 64 - 27)).contiguous()
+            s3, b3 = fold_bn(self.bn3)
+            w3 = self.conv3.weight.detach().float().view(-1, s, w)
+            d['w3'] = F.pad(w3, (0, wp - w)).reshape(-1, 1, 1, s * wp).to(dtype).contiguous()
+            d['s3'], d['b3'] = s3, b3
+            return d
+        srcs = [p for p in self.parameters()] + [b for b in self.buffers() if b.dtype.is_floating_point]
+        return self._cache16.setdefault(dtype, PackedCache()).get(srcs, builder)
+
+    def _conv_i16(self, d, i, sp):
+        """convs[i] + bns[i] + ReLU on a 16-bit (N,h,w,wp) split; DCN: the offset conv with an fp32 result (offsets are
+        not rounded to 16 bits), then the fused deformable conv with BN + ReLU in its epilogue (csrc/deform_conv_bf16.hip)"""
+        if not self.with_dcn:
+            return ops.conv2d_nhwc(sp, d[f'cw{i}'], d[f'cs{i}'], d[f'cb{i}'], None, True, self.conv2_stride, 1)
+        om = ops.conv2d_nhwc(sp, d[f'wo{i}'], None, d[f'bo{i}'], None, False, self.conv2_stride, 1, out_f32=True)
+        return ops.deform_conv_nhwc(sp, om, d[f'cw{i}'], d[f'cs{i}'], d[f'cb{i}'], True, self.conv2_stride, 1)
+
     def _conv_i(self, d, i, sp):
         """convs[i] + bns[i] + ReLU on a (N,h,w,wp) split"""
         conv = self.convs[i]
@@ -422,8 +467,10 @@ class Bottle2neck(nn.Module):
 
     def _forward_train(self, x):
         import torch.nn.functional as F
-        from .autograd import conv2d_nhwc_autograd, deform_im2col_autograd, linear_autograd
-        w, s, wp = self.width, self.scales, _pad_to(self.width)
+        from .autograd import conv2d_nhwc_autograd, deform_conv_autograd, deform_im2col_autograd, linear_autograd
+        sixteen = x.dtype != torch.float32
+        # (16-bit: splits padded to 64 channels, the Cin % 64 of the 16-bit conv kernels)
+        w, s, wp = self.width, self.scales, _pad_to(self.width, 64 if sixteen else 32)
         pw = wp - w
         s1, b1 = self._affine(self.bn1)
         w1 = F.pad(self.conv1.weight.view(s, w, self.inplanes), (0, 0, 0, pw)).reshape(s * wp, self.inplanes, 1, 1)
@@ -439,10 +486,15 @@ class Bottle2neck(nn.Module):
             wi = F.pad(conv.weight, (0, 0, 0, 0, 0, pw, 0, pw))                      # (wp, wp, 3, 3)
             if self.with_dcn:
                 wo = F.pad(conv.conv_offset.weight, (0, 0, 0, 0, 0, pw))             # (27, wp, 3, 3)
-                om = conv2d_nhwc_autograd(sp, wo, conv.conv_offset.bias, self.conv2_stride, 1)
-                col = deform_im2col_autograd(sp, om, self.conv2_stride, 1)
-                n, ho, wo_ = om.shape[0], om.shape[1], om.shape[2]
-                y = linear_autograd(col, wi.permute(0, 2, 3, 1).reshape(wp, 9 * wp), None).view(n, ho, wo_, wp)
+                if sixteen:
+                    # offsets / mask logits in fp32 from the 16-bit operands, then the fused deformable conv (raw output)
+                    om = conv2d_nhwc_autograd(sp, wo, conv.conv_offset.bias, self.conv2_stride, 1, out_f32=True)
+                    y = deform_conv_autograd(sp, om, wi, self.conv2_stride, 1)
+                else:
+                    om = conv2d_nhwc_autograd(sp, wo, conv.conv_offset.bias, self.conv2_stride, 1)
+                    col = deform_im2col_autograd(sp, om, self.conv2_stride, 1)
+                    n, ho, wo_ = om.shape[0], om.shape[1], om.shape[2]
+                    y = linear_autograd(col, wi.permute(0, 2, 3, 1).reshape(wp, 9 * wp), None).view(n, ho, wo_, wp)
             else:
                 y = conv2d_nhwc_autograd(sp, wi, None, self.conv2_stride, 1)
             sp = self._bn_act(y, F.pad(si, (0, pw)), F.pad(bi, (0, pw)), None, True)
@@ -465,19 +517,22 @@ class Bottle2neck(nn.Module):
         return self._bn_act(y, s3, b3, identity.contiguous(), True)
 
     def forward_nhwc(self, x):
-        if x.dtype != torch.float32:
-            raise NotImplementedError('Res2Net runs in fp32 only this round')
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise NotImplementedError(f'Res2Net runs in fp32, bf16 or fp16 (got {x.dtype})')
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             return self._forward_train(x)
-        d = self._packed()
-        wp, s = _pad_to(self.width), self.scales
+        if x.dtype == torch.float32:
+            d, wp, conv_i = self._packed(), _pad_to(self.width), self._conv_i
+        else:
+            d, wp, conv_i = self._packed16(x.dtype), _pad_to(self.width, 64), self._conv_i16
+        s = self.scales
         out = ops.conv2d_nhwc(x, d['w1'], d['s1'], d['b1'], None, True, 1, 0)     # (N,h,w,s*wp)
         spx = [out[..., i * wp:(i + 1) * wp] for i in range(s)]
-        sp = self._conv_i(d, 0, spx[0].contiguous())
+        sp = conv_i(d, 0, spx[0].contiguous())
         outs = [sp]
         for i in range(1, s - 1):
             sp = spx[i].contiguous() if self.stage_type == 'stage' else sp + spx[i]
-            sp = self._conv_i(d, i, sp)
+            sp = conv_i(d, i, sp)
             outs.append(sp)
         if self.stage_type == 'normal' or self.conv2_stride == 1:
             outs.append(spx[s - 1])
@@ -619,6 +674,12 @@ class Res2Net(nn.Module):
         for j in range(3):
             x = conv_bn_act_nhwc(x, self.stem[3 * j], self.stem[3 * j + 1], self._stem_caches[j], True)
         x = ops.maxpool3x3s2_nhwc(x)
+        dt = compute_dtype()
+        if x.dtype != dt:
+            # the deep stem (frozen in the recipes) stays fp32; its max-pooled output is cast to the 16-bit compute dtype
+            # once.  Rounding to nearest is monotonic, so max and rounding commute: this equals pooling the rounded stem
+            # output exactly
+            x = x.to(dt)
         outs = []
         for i, name in enumerate(self.res_layers):
             x = getattr(self, name).forward_nhwc(x)

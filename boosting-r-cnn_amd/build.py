@@ -28,7 +28,8 @@ FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-ffp-contract=
 # vectoriser, some of them in the cross-swizzled op_sel form that tools/check_isa.py refuses; the kernels
 # are latency- or HBM-bound, the scalar form costs nothing measurable
 EXTRA_FLAGS = {'roi_align.hip': ['-fno-slp-vectorize'], 'focal_loss.hip': ['-fno-slp-vectorize'],
-               'train_loss.hip': ['-fno-slp-vectorize'], 'deform.hip': ['-fno-slp-vectorize']}
+               'train_loss.hip': ['-fno-slp-vectorize'], 'deform.hip': ['-fno-slp-vectorize'],
+               'deform_conv_bf16.hip': ['-fno-slp-vectorize']}
 
 
 def hipcc():

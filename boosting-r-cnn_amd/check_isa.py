@@ -16,7 +16,7 @@ read the pair's low register; what a scalar scale / shift times two outputs comp
 not refused: the conv read-outs hold ~5 000 of them, they never read the high register out of order, and the 200- to
 400-repetition bit-reproducibility stress tests (tests/test_stress_gpu.py) run exactly those read-outs under a
 co-resident load.  Where the compiler's SLP vectoriser was the only source of packed fp32 (roi_align, focal_loss,
-train_loss, deform: latency- or HBM-bound kernels) the translation unit is built with -fno-slp-vectorize
+train_loss, deform, and the blend of deform_conv_bf16: latency- or gather-bound code) the translation unit is built with -fno-slp-vectorize
 (build.py EXTRA_FLAGS) and holds none at all.  `build.py` calls `check_objects` after compiling;
 `python tools/check_isa.py [objects...]` (a shim over this module) runs it by hand and prints the per-object counts.
 """
@@ -102,7 +102,7 @@ def swizzled_packed_fp32(code_object):
 # with no `s_waitcnt vmcnt` in between must not fall under the listed count again.
 MIN_LOADS_IN_FLIGHT = {'stem_pool_kernel': 12, 'gn_stats_kernel': 8, 'sqnorm_partial_kernel': 4,
                        'roi_grad_gather_kernel': 7, 'roi_align_fwd_nhwc_fp_kernel': 7, 'colsum_partial_kernel': 7,
-                       'pack_batch_kernel': 4}
+                       'pack_batch_kernel': 4, 'deform_conv16_kernel': 16}
 _LOAD = re.compile(r'^\s*(global_load_|buffer_load_)(?!.*\blds\b)')
 _WAITVM = re.compile(r'^\s*s_waitcnt\b.*vmcnt')
 

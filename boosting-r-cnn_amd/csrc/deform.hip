@@ -10,10 +10,34 @@
 //     follows is the ordinary MFMA linear kernel with its fused BN / ReLU epilogue.
 // Both are HBM-bound streams, 16 bytes of channels per lane.
 #include "common.h"
+#include "deform_common.h"
 
 namespace {
 
-__global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y,
+// four channels of an NHWC map at element index i as fp32 (DT: BRCNN_DT_F32 / _BF16 / _F16), and back (one rounding)
+template <int DT> __device__ __forceinline__ float4 ld4f(const void* p, size_t i) {
+    if constexpr (DT == BRCNN_DT_F32) {
+        return *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + i);
+    } else {
+        const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(p) + i);
+        return make_float4(deform_e2f<DT>((unsigned short)q.x), deform_e2f<DT>((unsigned short)(q.x >> 16)),
+                           deform_e2f<DT>((unsigned short)q.y), deform_e2f<DT>((unsigned short)(q.y >> 16)));
+    }
+}
+template <int DT> __device__ __forceinline__ void st4f(void* p, size_t i, float4 v) {
+    if constexpr (DT == BRCNN_DT_F32) {
+        *reinterpret_cast<float4*>(reinterpret_cast<float*>(p) + i) = v;
+    } else {
+        uint2 q;
+        q.x = DT == BRCNN_DT_F16 ? brcnn_pk2h(v.x, v.y) : brcnn_pk2b(v.x, v.y);
+        q.y = DT == BRCNN_DT_F16 ? brcnn_pk2h(v.z, v.w) : brcnn_pk2b(v.z, v.w);
+        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p) + i) = q;
+    }
+}
+
+// fp32 sums and divisor in every element type; the 16-bit forms round the mean once
+template <int DT>
+__global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const void* __restrict__ x, void* __restrict__ y,
                                                           int N, int H, int W, int C, int Ho, int Wo, int k,
                                                           int stride, int pad, int count_include_pad) {
     const int c4n = C >> 2;
@@ -34,18 +58,24 @@ __global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float* __restri
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int h = hs; h < he; h++)
             for (int w = ws; w < we; w++) {
-                const float4 v = *reinterpret_cast<const float4*>(x + (((size_t)n * H + h) * W + w) * C + c4 * 4);
+                const float4 v = ld4f<DT>(x, (((size_t)n * H + h) * W + w) * C + c4 * 4);
                 a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
             }
         const float div = (float)(count_include_pad ? pool_size : (he - hs) * (we - ws));
         a.x /= div; a.y /= div; a.z /= div; a.w /= div;
-        *reinterpret_cast<float4*>(y + (size_t)idx * 4) = a;
+        st4f<DT>(y, (size_t)idx * 4, a);
     }
 }
 
 __device__ __forceinline__ float4 ld4z(const float* x, int H, int W, int C, int n, int h, int w, int c, bool ok) {
     if (!ok) return make_float4(0.f, 0.f, 0.f, 0.f);
     return *reinterpret_cast<const float4*>(x + (((size_t)n * H + h) * W + w) * C + c);
+}
+
+template <int DT>
+__device__ __forceinline__ float4 ld4z_t(const void* x, int H, int W, int C, int n, int h, int w, int c, bool ok) {
+    if (!ok) return make_float4(0.f, 0.f, 0.f, 0.f);
+    return ld4f<DT>(x, (((size_t)n * H + h) * W + w) * C + c);
 }
 
 // one thread: one (output pixel, tap, 4 channels)
@@ -99,7 +129,9 @@ __global__ __launch_bounds__(256) void deform_im2col_nhwc_kernel(const float* __
 // offset / mask gradients are channel sums, reduced across the wave and written once:
 //   d off_h = mask * sum_c dcol_c * d val_c / d h,   d off_w likewise,
 //   d mask_logit = mask (1 - mask) * sum_c dcol_c * val_c          (sigmoid applied in the forward)
-__global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const float* __restrict__ x,
+// (16-bit x: the same arithmetic on the widened corners; dx stays an fp32 accumulator the caller converts)
+template <int DT>
+__global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const void* __restrict__ x,
                                                                 const float* __restrict__ om,
                                                                 const float* __restrict__ dcol,
                                                                 float* __restrict__ dx, float* __restrict__ dom,
@@ -134,10 +166,10 @@ __global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const float* __
         const float* dc = dcol + ((size_t)m * taps + tap) * Cpad;
         for (int c = lane * 4; c < C; c += 256) {
             const float4 g = *reinterpret_cast<const float4*>(dc + c);
-            const float4 v1 = ld4z(x, H, W, C, n, h_low, w_low, c, ok1);
-            const float4 v2 = ld4z(x, H, W, C, n, h_low, w_high, c, ok2);
-            const float4 v3 = ld4z(x, H, W, C, n, h_high, w_low, c, ok3);
-            const float4 v4 = ld4z(x, H, W, C, n, h_high, w_high, c, ok4);
+            const float4 v1 = ld4z_t<DT>(x, H, W, C, n, h_low, w_low, c, ok1);
+            const float4 v2 = ld4z_t<DT>(x, H, W, C, n, h_low, w_high, c, ok2);
+            const float4 v3 = ld4z_t<DT>(x, H, W, C, n, h_high, w_low, c, ok3);
+            const float4 v4 = ld4z_t<DT>(x, H, W, C, n, h_high, w_high, c, ok4);
             const float gg[4] = {g.x, g.y, g.z, g.w};
             const float a1[4] = {v1.x, v1.y, v1.z, v1.w}, a2[4] = {v2.x, v2.y, v2.z, v2.w};
             const float a3[4] = {v3.x, v3.y, v3.z, v3.w}, a4[4] = {v4.x, v4.y, v4.z, v4.w};
@@ -169,6 +201,45 @@ __global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const float* __
     }
 }
 
+// 16-bit im2col: one thread per (output pixel, tap, 8 channels); the sample comes from deform_sample8, the routine
+// the fused conv (deform_conv_bf16.hip) builds its A operand with.  Corner loads from clamped addresses, unconditional.
+template <int DT>
+__global__ __launch_bounds__(256) void deform_im2col_nhwc16_kernel(const unsigned short* __restrict__ x,
+                                                                  const float* __restrict__ om,
+                                                                  unsigned short* __restrict__ col, int N, int H, int W,
+                                                                  int C, int Ho, int Wo, int KH, int KW, int stride,
+                                                                  int pad, int dilation, int om_stride, int Cpad) {
+    const int c8n = Cpad >> 3, taps = KH * KW;
+    const long long total = (long long)N * Ho * Wo * taps * c8n;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(idx % c8n) * 8;
+        long long r = idx / c8n;
+        const int tap = (int)(r % taps); r /= taps;
+        const long long m = r;
+        const int wo = (int)(m % Wo);
+        const int ho = (int)((m / Wo) % Ho);
+        const int n = (int)(m / ((long long)Wo * Ho));
+        const int i = tap / KW, j = tap - i * KW;
+        const float* o = om + (size_t)m * om_stride;
+        const DeformTapGeom g = deform_tap_geom(o[2 * tap], o[2 * tap + 1], o[2 * taps + tap], ho * stride - pad + i * dilation,
+                                                wo * stride - pad + j * dilation, H, W, C, c < C);
+        const unsigned short* xc = x + (size_t)n * H * W * C + (c < C ? c : 0);
+        const uint4 v1 = *reinterpret_cast<const uint4*>(xc + g.off1);
+        const uint4 v2 = *reinterpret_cast<const uint4*>(xc + g.off2);
+        const uint4 v3 = *reinterpret_cast<const uint4*>(xc + g.off3);
+        const uint4 v4 = *reinterpret_cast<const uint4*>(xc + g.off4);
+        *reinterpret_cast<uint4*>(col + (size_t)idx * 8) = deform_sample8<DT>(g, v1, v2, v3, v4);
+    }
+}
+
+// torch AvgPool2d output size (the last window must start inside the input in ceil mode)
+inline int brcnn_avgpool_out(int in, int kernel, int stride, int pad, int ceil_mode) {
+    int o = ceil_mode ? (in + 2 * pad - kernel + stride - 1) / stride + 1 : (in + 2 * pad - kernel) / stride + 1;
+    if (ceil_mode && (o - 1) * stride >= in + pad) o--;
+    return o;
+}
+
 inline int stream_grid(long long total) {
     long long g = (total + 255) / 256;
     return (int)(g > 32768 ? 32768 : (g < 1 ? 1 : g));
@@ -190,7 +261,7 @@ BRCNN_API int brcnn_avgpool_nhwc(const float* x, float* y, int batch, int height
     const int Ho = osz(height), Wo = osz(width);
     if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
     const long long total = (long long)batch * Ho * Wo * (channels >> 2);
-    hipLaunchKernelGGL(avgpool_nhwc_kernel, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, batch,
+    hipLaunchKernelGGL(avgpool_nhwc_kernel<BRCNN_DT_F32>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, batch,
                        height, width, channels, Ho, Wo, kernel, stride, pad, count_include_pad);
     BRCNN_LAUNCH_CHECK();
     return 0;
@@ -227,9 +298,88 @@ BRCNN_API int brcnn_deform_col2im_nhwc(const float* x, const float* offset_mask,
     const int Wo = (width + 2 * pad - (dilation * (kw - 1) + 1)) / stride + 1;
     if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
     const long long items = (long long)batch * Ho * Wo * kh * kw;
-    hipLaunchKernelGGL(deform_col2im_nhwc_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_F32>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        x, offset_mask, dcol, dx, d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride,
                        pad, dilation, om_stride, channels_padded);
+    BRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+
+// ---- 16-bit forms (bf16 / fp16 activations; the offsets / mask logits and every gradient stay fp32) ----------------
+BRCNN_API int brcnn_avgpool_nhwc_ex(const void* x, void* y, int batch, int height, int width, int channels, int kernel,
+                                    int stride, int pad, int ceil_mode, int count_include_pad, int dtype, void* stream) {
+    if (dtype == BRCNN_DT_F32)
+        return brcnn_avgpool_nhwc((const float*)x, (float*)y, batch, height, width, channels, kernel, stride, pad, ceil_mode,
+                                  count_include_pad, stream);
+    if (!x || !y || batch <= 0 || height <= 0 || width <= 0 || channels <= 0 || (channels & 3) || kernel <= 0 ||
+        stride <= 0 || pad < 0 || pad > kernel / 2 || (dtype != BRCNN_DT_BF16 && dtype != BRCNN_DT_F16))
+        return BRCNN_EINVAL;
+    const int Ho = (int)brcnn_avgpool_out(height, kernel, stride, pad, ceil_mode);
+    const int Wo = (int)brcnn_avgpool_out(width, kernel, stride, pad, ceil_mode);
+    if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
+    const long long total = (long long)batch * Ho * Wo * (channels >> 2);
+    if (dtype == BRCNN_DT_F16)
+        hipLaunchKernelGGL(avgpool_nhwc_kernel<BRCNN_DT_F16>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x,
+                           y, batch, height, width, channels, Ho, Wo, kernel, stride, pad, count_include_pad);
+    else
+        hipLaunchKernelGGL(avgpool_nhwc_kernel<BRCNN_DT_BF16>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x,
+                           y, batch, height, width, channels, Ho, Wo, kernel, stride, pad, count_include_pad);
+    BRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+BRCNN_API int brcnn_deform_im2col_nhwc_ex(const void* x, const float* offset_mask, void* col, int batch, int height,
+                                          int width, int channels, int kh, int kw, int stride, int pad, int dilation,
+                                          int om_stride, int channels_padded, int dtype, void* stream) {
+    if (dtype == BRCNN_DT_F32)
+        return brcnn_deform_im2col_nhwc((const float*)x, offset_mask, (float*)col, batch, height, width, channels, kh, kw,
+                                        stride, pad, dilation, om_stride, channels_padded, stream);
+    if (!x || !offset_mask || !col || batch <= 0 || height <= 0 || width <= 0 || channels <= 0 || (channels & 7) ||
+        kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dilation <= 0 || om_stride < 3 * kh * kw ||
+        channels_padded < channels || (channels_padded & 7) || (dtype != BRCNN_DT_BF16 && dtype != BRCNN_DT_F16) ||
+        (long long)batch * height * width * channels >= 0x7fffffffLL)
+        return BRCNN_EINVAL;
+    const int Ho = (height + 2 * pad - (dilation * (kh - 1) + 1)) / stride + 1;
+    const int Wo = (width + 2 * pad - (dilation * (kw - 1) + 1)) / stride + 1;
+    if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
+    const long long total = (long long)batch * Ho * Wo * kh * kw * (channels_padded >> 3);
+    if (dtype == BRCNN_DT_F16)
+        hipLaunchKernelGGL(deform_im2col_nhwc16_kernel<BRCNN_DT_F16>, dim3(stream_grid(total)), dim3(256), 0,
+                           (hipStream_t)stream, (const unsigned short*)x, offset_mask, (unsigned short*)col, batch, height,
+                           width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded);
+    else
+        hipLaunchKernelGGL(deform_im2col_nhwc16_kernel<BRCNN_DT_BF16>, dim3(stream_grid(total)), dim3(256), 0,
+                           (hipStream_t)stream, (const unsigned short*)x, offset_mask, (unsigned short*)col, batch, height,
+                           width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded);
+    BRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+BRCNN_API int brcnn_deform_col2im_nhwc_ex(const void* x, const float* offset_mask, const float* dcol, float* dx,
+                                          float* d_offset_mask, int batch, int height, int width, int channels, int kh,
+                                          int kw, int stride, int pad, int dilation, int om_stride, int channels_padded,
+                                          int dtype, void* stream) {
+    if (dtype == BRCNN_DT_F32)
+        return brcnn_deform_col2im_nhwc((const float*)x, offset_mask, dcol, dx, d_offset_mask, batch, height, width,
+                                        channels, kh, kw, stride, pad, dilation, om_stride, channels_padded, stream);
+    if (!x || !offset_mask || !dcol || !dx || !d_offset_mask || batch <= 0 || height <= 0 || width <= 0 ||
+        channels <= 0 || (channels & 3) || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dilation <= 0 ||
+        om_stride != 3 * kh * kw || channels_padded < channels || (channels_padded & 3) ||
+        (dtype != BRCNN_DT_BF16 && dtype != BRCNN_DT_F16))
+        return BRCNN_EINVAL;
+    const int Ho = (height + 2 * pad - (dilation * (kh - 1) + 1)) / stride + 1;
+    const int Wo = (width + 2 * pad - (dilation * (kw - 1) + 1)) / stride + 1;
+    if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
+    const long long items = (long long)batch * Ho * Wo * kh * kw;
+    if (dtype == BRCNN_DT_F16)
+        hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_F16>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0,
+                           (hipStream_t)stream, x, offset_mask, dcol, dx, d_offset_mask, batch, height, width, channels, Ho,
+                           Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded);
+    else
+        hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_BF16>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0,
+                           (hipStream_t)stream, x, offset_mask, dcol, dx, d_offset_mask, batch, height, width, channels, Ho,
+                           Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }

@@ -118,6 +118,10 @@ SIGNATURES = {
     'brcnn_conv2d_dgrad_nhwc_grouped': (c_int, [c_ptr] * 3 + [c_int] * 13 + [c_ptr]),
     'brcnn_conv2d_wgrad_nhwc_grouped': (c_int, [c_ptr] * 3 + [c_int] * 11 + [c_ptr]),
     'brcnn_deform_col2im_nhwc': (c_int, [c_ptr] * 5 + [c_int] * 11 + [c_ptr]),
+    'brcnn_avgpool_nhwc_ex': (c_int, [c_ptr, c_ptr] + [c_int] * 10 + [c_ptr]),
+    'brcnn_deform_im2col_nhwc_ex': (c_int, [c_ptr] * 3 + [c_int] * 12 + [c_ptr]),
+    'brcnn_deform_col2im_nhwc_ex': (c_int, [c_ptr] * 5 + [c_int] * 12 + [c_ptr]),
+    'brcnn_deform_conv_nhwc': (c_int, [c_ptr] * 6 + [c_int] * 10 + [c_ptr]),
     'brcnn_pack_conv_weights': (c_int, [c_ptr] * 3 + [c_int] * 5 + [c_ptr]),
     'brcnn_rpn_topk_workspace_bytes': (ctypes.c_size_t, [c_ptr, c_int, c_int, c_int]),
     'brcnn_rpn_topk': (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, ctypes.c_size_t, c_ptr]),

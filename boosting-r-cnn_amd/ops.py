@@ -1117,11 +1117,17 @@ def avgpool_out_size(size, kernel, stride, pad, ceil_mode):
 
 
 def avgpool_nhwc(x, kernel, stride, pad=0, ceil_mode=False, count_include_pad=True):
-    """torch.nn.AvgPool2d on an NHWC fp32 map"""
+    """torch.nn.AvgPool2d on an NHWC map: fp32, or bf16 / fp16 (fp32 sums, the mean rounded once)"""
     _require_gpu(x)
-    assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
+    assert x.dim() == 4 and x.is_contiguous()
     n, h, w, c = x.shape
     ho, wo = avgpool_out_size(h, kernel, stride, pad, ceil_mode), avgpool_out_size(w, kernel, stride, pad, ceil_mode)
+    if x.dtype != torch.float32:
+        y = torch.empty((n, ho, wo, c), dtype=x.dtype, device=x.device)
+        st = _L.load().brcnn_avgpool_nhwc_ex(_ptr(x), _ptr(y), n, h, w, c, int(kernel), int(stride), int(pad),
+                                             int(bool(ceil_mode)), int(bool(count_include_pad)), _dt(x), _stream())
+        _L.check(st, 'brcnn_avgpool_nhwc_ex')
+        return y
     y = torch.empty((n, ho, wo, c), dtype=torch.float32, device=x.device)
     st = _L.load().brcnn_avgpool_nhwc(_ptr(x), _ptr(y), n, h, w, c, int(kernel), int(stride), int(pad),
                                       int(bool(ceil_mode)), int(bool(count_include_pad)), _stream())
@@ -1131,15 +1137,48 @@ def avgpool_nhwc(x, kernel, stride, pad=0, ceil_mode=False, count_include_pad=Tr
 
 def deform_im2col_nhwc(x, offset_mask, kernel=3, stride=1, pad=1, dilation=1, channels_padded=None):
     """mmcv modulated deformable im2col (deform_groups 1): x (N,H,W,C), offset_mask (N,Ho,Wo,>=27)
-    raw conv_offset output -> columns (N*Ho*Wo, k*k*Cp), K order (tap, c), zero in the pad channels"""
+    raw conv_offset output -> columns (N*Ho*Wo, k*k*Cp), K order (tap, c), zero in the pad channels.
+    bf16 / fp16 x: 16-bit columns, each the fp32 sample of the widened input rounded once (offset_mask stays fp32)"""
     _require_gpu(x, offset_mask)
-    assert x.dim() == 4 and x.is_contiguous() and x.dtype == torch.float32
+    assert x.dim() == 4 and x.is_contiguous()
     n, h, w, c = x.shape
     cp = c if channels_padded is None else channels_padded
     ho, wo = conv_out_size(h, w, dilation * (kernel - 1) + 1, dilation * (kernel - 1) + 1, stride, pad)
     assert tuple(offset_mask.shape[:3]) == (n, ho, wo) and offset_mask.is_contiguous()
+    if x.dtype != torch.float32:
+        assert offset_mask.dtype == torch.float32, 'deform_im2col_nhwc: offset_mask stays fp32'
+        col = torch.empty((n * ho * wo, kernel * kernel * cp), dtype=x.dtype, device=x.device)
+        st = _L.load().brcnn_deform_im2col_nhwc_ex(_ptr(x), _ptr(offset_mask), _ptr(col), n, h, w, c, kernel, kernel,
+                                                   int(stride), int(pad), int(dilation), offset_mask.shape[3], cp, _dt(x),
+                                                   _stream())
+        _L.check(st, 'brcnn_deform_im2col_nhwc_ex')
+        return col, (ho, wo)
     col = torch.empty((n * ho * wo, kernel * kernel * cp), dtype=torch.float32, device=x.device)
     st = _L.load().brcnn_deform_im2col_nhwc(_ptr(x), _ptr(offset_mask), _ptr(col), n, h, w, c, kernel, kernel,
                                             int(stride), int(pad), int(dilation), offset_mask.shape[3], cp, _stream())
     _L.check(st, 'brcnn_deform_im2col_nhwc')
     return col, (ho, wo)
+
+
+def deform_conv_nhwc(x, offset_mask, w, scale=None, shift=None, relu=False, stride=1, pad=1):
+    """fused modulated deformable 3x3 conv, 16-bit only: y = [relu](scale * (im2col(x, offset_mask) . w^T) + shift) in
+    one launch.  x (N,H,W,Cp) bf16 / fp16 with Cp % 64 == 0; offset_mask (N,Ho,Wo,>=27) fp32 raw conv_offset output
+    (a padded row, e.g. the 64-channel output of the offset conv, is read in place); w (Cout,3,3,Cp) in x's dtype,
+    Cout in {64, 128, 256}; scale / shift (Cout) fp32 or None.  Returns y (N,Ho,Wo,Cout) in x's dtype."""
+    _require_gpu(x, offset_mask, w, scale, shift)
+    assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and offset_mask.is_contiguous()
+    if x.dtype not in (torch.bfloat16, torch.float16) or w.dtype != x.dtype:
+        raise _L.BrcnnHipError(f'deform_conv_nhwc: bf16 / fp16 x and w of the same dtype (got {x.dtype}, {w.dtype})')
+    if offset_mask.dtype != torch.float32:
+        raise _L.BrcnnHipError('deform_conv_nhwc: offset_mask stays fp32')
+    n, h, wd, cp = x.shape
+    cout = w.shape[0]
+    assert tuple(w.shape[1:]) == (3, 3, cp), f'deform_conv_nhwc: w {tuple(w.shape)} vs Cp {cp}'
+    ho, wo = conv_out_size(h, wd, 3, 3, stride, pad)
+    assert tuple(offset_mask.shape[:3]) == (n, ho, wo)
+    y = torch.empty((n, ho, wo, cout), dtype=x.dtype, device=x.device)
+    st = _L.load().brcnn_deform_conv_nhwc(_ptr(x), _ptr(offset_mask), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), n, h,
+                                          wd, cp, cout, int(stride), int(pad), int(bool(relu)), offset_mask.shape[3],
+                                          _dt(x), _stream())
+    _L.check(st, 'brcnn_deform_conv_nhwc')
+    return y

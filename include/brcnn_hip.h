@@ -586,6 +586,28 @@ int brcnn_deform_col2im_nhwc(const float *x, const float *offset_mask, const flo
                              float *d_offset_mask, int batch, int height, int width, int channels, int kh,
                              int kw, int stride, int pad, int dilation, int om_stride, int channels_padded,
                              void *stream);
+/* 16-bit forms (dtype BRCNN_DT_BF16 | BRCNN_DT_F16; BRCNN_DT_F32 runs the fp32 entries above unchanged).  x / y / col
+ * in the 16-bit type, offset_mask and every gradient in fp32.  avgpool: fp32 sums and divisor, one rounding.  im2col:
+ * channels and channels_padded multiples of 8; each sample is the fp32 value of the fp32 im2col on the widened input,
+ * rounded once to nearest even.  col2im: dcol (N*Ho*Wo, KH*KW*channels_padded) fp32 -> dx fp32 (zero-filled by the
+ * caller, atomics; the caller converts it) and d_offset_mask fp32. */
+int brcnn_avgpool_nhwc_ex(const void *x, void *y, int batch, int height, int width, int channels, int kernel,
+                          int stride, int pad, int ceil_mode, int count_include_pad, int dtype, void *stream);
+int brcnn_deform_im2col_nhwc_ex(const void *x, const float *offset_mask, void *col, int batch, int height,
+                                int width, int channels, int kh, int kw, int stride, int pad, int dilation,
+                                int om_stride, int channels_padded, int dtype, void *stream);
+int brcnn_deform_col2im_nhwc_ex(const void *x, const float *offset_mask, const float *dcol, float *dx,
+                                float *d_offset_mask, int batch, int height, int width, int channels, int kh,
+                                int kw, int stride, int pad, int dilation, int om_stride, int channels_padded,
+                                int dtype, void *stream);
+/* Fused modulated deformable 3x3 conv (csrc/deform_conv_bf16.hip), 16-bit only (dtype BRCNN_DT_BF16 | BRCNN_DT_F16):
+ * y = [relu](scale * (im2col16(x, offset_mask) . w^T) + shift) in one launch, the columns never stored.
+ * x (N,H,W,channels) with channels % 64 == 0; offset_mask (N,Ho,Wo,om_stride >= 27) fp32 raw conv_offset output;
+ * w (cout,3,3,channels) with cout in {64, 128, 256}; stride 1 or 2; scale / shift (cout) fp32 or NULL (shift alone:
+ * a bias); y (N,Ho,Wo,cout) 16-bit.  The A operand equals brcnn_deform_im2col_nhwc_ex's columns bit for bit. */
+int brcnn_deform_conv_nhwc(const void *x, const float *offset_mask, const void *w, const float *scale,
+                           const float *shift, void *y, int batch, int height, int width, int channels, int cout,
+                           int stride, int pad, int relu, int om_stride, int dtype, void *stream);
 
 /* FPN top-down path: dst[n,y,x,c] += src[n, y*Hs/Hd, x*Ws/Wd, c]  (nearest,
  * F.interpolate(size=...) at necks/pafpn.py:113-115, fpn.py:178-181) */

@@ -1,4 +1,5 @@
-"""inference throughput of every shipped recipe (seeded synthetic weights, batch B x 3x800x1344, fp32)"""
+"""inference throughput of every shipped recipe (seeded synthetic weights, batch B x 3x800x1344; BRCNN_DTYPE=f32|bf16|f16;
+RECIPES=substring[,substring...]: only the recipes whose file name contains one of them)"""
 import json, os, sys, time
 sys.path.insert(0, os.getcwd())
 import torch
@@ -12,6 +13,8 @@ out = {}
 d = 'configs/boosting_rcnn'
 for f in sorted(os.listdir(d)):
     if not f.endswith('.py'):
+        continue
+    if os.environ.get('RECIPES') and not any(k in f for k in os.environ['RECIPES'].split(',')):
         continue
     cfg = Config.fromfile(os.path.join(d, f))
     m = build_detector(cfg.model)
