@@ -518,6 +518,74 @@ def bbox2roi(bbox_list):
     return torch.cat(rows, 0)
 
 
+# ---- test-time augmentation: the per-image torch chain (registry seam; the parity chain of the device kernels in
+# csrc/tta.hip, which repeat these fp32 operations in this order)
+_FLIP_AXES = {'horizontal': (1,), 'vertical': (0,), 'diagonal': (1, 0)}     # img_shape index of every mirrored axis
+
+
+def bbox_flip(bboxes, img_shape, direction='horizontal'):
+    """core/bbox/transforms.py:6-32: (..., 4k) boxes mirrored about `img_shape` (h, w[, c]): the low corner of an axis
+    becomes `extent - high corner` and the other way round"""
+    assert bboxes.shape[-1] % 4 == 0 and direction in _FLIP_AXES
+    flipped = bboxes.clone()
+    for dim in _FLIP_AXES[direction]:
+        lo, hi = (0, 2) if dim == 1 else (1, 3)
+        flipped[..., lo::4] = img_shape[dim] - bboxes[..., hi::4]
+        flipped[..., hi::4] = img_shape[dim] - bboxes[..., lo::4]
+    return flipped
+
+
+def bbox_mapping(bboxes, img_shape, scale_factor, flip, flip_direction='horizontal'):
+    """core/bbox/transforms.py:35-44: original image -> test frame (scale, then flip)"""
+    mapped = bboxes * bboxes.new_tensor(scale_factor)
+    return bbox_flip(mapped, img_shape, flip_direction) if flip else mapped
+
+
+def bbox_mapping_back(bboxes, img_shape, scale_factor, flip, flip_direction='horizontal'):
+    """core/bbox/transforms.py:47-56: test frame -> original image (un-flip, then a true division by the scale)"""
+    unflipped = bbox_flip(bboxes, img_shape, flip_direction) if flip else bboxes
+    return (unflipped.view(-1, 4) / unflipped.new_tensor(scale_factor)).view(bboxes.shape)
+
+
+def _meta_flip(meta):
+    """(flip, direction) of an img_meta; the direction is only read where the image is flipped"""
+    flip = bool(meta.get('flip', False))
+    if flip and meta.get('flip_direction') not in _FLIP_AXES:
+        raise ValueError(f"img_metas: a flipped meta carries flip_direction={meta.get('flip_direction')!r}")
+    return flip, meta.get('flip_direction') or 'horizontal'
+
+
+def merge_aug_proposals(aug_proposals, img_metas, cfg, nms=None):
+    """core/post_processing/merge_augs.py:13-81 for the `nms=dict(...)` / `max_per_img` form of the RPN test cfg (the
+    only one the recipes use): one image's (n_a, 5) proposals of every aug mapped back to the original image,
+    concatenated in aug order, one plain NMS, the best `max_per_img` in score order -> (n, 5).
+    `nms`: the operator (mmcv.ops.nms signature); default this package's device NMS, which refuses host tensors."""
+    if nms is None:
+        from .ops import nms
+    back = []
+    for props, meta in zip(aug_proposals, img_metas):
+        flip, direction = _meta_flip(meta)
+        boxes = bbox_mapping_back(props[:, :4], meta['img_shape'], meta['scale_factor'], flip, direction)
+        back.append(torch.cat([boxes, props[:, 4:]], dim=1))
+    cand = torch.cat(back, dim=0)
+    merged, _ = nms(cand[:, :4].contiguous(), cand[:, -1].contiguous(), cfg.nms.iou_threshold)
+    order = merged[:, 4].sort(dim=0, descending=True, stable=True)[1][:min(cfg.max_per_img, merged.shape[0])]
+    return merged[order]
+
+
+def merge_aug_bboxes(aug_bboxes, aug_scores, img_metas, rcnn_test_cfg):
+    """core/post_processing/merge_augs.py:84-110: the mean over the augs of the mapped-back (n, 4C) class boxes and of
+    the (n, C+1) scores.  `img_metas`: per aug the one-image meta list, as the reference passes it."""
+    back = []
+    for boxes, metas in zip(aug_bboxes, img_metas):
+        flip, direction = _meta_flip(metas[0])
+        back.append(bbox_mapping_back(boxes, metas[0]['img_shape'], metas[0]['scale_factor'], flip, direction))
+    bboxes = torch.stack(back).mean(dim=0)
+    if aug_scores is None:
+        return bboxes
+    return bboxes, torch.stack(aug_scores).mean(dim=0)
+
+
 def bbox2result(bboxes, labels, num_classes):
     """(n,5),(n,) -> list[num_classes] of ndarray (k,5) (core/bbox/transforms.py:100-117)"""
     if bboxes.shape[0] == 0:

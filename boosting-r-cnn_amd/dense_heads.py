@@ -729,3 +729,36 @@ class ATSSRPNHead(AnchorHead):
     def simple_test_rpn(self, x, img_metas):
         cls_scores, bbox_preds, iou_preds = self(x)
         return self.get_bboxes(cls_scores, bbox_preds, iou_preds, img_metas)
+
+    # ------------------------------------------------------------------ test-time augmentation
+    def aug_test_rpn(self, feats, img_metas):
+        """dense_test_mixins.py:128-160: `feats` per aug the NCHW pyramid, `img_metas` per aug the batch's metas; per aug
+        the plain proposal stage, per image the proposals of all augs merged in the original frame
+        (core.merge_aug_proposals) -> list over images of (n, 5)"""
+        from .core import merge_aug_proposals
+        per_aug = [self.simple_test_rpn(x, metas) for x, metas in zip(feats, img_metas)]
+        return [merge_aug_proposals([props[b] for props in per_aug], [metas[b] for metas in img_metas], self.test_cfg)
+                for b in range(len(img_metas[0]))]
+
+    def aug_test_rpn_padded(self, feats_per_aug, img_metas_per_aug, geom=None, reg_scales=None):
+        """`aug_test_rpn` for the whole batch on the device, no host sync: per aug the fused tower and
+        `get_bboxes_padded` on its NHWC pyramid, then one launch that maps every aug's proposals back to the original
+        image into aug-major candidate slots and ONE segmented NMS (a segment per image, `max_per_img` survivors).
+        Returns the merged (dets (B, max_per_img, 5), num (B,) int32) and the geometry table."""
+        cfg = self.test_cfg
+        nms_cfg = dict(cfg.nms)
+        assert nms_cfg.pop('type', 'nms') == 'nms', 'RPN proposals use greedy NMS'
+        dets_l, num_l = [], []
+        for feats, metas in zip(feats_per_aug, img_metas_per_aug):
+            cls, reg, iou = self.split_fused(self.forward_fused(list(feats)))
+            if reg_scales is None:      # the live Scale parameters, read on the device
+                reg_scales = torch.stack([m.scale.detach().reshape(()) for m in self.scales]).float().contiguous()
+            dets, num = self.get_bboxes_padded(cls, reg, iou, metas, reg_scales=reg_scales)
+            dets_l.append(dets)
+            num_l.append(num)
+        if geom is None:
+            geom = ops.tta_geometry(img_metas_per_aug, dets_l[0])
+        _, boxes, scores, valid = ops.tta_gather_proposals(dets_l, num_l, geom)
+        merged, _, num = batched_nms_images(boxes, scores, torch.zeros_like(scores, dtype=torch.long), valid,
+                                            nms_cfg['iou_threshold'], cfg.max_per_img, nms_cfg.get('offset', 0))
+        return merged, num, geom

@@ -109,8 +109,8 @@ class BaseDetector(nn.Module):
                 raise TypeError(f'{name} must be a list, but got {type(var)}')
         num_augs = len(imgs)
         if num_augs != len(img_metas):
-            raise ValueError(f'num of augmentations ({len(imgs)}) '
-                             f'!= num of image meta ({len(img_metas)})')
+            raise ValueError(f'num of augmentations ({len(imgs)}, imgs) '
+                             f'!= num of image meta ({len(img_metas)}, img_metas)')
         for img, img_meta in zip(imgs, img_metas):
             for img_id in range(len(img_meta)):
                 img_meta[img_id]['batch_input_shape'] = tuple(img.size()[-2:])
@@ -118,7 +118,12 @@ class BaseDetector(nn.Module):
             if 'proposals' in kwargs:
                 kwargs['proposals'] = kwargs['proposals'][0]
             return self.simple_test(imgs[0], img_metas[0], **kwargs)
-        raise NotImplementedError('test-time augmentation is outside the hot path')
+        if 'proposals' in kwargs:
+            raise ValueError('proposals: precomputed proposals are not supported with test-time augmentation')
+        return self.aug_test(imgs, img_metas, **kwargs)
+
+    def aug_test(self, imgs, img_metas, **kwargs):
+        raise NotImplementedError(f'{type(self).__name__} has no test-time augmentation')
 
     def forward(self, img, img_metas, return_loss=True, **kwargs):
         if return_loss:
@@ -398,6 +403,53 @@ class TwoStageDetector(BaseDetector):
         x = self.extract_feat(img)
         proposal_list = self.rpn_head.simple_test_rpn(x, img_metas) if proposals is None else proposals
         return self.roi_head.simple_test(x, proposal_list, img_metas, rescale=rescale)
+
+    # ---- test-time augmentation (two_stage.py:184-193) -------------------------------------------
+    @staticmethod
+    def _check_augs(imgs, img_metas):
+        """argument errors of the aug lists, raised before anything is queued on the device"""
+        from .ops import TTA_MAX_AUGS, tta_geometry_rows
+        if len(imgs) != len(img_metas):
+            raise ValueError(f'imgs / img_metas: {len(imgs)} augmentations but {len(img_metas)} meta lists')
+        if len(imgs) > TTA_MAX_AUGS:
+            raise ValueError(f'imgs: {len(imgs)} augmentations, at most {TTA_MAX_AUGS} are supported')
+        B = imgs[0].shape[0]
+        for a, (img, metas) in enumerate(zip(imgs, img_metas)):
+            if img.shape[0] != B:
+                raise ValueError(f'imgs[{a}] holds {img.shape[0]} images, imgs[0] holds {B}')
+            if len(metas) != B:
+                raise ValueError(f'img_metas[{a}] holds {len(metas)} metas for {B} images')
+        tta_geometry_rows(img_metas)        # (flip / flip_direction / scale_factor of every meta)
+
+    def aug_test_device(self, imgs, img_metas, rescale=False):
+        """`aug_test` with no host synchronisation: one trunk + RPN pass per aug, the proposals of all augs merged per
+        image on the device, one RoI / box-head pass per aug on the merged proposals, the averaged decode and the NMS of
+        `simple_test_device`.  Returns device tensors (det_bboxes (B,M,5), det_labels (B,M), num_dets (B,)); image b
+        gets what it would get alone with the same padded tensors."""
+        feats = [self.extract_feat_nhwc(img) for img in imgs]
+        merged, num, geom = self.rpn_head.aug_test_rpn_padded(feats, img_metas)
+        stage_mark('rpn_postprocess')
+        out = self.roi_head.aug_test_padded(feats, merged, num, img_metas, rescale=rescale, geom=geom)
+        stage_mark('rcnn_decode_nms')
+        return out
+
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """Test with augmentations (multi-scale + flip): `imgs` / `img_metas` one entry per aug, each a whole batch.
+        Unlike the reference, whose RoI stage reads `img_meta[0]` only, batches of more than one image are served.
+        Without `rescale` the boxes fit the frame of imgs[0]."""
+        assert self.with_roi_head, 'Bbox head must be implemented.'
+        self._check_augs(imgs, img_metas)
+        if self._device_path_ok() and self.roi_head.tta_device_ok():
+            det, lab, nd = self.aug_test_device(imgs, img_metas, rescale)
+            B, M = lab.shape
+            # boxes, labels and counts leave in ONE copy, the one host sync (class ids and counts are exact in fp32)
+            host = torch.cat([det.reshape(B, M * 5), lab.to(det.dtype), nd.to(det.dtype).reshape(B, 1)], dim=1).cpu()
+            det, lab, nd = host[:, :M * 5].reshape(B, M, 5), host[:, M * 5:M * 6].long(), host[:, M * 6].long().tolist()
+            nc = self.roi_head.bbox_head.num_classes
+            return [bbox2result(det[i, :nd[i]], lab[i, :nd[i]], nc) for i in range(B)]
+        x = [self.extract_feat(img) for img in imgs]
+        proposal_list = self.rpn_head.aug_test_rpn(x, img_metas)
+        return self.roi_head.aug_test(x, proposal_list, img_metas, rescale=rescale)
 
     def _device_path_ok(self):
         rc, rp = self.test_cfg.rcnn, self.test_cfg.rpn

@@ -11,6 +11,7 @@ stream.  There is no CPU path: CPU tensors raise.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -1087,6 +1088,104 @@ def rcnn_decode(probs, bbox_pred, dets, num, max_shape, scale_factor, num_classe
 
 # --------------------------------------------------------------------------- input front door
 _FLIP_CODE = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}
+
+
+# --------------------------------------------------------------------------- test-time augmentation
+TTA_MAX_AUGS = 16
+_TTA_MODE = {'fused': 0, 'raw': 1}
+
+
+def tta_geometry_rows(img_metas_per_aug):
+    """host rows of the TTA geometry table, one per (aug, image): [img_h, img_w, sf0, sf1, sf2, sf3, flip code, 0]
+    from `img_metas` (list over augs of lists over images).  Raises ValueError naming `img_metas` on a flipped meta
+    without `flip_direction` or an unknown direction."""
+    rows = []
+    for a, metas in enumerate(img_metas_per_aug):
+        for b, m in enumerate(metas):
+            direction = None
+            if m.get('flip', False):
+                direction = m.get('flip_direction')
+                if direction not in ('horizontal', 'vertical', 'diagonal'):
+                    raise ValueError(f'img_metas[{a}][{b}] is flipped but its flip_direction is {direction!r}')
+            sf = [float(v) for v in np.broadcast_to(np.asarray(m['scale_factor'], dtype=np.float32).reshape(-1), (4,))]
+            rows.append([float(m['img_shape'][0]), float(m['img_shape'][1])] + sf + [float(_FLIP_CODE[direction]), 0.0])
+    return rows
+
+
+def tta_geometry(img_metas_per_aug, like):
+    """the (A, B, 8) fp32 geometry table of the TTA kernels on `like`'s device (uploaded once per distinct value set)"""
+    from .core import const_rows
+    A, B = len(img_metas_per_aug), len(img_metas_per_aug[0])
+    return const_rows(tta_geometry_rows(img_metas_per_aug), like).view(A, B, 8)
+
+
+def tta_gather_proposals(props_per_aug, num_per_aug, geom):
+    """brcnn_tta_gather_proposals: the A augs' padded proposals (B, K_a, 5) + counts (B,) -> candidates (B, sum K_a, 5)
+    in the original frame (aug-major), boxes (B, T, 4), scores (B, T), valid (B, T) bool."""
+    import ctypes
+    A = len(props_per_aug)
+    _require_gpu(geom, *props_per_aug, *num_per_aug)
+    assert len(num_per_aug) == A and geom.dtype == torch.float32 and geom.is_contiguous()
+    B = props_per_aug[0].shape[0]
+    props = [p.contiguous().float() for p in props_per_aug]
+    nums = [n.to(torch.int32).contiguous() for n in num_per_aug]
+    assert all(p.dim() == 3 and p.shape[0] == B and p.shape[2] == 5 for p in props) and all(n.shape == (B,) for n in nums)
+    assert tuple(geom.shape) == (A, B, 8)
+    T = sum(p.shape[1] for p in props)
+    dev = props[0].device
+    cand = torch.empty((B, T, 5), dtype=torch.float32, device=dev)
+    boxes = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, T), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, T), dtype=torch.bool, device=dev)
+    st = _L.load().brcnn_tta_gather_proposals((ctypes.c_void_p * A)(*[p.data_ptr() for p in props]),
+                                              (ctypes.c_void_p * A)(*[n.data_ptr() for n in nums]),
+                                              (ctypes.c_int * A)(*[p.shape[1] for p in props]), A, _ptr(geom), B,
+                                              _ptr(cand), _ptr(boxes), _ptr(scores), _ptr(valid), _stream())
+    _L.check(st, 'brcnn_tta_gather_proposals')
+    return cand, boxes, scores, valid
+
+
+def tta_map_rois(merged, geom):
+    """brcnn_tta_map_rois: merged proposals (B, K, 5) in the original frame -> rois (A, B*K, 5) [image, x1, y1, x2, y2]
+    in every aug's frame (bbox_mapping)"""
+    _require_gpu(merged, geom)
+    B, K, _ = merged.shape
+    A = geom.shape[0]
+    assert tuple(geom.shape) == (A, B, 8) and geom.dtype == torch.float32 and geom.is_contiguous()
+    merged = merged.contiguous().float()
+    rois = torch.empty((A, B * K, 5), dtype=torch.float32, device=merged.device)
+    st = _L.load().brcnn_tta_map_rois(_ptr(merged), _ptr(geom), A, B, K, _ptr(rois), _stream())
+    _L.check(st, 'brcnn_tta_map_rois')
+    return rois
+
+
+def rcnn_decode_tta(cls_score, bbox_pred, merged, num, geom, out_scale, num_classes, score_thr, means, stds,
+                    mode='fused', wh_ratio_clip=16 / 1000):
+    """brcnn_rcnn_decode_tta: cls_score (A, B*K, C+1) raw logits, bbox_pred (A, B*K, 4C), merged (B, K, 5) proposals in
+    the original frame, num (B,), geom (A, B, 8), out_scale (B, 4) or None; mode 'fused' | 'raw'.
+    Returns boxes (B, K*C, 4), scores (B, K*C), labels (B, K*C) int64, valid (B, K*C) bool: the means over the augs."""
+    import ctypes
+    _require_gpu(cls_score, bbox_pred, merged, num, geom, out_scale)
+    B, K, _ = merged.shape
+    A, C = geom.shape[0], int(num_classes)
+    assert tuple(geom.shape) == (A, B, 8) and geom.dtype == torch.float32 and geom.is_contiguous()
+    assert tuple(cls_score.shape) == (A, B * K, C + 1) and tuple(bbox_pred.shape) == (A, B * K, 4 * C)
+    cls_score, bbox_pred, merged = cls_score.contiguous().float(), bbox_pred.contiguous().float(), merged.contiguous().float()
+    dev = merged.device
+    boxes = torch.empty((B, K * C, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, K * C), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, K * C), dtype=torch.int64, device=dev)
+    valid = torch.empty((B, K * C), dtype=torch.bool, device=dev)
+    m4 = (ctypes.c_float * 4)(*[float(v) for v in means])
+    s4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    sf = out_scale.contiguous().float() if out_scale is not None else None
+    assert sf is None or tuple(sf.shape) == (B, 4)
+    st = _L.load().brcnn_rcnn_decode_tta(_ptr(cls_score), _ptr(bbox_pred), _ptr(merged), _ptr(num.to(torch.int32).contiguous()),
+                                         _ptr(geom), _ptr(sf), A, B, K, C, _TTA_MODE[mode], float(score_thr), m4, s4,
+                                         float(wh_ratio_clip), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(valid),
+                                         _stream())
+    _L.check(st, 'brcnn_rcnn_decode_tta')
+    return boxes, scores, labels, valid
 
 
 def preprocess_u8(src_u8, out, new_w, new_h, flip_direction, mean, std, to_rgb=True):

@@ -739,6 +739,111 @@ class ProbRoIHead(nn.Module):
                                           nms_cfg.get('offset', 0))
         return det, lab, nd
 
+    # ---- test-time augmentation ----------------------------------------------------------
+    def tta_score_mode(self):
+        """`test_cfg.tta_scores`: 'fused' (default) -- per aug the head's own `fuse_scores` (sqrt(softmax * prior), the
+        prior being the merged proposal's score), then the mean over the augs; with one aug this is `simple_test`.
+        'raw' -- the reference literally: its ProbRoIHead inherits `aug_test_bboxes` unchanged, which hands the raw
+        `cls_score` to a `get_bboxes` that applies no softmax and drops the prior, so the averaged "scores" are logits
+        (test_mixins.py:138-176, convfc_bbox_head.py:303-308).  Nobody wants those as detections; the mode exists so
+        that the whole TTA path can be pinned end to end against the reference's own `forward_test`."""
+        mode = self.test_cfg.get('tta_scores', 'fused')
+        if mode not in ('fused', 'raw'):
+            raise ValueError(f"test_cfg.rcnn.tta_scores must be 'fused' or 'raw', got {mode!r}")
+        return mode
+
+    def _tta_prior(self, proposals):
+        """the prior `fuse_scores` takes, from one image's merged (n, 5) proposals"""
+        return proposals[:, -1]
+
+    def tta_device_ok(self, feats_nhwc=None):
+        """the configurations `aug_test_padded` covers: what `simple_test_padded`'s fused-decode branch asks of the head
+        (the stock score fusion, a clipping coder without centre clamp, class-wise regression), hard NMS or soft-NMS
+        above split_thr as on the plain device path"""
+        coder = self.bbox_head.bbox_coder
+        return bool(type(self).fuse_scores is ProbRoIHead.fuse_scores and not getattr(coder, 'add_ctr_clamp', False) and
+                    getattr(coder, 'clip_border', True) and not self.bbox_head.reg_class_agnostic and
+                    self.bbox_roi_extractor._fusable())
+
+    def aug_test_padded(self, feats_per_aug, merged, num, img_metas_per_aug, rescale=False, geom=None):
+        """Device-resident second stage of TwoStageDetector.aug_test for the whole batch (test_mixins.py:138-176 +
+        prob_roi_head.py:180-203): `feats_per_aug` the A NHWC pyramids, `merged` (B,K,5) / `num` (B,) the merged
+        proposals in the original frame (`ATSSRPNHead.aug_test_rpn_padded`).  Three launches of its own (RoIs of every
+        aug, the averaged decode) around the A extractor / box-head passes, then the NMS of `simple_test_padded`.
+        Returns (det_bboxes (B,M,5), det_labels (B,M), num_dets (B,)), no host sync; boxes in the original frame for
+        `rescale`, else in the frame of aug 0."""
+        cfg = self.test_cfg
+        nms_cfg = dict(cfg.nms)
+        nms_type = nms_cfg.pop('type', 'nms')
+        head = self.bbox_head
+        B, K, _ = merged.shape
+        A, C = len(feats_per_aug), head.num_classes
+        assert self.tta_device_ok() and nms_type in ('nms', 'soft_nms') and not nms_cfg.get('class_agnostic', False)
+        split = K * C >= nms_cfg.get('split_thr', 10000)
+        assert nms_type == 'nms' or split, 'soft-NMS below split_thr keeps pick order: per-image path'
+        if geom is None:
+            geom = ops.tta_geometry(img_metas_per_aug, merged)
+        rois = ops.tta_map_rois(merged, geom)
+        cls_l, reg_l = [], []
+        for a in range(A):
+            roi_feats = self.bbox_roi_extractor.forward_nhwc(feats_per_aug[a], rois[a])
+            cls_score, bbox_pred = head.forward_nhwc(roi_feats)
+            cls_l.append(cls_score)
+            reg_l.append(bbox_pred)
+        stage_mark('fc_head')
+        mode = self.tta_score_mode() if self.prob else 'raw'        # (prob=False: fuse_scores is the identity)
+        out_scale = None if rescale else const_rows([list(m['scale_factor']) for m in img_metas_per_aug[0]], merged)
+        coder = head.bbox_coder
+        bb, sc, lb, va = ops.rcnn_decode_tta(torch.stack(cls_l).float(), torch.stack(reg_l).float(), merged, num, geom,
+                                             out_scale, C, cfg.score_thr, coder.means, coder.stds, mode)
+        if split:
+            # mmcv's per-class branch, as in simple_test_padded: class-major slots, one segmented (soft-)NMS launch
+            from .postprocess import batched_nms_images_by_level
+            cm = lambda t: t.view(B, K, C, *t.shape[2:]).transpose(1, 2).reshape(B, C * K, *t.shape[2:]).contiguous()   # noqa: E731
+            return batched_nms_images_by_level(cm(bb), cm(sc), cm(lb), cm(va), [K] * C, nms_cfg.get('iou_threshold', 0.3),
+                                               cfg.max_per_img, nms_cfg.get('offset', 0), return_ids=True,
+                                               soft=nms_cfg if nms_type == 'soft_nms' else None)
+        return batched_nms_images(bb, sc, lb, va, nms_cfg['iou_threshold'], cfg.max_per_img, nms_cfg.get('offset', 0))
+
+    def aug_test_bboxes(self, feats, img_metas, proposal_list, rcnn_test_cfg, image=0):
+        """test_mixins.py:138-176 for image `image` of the batch (the reference reads image 0 only): per aug the merged
+        proposals mapped into the aug's frame, RoI extract + box head, scores by `tta_score_mode`, decode clipped at the
+        aug's img_shape; the mean over the augs; multiclass NMS.  -> (det_bboxes (n,5) original frame, det_labels)"""
+        from .core import bbox_mapping, merge_aug_bboxes, _meta_flip
+        proposals = proposal_list[image]
+        if proposals.shape[0] == 0:
+            return proposals.new_zeros(0, 5), proposals.new_zeros((0,), dtype=torch.long)
+        fused = self.tta_score_mode() == 'fused'
+        aug_bboxes, aug_scores = [], []
+        for x, metas in zip(feats, img_metas):
+            meta = metas[image]
+            flip, direction = _meta_flip(meta)
+            boxes = bbox_mapping(proposals[:, :4], meta['img_shape'], meta['scale_factor'], flip, direction)
+            rois = torch.cat([boxes.new_full((boxes.size(0), 1), image), boxes], dim=-1)
+            res = self._bbox_forward(x, rois)
+            scores = self.fuse_scores(res['cls_score'], self._tta_prior(proposals)) if fused else res['cls_score']
+            bboxes, scores = self.bbox_head.get_bboxes(rois, scores, res['bbox_pred'], meta['img_shape'],
+                                                       meta['scale_factor'], rescale=False, cfg=None)
+            aug_bboxes.append(bboxes)
+            aug_scores.append(scores)
+        merged_bboxes, merged_scores = merge_aug_bboxes(aug_bboxes, aug_scores, [[m[image]] for m in img_metas],
+                                                        rcnn_test_cfg)
+        return multiclass_nms(merged_bboxes, merged_scores, rcnn_test_cfg.score_thr, rcnn_test_cfg.nms,
+                              rcnn_test_cfg.max_per_img)
+
+    def aug_test(self, x, proposal_list, img_metas, rescale=False):
+        """prob_roi_head.py:180-203, for every image of the batch: `x` the augs' feature tuples, `proposal_list` the merged
+        proposals per image (original frame), `img_metas` per aug the batch's metas.  Without `rescale` the boxes fit
+        the frame of imgs[0].  -> per image the per-class result list"""
+        results = []
+        for b in range(len(proposal_list)):
+            det_bboxes, det_labels = self.aug_test_bboxes(x, img_metas, proposal_list, self.test_cfg, image=b)
+            if not rescale:
+                det_bboxes = det_bboxes.clone()
+                det_bboxes[:, :4] *= det_bboxes.new_tensor(img_metas[0][b]['scale_factor'])
+            results.append(bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes))
+        return results
+
 
 # ----------------------------------------------------------------------------- variants
 @HEADS.register_module()
@@ -846,7 +951,10 @@ class BoostRoIHead(ProbRoIHead):
         prior = torch.cat((prior, prior.new_ones(prior.shape[0], 1)), dim=1)
         return self._simple_test_bboxes_with_prior(x, img_metas, proposals, prior, rcnn_test_cfg, rescale)
 
-    device_test_path = False    # per-class priors: the per-image test path (simple_test) serves it
+    def _tta_prior(self, proposals):
+        return torch.cat((proposals[:, 4:], proposals.new_ones(proposals.shape[0], 1)), dim=1)
+
+    device_test_path = False    # per-class priors: the per-image test path (simple_test / aug_test) serves it
 
 
 EPS = 1e-15

@@ -699,6 +699,52 @@ int brcnn_rcnn_decode(const float *probs, const float *bbox_pred, const float *p
                       int num_classes, float score_thr, const float *means4_host, const float *stds4_host,
                       double wh_ratio_clip, float *boxes, float *scores, int64_t *labels, uint8_t *valid,
                       void *stream);
+
+/* ------------------------------------------------------------------------------
+ * Test-time augmentation (multi-scale + flip), whole batch, no host round trip: the device form of
+ * TwoStageDetector.aug_test (detectors/two_stage.py:184-193).  Per-(aug, image) geometry is one device
+ * table geom (num_augs, batch, 8) = [img_h, img_w, sf0, sf1, sf2, sf3, flip, 0] built by the host from
+ * img_metas (scale_factor as the meta carries it, [sx, sy, sx, sy]; flip 0 none, 1 horizontal, 2
+ * vertical, 3 diagonal).  Coordinates are mapped with the reference's fp32 operations in its order
+ * (core/bbox/transforms.py:6-56: `w - x2`, true division by the scale factor), bit for bit.
+ * -------------------------------------------------------------------------- */
+#define BRCNN_TTA_MAX_AUGS 16
+#define BRCNN_TTA_FUSED 0 /* per aug sqrt(softmax(cls_score) * prior) (prob_roi_head.py:232-240), then the mean */
+#define BRCNN_TTA_RAW 1   /* the mean of the logits, prior ignored: aug_test_bboxes as the reference runs it    */
+
+/* merge_aug_proposals up to its NMS call (core/post_processing/merge_augs.py:61-72).  proposals[a]
+ * (batch, per_aug_host[a], 5) [x1,y1,x2,y2,score] zero padded with num[a][b] real rows (host arrays of
+ * num_augs device pointers).  Writes the T = sum per_aug_host candidate slots of every image, aug-major
+ * (the reference's torch.cat order = the tie order of the NMS), mapped back to the original image
+ * (bbox_mapping_back): candidates (batch, T, 5), valid (batch, T) = the row is real (others are zero),
+ * and, where not NULL, the same rows split as boxes (batch, T, 4) / scores (batch, T) for
+ * brcnn_nms_prepare. */
+int brcnn_tta_gather_proposals(const float *const *proposals, const int32_t *const *num, const int *per_aug_host,
+                               int num_augs, const float *geom, int batch, float *candidates, float *boxes,
+                               float *scores, uint8_t *valid, void *stream);
+
+/* bbox_mapping (transforms.py:35-44) of the merged proposals into every aug's frame, as RoIs (the loop
+ * head of aug_test_bboxes, roi_heads/test_mixins.py:142-151): merged (batch, per_image, 5) in the
+ * original frame -> rois (num_augs, batch*per_image, 5) [image, x1, y1, x2, y2], x scale factor then
+ * flip. */
+int brcnn_tta_map_rois(const float *merged, const float *geom, int num_augs, int batch, int per_image,
+                       float *rois, void *stream);
+
+/* The TTA form of brcnn_rcnn_decode: aug_test_bboxes + merge_aug_bboxes (test_mixins.py:138-165,
+ * merge_augs.py:84-110) up to the NMS call.  cls_score (num_augs, batch*per_image, C+1) RAW logits,
+ * bbox_pred (num_augs, batch*per_image, 4C), merged (batch, per_image, 5) proposals in the original
+ * frame with num[b] real rows, out_scale (batch, 4) or NULL (aug 0's scale factor: results in the frame
+ * of imgs[0], prob_roi_head.py:190-193).  Per (proposal, class), over the augs in order: the score
+ * (mode BRCNN_TTA_FUSED: max-subtracted fp32 softmax of the row, sqrt(p * prior); BRCNN_TTA_RAW: the
+ * logit) and delta2bbox of the proposal as mapped into the aug's frame, clipped at the aug's img_shape
+ * and mapped back; sums divided by num_augs.  Outputs as brcnn_rcnn_decode: boxes (batch, per_image*C,
+ * 4), scores, labels = class, valid = score > score_thr and the row is real. */
+int brcnn_rcnn_decode_tta(const float *cls_score, const float *bbox_pred, const float *merged, const int32_t *num,
+                          const float *geom, const float *out_scale, int num_augs, int batch, int per_image,
+                          int num_classes, int mode, float score_thr, const float *means4_host,
+                          const float *stds4_host, double wh_ratio_clip, float *boxes, float *scores,
+                          int64_t *labels, uint8_t *valid, void *stream);
+
 size_t brcnn_rpn_topk_workspace_bytes(const int *n_host, int num_levels, int batch, int k);
 int brcnn_rpn_topk(const float *const *score_levels, const int *n_host, int num_levels,
                    int batch, int k, float *const *out_score, int64_t *const *out_idx,
