@@ -26,3 +26,4 @@ from .registry import (MODELS, BACKBONES, NECKS, HEADS, LOSSES, DETECTORS, ROI_E
 from . import pipelines, datasets, evaluation, apis  # noqa: E402,F401
 from .pipelines import PIPELINES, Compose  # noqa: E402,F401
 from .datasets import DATASETS, build_dataset, build_dataloader  # noqa: E402,F401
+from .apis import init_detector, inference_detector, inference_stream  # noqa: E402,F401

@@ -24,7 +24,8 @@ from .datasets import build_dataloader, build_dataset
 
 __all__ = ['set_random_seed', 'get_root_logger', 'build_optimizer', 'StepLrUpdater', 'save_checkpoint',
            'load_checkpoint', 'EpochBasedRunner', 'train_detector', 'single_gpu_test', 'multi_gpu_test',
-           'init_dist', 'get_dist_info', 'replace_ImageToTensor', 'host_cpus', 'limit_host_threads']
+           'init_dist', 'get_dist_info', 'replace_ImageToTensor', 'host_cpus', 'limit_host_threads',
+           'init_detector', 'inference_detector', 'inference_stream']
 
 
 def host_cpus():
@@ -663,3 +664,203 @@ def multi_gpu_test(model, data_loader, tmpdir=None, gpu_collect=True):
     for res in zip(*parts):
         ordered.extend(list(res))
     return ordered[:len(data_loader.dataset)]
+
+
+# --------------------------------------------------------------------------- inference (apis/inference.py)
+def init_detector(config, checkpoint=None, device='cuda:0', cfg_options=None, dtype=None):
+    """apis/inference.py:17-54: a detector ready for `inference_detector` from a config (path or Config) and an
+    optional checkpoint.  `dtype` ('bf16' / 'f16' / 'f32', default: leave as is) sets the conv stack's arithmetic
+    (`set_compute_dtype`)."""
+    import warnings
+    from .config import Config
+    from .registry import build_detector
+    if isinstance(config, str):
+        config = Config.fromfile(config)
+    elif not isinstance(config, Config):
+        raise TypeError(f'config must be a filename or Config object, but got {type(config)}')
+    if cfg_options is not None:
+        config.merge_from_dict(cfg_options)
+    config.model.pretrained = None
+    config.model.train_cfg = None
+    model = build_detector(config.model, test_cfg=config.get('test_cfg'))
+    if checkpoint is not None:
+        ckpt = load_checkpoint(model, checkpoint, map_location='cpu')
+        if 'CLASSES' in ckpt.get('meta', {}):
+            model.CLASSES = ckpt['meta']['CLASSES']
+        else:
+            from .datasets import CocoDataset
+            warnings.simplefilter('once')
+            warnings.warn('Class names are not saved in the checkpoint\'s meta data, use COCO classes by default.')
+            model.CLASSES = CocoDataset.CLASSES
+    model.cfg = config          # save the config in the model for convenience
+    model.to(device)
+    model.eval()
+    if dtype is not None:
+        model.set_compute_dtype(dtype)
+    if torch.device(device).type == 'cuda' and hasattr(model, 'freeze_for_inference'):
+        model.freeze_for_inference()        # host copies of the rpn scales: no device read per call
+    return model
+
+
+def _front_door(model):
+    """the model's cached pipelines.BatchFrontDoor, or None where the test pipeline (or the device) is outside it"""
+    from .pipelines import BatchFrontDoor
+    pipe = model.cfg.data.test.pipeline
+    device = next(model.parameters()).device
+    key = (repr(pipe), str(device))
+    cached = model.__dict__.get('_front_door_cache')
+    if cached is None or cached[0] != key:
+        door = BatchFrontDoor(pipe, device) if device.type == 'cuda' and BatchFrontDoor.supported(pipe) else None
+        model.__dict__['_front_door_cache'] = cached = (key, door)
+    return cached[1]
+
+
+def _compose_data(cfg, imgs, device):
+    """the reference's chain (apis/inference.py:109-139): per-image Compose of the test pipeline, then collate"""
+    import copy
+    from .datasets import collate
+    from .pipelines import Compose
+    pipe = copy.deepcopy(list(cfg.data.test.pipeline))
+    if isinstance(imgs[0], np.ndarray):
+        pipe[0]['type'] = 'LoadImageFromWebcam'
+    test_pipeline = Compose(replace_ImageToTensor(pipe))
+    datas = []
+    for img in imgs:
+        data = dict(img=img) if isinstance(img, np.ndarray) else dict(img_info=dict(filename=img), img_prefix=None)
+        datas.append(test_pipeline(data))
+    data = collate(datas, samples_per_gpu=len(imgs))
+    return _to_device(data, device) if device.type == 'cuda' else data
+
+
+def inference_detector(model, imgs):
+    """apis/inference.py:90-153.  `imgs`: str / ndarray or a list / tuple of them; the result of the one image, or
+    a list.  A supported test pipeline takes the batched front door (one upload, one launch for all images and
+    augs; `model.last_path == 'batched'`), anything else the per-image Compose + collate chain ('compose')."""
+    is_batch = isinstance(imgs, (list, tuple))
+    imgs = list(imgs) if is_batch else [imgs]
+    door = _front_door(model)
+    if door is not None and door.accepts(imgs):
+        data, path = door(imgs), 'batched'
+    else:
+        data, path = _compose_data(model.cfg, imgs, next(model.parameters()).device), 'compose'
+    model.last_path = path
+    with torch.no_grad():
+        results = model(return_loss=False, rescale=True, **data)
+    return results if is_batch else results[0]
+
+
+def inference_stream(model, images, batch_size=8, prefetch=2):
+    """Generator over an iterable of paths / arrays: one result per image, in input order (the counterpart of
+    `async_inference_detector` for folders and video frames).  A worker thread decodes the next batches and fills
+    pinned staging blocks (at most `prefetch` wait); the upload and the preprocess launch of batch i + 1 are queued
+    on a side stream before batch i's pass is queued on the current stream, which waits for the side stream's event
+    only.  The last batch may be partial; a worker exception is raised here once the batches before it were
+    delivered; closing the generator early joins the worker and the side stream."""
+    import itertools
+    import queue
+    import threading
+    assert batch_size >= 1 and prefetch >= 1
+    door = _front_door(model)
+    it = iter(images)
+
+    def batches():
+        while True:
+            chunk = list(itertools.islice(it, batch_size))
+            if not chunk:
+                return
+            yield chunk
+
+    if door is None:
+        for chunk in batches():
+            for r in inference_detector(model, chunk):
+                yield r
+        return
+
+    door.ensure_slots(prefetch + 2)     # `prefetch` staged + one being filled + one spare: acquire() never starves
+    staged = queue.Queue(maxsize=prefetch)
+    stop = threading.Event()
+
+    def put(item):
+        while not stop.is_set():
+            try:
+                staged.put(item, timeout=0.05)
+                return True
+            except queue.Full:
+                pass
+        return False
+
+    def work():
+        try:
+            for chunk in batches():
+                if stop.is_set():
+                    return
+                if not door.accepts(chunk):
+                    if not put(('compose', chunk, None)):
+                        return
+                    continue
+                arrays, names = door.decode(chunk)
+                slot = door.acquire()
+                try:
+                    plan = door.stage(slot, arrays, names)
+                except BaseException:
+                    door.release(slot)
+                    raise
+                if not put(('staged', slot, plan)):
+                    door.release(slot)
+                    return
+            put(('end', None, None))
+        except BaseException as e:      # delivered to the consumer
+            put(('error', e, None))
+
+    device = next(model.parameters()).device
+    side = torch.cuda.Stream(device)
+    worker = threading.Thread(target=work, name='brcnn-front-door', daemon=True)
+
+    def run(pending):
+        if pending[0] == 'compose':
+            return inference_detector(model, pending[1])
+        _, data, event = pending
+        main = torch.cuda.current_stream(device)
+        main.wait_event(event)
+        for t in data['img']:
+            t.record_stream(main)
+        model.last_path = 'batched'
+        with torch.no_grad():
+            return model(return_loss=False, rescale=True, **data)
+
+    def drain():
+        while True:
+            try:
+                item = staged.get_nowait()
+            except queue.Empty:
+                return
+            if item[0] == 'staged':
+                door.release(item[1])
+
+    worker.start()
+    pending = None
+    try:
+        while True:
+            kind, x, plan = staged.get()
+            nxt = None
+            if kind == 'staged':
+                data = door.submit(x, plan, stream=side)
+                nxt = ('device', data, x.event)
+                door.release(x)
+            elif kind == 'compose':
+                nxt = ('compose', x)
+            if pending is not None:
+                for r in run(pending):
+                    yield r
+                pending = None
+            if kind == 'end':
+                break
+            if kind == 'error':
+                raise x
+            pending = nxt
+    finally:
+        stop.set()
+        drain()
+        worker.join()
+        drain()
+        side.synchronize()

@@ -1205,6 +1205,41 @@ def preprocess_u8(src_u8, out, new_w, new_h, flip_direction, mean, std, to_rgb=T
     return out
 
 
+# include/brcnn_hip.h: brcnn_pre_job (64 bytes), one row per (aug, image) of a batched front-door launch
+PRE_JOB_DTYPE = np.dtype([('src_off', '<i8'), ('dst_off', '<i8'), ('scale_x', '<f8'), ('scale_y', '<f8'),
+                          ('src_h', '<i4'), ('src_w', '<i4'), ('new_h', '<i4'), ('new_w', '<i4'),
+                          ('pad_h', '<i4'), ('pad_w', '<i4'), ('flip', '<i4'), ('first_block', '<i4')])
+PRE_TILE_H, PRE_TILE_W = 64, 128        # csrc/preprocess_batch.hip (brcnn_preprocess_u8_batch_blocks)
+PRE_MAX_JOBS = 4096
+
+
+def preprocess_blocks(pad_h, pad_w):
+    """workgroups one (pad_h, pad_w) image takes in the batched launch (brcnn_preprocess_u8_batch_blocks)"""
+    return -(-int(pad_h) // PRE_TILE_H) * -(-int(pad_w) // PRE_TILE_W)
+
+
+def preprocess_u8_batch(src, jobs_dev, jobs_host, dst, mean, std, to_rgb=True):
+    """Resize -> flip -> Normalize -> Pad of a whole (augs x images) batch in ONE launch.  `src` 1-D uint8 device
+    tensor holding the source images back to back, `jobs_dev` the device copy (uint8 view or any tensor at the
+    table's address) of `jobs_host`, a PRE_JOB_DTYPE array with one row per (aug, image); `dst` 1-D fp32 device
+    tensor every job writes its (3, pad_h, pad_w) image into at `dst_off`.  The rows are validated on `jobs_host`
+    before anything is queued."""
+    import ctypes
+    _require_gpu(src, jobs_dev, dst)
+    assert src.dtype == torch.uint8 and src.dim() == 1 and src.is_contiguous()
+    assert dst.dtype == torch.float32 and dst.dim() == 1 and dst.is_contiguous()
+    assert isinstance(jobs_host, np.ndarray) and jobs_host.dtype == PRE_JOB_DTYPE and jobs_host.ndim == 1 and \
+        jobs_host.flags['C_CONTIGUOUS']
+    assert jobs_dev.is_contiguous() and jobs_dev.numel() * jobs_dev.element_size() >= jobs_host.nbytes
+    m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+    st = _L.load().brcnn_preprocess_u8_batch(_ptr(src), src.numel(), _ptr(jobs_dev), jobs_host.ctypes.data,
+                                             len(jobs_host), _ptr(dst), dst.numel(), m3, s3, int(bool(to_rgb)),
+                                             _stream())
+    _L.check(st, 'brcnn_preprocess_u8_batch')
+    return dst
+
+
 # --------------------------------------------------------------------------- Res2Net / DCNv2
 def avgpool_out_size(size, kernel, stride, pad, ceil_mode):
     if ceil_mode:

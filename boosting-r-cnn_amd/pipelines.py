@@ -225,6 +225,23 @@ class LoadImageFromFile:
 
 
 @PIPELINES.register_module()
+class LoadImageFromWebcam(LoadImageFromFile):
+    """loading.py:188-201: the image is already an array in results['img']"""
+
+    def __call__(self, results):
+        img = results['img']
+        if self.to_float32:
+            img = img.astype(np.float32)
+        results['filename'] = None
+        results['ori_filename'] = None
+        results['img'] = img
+        results['img_shape'] = img.shape
+        results['ori_shape'] = img.shape
+        results['img_fields'] = ['img']
+        return results
+
+
+@PIPELINES.register_module()
 class LoadAnnotations:
     """loading.py:204-390, bbox / label part (masks and seg maps are outside the path)"""
 
@@ -829,3 +846,274 @@ def fuse_device_pipeline(pipeline_cfg, device='cuda'):
         out.append(c)
         i += 1
     return out
+
+
+# --------------------------------------------------------------------------- batched front door
+_META_KEYS = ('filename', 'ori_filename', 'ori_shape', 'img_shape', 'pad_shape', 'scale_factor', 'flip',
+              'flip_direction', 'img_norm_cfg')
+_FLIP_CODE = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}
+
+
+class BatchPlan:
+    """what `BatchFrontDoor.plan_batch` derives from the B source shapes (host arithmetic only):
+    jobs         ops.PRE_JOB_DTYPE[A * B], row a * B + b = (aug a, image b)
+    src_offsets  byte offset of every source image in the pixel region; src_bytes its size
+    aug_shapes   per aug the (B, 3, PH, PW) of its tensor; aug_offsets its first element in the destination
+                 buffer of dst_elems floats
+    img_metas    per aug a list of B dicts, the host chain's keys and values
+    table_bytes + src_bytes = block_bytes: the staging block is [job table | pixels]"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _Slot:
+    def __init__(self):
+        self.pinned = self.host = self.dev = self.event = None
+
+
+class BatchFrontDoor:
+    """The test pipeline `[LoadImageFromFile | LoadImageFromWebcam, MultiScaleFlipAug([Resize, RandomFlip, Normalize,
+    Pad, ImageToTensor | DefaultFormatBundle, Collect])]` for a whole batch of decoded uint8 BGR images as ONE
+    host-to-device copy and ONE launch (`brcnn_preprocess_u8_batch`): the pixels of the B images and the job table of
+    the A x B (aug, image) pairs go into one pinned staging block, and the launch writes, per aug, the zero-padded
+    `(B, 3, PH, PW)` tensor `collate` would have stacked.  `__call__` returns `dict(img=[A tensors], img_metas=[A
+    lists of B dicts])`, the arguments of `model(return_loss=False, rescale=True, **data)`, bit-identical to the host
+    chain `Compose` + `collate`.
+
+    Staging blocks (pinned host + device) belong to the object, grow geometrically and rotate; a block is rewritten
+    only after the event recorded behind the launch that read it has completed.  `acquire` / `stage` touch host memory
+    only and may run on a worker thread; `submit` queues the copy and the launch on the current (or given) stream."""
+
+    def __init__(self, pipeline_cfg, device='cuda', slots=2):
+        plan = self.parse(pipeline_cfg)
+        if plan is None:
+            raise ValueError('BatchFrontDoor: the pipeline is not of the supported test-pipeline form')
+        self.__dict__.update(plan)
+        self.device = torch.device(device)
+        import queue
+        self._free = queue.Queue()
+        self._slots = []
+        self.ensure_slots(slots)
+
+    # ---- the pipeline config -> a plan ---------------------------------------------------------------------------
+    @staticmethod
+    def parse(pipeline_cfg):
+        """dict(augs, keep_ratio, size, size_divisor, mean, std, to_rgb, meta_keys) or None when the pipeline holds
+        anything this door does not reproduce exactly"""
+        try:
+            cfgs = [dict(c) for c in pipeline_cfg]
+        except Exception:
+            return None
+        if len(cfgs) != 2 or cfgs[0].get('type') not in ('LoadImageFromFile', 'LoadImageFromWebcam') or \
+                cfgs[1].get('type') != 'MultiScaleFlipAug':
+            return None
+        load = cfgs[0]
+        if load.get('to_float32', False) or load.get('color_type', 'color') != 'color' or \
+                set(load) - {'type', 'to_float32', 'color_type', 'file_client_args'}:
+            return None
+        msfa = cfgs[1]
+        if set(msfa) - {'type', 'transforms', 'img_scale', 'scale_factor', 'flip', 'flip_direction'}:
+            return None
+        ts = [dict(t) for t in msfa.get('transforms', [])]
+        types = [t.get('type') for t in ts]
+        if types[:4] != ['Resize', 'RandomFlip', 'Normalize', 'Pad'] or len(types) != 6 or \
+                types[4] not in ('ImageToTensor', 'DefaultFormatBundle') or types[5] != 'Collect':
+            return None
+        resize, flip, norm, pad, fmt, collect = ts
+        # MultiScaleFlipAug fixes scale and flip, so Resize / RandomFlip's own random arguments are never drawn
+        if set(resize) - {'type', 'keep_ratio', 'img_scale', 'multiscale_mode', 'bbox_clip_border', 'backend'} or \
+                resize.get('backend', 'cv2') != 'cv2':
+            return None
+        if set(flip) - {'type', 'flip_ratio', 'direction'}:
+            return None
+        if set(norm) - {'type', 'mean', 'std', 'to_rgb'} or 'mean' not in norm or 'std' not in norm or \
+                len(norm['mean']) != 3 or len(norm['std']) != 3 or any(float(s) == 0 for s in norm['std']):
+            return None
+        if set(pad) - {'type', 'size', 'size_divisor', 'pad_val'} or pad.get('pad_val', 0) != 0 or \
+                (pad.get('size') is None) == (pad.get('size_divisor') is None):
+            return None
+        if types[4] == 'ImageToTensor' and list(fmt.get('keys', [])) != ['img']:
+            return None
+        if set(fmt) - {'type', 'keys'} or set(collect) - {'type', 'keys', 'meta_keys'} or \
+                list(collect.get('keys', [])) != ['img']:
+            return None
+        meta_keys = tuple(collect.get('meta_keys', _META_KEYS))
+        if set(meta_keys) - set(_META_KEYS):
+            return None
+        if (msfa.get('img_scale') is None) == (msfa.get('scale_factor') is None):
+            return None
+        if msfa.get('img_scale') is not None:
+            s = msfa['img_scale']
+            scales = [tuple(int(v) for v in x) for x in (s if isinstance(s, list) else [s])]
+            key = 'scale'
+            if any(len(x) != 2 for x in scales):
+                return None
+        else:
+            s = msfa['scale_factor']
+            scales = list(s) if isinstance(s, list) else [s]
+            key = 'scale_factor'
+            if not all(isinstance(x, float) and x > 0 for x in scales):      # (Resize asserts a float here)
+                return None
+        directions = msfa.get('flip_direction', 'horizontal')
+        directions = list(directions) if isinstance(directions, (list, tuple)) else [directions]
+        if any(d not in ('horizontal', 'vertical', 'diagonal') for d in directions):
+            return None
+        flips = [(False, None)] + ([(True, d) for d in directions] if msfa.get('flip', False) else [])
+        augs = [(key, sc, f, d) for sc in scales for f, d in flips]         # MultiScaleFlipAug's own order
+        if not augs or len(augs) > 16:
+            return None
+        size = pad.get('size')
+        return dict(augs=augs, keep_ratio=bool(resize.get('keep_ratio', True)),
+                    size=None if size is None else (int(size[0]), int(size[1])), size_divisor=pad.get('size_divisor'),
+                    mean=np.array(norm['mean'], dtype=np.float32), std=np.array(norm['std'], dtype=np.float32),
+                    to_rgb=norm.get('to_rgb', True), meta_keys=meta_keys)
+
+    @classmethod
+    def supported(cls, cfg):
+        """`cfg`: a Config (its `data.test.pipeline`) or a pipeline list"""
+        pipe = cfg
+        if not isinstance(cfg, (list, tuple)):
+            try:
+                pipe = cfg.data.test.pipeline
+            except Exception:
+                return False
+        return cls.parse(pipe) is not None
+
+    @staticmethod
+    def accepts(images):
+        """decoded inputs this door takes: uint8 H x W x 3 arrays (paths decode to that)"""
+        return all(isinstance(i, str) or (isinstance(i, np.ndarray) and i.dtype == np.uint8 and i.ndim == 3 and
+                                          i.shape[2] == 3 and i.shape[0] > 0 and i.shape[1] > 0) for i in images)
+
+    # ---- shapes -> job table, batch shapes, metas ------------------------------------------------------------
+    def plan_batch(self, shapes, filenames=None):
+        from .ops import PRE_JOB_DTYPE, PRE_MAX_JOBS, preprocess_blocks
+        shapes = [(int(s[0]), int(s[1])) for s in shapes]
+        B, A = len(shapes), len(self.augs)
+        if B == 0 or A * B > PRE_MAX_JOBS:
+            raise ValueError(f'BatchFrontDoor: {B} images x {A} augs: between 1 and {PRE_MAX_JOBS} jobs per launch')
+        filenames = list(filenames) if filenames is not None else [None] * B
+        src_offsets, n = [], 0
+        for h, w in shapes:
+            if h <= 0 or w <= 0:
+                raise ValueError(f'BatchFrontDoor: empty image {h}x{w}')
+            src_offsets.append(n)
+            n += h * w * 3
+        jobs = np.zeros(A * B, dtype=PRE_JOB_DTYPE)
+        aug_shapes, aug_offsets, img_metas, elems, blocks = [], [], [], 0, 0
+        for a, (key, scale, flip, direction) in enumerate(self.augs):
+            new, own = [], []
+            for h, w in shapes:
+                sc = scale if key == 'scale' else (int(w * scale), int(h * scale))       # Resize._pick_scale
+                nw, nh = rescale_size((w, h), sc) if self.keep_ratio else (int(sc[0]), int(sc[1]))
+                if nw <= 0 or nh <= 0:
+                    raise ValueError(f'BatchFrontDoor: a {h}x{w} image resizes to {nh}x{nw} under {key}={scale}')
+                if self.size is not None:
+                    ph, pw = self.size
+                    if ph < nh or pw < nw:
+                        raise ValueError(f'BatchFrontDoor: Pad(size={self.size}) is smaller than a resized image '
+                                         f'({nh}, {nw})')
+                else:
+                    d = self.size_divisor
+                    ph, pw = int(np.ceil(nh / d)) * d, int(np.ceil(nw / d)) * d
+                new.append((nh, nw))
+                own.append((ph, pw))
+            PH, PW = max(p[0] for p in own), max(p[1] for p in own)        # what collate pads the stack to
+            elems = -(-elems // 4) * 4                                    # 16-byte aligned start of every aug
+            aug_shapes.append((B, 3, PH, PW))
+            aug_offsets.append(elems)
+            metas = []
+            for b, ((h, w), (nh, nw), (ph, pw)) in enumerate(zip(shapes, new, own)):
+                j = jobs[a * B + b]
+                j['src_off'], j['dst_off'] = src_offsets[b], elems + b * 3 * PH * PW
+                j['scale_x'], j['scale_y'] = 1.0 / (float(nw) / float(w)), 1.0 / (float(nh) / float(h))
+                j['src_h'], j['src_w'], j['new_h'], j['new_w'], j['pad_h'], j['pad_w'] = h, w, nh, nw, PH, PW
+                j['flip'], j['first_block'] = _FLIP_CODE[direction if flip else None], blocks
+                blocks += preprocess_blocks(PH, PW)
+                full = dict(filename=filenames[b], ori_filename=filenames[b], ori_shape=(h, w, 3), img_shape=(nh, nw, 3),
+                            pad_shape=(ph, pw, 3),
+                            scale_factor=np.array([nw / w, nh / h, nw / w, nh / h], dtype=np.float32), flip=flip,
+                            flip_direction=direction,
+                            img_norm_cfg=dict(mean=self.mean, std=self.std, to_rgb=self.to_rgb))
+                metas.append({k: full[k] for k in self.meta_keys})
+            img_metas.append(metas)
+            elems += B * 3 * PH * PW
+        if blocks >= 2 ** 31:
+            raise ValueError('BatchFrontDoor: the batch needs more workgroups than one launch holds')
+        return BatchPlan(jobs=jobs, src_offsets=src_offsets, src_bytes=n, table_bytes=jobs.nbytes,
+                         block_bytes=jobs.nbytes + n, aug_shapes=aug_shapes, aug_offsets=aug_offsets, dst_elems=elems,
+                         img_metas=img_metas, num_blocks=blocks, shapes=shapes)
+
+    # ---- staging blocks ----------------------------------------------------------------------------------------
+    def ensure_slots(self, n):
+        while len(self._slots) < n:
+            s = _Slot()
+            self._slots.append(s)
+            self._free.put(s)
+
+    def acquire(self):
+        """the least recently used staging block, once the launch that last read it has completed"""
+        slot = self._free.get()
+        if slot.event is not None:
+            if not slot.event.query():
+                slot.event.synchronize()
+            slot.event = None
+        return slot
+
+    def release(self, slot):
+        self._free.put(slot)
+
+    @staticmethod
+    def decode(images):
+        """-> (arrays, filenames): paths are read with `imread`, arrays pass"""
+        arrays, names = [], []
+        for i in images:
+            if isinstance(i, str):
+                arrays.append(imread(i))
+                names.append(i)
+            else:
+                arrays.append(i)
+                names.append(None)
+        if not BatchFrontDoor.accepts(arrays):
+            raise TypeError('BatchFrontDoor takes uint8 H x W x 3 images')
+        return arrays, names
+
+    def stage(self, slot, arrays, filenames=None):
+        """plan the batch and fill `slot`'s pinned block with [job table | pixels]; host work only"""
+        plan = self.plan_batch([a.shape for a in arrays], filenames)
+        if slot.pinned is None or slot.pinned.numel() < plan.block_bytes:
+            cap = max(plan.block_bytes, 2 * (slot.pinned.numel() if slot.pinned is not None else 0), 1 << 16)
+            slot.pinned = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
+            slot.host = slot.pinned.numpy()
+            slot.dev = torch.empty(cap, dtype=torch.uint8, device=self.device)
+        slot.host[:plan.table_bytes].view(plan.jobs.dtype)[:] = plan.jobs
+        for off, a in zip(plan.src_offsets, arrays):
+            o = plan.table_bytes + off
+            slot.host[o:o + a.size].reshape(a.shape)[...] = a
+        return plan
+
+    def submit(self, slot, plan, stream=None):
+        """ONE copy and ONE launch on `stream` (default: the current stream); records the slot's fence"""
+        from . import ops
+        import contextlib
+        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+            n = plan.block_bytes
+            slot.dev[:n].copy_(slot.pinned[:n], non_blocking=True)
+            dst = torch.empty(plan.dst_elems, dtype=torch.float32, device=self.device)
+            ops.preprocess_u8_batch(slot.dev[plan.table_bytes:n], slot.dev,
+                                    slot.host[:plan.table_bytes].view(plan.jobs.dtype), dst, self.mean, self.std,
+                                    self.to_rgb)
+            slot.event = torch.cuda.Event()
+            slot.event.record()
+        imgs = [dst[o:o + s[0] * s[1] * s[2] * s[3]].view(s) for o, s in zip(plan.aug_offsets, plan.aug_shapes)]
+        return dict(img=imgs, img_metas=plan.img_metas)
+
+    def __call__(self, images, stream=None):
+        arrays, names = self.decode(images)
+        slot = self.acquire()
+        try:
+            plan = self.stage(slot, arrays, names)
+            return self.submit(slot, plan, stream)
+        finally:
+            self.release(slot)

@@ -766,6 +766,39 @@ int brcnn_preprocess_u8(const uint8_t *src, int src_h, int src_w, float *dst, in
                         const float *std3_host, int to_rgb, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Batched input front door: the same transform chain for a whole (augmentations x images) batch
+ * in ONE launch (test pipelines: MultiScaleFlipAug over a batch of decoded images).
+ *   src       ONE device buffer of src_bytes bytes: the source images back to back, each
+ *             (src_h, src_w, 3) uint8 BGR dense, ragged sizes; uploaded once whatever the number of augs
+ *   jobs_dev  device copy of the job table, one row per (aug a, image b), 8-byte aligned
+ *   jobs_host the host copy of the same num_jobs rows (<= BRCNN_PRE_MAX_JOBS): every row is
+ *             validated on it before anything is queued (sizes, flip, both blocks' bounds, the
+ *             scales, first_block), and the grid is sized from it -- the kernel trusts the table
+ *   dst       device buffer of dst_elems floats, 16-byte aligned; job (a, b) writes EVERY element of
+ *             the (3, pad_h, pad_w) fp32 CHW image at dst + dst_off: pixels, then zeros -- with
+ *             dst_off = off_a + b * 3 * pad_h * pad_w and (pad_h, pad_w) the aug's batch shape, aug a's
+ *             rows form one contiguous (B, 3, pad_h, pad_w) tensor
+ *   a row:    src_off (bytes into src), dst_off (floats into dst), scale_x = 1.0 / ((double)new_w /
+ *             (double)src_w) and scale_y likewise (exactly these doubles, as brcnn_preprocess_u8
+ *             computes them), src_h, src_w, new_h, new_w, pad_h, pad_w, flip (0-3 as above), and
+ *             first_block = the sum of brcnn_preprocess_u8_batch_blocks(pad_h, pad_w) of the rows before it
+ *   mean / std / to_rgb as above, per launch.  16-byte stores where pad_w % 4 == 0 and dst_off % 4 == 0,
+ *   4-byte stores otherwise.  Every image equals brcnn_preprocess_u8's bit for bit.
+ * -------------------------------------------------------------------------- */
+#define BRCNN_PRE_MAX_JOBS 4096
+typedef struct brcnn_pre_job {
+    int64_t src_off, dst_off;
+    double scale_x, scale_y;
+    int32_t src_h, src_w, new_h, new_w, pad_h, pad_w, flip, first_block;
+} brcnn_pre_job;                                   /* 64 bytes */
+
+int64_t brcnn_preprocess_u8_batch_blocks(int pad_h, int pad_w);
+int brcnn_preprocess_u8_batch(const uint8_t *src, size_t src_bytes, const brcnn_pre_job *jobs_dev,
+                              const brcnn_pre_job *jobs_host, int num_jobs, float *dst,
+                              size_t dst_elems, const float *mean3_host, const float *std3_host,
+                              int to_rgb, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Train step: whole-batch target assignment, RoI sampling and the fused losses.
  * The reference runs these per image / per level as chains of small torch ops with host
  * synchronisations (nonzero / unique / .item()); each entry below serves the whole batch.
