@@ -315,10 +315,14 @@ class CocoDataset(CustomDataset):
         return self.results2json(results, jsonfile_prefix), tmp_dir
 
     def evaluate(self, results, metric='bbox', logger=None, jsonfile_prefix=None, classwise=False,
-                 proposal_nums=(100, 300, 1000), iou_thrs=None, metric_items=None):
+                 proposal_nums=(100, 300, 1000), iou_thrs=None, metric_items=None, backend='host'):
         """coco.py:362-560: 'bbox' (COCO mAP), 'proposal' (class-agnostic AR: useCats = 0) through this repo's COCOeval
-        restatement, 'proposal_fast' (eval_recalls on per-image proposals).  'segm' needs masks: outside the hot path."""
+        restatement, 'proposal_fast' (eval_recalls on per-image proposals).  'segm' needs masks: outside the hot path.
+        backend 'host' (COCOeval) or 'device' (DeviceCOCOeval: the same numbers from the HIP evaluator; 'proposal_fast'
+        keeps its host path)"""
         from .evaluation import COCOeval
+        if backend not in ('host', 'device'):
+            raise ValueError(f"backend {backend!r} is not supported ('host' or 'device')")
         metrics = metric if isinstance(metric, list) else [metric]
         for m in metrics:
             if m not in ('bbox', 'proposal', 'proposal_fast'):
@@ -336,15 +340,37 @@ class CocoDataset(CustomDataset):
                 if logger is not None:
                     logger.info(''.join(f'\nAR@{num}\t{ar[i]:.4f}' for i, num in enumerate(proposal_nums)))
                 continue
-            part = self._evaluate_coco(results, m, logger, jsonfile_prefix, classwise, proposal_nums, iou_thrs, metric_items)
+            part = self._evaluate_coco(results, m, logger, jsonfile_prefix, classwise, proposal_nums, iou_thrs, metric_items,
+                                       backend)
             if part is None:
                 break
             eval_results.update(part)
         return eval_results
 
-    def _evaluate_coco(self, results, metric, logger, jsonfile_prefix, classwise, proposal_nums, iou_thrs, metric_items):
+    def _evaluate_coco_device(self, results, metric, logger, jsonfile_prefix):
+        """the head of `_evaluate_coco` for backend='device': the same checks in the same order, no dict per detection
+        (the json file, when asked for, still goes through `_det2json`); the evaluator, or None when there is nothing"""
+        from .evaluation import DeviceCOCOeval
+        per_class = isinstance(results[0], list)
+        if jsonfile_prefix is not None:
+            with open(f"{jsonfile_prefix}.{'bbox' if per_class else 'proposal'}.json", 'w') as f:
+                json.dump(self._det2json(results) if per_class else self._proposal2json(results), f)
+        if metric == 'bbox' and not per_class:
+            raise KeyError('bbox is not in results')
+        if sum(len(b) for r in results for b in (r if per_class else [r])) == 0:
+            if logger is not None:
+                logger.error('The testing results of the whole dataset is empty.')
+            return None
+        return DeviceCOCOeval(self.coco, results, img_ids=self.img_ids, cat_ids=self.cat_ids)
+
+    def _evaluate_coco(self, results, metric, logger, jsonfile_prefix, classwise, proposal_nums, iou_thrs, metric_items,
+                       backend='host'):
         from .evaluation import COCOeval
-        eval_results = {}
+        if backend == 'device':
+            ev = self._evaluate_coco_device(results, metric, logger, jsonfile_prefix)
+            if ev is None:
+                return None
+            return self._evaluate_coco_tail(ev, metric, logger, classwise, proposal_nums, iou_thrs, metric_items)
         dets = self._det2json(results) if isinstance(results[0], list) else self._proposal2json(results)
         if jsonfile_prefix is not None:
             kind = 'bbox' if isinstance(results[0], list) else 'proposal'
@@ -358,6 +384,10 @@ class CocoDataset(CustomDataset):
             return None
         coco_dt = self.coco.loadRes(dets)
         ev = COCOeval(self.coco, coco_dt, 'bbox')
+        return self._evaluate_coco_tail(ev, metric, logger, classwise, proposal_nums, iou_thrs, metric_items)
+
+    def _evaluate_coco_tail(self, ev, metric, logger, classwise, proposal_nums, iou_thrs, metric_items):
+        eval_results = {}
         ev.params.catIds = self.cat_ids
         ev.params.imgIds = self.img_ids
         ev.params.maxDets = list(proposal_nums)

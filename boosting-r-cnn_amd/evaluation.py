@@ -440,3 +440,243 @@ def eval_recalls(gts, proposals, proposal_nums=None, iou_thrs=0.5, logger=None, 
         rows += [f'{int(n):9d} | ' + ' '.join(f'{v:.3f}' for v in recalls[k]) for k, n in enumerate(nums)]
         logger.info('\n' + '\n'.join(rows))
     return recalls
+
+
+# ------------------------------------------------------------------------------------------
+# The device back end of COCOeval (csrc/coco_eval.hip: match, order, accumulate).  The host side below is packing only,
+# vectorised numpy: one pass over the ground-truth annotations (cached), none over the detections.
+# ------------------------------------------------------------------------------------------
+MAX_GT_PER_PAIR = 1024      # csrc/coco_eval.hip: CE_MAX_GT
+MAX_REC_THRS = 1024         # csrc/coco_eval.hip: CE_MAX_REC
+
+
+def _eval_ids(img_ids, cat_ids, use_cats):
+    """the image / category axes as COCOeval.evaluate fixes them: sorted unique image ids; categories sorted unique, or
+    (pooled: useCats == 0) in the order given -- the order `_of` pools a pair's boxes in"""
+    img_ids = np.unique(np.asarray(img_ids, dtype=np.int64))
+    cats = np.asarray(cat_ids, dtype=np.int64)
+    if use_cats:
+        cats = np.unique(cats)
+    elif len(np.unique(cats)) != len(cats):
+        raise ValueError('catIds must not repeat a category')
+    return img_ids, cats
+
+
+def _cat_slots(cats, ids):
+    """position of every id of `ids` in `cats` (any order), -1 where absent"""
+    ids = np.asarray(ids, dtype=np.int64)
+    if len(cats) == 0:
+        return np.full(ids.shape, -1, np.int64)
+    by = np.argsort(cats, kind='stable')
+    at = np.minimum(np.searchsorted(cats[by], ids), len(cats) - 1)
+    return np.where(cats[by][at] == ids, by[at], -1)
+
+
+def pack_ground_truth(cocoGt, img_ids, cat_ids, use_cats=1):
+    """The ground truths of (img_ids x cat_ids) as a pair-major table.  pair = category slot * I + image slot (image slot
+    alone when categories are pooled); inside a pair the order COCOeval sees: annotation order (pooled: category order
+    first).  Returns dict(img_ids, cat_ids, num_cats, box (G, 4) fp64 xywh, area (G,) fp64, flags (G,) uint8 [bit 0
+    iscrowd, bit 1 id != 0], ids (G,) int64, off (P + 1,) int32)."""
+    img_ids, cats = _eval_ids(img_ids, cat_ids, use_cats)
+    slot = {c: n for n, c in enumerate(cats.tolist())}
+    rows = [(ii, slot[a['category_id']], a) for ii, i in enumerate(img_ids.tolist())
+            for a in cocoGt.imgToAnns.get(i, ()) if a['category_id'] in slot]
+    G, I = len(rows), len(img_ids)
+    K = len(cats) if use_cats else 1
+    ii = np.fromiter((r[0] for r in rows), np.int64, G)
+    cs = np.fromiter((r[1] for r in rows), np.int64, G)
+    box = np.array([r[2]['bbox'] for r in rows], dtype=np.float64).reshape(G, 4)
+    area = np.array([r[2]['area'] for r in rows], dtype=np.float64).reshape(G)
+    flags = np.fromiter(((1 if r[2].get('iscrowd', 0) else 0) | (2 if r[2]['id'] else 0) for r in rows), np.uint8, G)
+    ids = np.fromiter((r[2]['id'] for r in rows), np.int64, G)
+    pair = cs * I + ii if use_cats else ii
+    by = np.lexsort((cs, pair))             # stable: annotation order inside (pair, category)
+    off = np.zeros(K * I + 1, np.int64)
+    np.cumsum(np.bincount(pair, minlength=K * I), out=off[1:])
+    return dict(img_ids=img_ids, cat_ids=cats, num_cats=K, use_cats=int(bool(use_cats)), box=np.ascontiguousarray(box[by]),
+                area=area[by], flags=flags[by], ids=ids[by], off=off.astype(np.int32))
+
+
+def pack_detections(results, result_img_ids, label_cat_ids, img_ids, cat_ids, use_cats, max_det):
+    """`results` (per image a list of per-class (k, 5) float32 arrays, or one (k, 5) array of proposals = category 1) as
+    the pair-major table of the device evaluator: inside a pair by descending score, ties in the order COCOeval's stable
+    sort leaves them (pooled: category order, then row; else row), cut to `max_det`.  `img_ids` / `cat_ids` are the axes
+    of `_eval_ids`.  No Python object per detection: every step is one numpy call over all of them.
+    Returns dict(det (D, 5) float32 xyxy + score, off (P + 1,) int32, src (D,) int64 row in the concatenated results,
+    num_results) -- num_results counts the detections before any is dropped."""
+    I = len(img_ids)
+    K = len(cat_ids) if use_cats else 1
+    if len(results) and isinstance(results[0], (list, tuple)):
+        L = len(results[0])
+        flat = [b for r in results for b in r]
+        label_cat_ids = np.asarray(label_cat_ids, dtype=np.int64)
+        assert len(label_cat_ids) == L and len(flat) == L * len(results), 'one array per class and image'
+    else:
+        L, flat, label_cat_ids = 1, list(results), np.array([1], dtype=np.int64)
+    counts = np.fromiter(map(len, flat), np.int64, len(flat))
+    N = int(counts.sum())
+    empty = dict(det=np.zeros((0, 5), np.float32), off=np.zeros(K * I + 1, np.int32), src=np.zeros(0, np.int64), num_results=N)
+    if N == 0:
+        return empty
+    allv = np.concatenate([b for b in flat if len(b)] if N < len(flat) else flat)
+    if allv.dtype != np.float32 or allv.ndim != 2 or allv.shape[1] != 5:
+        raise TypeError(f'detections must be (k, 5) float32 arrays (got {allv.dtype}, shape {allv.shape})')
+    # per slot (image of the results, label): image slot, category slot, whether the evaluation covers it
+    res_ids = np.asarray(result_img_ids, dtype=np.int64)
+    assert len(res_ids) == len(results), 'one image id per result'
+    at = np.minimum(np.searchsorted(img_ids, res_ids), max(I - 1, 0))
+    img_slot = np.where(img_ids[at] == res_ids, at, -1) if I else np.full(len(res_ids), -1)
+    cat_slot = _cat_slots(np.asarray(cat_ids, dtype=np.int64), label_cat_ids)
+    s_img, s_cat = np.repeat(img_slot, L), np.tile(cat_slot, len(results))
+    s_ok = (s_img >= 0) & (s_cat >= 0)
+    s_pair = s_cat * I + s_img if use_cats else s_img
+    ok = np.repeat(s_ok, counts)
+    src = np.flatnonzero(ok)
+    if len(src) == 0:
+        return empty
+    pair, cs = np.repeat(s_pair, counts)[src], np.repeat(s_cat, counts)[src]
+    neg = -allv[src, 4]
+    by = np.lexsort((neg, pair)) if use_cats else np.lexsort((cs, neg, pair))       # (stable)
+    n_pair = np.bincount(pair, minlength=K * I)
+    start = np.zeros(K * I + 1, np.int64)
+    np.cumsum(n_pair, out=start[1:])
+    pair = pair[by]
+    keep = (np.arange(len(by)) - start[pair]) < max_det
+    by = by[keep]
+    off = np.zeros(K * I + 1, np.int64)
+    np.cumsum(np.minimum(n_pair, max_det), out=off[1:])
+    return dict(det=np.ascontiguousarray(allv[src[by]]), off=off.astype(np.int32), src=src[by], num_results=N)
+
+
+class DeviceCOCOeval(COCOeval):
+    """COCOeval with `evaluate` / `accumulate` on the HIP device; `summarize`, `stats`, `eval[...]` are the host class's.
+    `results` is what the detectors return (see `pack_detections`); `img_ids[i]` is the image of `results[i]` and
+    `cat_ids[l]` the category of label l (defaults: the ground truth's own lists, as CocoDataset uses them).  There are
+    no `evalImgs`; `match_records()` gives the same information as flat arrays.  No CPU fallback."""
+
+    def __init__(self, cocoGt, results, img_ids=None, cat_ids=None, device=None, profile=False):
+        import torch
+        from .lib import BrcnnHipError
+        if not torch.cuda.is_available():
+            raise BrcnnHipError('DeviceCOCOeval runs on the HIP device only (none is visible); there is no CPU fallback: '
+                                "use COCOeval / backend='host'")
+        self.cocoGt, self.cocoDt, self.results = cocoGt, None, results
+        self.result_img_ids = list(cocoGt.get_img_ids()) if img_ids is None else list(img_ids)
+        self.label_cat_ids = list(cocoGt.get_cat_ids()) if cat_ids is None else list(cat_ids)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.params = Params()
+        self.params.imgIds = sorted(cocoGt.get_img_ids())
+        self.params.catIds = sorted(cocoGt.get_cat_ids())
+        self.evalImgs, self.eval, self.stats = [], {}, []
+        self.profile, self.kernel_ms, self._events = profile, {}, []
+        self._run = None
+
+    # ---- the cached ground-truth table --------------------------------------------------
+    def _ground_truth(self):
+        import torch
+        p = self.params
+        cache = self.cocoGt.__dict__.setdefault('_device_eval_tables', {})
+        key = (tuple(int(i) for i in p.imgIds), tuple(int(c) for c in p.catIds), int(bool(p.useCats)), str(self.device))
+        if key not in cache:
+            host = pack_ground_truth(self.cocoGt, p.imgIds, p.catIds, p.useCats)
+            per_pair = np.diff(host['off'])
+            if len(per_pair) and per_pair.max() > MAX_GT_PER_PAIR:
+                raise ValueError(f'{per_pair.max()} ground truths in one (image, category) pair: the device evaluator '
+                                 f'holds at most {MAX_GT_PER_PAIR}')
+            f64 = np.concatenate([host['box'].reshape(-1), host['area']])
+            dev = dict(f64=torch.from_numpy(f64).to(self.device), flags=torch.from_numpy(host['flags']).to(self.device),
+                       off=torch.from_numpy(host['off']).to(self.device))
+            cache[key] = dict(host=host, dev=dev, max_gt=int(per_pair.max()) if len(per_pair) else 0)
+        return cache[key]
+
+    def _mark(self, name):
+        import torch
+        if self.profile:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self._events.append((name, e))
+
+    def evaluate(self):
+        import torch
+        from . import ops
+        p = self.params
+        p.imgIds = list(np.unique(p.imgIds))
+        if p.useCats:
+            p.catIds = list(np.unique(p.catIds))
+        p.maxDets = sorted(p.maxDets)
+        iou = np.ascontiguousarray(p.iouThrs, dtype=np.float64).reshape(-1)
+        rec = np.ascontiguousarray(p.recThrs, dtype=np.float64).reshape(-1)
+        area = np.ascontiguousarray(p.areaRng, dtype=np.float64).reshape(-1, 2)
+        mdets = np.asarray(p.maxDets, dtype=np.int32).reshape(-1)
+        T, R, A, M = len(iou), len(rec), len(area), len(mdets)
+        if not (1 <= T <= 16 and 1 <= A <= 8 and T * A <= 64 and 1 <= R <= MAX_REC_THRS and M >= 1):
+            raise ValueError(f'device evaluator: {T} IoU thresholds (1..16), {A} area ranges (T * A <= 64), {R} recall '
+                             f'points (1..{MAX_REC_THRS})')
+        if np.any(np.diff(rec) < 0):
+            raise ValueError('recThrs must be ascending')
+        gt = self._ground_truth()
+        host = gt['host']
+        I, K = len(host['img_ids']), host['num_cats']
+        if I == 0 or (p.useCats and len(host['cat_ids']) == 0):
+            raise ValueError('nothing to evaluate: no image or no category')
+        dt = pack_detections(self.results, self.result_img_ids, self.label_cat_ids, host['img_ids'], host['cat_ids'],
+                             p.useCats, int(mdets[-1]))
+        D, G = len(dt['det']), len(host['area'])
+        assert dt['off'][-1] == D and np.all(np.diff(dt['off']) >= 0) and host['off'][-1] == G
+        # one upload: thresholds, recall points, area ranges | maxDets, detection offsets | detections
+        head = np.concatenate([iou, rec, area.reshape(-1)])
+        ints = np.concatenate([mdets, dt['off']])
+        ints = np.concatenate([ints, np.zeros(len(ints) % 2, np.int32)])
+        blob = np.concatenate([head.view(np.uint8), ints.view(np.uint8), dt['det'].reshape(-1).view(np.uint8)])
+        with torch.cuda.device(self.device):
+            self._events = []
+            self._mark('start')
+            buf = torch.from_numpy(blob).pin_memory().to(self.device, non_blocking=True)
+            nh, ni = head.size * 8, ints.size * 4
+            f64, i32 = buf[:nh].view(torch.float64), buf[nh:nh + ni].view(torch.int32)
+            det = buf[nh + ni:].view(torch.float32).view(-1, 5)
+            d_iou, d_rec, d_area = f64[:T], f64[T:T + R], f64[T + R:]
+            d_mdets, d_off = i32[:M], i32[M:M + K * I + 1]
+            g = gt['dev']
+            self._mark('upload')
+            dtm, dtig, gtig, num_gt, rank, key = ops.coco_match(g['f64'][:4 * G], g['f64'][4 * G:], g['flags'], g['off'], det, d_off,
+                                                                K, I, d_iou, d_area, gt['max_gt'])
+            self._mark('match')
+            order = ops.coco_order(key, K)
+            self._mark('order')
+        self._run = dict(T=T, R=R, K=K, A=A, M=M, I=I, det=det, off=d_off, rec=d_rec, mdets=d_mdets, dtm=dtm, dtig=dtig, gtig=gtig,
+                         num_gt=num_gt, rank=rank, order=order, packed=dt, gt=gt, buf=buf)
+
+    def accumulate(self):
+        import torch
+        from . import ops
+        r = self._run
+        if r is None:
+            raise Exception('Please run evaluate() first')
+        T, R, K, A, M = r['T'], r['R'], r['K'], r['A'], r['M']
+        with torch.cuda.device(self.device):
+            out = torch.empty(2 * T * R * K * A * M + T * K * A * M, dtype=torch.float64, device=self.device)
+            ops.coco_accumulate(r['order'], r['off'], r['I'], r['det'], r['rank'], r['dtm'], r['dtig'], r['num_gt'], r['rec'],
+                                r['mdets'], T, out)
+            self._mark('accumulate')
+            host = out.cpu().numpy()            # the one copy back, the one synchronisation
+        n5 = T * R * K * A * M
+        self.eval = dict(params=self.params, counts=[T, R, K, A, M], precision=host[:n5].reshape(T, R, K, A, M),
+                         recall=host[2 * n5:].reshape(T, K, A, M), scores=host[n5:2 * n5].reshape(T, R, K, A, M))
+        if self.profile:
+            self.kernel_ms = {n: self._events[i - 1][1].elapsed_time(e) for i, (n, e) in enumerate(self._events) if i}
+
+    def match_records(self):
+        """what `evalImgs` holds on the host, as flat arrays (pairs are dense: pair = category slot * I + image slot):
+        pair_cat / pair_img (slots of every non-empty pair), det_off / gt_off (P + 1,), dt_matched / dt_ignored (D, A)
+        uint16 with bit t = IoU threshold t, dt_scores (D,), dt_src (D,) row in the concatenated results, gt_ignored (G,)
+        uint8 with bit a = area range a, gt_ids (G,), num_gt (K, A)"""
+        r = self._run
+        if r is None:
+            raise Exception('Please run evaluate() first')
+        host, dt = r['gt']['host'], r['packed']
+        pairs = np.flatnonzero((np.diff(host['off']) > 0) | (np.diff(dt['off']) > 0))
+        return dict(pair_cat=pairs // r['I'], pair_img=pairs % r['I'], det_off=dt['off'], gt_off=host['off'],
+                    dt_matched=r['dtm'].cpu().numpy().view(np.uint16), dt_ignored=r['dtig'].cpu().numpy().view(np.uint16),
+                    dt_scores=dt['det'][:, 4].copy(), dt_src=dt['src'], gt_ignored=r['gtig'].cpu().numpy(),
+                    gt_ids=host['ids'], num_gt=r['num_gt'].cpu().numpy())

@@ -1316,3 +1316,60 @@ def deform_conv_nhwc(x, offset_mask, w, scale=None, shift=None, relu=False, stri
                                           _dt(x), _stream())
     _L.check(st, 'brcnn_deform_conv_nhwc')
     return y
+
+
+# ----------------------------------------------------------------------------- COCO evaluation (csrc/coco_eval.hip)
+def coco_match(gt_box, gt_area, gt_flags, gt_off, det, det_off, num_cats, num_imgs, iou_thrs, area_rng, max_gt_per_pair):
+    """brcnn_coco_match: COCOeval.evaluateImg of every (category, image) pair in one launch.  Returns dt_matched,
+    dt_ignored (D, A) int16 (bit t: IoU threshold t), gt_ignored (G,) uint8 (bit a), num_gt (K, A) int32, det_rank (D,)
+    int32, det_key (D,) int64 -- all left on the device."""
+    _require_gpu(gt_box, gt_area, gt_flags, gt_off, det, det_off, iou_thrs, area_rng)
+    assert gt_box.dtype == torch.float64 and gt_area.dtype == torch.float64 and gt_flags.dtype == torch.uint8
+    assert gt_off.dtype == torch.int32 and det_off.dtype == torch.int32 and det.dtype == torch.float32
+    assert iou_thrs.dtype == torch.float64 and area_rng.dtype == torch.float64
+    P = int(num_cats) * int(num_imgs)
+    assert gt_off.numel() == P + 1 and det_off.numel() == P + 1
+    T, A, D, G = iou_thrs.numel(), area_rng.numel() // 2, det.shape[0], gt_area.numel()
+    dev = det.device
+    dtm = torch.empty((max(D, 1), A), dtype=torch.int16, device=dev)
+    dtig = torch.empty((max(D, 1), A), dtype=torch.int16, device=dev)
+    gtig = torch.empty((max(G, 1),), dtype=torch.uint8, device=dev)
+    num_gt = torch.empty((int(num_cats), A), dtype=torch.int32, device=dev)
+    rank = torch.empty((max(D, 1),), dtype=torch.int32, device=dev)
+    key = torch.empty((max(D, 1),), dtype=torch.int64, device=dev)
+    st = _L.load().brcnn_coco_match(_ptr(gt_box), _ptr(gt_area), _ptr(gt_flags), _ptr(gt_off), _ptr(det), _ptr(det_off),
+                                    int(num_cats), int(num_imgs), _ptr(iou_thrs), T, _ptr(area_rng), A, int(max_gt_per_pair),
+                                    _ptr(dtm), _ptr(dtig), _ptr(gtig), _ptr(num_gt), _ptr(rank), _ptr(key), _stream())
+    _L.check(st, 'brcnn_coco_match')
+    return dtm[:D], dtig[:D], gtig[:G], num_gt, rank[:D], key[:D]
+
+
+def coco_order(det_key, num_cats):
+    """brcnn_coco_order: the detection indices by (category, descending score), ties in table order; (D,) int32"""
+    _require_gpu(det_key)
+    assert det_key.dtype == torch.int64 and det_key.is_contiguous()
+    D = det_key.numel()
+    order = torch.empty((max(D, 1),), dtype=torch.int32, device=det_key.device)
+    nb = int(_L.load().brcnn_coco_order_workspace_bytes(D))
+    ws = torch.empty((max(nb, 1),), dtype=torch.uint8, device=det_key.device)
+    st = _L.load().brcnn_coco_order(_ptr(det_key), D, int(num_cats), _ptr(order), _ptr(ws), nb, _stream())
+    _L.check(st, 'brcnn_coco_order')
+    return order[:D]
+
+
+def coco_accumulate(order, det_off, num_imgs, det, det_rank, dt_matched, dt_ignored, num_gt, rec_thrs, max_dets, num_thrs,
+                    out):
+    """brcnn_coco_accumulate into `out`, one fp64 device buffer laid out precision (T, R, K, A, M) | scores (T, R, K, A,
+    M) | recall (T, K, A, M); returns the three views"""
+    _require_gpu(order, det_off, det, det_rank, dt_matched, dt_ignored, num_gt, rec_thrs, max_dets, out)
+    assert rec_thrs.dtype == torch.float64 and max_dets.dtype == torch.int32 and out.dtype == torch.float64
+    K, A = num_gt.shape
+    T, R, M = int(num_thrs), rec_thrs.numel(), max_dets.numel()
+    n5, n4 = T * R * K * A * M, T * K * A * M
+    assert out.numel() == 2 * n5 + n4 and out.is_contiguous()
+    precision, scores, recall = out[:n5], out[n5:2 * n5], out[2 * n5:]
+    st = _L.load().brcnn_coco_accumulate(_ptr(order), _ptr(det_off), int(num_imgs), _ptr(det), _ptr(det_rank),
+                                         _ptr(dt_matched), _ptr(dt_ignored), _ptr(num_gt), _ptr(rec_thrs), _ptr(max_dets),
+                                         T, R, K, A, M, _ptr(precision), _ptr(scores), _ptr(recall), _stream())
+    _L.check(st, 'brcnn_coco_accumulate')
+    return precision.view(T, R, K, A, M), scores.view(T, R, K, A, M), recall.view(T, K, A, M)

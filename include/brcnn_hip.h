@@ -953,6 +953,39 @@ int brcnn_pack_conv_weights_batch(const float *const *weights, void *const *fwd,
 int brcnn_pack_fc_weight_permuted(const float *weight, void *fwd, void *dgrad, int out_features, int channels,
                                   int positions, int dtype, const float *ctl3, void *stream);
 
+/* ------------------------------------------------------------------------------
+ * COCO bbox / proposal evaluation (evaluation.py: COCOeval.evaluateImg / accumulate) on the device.
+ * Pairs are dense: pair = category * num_imgs + image (images in sorted-id order; one category when
+ * categories are pooled).  gt_off / det_off (num_cats*num_imgs + 1) are the CSR offsets of the pair-major
+ * ground-truth and detection tables: gt_box (G, 4) fp64 xywh, gt_area (G) fp64, gt_flags (G) bit 0 iscrowd,
+ * bit 1 "id != 0"; det (D, 5) fp32 x1 y1 x2 y2 score, inside a pair in descending-score order and already
+ * cut to the largest maxDet.  Every result is bit-equal to the host evaluator's.
+ *
+ * brcnn_coco_match: one launch for all pairs.  iou_thrs (num_thrs <= 16), area_rng (num_areas, 2) fp64 on
+ * the device, num_thrs * num_areas <= 64; max_gt_per_pair (host-known) <= 1024.  Writes per detection and
+ * area range the matched / ignored bits of every threshold (bit t) into dt_matched / dt_ignored
+ * (D, num_areas) uint16, per ground truth its ignore bits (bit a) into gt_ignored (G), the number of
+ * ground truths that count into num_gt (num_cats, num_areas), and for the later stages det_rank (D) and
+ * det_key (D) = category << 32 | score bits flipped for an ascending sort.
+ * brcnn_coco_order: stable LSD radix sort of det_key -> order (D) uint32, the detection indices by
+ * (category, descending score), ties in table order; workspace from brcnn_coco_order_workspace_bytes.
+ * brcnn_coco_accumulate: precision / scores (T, R, K, A, M) and recall (T, K, A, M) fp64 with the host's
+ * conventions (-1: nothing to find; 0: nothing found); rec_thrs (num_recs <= 1024, ascending) fp64 and
+ * max_dets (num_max_dets) int32 on the device. */
+size_t brcnn_coco_order_workspace_bytes(int64_t num_dets);
+int brcnn_coco_match(const double *gt_box, const double *gt_area, const uint8_t *gt_flags, const int32_t *gt_off,
+                     const float *det, const int32_t *det_off, int num_cats, int num_imgs, const double *iou_thrs,
+                     int num_thrs, const double *area_rng, int num_areas, int max_gt_per_pair, uint16_t *dt_matched,
+                     uint16_t *dt_ignored, uint8_t *gt_ignored, int32_t *num_gt, int32_t *det_rank, uint64_t *det_key,
+                     void *stream);
+int brcnn_coco_order(const uint64_t *det_key, int64_t num_dets, int num_cats, uint32_t *order, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int brcnn_coco_accumulate(const uint32_t *order, const int32_t *det_off, int num_imgs, const float *det,
+                          const int32_t *det_rank, const uint16_t *dt_matched, const uint16_t *dt_ignored,
+                          const int32_t *num_gt, const double *rec_thrs, const int32_t *max_dets, int num_thrs,
+                          int num_recs, int num_cats, int num_areas, int num_max_dets, double *precision,
+                          double *scores, double *recall, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
