@@ -341,6 +341,23 @@ def test_sigmoid_focal_loss_fwd_bwd(c):
     # closed form vs python form: 1-sigmoid(x) cancellation at large |x| -> 1e-3 (north_star fp32 bar)
     assert torch.allclose(out.detach().cpu(), py, rtol=1e-2, atol=1e-5)
     assert abs(out.sum().item() - py.sum().item()) < 1e-4 * abs(py.sum().item())
+    # the closed form itself in float64 where nothing saturates (|x| <= 12), forward and backward, under the rule of
+    # tests/test_loss_edges_gpu.py: kernel error <= 4 x the error of the same closed form evaluated in fp32 on the CPU
+    # (the 1 - p cancellation these logits amplify) + 4 ulps; once per element relative to its own magnitude, once
+    # relative to the largest element
+    from tests import loss_ref as R
+    m = x.abs() <= 12
+    assert m.float().mean() > 0.99
+    is_pos = t[:, None] == torch.arange(c)[None, :]
+    refs = []
+    for dt in (torch.float64, torch.float32):
+        xr = x.to(dt).requires_grad_()
+        f = R.focal_closed_form(xr, is_pos, 2.0, 0.25)
+        refs.append((f.detach()[m], torch.autograd.grad(f.sum(), xr)[0][m]))
+    for i, (nm, got) in enumerate((('fwd', out.detach().cpu()[m]), ('bwd', xg.grad.cpu()[m]))):
+        R.check_against_fp64(f'focal[{c}] {nm} per element', got, refs[0][i], refs[1][i], None, R.CEILING_FOCAL_ELEMENT)
+        R.check_against_fp64(f'focal[{c}] {nm} vs max', got, refs[0][i], refs[1][i], refs[0][i].abs().max().reshape(1),
+                             1e-3)
 
 
 # --------------------------------------------------------------------------- conv stack
