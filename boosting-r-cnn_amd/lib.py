@@ -152,6 +152,7 @@ SIGNATURES = {
     'brcnn_boost_loss_backward_ex': (c_int, [c_ptr] * 6 + [c_int, c_int, c_int] + [c_ptr] * 6),
     'brcnn_preprocess_u8_batch_blocks': (c_i64, [c_int, c_int]),
     'brcnn_preprocess_u8_batch': (c_int, [c_ptr, c_size, c_ptr, c_ptr, c_int, c_ptr, c_size, c_ptr, c_ptr, c_int, c_ptr]),
+    'brcnn_preprocess_u8_chain': (c_int, [c_ptr] + [c_int] * 9 + [c_ptr] + [c_int] * 5 + [c_ptr, c_ptr, c_int, c_ptr]),
     'brcnn_tta_gather_proposals': (c_int, [c_ptr] * 3 + [c_int, c_ptr, c_int] + [c_ptr] * 5),
     'brcnn_tta_map_rois': (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     'brcnn_rcnn_decode_tta': (c_int, [c_ptr] * 6 + [c_int] * 5 + [c_f32, c_ptr, c_ptr, c_f64] + [c_ptr] * 5),

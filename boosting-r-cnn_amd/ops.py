@@ -1205,6 +1205,29 @@ def preprocess_u8(src_u8, out, new_w, new_h, flip_direction, mean, std, to_rgb=T
     return out
 
 
+def preprocess_u8_chain(src_u8, out, mid_hw, window, new_hw, flip_direction, mean, std, to_rgb=True,
+                        src_flip_direction=None):
+    """[flip ->] Resize(mid) -> crop(window) -> Resize(new) [-> flip] -> Normalize -> Pad of one decoded uint8 BGR image
+    in one launch (brcnn_preprocess_u8_chain): the (mid_h, mid_w) image between the two resizes is never stored.
+    `src_u8` (H,W,3) uint8 on the device, `mid_hw` = (mid_h, mid_w), `window` = (top, left, crop_h, crop_w) inside it,
+    `new_hw` = (new_h, new_w), `out` (3,PH,PW) fp32 on the device (PH >= new_h, PW >= new_w; the rest is zeroed).
+    `src_flip_direction` mirrors the source first, `flip_direction` the result.  Bad geometry raises and launches
+    nothing."""
+    import ctypes
+    _require_gpu(src_u8, out)
+    assert src_u8.dtype == torch.uint8 and src_u8.dim() == 3 and src_u8.shape[2] == 3 and src_u8.is_contiguous()
+    assert out.dtype == torch.float32 and out.dim() == 3 and out.shape[0] == 3 and out.is_contiguous()
+    m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
+    top, left, ch, cw = (int(v) for v in window)
+    st = _L.load().brcnn_preprocess_u8_chain(_ptr(src_u8), src_u8.shape[0], src_u8.shape[1], _FLIP_CODE[src_flip_direction],
+                                             int(mid_hw[0]), int(mid_hw[1]), top, left, ch, cw, _ptr(out), int(new_hw[0]),
+                                             int(new_hw[1]), out.shape[1], out.shape[2], _FLIP_CODE[flip_direction], m3, s3,
+                                             int(bool(to_rgb)), _stream())
+    _L.check(st, 'brcnn_preprocess_u8_chain')
+    return out
+
+
 # include/brcnn_hip.h: brcnn_pre_job (64 bytes), one row per (aug, image) of a batched front-door launch
 PRE_JOB_DTYPE = np.dtype([('src_off', '<i8'), ('dst_off', '<i8'), ('scale_x', '<f8'), ('scale_y', '<f8'),
                           ('src_h', '<i4'), ('src_w', '<i4'), ('new_h', '<i4'), ('new_w', '<i4'),

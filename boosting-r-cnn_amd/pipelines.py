@@ -20,6 +20,16 @@ transform LOGIC around it is pinned by golden fixtures from the imported referen
 `FusedResizeNormalizePad` is the device form of Resize+RandomFlip+Normalize+Pad for one
 decoded uint8 image (HIP kernel `brcnn_preprocess_u8`, csrc/preprocess.hip), bit-identical to
 the host chain above; `fuse_device_pipeline` rewrites a pipeline config to use it.
+
+`FusedAugResizeNormalizePad` is the device form of the multi-scale COCO recipes' train pipeline
+
+    RandomFlip -> AutoAugment([[Resize], [Resize, RandomCrop, Resize(override)]]) -> Normalize -> Pad
+
+(RandomFlip on either side of AutoAugment) for one decoded uint8 image: `plan` draws every random number and updates
+boxes, labels and metas on the host through the Resize / RandomCrop / RandomFlip / Pad objects' own methods, and ONE
+launch of `brcnn_preprocess_u8_chain` (csrc/preprocess_chain.hip) does resize, crop, resize, flip, normalise and pad
+without ever storing the image between the two resizes, bit-identical to the host chain;
+`fuse_device_pipeline(..., policies=True)` rewrites a config to use it.
 """
 import collections
 import os.path as osp
@@ -816,21 +826,195 @@ class DeviceFormatBundle(DefaultFormatBundle):
         return results
 
 
-def fuse_device_pipeline(pipeline_cfg, device='cuda'):
+class _ShapeOnly:
+    """what the host bookkeeping of `FusedAugResizeNormalizePad.plan` sees in place of the pixels: an image that has a
+    shape and can be cropped (`img[top:top + h, left:left + w, ...]`, as RandomCrop._crop_data does), and remembers
+    where the crop sits in the image it was taken from"""
+
+    def __init__(self, shape, origin=(0, 0)):
+        self.shape, self.origin = tuple(int(v) for v in shape), origin
+
+    def __getitem__(self, key):
+        rows, cols = key[0], key[1]
+        (t, b, _), (l, r, _) = rows.indices(self.shape[0]), cols.indices(self.shape[1])
+        return _ShapeOnly((max(b - t, 0), max(r - l, 0)) + self.shape[2:], (self.origin[0] + t, self.origin[1] + l))
+
+
+class ChainPlan:
+    """geometry of one sample, all host numbers: src_flip / flip (direction or None), mid (H1, W1), window (top, left,
+    ch, cw) in it, new (H2, W2), pad (PH, PW)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _supported_policy(policy):
+    """a policy the chain kernel reproduces: [Resize] or [Resize, RandomCrop, Resize(override)], uint8 images and boxes
+    only (no ratio_range next to a crop, cv2 backend)"""
+    try:
+        steps = [dict(s) for s in policy]
+    except Exception:
+        return False
+    types = [s.get('type') for s in steps]
+    if types not in (['Resize'], ['Resize', 'RandomCrop', 'Resize']):
+        return False
+    for s in steps:
+        if s['type'] == 'Resize':
+            if set(s) - {'type', 'img_scale', 'multiscale_mode', 'ratio_range', 'keep_ratio', 'bbox_clip_border', 'backend',
+                         'override'} or s.get('backend', 'cv2') != 'cv2' or s.get('img_scale') is None:
+                return False
+            if len(steps) == 3 and s.get('ratio_range') is not None:
+                return False
+        elif set(s) - {'type', 'crop_size', 'crop_type', 'allow_negative_crop', 'recompute_bbox', 'bbox_clip_border'}:
+            return False
+    return len(steps) == 1 or bool(steps[2].get('override', False))
+
+
+@PIPELINES.register_module()
+class FusedAugResizeNormalizePad:
+    """AutoAugment(policies) + RandomFlip + Normalize + Pad of one decoded uint8 BGR image as ONE upload of the uint8
+    source and ONE HIP launch (`brcnn_preprocess_u8_chain`), bit-identical to the host chain.  Every policy is `[Resize]`
+    or `[Resize, RandomCrop, Resize(override=True)]`: the multi-scale COCO recipes' pair.  `flip_first=True` is the order
+    the shipped recipes use (RandomFlip in front of AutoAugment, the source is mirrored), False the order RandomFlip behind
+    it (the result is mirrored); the two differ in the last bit of a resize and in the order of the random draws.
+
+    `plan` is the host half: it draws from `np.random` in the host chain's order (flip when first, policy, first scale,
+    crop size, window rows then columns, second scale, flip when last) through the Resize / RandomCrop / RandomFlip / Pad
+    objects' own methods on a shape-only stand-in for the image, updates boxes, labels and every meta key, and returns
+    the geometry -- or None where RandomCrop rejects the sample (no ground truth left, allow_negative_crop=False), before
+    any device work.  `__call__` then uploads and launches.  Under `datasets.build_dataloader` a rejected sample is an
+    error (MainProcessTail: only the host part of a pipeline may drop samples); the shipped recipes all crop with
+    allow_negative_crop=True and never reject."""
+
+    def __init__(self, policies, mean, std, to_rgb=True, flip_ratio=None, direction='horizontal', flip_first=False,
+                 size=None, size_divisor=None, pad_val=0, device='cuda'):
+        assert pad_val == 0
+        if not all(_supported_policy(p) for p in policies):
+            raise ValueError('FusedAugResizeNormalizePad: every policy must be [Resize] or [Resize, RandomCrop, '
+                             'Resize(override=True)]')
+        self.runs_on_device = True
+        self.aug = AutoAugment(policies)
+        self.flip = RandomFlip(flip_ratio, direction)
+        self.flip_first = bool(flip_first)
+        self.pad = Pad(size, size_divisor, pad_val)
+        self.mean = np.array(mean, dtype=np.float32)
+        self.std = np.array(std, dtype=np.float32)
+        self.to_rgb = to_rgb
+        self.device = device
+
+    def _flip(self, results):
+        self.flip.decide(results)
+        if results['flip']:
+            for key in results.get('bbox_fields', []):
+                results[key] = self.flip.bbox_flip(results[key], results['img_shape'], results['flip_direction'])
+        return results['flip_direction'] if results['flip'] else None
+
+    @staticmethod
+    def _resize(step, results):
+        """Resize.__call__ without the pixels (Resize._resize_img's bookkeeping on the shapes)"""
+        step._pick_scale(results)
+        h, w = results['img'].shape[:2]
+        new_w, new_h = step.target_size(results)
+        results['img'] = _ShapeOnly((new_h, new_w, 3))
+        results['img_shape'] = results['pad_shape'] = (new_h, new_w, 3)
+        results['scale_factor'] = np.array([new_w / w, new_h / h, new_w / w, new_h / h], dtype=np.float32)
+        results['keep_ratio'] = step.keep_ratio
+        step._resize_bboxes(results)
+
+    def plan(self, results):
+        """host arithmetic only; `results['img']` is read for its shape and left in place"""
+        img = results['img']
+        assert results.get('img_fields', ['img']) == ['img'], 'FusedAugResizeNormalizePad handles the image field only'
+        h0, w0 = img.shape[:2]
+        results['img'] = _ShapeOnly((h0, w0, 3))
+        try:
+            src_flip = self._flip(results) if self.flip_first else None
+            steps = np.random.choice(self.aug.transforms).transforms
+            self._resize(steps[0], results)
+            mid = results['img'].shape[:2]
+            window = (0, 0) + mid
+            if len(steps) == 3:
+                if steps[1](results) is None:
+                    return None
+                crop = results['img']
+                window = crop.origin + crop.shape[:2]
+                self._resize(steps[2], results)
+            new = results['img'].shape[:2]
+            flip = None if self.flip_first else self._flip(results)
+        finally:
+            results['img'] = img
+        pad = self.pad.padded_shape(*new)
+        results['img_norm_cfg'] = dict(mean=self.mean, std=self.std, to_rgb=self.to_rgb)
+        results['pad_shape'] = pad + (3,)
+        results['pad_fixed_size'] = self.pad.size
+        results['pad_size_divisor'] = self.pad.size_divisor
+        return ChainPlan(src_flip=src_flip, flip=flip, mid=mid, window=window, new=new, pad=pad)
+
+    def __call__(self, results):
+        from . import ops
+        img = results['img']
+        assert img.dtype == np.uint8 and img.ndim == 3 and img.shape[2] == 3
+        plan = self.plan(results)
+        if plan is None:
+            return None
+        src = torch.from_numpy(np.ascontiguousarray(img)).to(self.device, non_blocking=True)
+        out = torch.empty((3,) + plan.pad, dtype=torch.float32, device=self.device)
+        ops.preprocess_u8_chain(src, out, plan.mid, plan.window, plan.new, plan.flip, self.mean, self.std, self.to_rgb,
+                                src_flip_direction=plan.src_flip)
+        results['img'] = out
+        return results
+
+    def __repr__(self):
+        return (f'{self.__class__.__name__}(aug={self.aug}, flip={self.flip}, flip_first={self.flip_first}, '
+                f'pad={self.pad})')
+
+
+def _fuse_policies(cfgs, i, device):
+    """the FusedAugResizeNormalizePad config for cfgs[i:i + 4] when that is [AutoAugment, RandomFlip, Normalize, Pad] or
+    [RandomFlip, AutoAugment, Normalize, Pad] with supported policies, else None"""
+    run = cfgs[i:i + 4]
+    types = [x['type'] for x in run]
+    if types == ['AutoAugment', 'RandomFlip', 'Normalize', 'Pad']:
+        (a, f, n, p), first = run, False
+    elif types == ['RandomFlip', 'AutoAugment', 'Normalize', 'Pad']:
+        (f, a, n, p), first = run, True
+    else:
+        return None
+    if set(a) - {'type', 'policies'} or not isinstance(a.get('policies'), (list, tuple)) or not a['policies'] or \
+            not all(_supported_policy(pol) for pol in a['policies']) or p.get('pad_val', 0) != 0:
+        return None
+    fused = dict(type='FusedAugResizeNormalizePad', device=device, flip_first=first)
+    for src in (a, f, n, p):
+        fused.update({k: v for k, v in src.items() if k != 'type'})
+    return fused
+
+
+def fuse_device_pipeline(pipeline_cfg, device='cuda', policies=False):
     """Rewrite a reference pipeline config so that its [Resize, RandomFlip, Normalize, Pad] run
     is replaced by one FusedResizeNormalizePad (and DefaultFormatBundle by DeviceFormatBundle).
-    Anything else is kept as is; pipelines without that exact run are returned unchanged."""
+    Anything else is kept as is; pipelines without that exact run are returned unchanged.
+    With `policies=True` the run [AutoAugment, RandomFlip, Normalize, Pad] (RandomFlip on either side of
+    AutoAugment) becomes one FusedAugResizeNormalizePad as well, provided every policy is one the chain
+    kernel reproduces; a pipeline that holds an AutoAugment it cannot take over is returned unchanged."""
     import copy
     out = []
     cfgs = [dict(c) for c in copy.deepcopy(list(pipeline_cfg))]
+    if policies and any(c['type'] == 'AutoAugment' for c in cfgs) and \
+            not any(_fuse_policies(cfgs, i, device) for i in range(len(cfgs))):
+        return cfgs
     i = 0
     while i < len(cfgs):
         c = cfgs[i]
         if c['type'] == 'MultiScaleFlipAug':
             c = dict(c)
-            c['transforms'] = fuse_device_pipeline(c['transforms'], device)
+            c['transforms'] = fuse_device_pipeline(c['transforms'], device, policies)
             out.append(c)
             i += 1
+            continue
+        fused = _fuse_policies(cfgs, i, device) if policies else None
+        if fused is not None:
+            out.append(fused)
+            i += 4
             continue
         types = [x['type'] for x in cfgs[i:i + 4]]
         if types == ['Resize', 'RandomFlip', 'Normalize', 'Pad']:

@@ -799,6 +799,27 @@ int brcnn_preprocess_u8_batch(const uint8_t *src, size_t src_bytes, const brcnn_
                               int to_rgb, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Training front door of the multi-scale recipes: AutoAugment's crop policy
+ * [RandomFlip ->] Resize -> RandomCrop -> Resize(override) [-> RandomFlip] -> Normalize -> Pad
+ * (mmdet/datasets/pipelines/auto_augment.py:44-109, transforms.py:742-896 and the lines cited above) of ONE
+ * decoded image as one pass.
+ *   src  (src_h, src_w, 3) uint8, BGR, dense        dst (3, pad_h, pad_w) fp32, CHW, every element written
+ *   the source, mirrored by src_flip (0-3 as above: a RandomFlip in FRONT of the policies), is resized to a
+ *   virtual (mid_h, mid_w) uint8 image that is never stored; its window [top, top + crop_h) x [left, left +
+ *   crop_w) is resized to (new_h, new_w) -- both with OpenCV's 8-bit fixed-point bilinear, both rounded to
+ *   uint8, the second with its taps clamped to the window -- then flipped by `flip` (a RandomFlip BEHIND the
+ *   policies), converted, normalised and zero-padded as brcnn_preprocess_u8 does.  A stage whose sizes match
+ *   is the identity: mid = src gives crop + resize, window = whole and new = crop gives brcnn_preprocess_u8
+ *   (bit for bit).  The host draws every random number; the launch only sees the geometry.
+ *   -22 and no launch for: a NULL pointer, a size <= 0, a window that leaves the virtual image, pad < new, a
+ *   flip code outside 0-3, a zero std, a source of 2 GiB or more.
+ * -------------------------------------------------------------------------- */
+int brcnn_preprocess_u8_chain(const uint8_t *src, int src_h, int src_w, int src_flip, int mid_h, int mid_w,
+                              int top, int left, int crop_h, int crop_w, float *dst, int new_h, int new_w,
+                              int pad_h, int pad_w, int flip, const float *mean3_host,
+                              const float *std3_host, int to_rgb, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Train step: whole-batch target assignment, RoI sampling and the fused losses.
  * The reference runs these per image / per level as chains of small torch ops with host
  * synchronisations (nonzero / unique / .item()); each entry below serves the whole batch.

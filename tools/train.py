@@ -42,7 +42,8 @@ def parse_args(argv=None):
                         '(init_cfg, resolved under $BRCNN_PRETRAINED_DIR) is not available')
     p.add_argument('--dist-backend', default=None, help="override dist_params.backend ('gloo' for CPU runs)")
     p.add_argument('--device-preprocess', action='store_true',
-                   help='run Resize/Flip/Normalize/Pad as the fused HIP kernel on the uploaded uint8 image')
+                   help='run Resize/Flip/Normalize/Pad (and the AutoAugment resize / crop policies of the multi-scale '
+                        'recipes) as the fused HIP kernel on the uploaded uint8 image')
     p.add_argument('--local_rank', type=int, default=0)
     args = p.parse_args(argv)
     os.environ.setdefault('LOCAL_RANK', str(args.local_rank))
@@ -84,7 +85,10 @@ def main(argv=None):
     cfg.seed = args.seed
     if args.device_preprocess:
         from brcnn.pipelines import fuse_device_pipeline
-        cfg.data.train.pipeline = fuse_device_pipeline(cfg.data.train.pipeline)
+        train = cfg.data.train
+        while train['type'] == 'RepeatDataset':         # the multi-scale recipes: the pipeline is the wrapped dataset's
+            train = train['dataset']
+        train['pipeline'] = fuse_device_pipeline(train['pipeline'], policies=True)
     model = build_detector(cfg.model, train_cfg=cfg.get('train_cfg'), test_cfg=cfg.get('test_cfg'))
     if args.allow_random_init:
         os.environ['BRCNN_ALLOW_RANDOM_INIT'] = '1'
