@@ -163,6 +163,13 @@ int dispatch_conv_pp128_bf16(ConvParams& p, hipStream_t s);
 // fills p.sk_*; p.sk_wgs = 0 when the plain one-tile-per-workgroup launch is the better one
 int sk_plan_pp(ConvParams& p, int slots, int bm, int bn, hipStream_t s);
 int sk_plan_pp_f32(ConvParams& p, int slots, int bm, int bn, hipStream_t s);
+// persistent launch of the fp32 64 x 64 kernel (conv_igemm.hip): one contiguous range of the tiles x K-tiles iteration
+// space per workgroup, `per_cu` (the resident count) workgroups on each of the `cus` CUs -- fewer per CU, down to two,
+// where the launch has fewer tiles than that (every range then still holds a whole tile's worth of K tiles, and the CUs
+// carry equal work instead of four or five K chains).  Fills p.sk_* with p.sk_wgs = the workgroups and p.sk_items =
+// [sk_wgs x (first item, count, 0, 0) | items (tile, first K tile, end K tile, hand-over slot)]; p.sk_wgs = 0: take the
+// plain launch (stream capture, fewer than two tiles per CU, a one-K-tile layer)
+int sk_plan_f32_tile(ConvParams& p, int per_cu, int cus, hipStream_t s);
 float* conv_ws_wgrad_slabs(hipStream_t s);          // the weight-gradient slab part of the stream's conv workspace (160 MiB)
 // deferred second stage of the sliced weight gradients (wgrad_defer.hip): slabs from the stream's deferral arena (nullptr:
 // deferral off / request larger than the arena; *err < 0: the flush it had to launch first failed), and the item of a

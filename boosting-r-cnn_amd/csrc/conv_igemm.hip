@@ -280,12 +280,18 @@ __global__ __launch_bounds__(128 * WM, 2) void conv_igemm_f32_kernel(ConvParams 
 // bank-conflict-free read pattern comes from an XOR swizzle applied on the SOURCE side: the
 // lane that lands at physical chunk c' of row r fetches logical chunk c' ^ ((r >> 1) & 7); the
 // fragment reads apply the same involution.  Tile 128 x (64*NT) x 32, 4 waves (2x2).
-template <int MT, int NT, bool RES>
-__global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p) {
+//
+// One work item: K tiles [kb, ke) of output tile `tile`.  The plain launch runs one item per workgroup, the whole K
+// loop of its tile (SK = false: kb = 0, ke = nk fold away).  The persistent launch (SK = true, below) hands a
+// workgroup a list of items: an item that stops short of the tile's last K tile stores its accumulators to
+// sk_ws[sk_slot] and publishes sk_flags[sk_slot] = sk_epoch instead of reading out; an item that starts past K tile 0
+// waits for that flag and continues the MFMA chain from those accumulators.
+template <int MT, int NT, bool RES, bool SK>
+__device__ __forceinline__ void conv_f32_dma_item(const ConvParams& p, float* smem, const int tile, const int kb_, const int ke_,
+                                                  const int sk_slot) {
     constexpr int BM = 64 * MT, BN = 64 * NT;
     constexpr int AG = BM / 8 / 4;      // 8-row groups of the A tile per wave (4)
     constexpr int BG = BN / 8 / 4;      // 8-row groups of the W tile per wave (4 or 2)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     float* As = smem;                   // [2][BM][32]
     float* Bs = smem + 2 * BM * 32;     // [2][BN][32]
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -296,8 +302,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p
     const int wm = wave >> 1, wn = wave & 1;
     const int li = lane & 31, lh = lane >> 5;
 
-    const int nwg = p.tiles_m * p.tiles_n;
-    const int tile = xcd_remap(blockIdx.x, nwg);
     const int tile_m = tile / p.tiles_n, tile_n = tile - tile_m * p.tiles_n;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -355,10 +359,21 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p
             for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
 
     const int nk = (p.K + BK - 1) / BK;
+    const int kb = SK ? kb_ : 0, ke = SK ? ke_ : nk;
+    const bool finish = !SK || ke == nk;    // this item ends with the read-out (else: the partial tile is handed over)
 
     // K tiles are staged in order, so the filter tap (kh, kw) and the channel offset of the next
     // tile are carried as scalar state instead of being re-derived by two integer divisions
-    int d_k0 = 0, d_ci0 = 0, d_kh = 0, d_kw = 0;
+    int d_ci0 = 0, d_kh = 0, d_kw = 0;
+    if constexpr (SK) {
+        if (kb > 0) {       // a K tail starts at chunk kb / T, tap kb % T (scalar, once per item)
+            const int T = p.KH * p.KW;
+            const int cc = kb / T, tap = kb - cc * T;
+            d_kh = tap / p.KW;
+            d_kw = tap - d_kh * p.KW;
+            d_ci0 = cc * BK;
+        }
+    }
     // plain (1x1 stride-1, one map) layers: the byte offset of every piece is its offset in K tile 0 plus 128 bytes per K
     // tile -- one add per piece and tile instead of the tap / bounds arithmetic (a row beyond M starts at OOB and the sum
     // stays beyond the buffer's extent: x and w are < 2 GiB)
@@ -367,7 +382,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p
     for (int j = 0; j < AG; j++) a_off4[j] = a_base[j] >= 0 ? (unsigned)(a_base[j] + a_lc[j] + tile_n * p.gstep) * 4u : (unsigned)OOB;
 #pragma unroll
     for (int j = 0; j < BG; j++) b_off4[j] = b_off[j] >= 0 ? (unsigned)b_off[j] * 4u : (unsigned)OOB;
-    unsigned d_plain = 0;
+    unsigned d_plain = (unsigned)kb * (BK * 4);
     auto dma_tile_plain = [&](int buf) {
         const unsigned step = d_plain;
         d_plain += BK * 4;
@@ -389,7 +404,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p
         // visits K in this order, so their results stay bit-identical to each other)
         const int ci0 = d_ci0, kh = d_kh, kw = d_kw;
         const int k0 = (kh * p.KW + kw) * p.Cin + ci0;
-        (void)d_k0;
         if (++d_kw == p.KW) {
             d_kw = 0;
             if (++d_kh == p.KH) { d_kh = 0; d_ci0 += BK; }
@@ -471,6 +485,36 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p
             }
         }
     };
+    if constexpr (SK) {
+        if (kb > 0) {
+            // the K head of this tile, published by the workgroup of the range below as its FIRST item: one lane polls
+            // (bounded), one agent-scope acquire, then plain loads into the accumulators (the DMA above stays in
+            // flight under them)
+            if (tid == 0) {
+                int spins = 0;
+                while (__hip_atomic_load(p.sk_flags + sk_slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != p.sk_epoch &&
+                       ++spins < p.sk_spin_limit)
+                    __builtin_amdgcn_s_sleep(4);
+                // a hand-over that never arrives must not end as a silent wrong result: the host-mapped error word
+                // makes the next launch on any stream (and brcnn_conv_handover_status) return BRCNN_EHANDOVER
+                if (spins >= p.sk_spin_limit)
+                    __hip_atomic_store(p.sk_err, p.sk_epoch | 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            }
+            __syncthreads();
+            const f32x4* src = reinterpret_cast<const f32x4*>(p.sk_ws) + (size_t)sk_slot * (BM * BN / 4) + wave * 64 + lane;
+#pragma unroll
+            for (int a = 0; a < MT; a++)
+#pragma unroll
+                for (int b = 0; b < NT; b++)
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        const f32x4 v = src[((a * NT + b) * 4 + g) * 256];
+                        acc[a][b][4 * g + 0] = v.x; acc[a][b][4 * g + 1] = v.y;
+                        acc[a][b][4 * g + 2] = v.z; acc[a][b][4 * g + 3] = v.w;
+                    }
+        }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -530,15 +574,42 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p
         }
     };
     int cur = 0;
-    for (int kt = 0; kt + 1 < nk; kt++) {
+    for (int kt = kb; kt + 1 < ke; kt++) {
         compute_tile(cur, true);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         cur ^= 1;
     }
     // last K tile: no prefetch, no barrier (nothing in LDS is read afterwards)
-    if (RES) load_residual();
+    if (RES && finish) load_residual();
     compute_tile(cur, false);
+
+    if constexpr (SK) {
+        if (!finish) {
+            // K head: the accumulators in their register layout (16 floats per lane, four 16-byte stores), then the flag
+            f32x4* dst = reinterpret_cast<f32x4*>(p.sk_ws) + (size_t)sk_slot * (BM * BN / 4) + wave * 64 + lane;
+#pragma unroll
+            for (int a = 0; a < MT; a++)
+#pragma unroll
+                for (int b = 0; b < NT; b++)
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        f32x4 v;
+                        v.x = acc[a][b][4 * g + 0]; v.y = acc[a][b][4 * g + 1];
+                        v.z = acc[a][b][4 * g + 2]; v.w = acc[a][b][4 * g + 3];
+                        dst[((a * NT + b) * 4 + g) * 256] = v;
+                    }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (!p.sk_drop_publish)       // (test hook: a lost hand-over)
+                    __hip_atomic_store(p.sk_flags + sk_slot, p.sk_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            return;
+        }
+    }
 
     // ---- epilogue.  Scale / shift in the accumulator layout; for channel counts that are
     // multiples of 4 each wave then transposes one 32x32 tile at a time through a private 4 KiB
@@ -637,9 +708,94 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p
     }
 }
 
+// SK = false: one workgroup per output tile.  SK = true: the persistent launch of exactly the resident workgroups;
+// workgroup b owns one contiguous range of the launch's (tile x K-tile) iteration space, cut into the items
+// sk_items[first .. first + count), (first, count) = sk_items[b] (sk_table_ranges, conv_igemm_bf16.hip): the K head of
+// the tile the range ends in (published at once: nobody waits long for it), its whole tiles, and last the K tail of the
+// tile it starts in.  Every accumulator sees K tiles 0 .. nk-1 in order through the same MFMA sequence either way, so
+// the two forms give the same bits.
+template <int MT, int NT, bool RES, bool SK = false>
+__global__ __launch_bounds__(256, 2) void conv_igemm_f32_dma_kernel(ConvParams p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if constexpr (SK) {
+        const int4 range = p.sk_items[blockIdx.x];       // wave-uniform: scalar loads
+        const int first = __builtin_amdgcn_readfirstlane(range.x), count = __builtin_amdgcn_readfirstlane(range.y);
+        for (int i = 0; i < count; i++) {
+            // the read-out slabs and the last K tile of the item before live in the operand buffers: every wave is
+            // past them before the next item's first DMA lands
+            if (i > 0) __syncthreads();
+            const int4 item = p.sk_items[first + i];
+            conv_f32_dma_item<MT, NT, RES, true>(p, smem, __builtin_amdgcn_readfirstlane(item.x),
+                                                 __builtin_amdgcn_readfirstlane(item.y), __builtin_amdgcn_readfirstlane(item.z),
+                                                 __builtin_amdgcn_readfirstlane(item.w));
+        }
+    } else {
+        conv_f32_dma_item<MT, NT, RES, false>(p, smem, xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), 0, 0, 0);
+    }
+}
+
+// Where the persistent launch of the 64 x 64 kernel wins (profiles/f32_tile_persistent.txt: plain against forced over the
+// shapes this kernel serves in the fp32 inference pass at batch 8, MI355X): the FEW-TILE launches -- fewer tiles than
+// resident workgroups, so that every tile is resident at once and the CUs carry unequal numbers of K chains (1056 tiles
+// on 256 CUs: 32 CUs run five chains, the others four; 528 tiles: three against two) -- with a K loop long enough that
+// the launch lasts as long as its busiest CU: stage-4 3x3 402 -> 329 us, 2048 -> 512 1x1 163 -> 135 us, the 25 x 42 neck
+// 3x3 124 -> 96 us and lateral 100 -> 75 us (K loops of 64 - 144 tiles; shorter ones were not measured in this class).
+// The gate is the imbalance itself, ceil(tiles / CUs) x CUs / tiles: what the busiest CU carries over the mean.  The two
+// measured ratios are 1.21 (1056 tiles) and 1.45 (528); from 1.2 on the persistent form is taken, below it -- 767 tiles
+// are three chains on all CUs but one, the 512 tiles of the FC layers two on every CU (measured: no gain) -- the plain
+// launch is already balanced and stays.  Launches with MORE tiles than places lose 3 - 50 % under the persistent form
+// whatever the number of workgroups per CU (profiles/r07_notes.md has the counters) and stay plain as well.
+static bool f32_tile_sk_wins(const ConvParams& p, int per_cu, int cus) {
+    const long long tiles = (long long)p.tiles_m * p.tiles_n;
+    if (tiles >= (long long)per_cu * cus || tiles < 2LL * cus || p.K / BK < 64) return false;
+    const long long busiest = (tiles + cus - 1) / cus * cus;
+    return busiest * 5 >= tiles * 6;        // imbalance >= 1.2
+}
+
+int g_f32_tile_sk = 1;              // tuning hook (brcnn_conv_set_tile(-5, 0 / 1 / 2)): persistent 64 x 64 launch never / heuristic / forced
+int g_f32_tile_sk_launches = 0;     // persistent launches so far (brcnn_conv_set_tile(-6, 0) reports it)
+int g_f32_tile_sk_wgs = 0;          // ... and the workgroups of the last one ((-6, 1))
+int g_f32_tile_sk_per_cu = 0;       // tuning hook ((-7, n)): workgroups per CU of the persistent launch, 0 = the occupancy query's
+int g_f32_num_cus = 0;
+
 template <int MT, int NT, bool RES>
-int launch_dma(const ConvParams& p, hipStream_t s) {
+int launch_dma(ConvParams& p, hipStream_t s, int persistent = 0) {      // persistent: 0 never, 1 heuristic, 2 forced
     const size_t lds = (size_t)2 * (64 * MT + 64 * NT) * 32 * sizeof(float);
+    if constexpr (MT == 1 && NT == 1) {
+        if (persistent) {
+            // exactly the resident workgroups (queried once; a surplus one only starts late: a K tail waits for the
+            // first item of the range below it, never for a higher one)
+            static int occ = -1;
+            if (occ < 0) {
+                BRCNN_HIP_CHECK(hipFuncSetAttribute((const void*)conv_igemm_f32_dma_kernel<1, 1, RES, true>,
+                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                int n = 0;
+                BRCNN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                    &n, (const void*)conv_igemm_f32_dma_kernel<1, 1, RES, true>, 256, lds));
+                if (g_f32_num_cus == 0) {
+                    int dev = 0;
+                    hipDeviceProp_t prop;
+                    BRCNN_HIP_CHECK(hipGetDevice(&dev));
+                    BRCNN_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+                    g_f32_num_cus = prop.multiProcessorCount;
+                }
+                occ = n;
+            }
+            const int per_cu = g_f32_tile_sk_per_cu > 0 && g_f32_tile_sk_per_cu < occ ? g_f32_tile_sk_per_cu : occ;
+            p.sk_wgs = 0;
+            if (persistent >= 2 || f32_tile_sk_wins(p, per_cu, g_f32_num_cus)) {
+                const int rc = sk_plan_f32_tile(p, per_cu, g_f32_num_cus, s);
+                if (rc) return rc;
+            }
+            if (p.sk_wgs > 0) {
+                hipLaunchKernelGGL((conv_igemm_f32_dma_kernel<1, 1, RES, true>), dim3(p.sk_wgs), dim3(256), lds, s, p);
+                BRCNN_LAUNCH_CHECK();
+                g_f32_tile_sk_launches = (g_f32_tile_sk_launches + 1) & 0x7fffffff;
+                g_f32_tile_sk_wgs = p.sk_wgs;
+                return 0;
+            }
+        }
+    }
     static bool attr_done = false;
     if (!attr_done) {
         BRCNN_HIP_CHECK(hipFuncSetAttribute((const void*)conv_igemm_f32_dma_kernel<MT, NT, RES>,
@@ -717,7 +873,10 @@ int dispatch_conv(ConvParams& p, hipStream_t s) {
     if (fast && g_use_dma && g_force_wm == 0 && g_force_nt == 0) {
         p.tiles_m = (p.M + 63) / 64;
         p.tiles_n = (p.Cout + 63) / 64;
-        return p.residual ? launch_dma<1, 1, true>(p, s) : launch_dma<1, 1, false>(p, s);
+        // the persistent, balanced launch (one contiguous range of tile x K-tile iterations per workgroup; same bits)
+        // where the table says it wins (f32_tile_sk_wins); never for grouped, scattering or zero-stuffed launches
+        const int sk = (!p.scatter && !p.gstep && p.dilate <= 1) ? g_f32_tile_sk : 0;
+        return p.residual ? launch_dma<1, 1, true>(p, s, sk) : launch_dma<1, 1, false>(p, s, sk);
     }
     int nt = (fast || p.Cout <= 64) ? 1 : 2;
     if (g_force_nt == 1 || (g_force_nt == 2 && p.Cout > 64)) nt = g_force_nt;
@@ -749,6 +908,10 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
     if (wm == -1) { g_use_dma = nt; return 0; }   // (-1, 0/1/2): register-staged / heuristic / always LDS-DMA
     if (wm == -3) { if (nt < 0 || nt > 2) return BRCNN_EINVAL; g_pp_f32_n128 = nt; return 0; }
     if (wm == -4) { if (nt != 0 && nt != 1) return BRCNN_EINVAL; g_no_fast = nt; return 0; }
+    if (wm == -5) { if (nt < 0 || nt > 2) return BRCNN_EINVAL; g_f32_tile_sk = nt; return 0; }
+    if (wm == -7) { if (nt < 0 || nt > 8) return BRCNN_EINVAL; g_f32_tile_sk_per_cu = nt; return 0; }
+    // (-6, 0): persistent 64 x 64 launches so far (>= 0), (-6, 1): workgroups of the last one
+    if (wm == -6) return nt == 0 ? g_f32_tile_sk_launches : nt == 1 ? g_f32_tile_sk_wgs : BRCNN_EINVAL;
     if (wm == -2) { if (nt != 0 && nt != 1 && nt != 2 && nt != 128 && nt != 256) return BRCNN_EINVAL; g_pp_f32_mode = nt; return 0; }
     if ((wm != 0 && wm != 1 && wm != 2 && wm != 4) || nt < 0 || nt > 2) return BRCNN_EINVAL;
     g_force_wm = wm;

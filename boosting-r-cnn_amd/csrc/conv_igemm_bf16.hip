@@ -999,7 +999,7 @@ int sk_table(long long tiles, int nk, int slots, const SkTable** out) {
 // its XCD has been started.
 int sk_table_par(long long tiles, int nk, int slots, const SkTable** out) {
     for (auto& t : g_sk_tables)
-        if (t.tiles == tiles && t.nk == nk && t.slots == slots && t.par) { *out = &t; return 0; }
+        if (t.tiles == tiles && t.nk == nk && t.slots == slots && t.par == 1) { *out = &t; return 0; }
     struct Item { int tile, kb, ke, w; };
     std::vector<Item> storing, finishing;
     const long long iters = tiles * nk;
@@ -1047,11 +1047,67 @@ int sk_table_par(long long tiles, int nk, int slots, const SkTable** out) {
     return 0;
 }
 
+// Range table of a PERSISTENT launch (fp32 64 x 64 kernel, conv_igemm.hip): `slots` workgroups, one contiguous range of
+// the tiles x nk iteration space each.  Block b walks the range of logical workgroup w = xcd_remap(b) (an XCD's blocks
+// own a contiguous run of tiles), cut into at most three kinds of item in this order: the K head of the tile the range
+// ends in (hand-over slot w), the whole tiles in ascending order, the K tail of the tile the range starts in (slot
+// w - 1: the head the range below publishes as its first item).  Layout: [slots x (first item, count, 0, 0) | items].
+int sk_table_ranges(long long tiles, int nk, int slots, const SkTable** out) {
+    for (auto& t : g_sk_tables)
+        if (t.tiles == tiles && t.nk == nk && t.slots == slots && t.par == 2) { *out = &t; return 0; }
+    const long long iters = tiles * nk, q = iters / slots, r = iters % slots;
+    if (q < nk) return BRCNN_EINVAL;                // a range inside one tile: the caller requires tiles >= slots
+    std::vector<int4> index((size_t)slots), items;
+    const int cq = slots >> 3, cr = slots & 7;
+    for (int b = 0; b < slots; b++) {
+        const int x = b & 7, loc = b >> 3;
+        const int w = ((x < cr) ? x * (cq + 1) : cr * (cq + 1) + (x - cr) * cq) + loc;        // xcd_remap(b, slots)
+        const long long sw = q * w + (w < r ? w : r), ew = sw + q + (w < r ? 1 : 0);
+        const long long t_first = sw / nk, t_end = ew / nk;         // tile holding sw; first tile not wholly below ew
+        const int kb = (int)(sw - t_first * nk), ke = (int)(ew - t_end * nk);
+        const int first = slots + (int)items.size();
+        if (ke > 0) items.push_back(make_int4((int)t_end, 0, ke, w));
+        for (long long t = t_first + (kb > 0 ? 1 : 0); t < t_end; t++) items.push_back(make_int4((int)t, 0, nk, 0));
+        if (kb > 0) items.push_back(make_int4((int)t_first, kb, nk, w - 1));
+        index[(size_t)b] = make_int4(first, slots + (int)items.size() - first, 0, 0);
+    }
+    index.insert(index.end(), items.begin(), items.end());
+    SkTable t = {tiles, nk, slots, slots, nullptr, 2};
+    BRCNN_HIP_CHECK(hipMalloc((void**)&t.items, index.size() * sizeof(int4)));
+    BRCNN_HIP_CHECK(hipMemcpy(t.items, index.data(), index.size() * sizeof(int4), hipMemcpyHostToDevice));
+    if (g_sk_tables.capacity() < 256) g_sk_tables.reserve(256);
+    if (g_sk_tables.size() >= 256) { (void)hipFree(t.items); return BRCNN_EINVAL; }
+    g_sk_tables.push_back(t);
+    *out = &g_sk_tables.back();
+    return 0;
+}
+
 // OFF by default: it is the one schedule whose result is not the unsplit chain's bits, so with it the value of a conv
 // would depend on the tile count -- i.e. on the batch size (the batched and the per-image paths stop agreeing bit for
 // bit, tests/test_golden_gpu.py) -- for +0.7 % on the fp32 inference pass (25.20 -> 25.02 ms; stage-4 3x3 402 -> 369 us,
 // first FC 476 -> 413 us, 2048 -> 512 1x1 184 -> 166 us); bf16 gains nothing (tools/experiments/splitk_try.py).
 int g_sk_par = 0;       // tuning hook (set_tile_bf16(-8 / -9 / -10)): split-K of few-tile launches off / heuristic / forced
+
+// under stream capture (brcnn/graphs.py: the trunk's forward / backward as HIP graphs) the launch is replayed with the
+// epoch baked into its arguments, and a flag left behind by the previous replay would pass for this one's: captured
+// launches take the plain schedule (same bits: the chained forms only move work between workgroups)
+static bool sk_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
+
+// a planned launch: the next epoch of the stream, its hand-over slots and flags, the item table (g_sk_mutex held)
+static void sk_fill(ConvParams& p, SkStream& st, const SkTable& tab) {
+    if (++st.epoch == 0) st.epoch = 1;
+    p.sk_wgs = tab.blocks;
+    p.sk_items = tab.items;
+    p.sk_ws = st.ws;
+    p.sk_flags = st.flags;
+    p.sk_epoch = st.epoch;
+    p.sk_err = g_sk_err_dev;
+    p.sk_spin_limit = g_sk_spin_limit;
+    p.sk_drop_publish = g_sk_drop_publish;
+}
 
 // the schedule of one launch, or sk_wgs = 0: `slots` = resident workgroups of this kernel on the whole device;
 // `min_nk`: shortest K loop (in K tiles) the heuristic cuts for this tile shape (0: the 128 x 128 rule below)
@@ -1059,13 +1115,7 @@ static int sk_plan(ConvParams& p, int slots, int bm, int bn, hipStream_t s, int 
     p.sk_wgs = 0;
     if (int e = sk_take_error()) return e;          // a K tail of an EARLIER launch gave up waiting for its head
     if (g_sk_mode == 0 || slots <= 0 || slots > SK_MAX_SLOTS) return 0;
-    {
-        // under stream capture (brcnn/graphs.py: the trunk's forward / backward as HIP graphs) the launch is replayed with
-        // the epoch baked into its arguments, and a flag left behind by the previous replay would pass for this one's:
-        // captured launches take the plain schedule (same bits: the chained form only moves work between workgroups)
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return 0;
-    }
+    if (sk_capturing(s)) return 0;
     const long long tiles = (long long)p.tiles_m * p.tiles_n;
     const int nk = p.K / bke;
     if (nk < 2 || tiles * nk >= 0x7fffffffLL) return 0;
@@ -1083,15 +1133,7 @@ static int sk_plan(ConvParams& p, int slots, int bm, int bn, hipStream_t s, int 
         const SkTable* tab = nullptr;
         rc = sk_table_par(tiles, nk, slots, &tab);
         if (rc) return rc == BRCNN_EINVAL ? 0 : rc;
-        if (++st->epoch == 0) st->epoch = 1;
-        p.sk_wgs = tab->blocks;
-        p.sk_items = tab->items;
-        p.sk_ws = st->ws;
-        p.sk_flags = st->flags;
-        p.sk_epoch = st->epoch;
-        p.sk_err = g_sk_err_dev;
-        p.sk_spin_limit = g_sk_spin_limit;
-        p.sk_drop_publish = g_sk_drop_publish;
+        sk_fill(p, *st, *tab);
         return 0;
     }
     // every slot must own at least one whole tile's worth of iterations: a tile then straddles two ranges at most
@@ -1115,15 +1157,7 @@ static int sk_plan(ConvParams& p, int slots, int bm, int bn, hipStream_t s, int 
     const SkTable* tab = nullptr;
     rc = sk_table(tiles, nk, slots, &tab);
     if (rc) return rc == BRCNN_EINVAL ? 0 : rc;
-    if (++st->epoch == 0) st->epoch = 1;
-    p.sk_wgs = tab->blocks;
-    p.sk_items = tab->items;
-    p.sk_ws = st->ws;
-    p.sk_flags = st->flags;
-    p.sk_epoch = st->epoch;
-    p.sk_err = g_sk_err_dev;
-    p.sk_spin_limit = g_sk_spin_limit;
-    p.sk_drop_publish = g_sk_drop_publish;
+    sk_fill(p, *st, *tab);
     return 0;
 }
 
@@ -1248,6 +1282,36 @@ int sk_plan_pp(ConvParams& p, int slots, int bm, int bn, hipStream_t s) { return
 bool sk_par_enabled() { return g_sk_par != 0 && g_sk_mode != 0; }
 // fp32 (K tiles of 32 values, 16x the MFMA time per tile): a hand-over is cheap against a tile, any idle CU is not
 int sk_plan_pp_f32(ConvParams& p, int slots, int bm, int bn, hipStream_t s) { return sk_plan(p, slots, bm, bn, s, 8, 32, 0.97); }
+
+// persistent launch of the fp32 64 x 64 kernel: the caller (dispatch_conv) decides per shape whether it pays; here only
+// what the schedule itself needs
+int sk_plan_f32_tile(ConvParams& p, int per_cu, int cus, hipStream_t s) {
+    p.sk_wgs = 0;
+    if (int e = sk_take_error()) return e;          // a K tail of an EARLIER launch gave up waiting for its head
+    if (g_sk_mode == 0 || per_cu <= 0 || cus <= 0) return 0;
+    // fewer tiles than resident workgroups (the 25 x 42 maps at batch 8: 1056 tiles for 5 x 256 places -- 32 CUs would
+    // carry five K chains, the others four): as many workgroups per CU as there are whole tiles for, two at least (one
+    // wave per SIMD hides no latency at all)
+    if ((long long)p.tiles_m * p.tiles_n < (long long)per_cu * cus) per_cu = (int)((long long)p.tiles_m * p.tiles_n / cus);
+    if (per_cu < 2) return 0;
+    const int slots = per_cu * cus;
+    if (slots > SK_MAX_SLOTS) return 0;
+    if (sk_capturing(s)) return 0;
+    const long long tiles = (long long)p.tiles_m * p.tiles_n;
+    const int nk = p.K / 32;
+    // (tiles >= slots: a range never lies inside one tile -- no three-way split)
+    if (nk < 2 || (p.K % 32) || tiles < slots || tiles * nk >= 0x7fffffffLL) return 0;
+    if ((size_t)slots * 64 * 64 * sizeof(float) > SK_WS_BYTES) return 0;
+    std::lock_guard<std::mutex> lock(g_sk_mutex);
+    SkStream* st = nullptr;
+    int rc = sk_stream_state(s, &st);
+    if (rc) return rc;
+    const SkTable* tab = nullptr;
+    rc = sk_table_ranges(tiles, nk, slots, &tab);
+    if (rc) return rc == BRCNN_EINVAL ? 0 : rc;
+    sk_fill(p, *st, *tab);
+    return 0;
+}
 
 // fp16 operands: the production tile shapes only (the tuning-hook variants stay bf16)
 static int dispatch_conv_f16(ConvParams& p, hipStream_t s) {

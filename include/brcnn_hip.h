@@ -332,8 +332,14 @@ int brcnn_conv_handover_status(void);
  * 128-row x 256-column tiles, two wave groups alternating MFMA and load blocks, chained stream-K) never /
  * by the heuristic / forced, forced with 128- / 256-row tiles.  (-3, 0 / 1 / 2): its 256 x 128 form for layers with 128
  * output channels never / by the heuristic / forced.  (-4, 0 / 1): test hook -- 1 = every conv launch (all dtypes) takes the
- * general set-up and read-out instead of the straight-line forms of full tiles and plain 1x1 layers.  Every choice gives the
- * same bits. */
+ * general set-up and read-out instead of the straight-line forms of full tiles and plain 1x1 layers.  (-5, 0 / 1 / 2): the
+ * persistent launch of the fp32 64 x 64 kernel (exactly the resident workgroups, one contiguous range of tile x K-tile
+ * iterations each, chained hand-over of the tiles a range boundary cuts) never / by the heuristic / wherever the schedule
+ * allows (not under stream capture, with fewer than two tiles per CU, on one-K-tile, grouped, scattering or zero-stuffed
+ * launches; a launch with fewer tiles than resident workgroups runs tiles / CUs workgroups per CU).  (-6, 0) returns the
+ * number of persistent launches so far (>= 0), (-6, 1) the workgroups of the last one.  (-7, n): at most n workgroups per
+ * CU in the persistent launch, 0 = as many as are resident (tools/f32_tile_persistent_bench.py).
+ * Every choice gives the same bits. */
 int brcnn_conv_set_tile(int wm, int nt);
 
 /* Tuning hook of the bf16 kernel: 0 heuristic; 11 / 21 / 22 = 64x64 / 128x64 / 128x128 tile on
