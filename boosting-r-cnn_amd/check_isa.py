@@ -53,7 +53,10 @@ _SYM = re.compile(r'^[0-9a-f]+ <(.+)>:')
 
 
 def device_code_object(obj, workdir):
-    """extract the gfx950 code object of a hipcc-compiled host object into `workdir`; returns its path"""
+    """extract the gfx950 code object of a hipcc-compiled host object into `workdir`; returns its path, or None for an
+    object of host code only (no `.hip_fatbin` section: csrc/policy.hip)"""
+    if '.hip_fatbin' not in subprocess.run([objdump(), '-h', obj], check=True, capture_output=True, text=True).stdout:
+        return None
     tmp = os.path.join(workdir, os.path.basename(obj))
     shutil.copy(obj, tmp)           # llvm-objdump --offloading writes the bundle entries next to its input
     subprocess.run([objdump(), '--offloading', tmp], check=True, capture_output=True)
@@ -139,6 +142,8 @@ def check_objects(objs, verbose=False, hipcc=None):
     with tempfile.TemporaryDirectory() as wd:
         for obj in objs:
             co = device_code_object(obj, wd)
+            if co is None:
+                continue
             bad, total, bcast = swizzled_packed_fp32(co)
             if verbose:
                 print(f'{os.path.basename(obj):32s} packed-fp32 instructions {total:6d}  broadcast form {bcast:5d}  cross-swizzled {len(bad)}')

@@ -14,6 +14,7 @@
 // makes the wait-count pass drain vmcnt in front of it (it cannot tell the ring from the slabs), which would serialise
 // the prefetch with the read-out.  Loads into registers (residual) are ordinary code: the compiler counts those itself.
 #include "conv_common.h"
+#include "policy.h"
 
 namespace {
 using namespace brcnn_conv;
@@ -296,19 +297,18 @@ int launch_stream(ConvParams& p, hipStream_t s) {
     return 0;
 }
 
-// tuning hook (brcnn_conv_set_tile_bf16(-15 / -16 / -17)): never / heuristic / wherever the shape allows.  Measured per layer
+// policy.h stream_mode: never / heuristic / wherever the shape allows.  Measured per layer
 // (tools/experiments/stream1x1.py, M = 537600 / 134400, bf16): K = 64 no residual N = 256 116-121 -> 81-88 us, K = 128 + residual
 // N = 512 84-88 -> 65-70 us, the others within 4 % (K = 64 + residual 138 -> 134, K = 128 no residual 54-57 -> 53-58, N = 128
 // 46-47 -> 45-49); bf16 inference step, interleaved on one box: off 6.49, those two cases only 6.44, every eligible layer
 // 6.39 ms -- the heuristic takes every eligible layer
-int g_stream_mode = 1;
 
 }  // namespace
 
 namespace brcnn_conv {
 // 1 launched, 0 not this kernel's shape, < 0 error
 int conv1x1_stream_try(ConvParams& p, hipStream_t s, int f16) {
-    if (g_stream_mode == 0 || p.no_fast) return 0;
+    if (brcnn::g_policy.stream_mode == 0 || p.no_fast) return 0;
     const bool plain = p.KH == 1 && p.KW == 1 && p.stride == 1 && p.pad == 0 && p.nseg == 1 && p.dilate <= 1;
     if (!plain || p.scatter || p.gstep || p.out_f32 || p.z_out || p.tail_z || p.tail_mask || p.sk_wgs) return 0;
     if ((p.K != 64 && p.K != 128) || (p.Cout % SBN) || p.pitch != p.Cin || p.M < 4096 || (long long)p.M * p.Cout * 2 >= 0x7fffffffLL) return 0;
@@ -319,6 +319,4 @@ int conv1x1_stream_try(ConvParams& p, hipStream_t s, int f16) {
     if (f16) return (p.residual ? launch_stream<2, true, 1>(p, s) : launch_stream<2, false, 1>(p, s)) ? BRCNN_EINVAL : 1;
     return (p.residual ? launch_stream<2, true, 0>(p, s) : launch_stream<2, false, 0>(p, s)) ? BRCNN_EINVAL : 1;
 }
-int conv1x1_stream_set(int mode) { g_stream_mode = mode; return 0; }
-int tuning_get_persistent_1x1() { return g_stream_mode; }
 }  // namespace brcnn_conv

@@ -152,7 +152,6 @@ __device__ __forceinline__ unsigned brcnn_relu_pk(unsigned w, unsigned floor2) {
 
 // persistent streaming kernel of the short-K plain 1x1 layers (conv1x1_stream_bf16.hip): 1 launched, 0 not taken, < 0 error
 int conv1x1_stream_try(ConvParams& p, hipStream_t s, int f16);
-int conv1x1_stream_set(int mode);
 // bf16 dispatch (conv_igemm_bf16.hip)
 int dispatch_conv_bf16(ConvParams& p, hipStream_t s);
 // 256 x 256 tile on the eight-phase two-group schedule (conv_pp_bf16.hip)
@@ -182,8 +181,6 @@ unsigned* conv_ws_wgrad_counters(hipStream_t s);   // 8192 zero-initialised, sel
 int wgrad_pp_bf16_try(const void* x, const void* dy, void* dw, int batch, int num_segments, const int* heights_host,
                       const int* widths_host, int cin, int cout, int kh, int kw, int stride, int pad, hipStream_t stream,
                       int f16);
-int wgrad_pp_set(int v);
-bool sk_par_enabled();       // split-K of few-tile launches is on (conv_igemm_bf16.hip, sk_table_par)
 // the same schedule on the exact-fp32 MFMA (conv_pp_f32.hip); plain epilogue
 int dispatch_conv_pp_f32(ConvParams& p, hipStream_t s);
 

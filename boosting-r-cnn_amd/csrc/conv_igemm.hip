@@ -31,6 +31,7 @@
 // Several feature maps that share one set of weights (pyramid levels) run as ONE launch: the
 // output rows of the segments are concatenated and each row carries its own geometry.
 #include "conv_common.h"
+#include "policy.h"
 
 namespace {
 using namespace brcnn_conv;
@@ -752,10 +753,6 @@ static bool f32_tile_sk_wins(const ConvParams& p, int per_cu, int cus) {
     return busiest * 5 >= tiles * 6;        // imbalance >= 1.2
 }
 
-int g_f32_tile_sk = 1;              // tuning hook (brcnn_conv_set_tile(-5, 0 / 1 / 2)): persistent 64 x 64 launch never / heuristic / forced
-int g_f32_tile_sk_launches = 0;     // persistent launches so far (brcnn_conv_set_tile(-6, 0) reports it)
-int g_f32_tile_sk_wgs = 0;          // ... and the workgroups of the last one ((-6, 1))
-int g_f32_tile_sk_per_cu = 0;       // tuning hook ((-7, n)): workgroups per CU of the persistent launch, 0 = the occupancy query's
 int g_f32_num_cus = 0;
 
 template <int MT, int NT, bool RES>
@@ -781,7 +778,7 @@ int launch_dma(ConvParams& p, hipStream_t s, int persistent = 0) {      // persi
                 }
                 occ = n;
             }
-            const int per_cu = g_f32_tile_sk_per_cu > 0 && g_f32_tile_sk_per_cu < occ ? g_f32_tile_sk_per_cu : occ;
+            const int per_cu = brcnn::g_policy.f32_tile_sk_per_cu > 0 && brcnn::g_policy.f32_tile_sk_per_cu < occ ? brcnn::g_policy.f32_tile_sk_per_cu : occ;
             p.sk_wgs = 0;
             if (persistent >= 2 || f32_tile_sk_wins(p, per_cu, g_f32_num_cus)) {
                 const int rc = sk_plan_f32_tile(p, per_cu, g_f32_num_cus, s);
@@ -790,8 +787,8 @@ int launch_dma(ConvParams& p, hipStream_t s, int persistent = 0) {      // persi
             if (p.sk_wgs > 0) {
                 hipLaunchKernelGGL((conv_igemm_f32_dma_kernel<1, 1, RES, true>), dim3(p.sk_wgs), dim3(256), lds, s, p);
                 BRCNN_LAUNCH_CHECK();
-                g_f32_tile_sk_launches = (g_f32_tile_sk_launches + 1) & 0x7fffffff;
-                g_f32_tile_sk_wgs = p.sk_wgs;
+                brcnn::g_counters.f32_tile_sk_launches = (brcnn::g_counters.f32_tile_sk_launches + 1) & 0x7fffffff;
+                brcnn::g_counters.f32_tile_sk_wgs = p.sk_wgs;
                 return 0;
             }
         }
@@ -828,40 +825,33 @@ int launch_res(const ConvParams& p, hipStream_t s) {
     return p.residual ? launch_conv<FAST, WM, NT, true>(p, s) : launch_conv<FAST, WM, NT, false>(p, s);
 }
 
-int g_use_dma = 1;                      // LDS-DMA staged kernel for the FAST path
-int g_force_wm = 0, g_force_nt = 0;   // tuning hooks (brcnn_conv_set_tile): 0 = heuristic
-
-int g_no_fast = 0;          // test hook (brcnn_conv_set_tile(-4, 0 / 1)): 1 = no straight-line read-out, no plain-layer set-up (every kernel, every dtype)
-int g_pp_f32_n128 = 1;      // tuning hook (brcnn_conv_set_tile(-3, 0 / 1 / 2)): the 256 x 128 eight-phase tile never / heuristic / forced
-int g_pp_f32_mode = 1;      // tuning hook (brcnn_conv_set_tile(-2, 0 / 1 / 2 / 128 / 256)): eight-phase fp32 kernel never / heuristic / forced (tile rows by the heuristic / 128 / 256)
-
 int dispatch_conv(ConvParams& p, hipStream_t s) {
     const bool fast = (p.Cin % 32 == 0);
     // The 256 x 256 eight-phase kernel (conv_pp_f32.hip; bit-identical results) where its tiles cover the device: whole
     // 256-channel column tiles and at least ~0.8 generations of tiles (one workgroup per CU; from 256 tiles on the
     // chained stream-K schedule evens out the last generation)
-    if (fast && g_pp_f32_mode && g_force_wm == 0 && g_force_nt == 0 && !p.gstep && (p.Cout % 256) == 0 && p.K >= 256 &&
+    if (fast && brcnn::g_policy.pp_f32_mode && brcnn::g_policy.force_wm == 0 && brcnn::g_policy.force_nt == 0 && !p.gstep && (p.Cout % 256) == 0 && p.K >= 256 &&
         p.KH * p.KW <= 32 && !(p.dilate > 1 && p.residual)) {
         // (128-row tiles where 256-row ones would leave CUs idle: the stage-3 / stage-4 maps)
         const long long t48 = (long long)((p.M + 127) / 128) * (p.Cout / 256);
-        p.pp_rows = g_pp_f32_mode >= 128 ? g_pp_f32_mode : 0;
+        p.pp_rows = brcnn::g_policy.pp_f32_mode >= 128 ? brcnn::g_policy.pp_f32_mode : 0;
         // (a K = 256 layer with a residual stream is eight K tiles deep and output-bound: measured 6 % behind the
         // 64 x 64 kernel, tools/conv_bench.py "s3 1x1 256->1024 +res")
         // ... and the few-tile layers of the 25 x 42 maps (66-132 such tiles on 256 CUs) with a K loop of >= 64 tiles: split-K
         // pieces summed at the end fill the device (stage-4 3x3: 444 -> 380 us, 2048 -> 512 1x1: 185 -> 171 us; reproducible,
         // equal to the unsplit sum to fp32 round-off -- the one place where the kernel choice changes the association)
-        const bool few = sk_par_enabled() && t48 >= 64 && t48 < 208 && p.K / 32 >= 64 && p.dilate <= 1;
-        if (g_pp_f32_mode >= 2 || ((t48 >= 208 || few) && (p.K >= 512 || !p.residual))) return dispatch_conv_pp_f32(p, s);
+        const bool few = brcnn::g_policy.sk_par != 0 && brcnn::g_policy.sk_mode != 0 && t48 >= 64 && t48 < 208 && p.K / 32 >= 64 && p.dilate <= 1;
+        if (brcnn::g_policy.pp_f32_mode >= 2 || ((t48 >= 208 || few) && (p.K >= 512 || !p.residual))) return dispatch_conv_pp_f32(p, s);
     }
     // ... and its 256 x 128 form (r04) for the layers with 128 output channels (stage 2: 3x3 128->128, 1x1 256/512->128)
-    if (fast && g_pp_f32_mode && g_pp_f32_n128 && g_force_wm == 0 && g_force_nt == 0 && !p.gstep && (p.Cout % 256) != 0 &&
+    if (fast && brcnn::g_policy.pp_f32_mode && brcnn::g_policy.pp_f32_n128 && brcnn::g_policy.force_wm == 0 && brcnn::g_policy.force_nt == 0 && !p.gstep && (p.Cout % 256) != 0 &&
         (p.Cout % 128) == 0 && p.K >= 256 && p.KH * p.KW <= 32 && !(p.dilate > 1 && p.residual)) {
         const long long t = (long long)((p.M + 255) / 256) * (p.Cout / 128);
         p.pp_rows = 0;
         p.pp_cols = 128;
         // (measured, batch 8: stage-2 3x3 128->128 1.43 -> 1.38 ms for the four layers, 105 -> 112 TF/s; the K = 256 / 512 1x1
         // layers are output-bound and no faster than on the 64 x 64 tile: 3x3-deep K loops only)
-        if (g_pp_f32_n128 >= 2 || (t >= 208 && p.K >= 1024)) return dispatch_conv_pp_f32(p, s);
+        if (brcnn::g_policy.pp_f32_n128 >= 2 || (t >= 208 && p.K >= 1024)) return dispatch_conv_pp_f32(p, s);
         p.pp_cols = 0;
     }
     // Measured on MI355X (profiles/r01_conv_tiles.txt): with LDS-DMA staging the SMALLEST tile,
@@ -870,23 +860,23 @@ int dispatch_conv(ConvParams& p, hipStream_t s) {
     // of the network, the 12544-deep FC included: the kernel is bound by MFMA issue and
     // latency hiding, not by L2->LDS bytes, so it is the default.  The other shapes stay
     // reachable through brcnn_conv_set_tile (tools/conv_bench.py).
-    if (fast && g_use_dma && g_force_wm == 0 && g_force_nt == 0) {
+    if (fast && brcnn::g_policy.use_dma && brcnn::g_policy.force_wm == 0 && brcnn::g_policy.force_nt == 0) {
         p.tiles_m = (p.M + 63) / 64;
         p.tiles_n = (p.Cout + 63) / 64;
         // the persistent, balanced launch (one contiguous range of tile x K-tile iterations per workgroup; same bits)
         // where the table says it wins (f32_tile_sk_wins); never for grouped, scattering or zero-stuffed launches
-        const int sk = (!p.scatter && !p.gstep && p.dilate <= 1) ? g_f32_tile_sk : 0;
+        const int sk = (!p.scatter && !p.gstep && p.dilate <= 1) ? brcnn::g_policy.f32_tile_sk : 0;
         return p.residual ? launch_dma<1, 1, true>(p, s, sk) : launch_dma<1, 1, false>(p, s, sk);
     }
     int nt = (fast || p.Cout <= 64) ? 1 : 2;
-    if (g_force_nt == 1 || (g_force_nt == 2 && p.Cout > 64)) nt = g_force_nt;
+    if (brcnn::g_policy.force_nt == 1 || (brcnn::g_policy.force_nt == 2 && p.Cout > 64)) nt = brcnn::g_policy.force_nt;
     int wm = 2;
-    if (g_force_wm == 4 && fast && nt == 2) wm = 4;
+    if (brcnn::g_policy.force_wm == 4 && fast && nt == 2) wm = 4;
     p.tiles_m = (p.M + 64 * wm - 1) / (64 * wm);
     p.tiles_n = (p.Cout + 64 * nt - 1) / (64 * nt);
     if (!fast) return nt == 1 ? launch_res<false, 2, 1>(p, s) : launch_res<false, 2, 2>(p, s);
-    if (wm == 2 && g_use_dma) {
-        if (g_force_wm == 1) {
+    if (wm == 2 && brcnn::g_policy.use_dma) {
+        if (brcnn::g_policy.force_wm == 1) {
             p.tiles_m = (p.M + 63) / 64;
             p.tiles_n = (p.Cout + 63) / 64;
             return p.residual ? launch_dma<1, 1, true>(p, s) : launch_dma<1, 1, false>(p, s);
@@ -899,25 +889,6 @@ int dispatch_conv(ConvParams& p, hipStream_t s) {
 }
 
 }  // namespace
-
-namespace brcnn_conv {
-int tuning_get_eight_phase_f32() { return g_pp_f32_mode; }
-}  // namespace brcnn_conv
-
-BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
-    if (wm == -1) { g_use_dma = nt; return 0; }   // (-1, 0/1/2): register-staged / heuristic / always LDS-DMA
-    if (wm == -3) { if (nt < 0 || nt > 2) return BRCNN_EINVAL; g_pp_f32_n128 = nt; return 0; }
-    if (wm == -4) { if (nt != 0 && nt != 1) return BRCNN_EINVAL; g_no_fast = nt; return 0; }
-    if (wm == -5) { if (nt < 0 || nt > 2) return BRCNN_EINVAL; g_f32_tile_sk = nt; return 0; }
-    if (wm == -7) { if (nt < 0 || nt > 8) return BRCNN_EINVAL; g_f32_tile_sk_per_cu = nt; return 0; }
-    // (-6, 0): persistent 64 x 64 launches so far (>= 0), (-6, 1): workgroups of the last one
-    if (wm == -6) return nt == 0 ? g_f32_tile_sk_launches : nt == 1 ? g_f32_tile_sk_wgs : BRCNN_EINVAL;
-    if (wm == -2) { if (nt != 0 && nt != 1 && nt != 2 && nt != 128 && nt != 256) return BRCNN_EINVAL; g_pp_f32_mode = nt; return 0; }
-    if ((wm != 0 && wm != 1 && wm != 2 && wm != 4) || nt < 0 || nt > 2) return BRCNN_EINVAL;
-    g_force_wm = wm;
-    g_force_nt = nt;
-    return 0;
-}
 
 BRCNN_API int brcnn_conv2d_nhwc(const void* x, const void* w, const float* scale, const float* shift,
                                 const void* residual, void* y, int batch, int height, int width,
@@ -955,7 +926,7 @@ static int conv_setup_and_launch(const void* x, const void* w, const float* scal
     if (dilate > 1 && (cin % 32 != 0 || stride != 1)) return BRCNN_EINVAL;
     if (bf16 && (cout & 7) && !brcnn_out_f32(dtype) && residual) return BRCNN_EINVAL;
     ConvParams p = {};
-    p.no_fast = g_no_fast;
+    p.no_fast = brcnn::g_policy.no_fast;
     p.x = (const float*)x; p.w = (const float*)w; p.scale = scale; p.shift = shift;
     p.residual = (const float*)residual; p.y = (float*)y;
     p.batch = batch; p.Cin = cin; p.Cout = cout; p.KH = kh; p.KW = kw;
@@ -1109,7 +1080,7 @@ static int grouped_launch(const void* x, const void* w_tiles, const float* scale
     const int esz = dtype == BRCNN_DT_F32 ? 4 : 2;
     if (Ho <= 0 || Wo <= 0 || Ho >= 4096 || Wo >= 4096) return BRCNN_EINVAL;
     ConvParams p = {};
-    p.no_fast = g_no_fast;
+    p.no_fast = brcnn::g_policy.no_fast;
     p.x = (const float*)x; p.w = (const float*)w_tiles; p.scale = scale; p.shift = shift;
     p.residual = (const float*)residual; p.y = (float*)y;
     p.batch = batch; p.Cin = window; p.Cout = cout; p.KH = kh; p.KW = kw;

@@ -16,6 +16,7 @@
 #include <mutex>
 #include <vector>
 #include "conv_common.h"
+#include "policy.h"
 
 namespace {
 using namespace brcnn_conv;
@@ -806,9 +807,6 @@ std::vector<SkTable> g_sk_tables;
 // hand-over time-outs: ONE host-mapped word every K tail can write (system scope) and every launch wrapper reads
 unsigned* g_sk_err_host = nullptr;
 unsigned* g_sk_err_dev = nullptr;
-int g_sk_spin_limit = 1 << 24;       // ~5 s of polling; test hook -11 / -12: 256 polls and heads that do not publish / back
-int g_sk_drop_publish = 0;
-int g_sk_mode = 1;      // tuning hook (set_tile_bf16(-3 / -4 / -5)): 0 off, 1 heuristic, 2 wherever the tile count allows
 int g_num_cus = 0;
 
 static int sk_error_word() {
@@ -1082,11 +1080,10 @@ int sk_table_ranges(long long tiles, int nk, int slots, const SkTable** out) {
     return 0;
 }
 
-// OFF by default: it is the one schedule whose result is not the unsplit chain's bits, so with it the value of a conv
+// split-K of few-tile launches (policy.h sk_par) is OFF by default: the one schedule whose result is not the unsplit chain's bits, so with it the value of a conv
 // would depend on the tile count -- i.e. on the batch size (the batched and the per-image paths stop agreeing bit for
 // bit, tests/test_golden_gpu.py) -- for +0.7 % on the fp32 inference pass (25.20 -> 25.02 ms; stage-4 3x3 402 -> 369 us,
 // first FC 476 -> 413 us, 2048 -> 512 1x1 184 -> 166 us); bf16 gains nothing (tools/experiments/splitk_try.py).
-int g_sk_par = 0;       // tuning hook (set_tile_bf16(-8 / -9 / -10)): split-K of few-tile launches off / heuristic / forced
 
 // under stream capture (brcnn/graphs.py: the trunk's forward / backward as HIP graphs) the launch is replayed with the
 // epoch baked into its arguments, and a flag left behind by the previous replay would pass for this one's: captured
@@ -1105,8 +1102,8 @@ static void sk_fill(ConvParams& p, SkStream& st, const SkTable& tab) {
     p.sk_flags = st.flags;
     p.sk_epoch = st.epoch;
     p.sk_err = g_sk_err_dev;
-    p.sk_spin_limit = g_sk_spin_limit;
-    p.sk_drop_publish = g_sk_drop_publish;
+    p.sk_spin_limit = brcnn::g_policy.sk_spin_limit;
+    p.sk_drop_publish = brcnn::g_policy.sk_drop_publish;
 }
 
 // the schedule of one launch, or sk_wgs = 0: `slots` = resident workgroups of this kernel on the whole device;
@@ -1114,7 +1111,7 @@ static void sk_fill(ConvParams& p, SkStream& st, const SkTable& tab) {
 static int sk_plan(ConvParams& p, int slots, int bm, int bn, hipStream_t s, int min_nk = 0, int bke = BKE, double max_eff = 0.9) {
     p.sk_wgs = 0;
     if (int e = sk_take_error()) return e;          // a K tail of an EARLIER launch gave up waiting for its head
-    if (g_sk_mode == 0 || slots <= 0 || slots > SK_MAX_SLOTS) return 0;
+    if (brcnn::g_policy.sk_mode == 0 || slots <= 0 || slots > SK_MAX_SLOTS) return 0;
     if (sk_capturing(s)) return 0;
     const long long tiles = (long long)p.tiles_m * p.tiles_n;
     const int nk = p.K / bke;
@@ -1123,8 +1120,8 @@ static int sk_plan(ConvParams& p, int slots, int bm, int bn, hipStream_t s, int 
     if (tiles < slots) {
         // fewer tiles than resident workgroups: split-K with a sum at the end (eight-phase kernels only: min_nk > 0),
         // where at least a fifth of the device would idle and every piece keeps >= min_nk / 2 K tiles
-        if (min_nk <= 0 || g_sk_par == 0) return 0;
-        if (g_sk_par == 1 && (tiles * 5 > (long long)slots * 4 || tiles * nk / slots < min_nk / 2 || tiles * nk / slots < 4)) return 0;
+        if (min_nk <= 0 || brcnn::g_policy.sk_par == 0) return 0;
+        if (brcnn::g_policy.sk_par == 1 && (tiles * 5 > (long long)slots * 4 || tiles * nk / slots < min_nk / 2 || tiles * nk / slots < 4)) return 0;
         if (tiles * nk / slots < 2) return 0;
         std::lock_guard<std::mutex> lock(g_sk_mutex);
         SkStream* st = nullptr;
@@ -1137,7 +1134,7 @@ static int sk_plan(ConvParams& p, int slots, int bm, int bn, hipStream_t s, int 
         return 0;
     }
     // every slot must own at least one whole tile's worth of iterations: a tile then straddles two ranges at most
-    if (g_sk_mode == 1) {
+    if (brcnn::g_policy.sk_mode == 1) {
         // where it pays (tools/conv_bench_bf16.py, profiles/r03_notes.md): the 128 x 128 tile with a last generation of
         // workgroups that leaves most of the device idle and a K loop of >= 32 tiles -- every slot pays one hand-over
         // (a tile of fp32 accumulators each way, a second prologue), about a tenth of a tile's time; the smaller tiles
@@ -1241,10 +1238,9 @@ int launch2(ConvParams& p, hipStream_t s) {
 // The 256 x 256 eight-phase kernel (conv_pp_bf16.hip) where it wins (tools/conv_bench_bf16.py, profiles/r03_notes.md):
 // whole 256-channel column tiles, at least half a generation of tiles (one workgroup per CU; on 132 tiles it still
 // beats the small tiles' two full generations: 58 vs 70 us), K >= 512 (on the 1 - 4 K-tile layers the prologue and the
-// partly filled second generation cost more than the schedule returns).  g_pp_mode: 0 never, 1 heuristic.
-int g_pp_mode = 1;
+// partly filled second generation cost more than the schedule returns).
 static bool pp_wins(const ConvParams& p) {
-    if (g_pp_mode == 0 || p.gstep || (p.Cout % 256) || p.K < 512 || (p.K % 64) || p.KH * p.KW > 32 || p.scatter) return false;
+    if (brcnn::g_policy.pp_mode == 0 || p.gstep || (p.Cout % 256) || p.K < 512 || (p.K % 64) || p.KH * p.KW > 32 || p.scatter) return false;
     if (p.tail_z && p.tail_mask) return false;
     const long long t88 = (long long)((p.M + 255) / 256) * (p.Cout / 256);
     return t88 >= 128;
@@ -1257,29 +1253,21 @@ static bool pp_wins(const ConvParams& p) {
 // fp32 accumulators each way per slot) costs what the second generation would.  It wins where neither of the other kernels
 // has a shape: few 256-row tiles AND a long K loop -- the stage-4 3x3 layers (M = 8400, N = 512, K = 4608: 71.5 -> 63.5 us).
 // The heuristic takes exactly those; `brcnn_conv_set_tile_bf16(8842)` forces it wherever its shape rules allow.
-// g_pp128_mode: 0 never, 1 heuristic.  g_pp128_min_k: shortest K the heuristic takes.
-int g_pp128_mode = 1;
-int g_pp128_min_k = 4096;
-int g_pp128_max_t88 = 128;      // N % 256 == 0 layers: 256 x 256 tiles from this count on (where pp_wins takes them)
 static bool pp128_ok(const ConvParams& p) {
     return !(p.gstep || (p.Cout % 128) || p.K < 192 || (p.K % 64) || p.KH * p.KW > 32 || p.scatter || (p.tail_z && p.tail_mask));
 }
 static bool pp128_wins(const ConvParams& p) {
-    if (g_pp128_mode == 0 || !pp128_ok(p) || p.K < g_pp128_min_k || p.KH * p.KW < 9) return false;     // (measured on 3x3 layers only)
+    if (brcnn::g_policy.pp128_mode == 0 || !pp128_ok(p) || p.K < brcnn::g_policy.pp128_min_k || p.KH * p.KW < 9) return false;     // (measured on 3x3 layers only)
     const long long tm = (p.M + 255) / 256;
-    if ((p.Cout % 256) == 0 && tm * (p.Cout / 256) >= g_pp128_max_t88) return false;
+    if ((p.Cout % 256) == 0 && tm * (p.Cout / 256) >= brcnn::g_policy.pp128_max_t88) return false;
     const long long t84 = tm * (p.Cout / 128);
     return t84 >= 128 && t84 <= 264;          // (one generation of workgroups: more go to the smaller tiles, several per CU)
 }
-
-int g_bf16_il = 0;     // tuning hook (set_tile_bf16(-1 / -2)): spread the LDS-DMA pieces between the MFMA groups
-int g_bf16_tile = 0;   // tuning hook: 0 heuristic, 11 / 21 / 22 = MT NT (4 waves), 42 = 256x128 (8 waves)
 
 }  // namespace
 
 namespace brcnn_conv {
 int sk_plan_pp(ConvParams& p, int slots, int bm, int bn, hipStream_t s) { return sk_plan(p, slots, bm, bn, s, 16); }
-bool sk_par_enabled() { return g_sk_par != 0 && g_sk_mode != 0; }
 // fp32 (K tiles of 32 values, 16x the MFMA time per tile): a hand-over is cheap against a tile, any idle CU is not
 int sk_plan_pp_f32(ConvParams& p, int slots, int bm, int bn, hipStream_t s) { return sk_plan(p, slots, bm, bn, s, 8, 32, 0.97); }
 
@@ -1288,7 +1276,7 @@ int sk_plan_pp_f32(ConvParams& p, int slots, int bm, int bn, hipStream_t s) { re
 int sk_plan_f32_tile(ConvParams& p, int per_cu, int cus, hipStream_t s) {
     p.sk_wgs = 0;
     if (int e = sk_take_error()) return e;          // a K tail of an EARLIER launch gave up waiting for its head
-    if (g_sk_mode == 0 || per_cu <= 0 || cus <= 0) return 0;
+    if (brcnn::g_policy.sk_mode == 0 || per_cu <= 0 || cus <= 0) return 0;
     // fewer tiles than resident workgroups (the 25 x 42 maps at batch 8: 1056 tiles for 5 x 256 places -- 32 CUs would
     // carry five K chains, the others four): as many workgroups per CU as there are whole tiles for, two at least (one
     // wave per SIMD hides no latency at all)
@@ -1327,7 +1315,7 @@ static int dispatch_conv_f16(ConvParams& p, hipStream_t s) {
     if (fill44 && p.Cout > 128) return launch2<2, 2, 4, 4, 2, 1>(p, s);
     if (p.Cout <= 64) return launch2<2, 1, 2, 2, 2, 1>(p, s);
     if (t22 < 256) return launch2<1, 1, 2, 2, 2, 1>(p, s);
-    const bool sk82 = g_sk_mode == 1 && (p.Cout % 128) == 0 && p.K >= 2048 && t22 >= 512 &&
+    const bool sk82 = brcnn::g_policy.sk_mode == 1 && (p.Cout % 128) == 0 && p.K >= 2048 && t22 >= 512 &&
                       (double)t22 / (double)(((t22 + 511) / 512) * 512) < 0.9;
     if (p.M >= 65536 || sk82) return launch2<1, 2, 4, 2, 2, 1>(p, s);
     if (p.M >= 16384) return launch2<1, 1, 4, 2, 2, 1>(p, s);
@@ -1336,12 +1324,12 @@ static int dispatch_conv_f16(ConvParams& p, hipStream_t s) {
 
 int dispatch_conv_bf16(ConvParams& p, hipStream_t s) {
     if (p.f16) return dispatch_conv_f16(p, s);
-    p.il = g_bf16_il;
-    if (g_bf16_tile == 0) {
+    p.il = brcnn::g_policy.bf16_il;
+    if (brcnn::g_policy.bf16_tile == 0) {
         if (const int rc = conv1x1_stream_try(p, s, 0)) return rc < 0 ? rc : 0;
     }
     if (p.gstep) return launch2<1, 1, 4, 2>(p, s);      // grouped conv: 64-channel N tiles (128x64 on 8 waves)
-    int t = ((p.z_out || p.tail_z) && g_bf16_tile != 8844 && g_bf16_tile != 8842) ? 0 : g_bf16_tile;
+    int t = ((p.z_out || p.tail_z) && brcnn::g_policy.bf16_tile != 8844 && brcnn::g_policy.bf16_tile != 8842) ? 0 : brcnn::g_policy.bf16_tile;
     if (t == 0 && pp128_wins(p)) return dispatch_conv_pp128_bf16(p, s);
     if (t == 0 && pp_wins(p)) return dispatch_conv_pp_bf16(p, s);
     if (t == 0) {
@@ -1358,7 +1346,7 @@ int dispatch_conv_bf16(ConvParams& p, hipStream_t s) {
                             (double)t44 / (double)(((t44 + 255) / 256) * 256) >= 0.85;
         // 128x128 under the stream-K schedule where its tile count sits just above a multiple of the 512 slots (the
         // stage-3 3x3 layers: 526 tiles) and K is long: 69 -> 65 us there, 214 -> 188 us on the 4608-deep layer
-        const bool sk82 = g_sk_mode == 1 && (p.Cout % 128) == 0 && p.K >= 2048 && t22 >= 512 &&
+        const bool sk82 = brcnn::g_policy.sk_mode == 1 && (p.Cout % 128) == 0 && p.K >= 2048 && t22 >= 512 &&
                           (double)t22 / (double)(((t22 + 511) / 512) * 512) < 0.9;
         if (fill44) t = 2244;
         else if (p.Cout <= 64) t = 21;
@@ -1394,30 +1382,4 @@ int dispatch_conv_bf16(ConvParams& p, hipStream_t s) {
 BRCNN_API int brcnn_conv_handover_status(void) {
     std::lock_guard<std::mutex> lock(g_sk_mutex);
     return sk_take_error();
-}
-
-namespace brcnn_conv {
-int tuning_get_stream_k() { return g_sk_mode; }
-int tuning_get_split_k() { return g_sk_par; }
-int tuning_get_eight_phase_16() { return g_pp_mode; }
-}  // namespace brcnn_conv
-
-BRCNN_API int brcnn_conv_set_tile_bf16(int mtnt) {
-    if (mtnt == -1 || mtnt == -2) { g_bf16_il = (mtnt == -1); return 0; }
-    if (mtnt <= -3 && mtnt >= -5) { g_sk_mode = -3 - mtnt; return 0; }       // stream-K: -3 off, -4 heuristic, -5 forced
-    if (mtnt <= -8 && mtnt >= -10) { g_sk_par = -8 - mtnt; return 0; }       // split-K of few-tile launches: -8 off, -9 heuristic, -10 forced
-    if (mtnt == -6 || mtnt == -7) { g_pp_mode = mtnt == -7; return 0; }      // eight-phase kernel: -6 never, -7 heuristic
-    if (mtnt == -18 || mtnt == -19) { g_pp128_mode = mtnt == -19; return 0; }   // 256 x 128 two-group kernel: -18 never, -19 heuristic
-    if (mtnt <= -1000 && mtnt > -2000) { g_pp128_min_k = -1000 - mtnt; return 0; }      // ... its shortest K (-1000 - K)
-    if (mtnt <= -2000 && mtnt > -3000) { g_pp128_max_t88 = -2000 - mtnt; return 0; }    // ... 256 x 256 tiles from this count on
-    // test hook: -11 = the K heads of the following stream-K launches do not publish and the tails give up after 256
-    // polls (a lost hand-over, to exercise BRCNN_EHANDOVER); -12 = back to normal
-    if (mtnt == -15 || mtnt == -16 || mtnt == -17) return conv1x1_stream_set(-15 - mtnt);      // persistent short-K 1x1 kernel never / heuristic / forced
-    if (mtnt == -11 || mtnt == -12) { g_sk_drop_publish = mtnt == -11; g_sk_spin_limit = mtnt == -11 ? 256 : 1 << 24; return 0; }
-    const int ok[] = {0, 11, 21, 22, 42, 82, 81, 164, 342, 382, 3164, 322, 482, 381, 2244, 2144, 8844, 8842};
-    bool found = false;
-    for (int v : ok) found |= (v == mtnt);
-    if (!found) return BRCNN_EINVAL;
-    g_bf16_tile = mtnt;
-    return 0;
 }

@@ -16,6 +16,7 @@
 #include <vector>
 #include "common.h"
 #include "conv_common.h"
+#include "policy.h"
 
 namespace {
 
@@ -368,10 +369,6 @@ __global__ __launch_bounds__(64 * WG * WG) void wgrad_reduce_kernel(float* __res
 // slab workspace of the sliced weight gradient: part of the stream's conv workspace (caller-provided through
 // brcnn_conv_set_workspace, conv_igemm_bf16.hip; launches on one stream are serialised)
 constexpr size_t WGRAD_WS_BYTES = (size_t)160 << 20;
-int g_wgrad_slabs = 1;       // tuning hook (brcnn_conv_set_tile_wgrad_bf16(10 / 11)): 0 atomics, 1 slabs + second stage
-int g_wgrad_slot_pct = 75;   // ... (2000 + n): n percent of a generation of workgroups per launch (75: the launches share the device with the main stream; same-box A/B 19.92 -> 19.75 ms per step, 50 % level, 35 % +0.9 ms)
-int g_wgrad_slot_pct_big = 75;   // ... (3000 + n): the same for launches of more than 2^17 reduction rows on the 256 x 256 tile
-int g_wgrad_two_pass = 24;   // ... (100 + n): more than n slices per tile -> the second stage runs as two passes
 
 void magic_for(unsigned d, unsigned* magic, unsigned* shift) {
     unsigned l = 0;
@@ -392,10 +389,10 @@ int launch(WgradHParams& p, hipStream_t s) {
     // tile of fp32 atomics into dW), each at least `minrows` reduction rows deep
     static int slots_env = getenv("BRCNN_WG_SLOTS") ? atoi(getenv("BRCNN_WG_SLOTS")) : 0;
     static int minrows = getenv("BRCNN_WG_MINROWS") ? atoi(getenv("BRCNN_WG_MINROWS")) : 1024;
-    // (g_wgrad_slot_pct: the weight-gradient launches share the device with the main stream's kernels -- a fraction of
+    // (wgrad_slot_pct: the weight-gradient launches share the device with the main stream's kernels -- a fraction of
     // a generation leaves them CUs and shrinks the slab traffic)
     const int slots = slots_env ? slots_env : (WG == 4 ? 256 : WT == 2 ? 512 : 1024) *
-                                                  ((WG == 4 && p.M >= (1 << 17)) ? g_wgrad_slot_pct_big : g_wgrad_slot_pct) / 100;
+                                                  ((WG == 4 && p.M >= (1 << 17)) ? brcnn::g_policy.wgrad_slot_pct_big : brcnn::g_policy.wgrad_slot_pct) / 100;
     int slices = slots / tiles;
     const int max_slices = (p.M + minrows - 1) / minrows;
     if (slices > max_slices) slices = max_slices;
@@ -413,7 +410,7 @@ int launch(WgradHParams& p, hipStream_t s) {
     }
     p.slab = nullptr;
     bool deferred = false;
-    if (g_wgrad_slabs && p.slices > 1 && (size_t)tiles * p.slices * T * T * sizeof(float) <= WGRAD_WS_BYTES) {
+    if (brcnn::g_policy.wgrad_slabs && p.slices > 1 && (size_t)tiles * p.slices * T * T * sizeof(float) <= WGRAD_WS_BYTES) {
         // second stage postponed to the stream's batched reduction (wgrad_defer.hip)?
         int derr = 0;
         p.slab = brcnn_conv::wgrad_defer_slabs(s, (size_t)tiles * p.slices * T * T * sizeof(float), &derr);
@@ -425,14 +422,14 @@ int launch(WgradHParams& p, hipStream_t s) {
     BRCNN_LAUNCH_CHECK();
     if (deferred) {
         int group = p.slices;
-        if (p.slices > g_wgrad_two_pass) {
+        if (p.slices > brcnn::g_policy.wgrad_two_pass) {
             group = 4;
             while (group * group < p.slices) group++;
         }
         brcnn_conv::wgrad_defer_push(s, p.slab, p.dw, tiles, p.tiles_k, p.slices, group, p.Cout, p.K, (WT << 4) | WG);
     } else if (p.slab) {
         int stride = 1, count = p.slices;
-        if (p.slices > g_wgrad_two_pass) {   // few output tiles, many slices: groups of ~sqrt(slices) first (more workgroups, shorter chains)
+        if (p.slices > brcnn::g_policy.wgrad_two_pass) {   // few output tiles, many slices: groups of ~sqrt(slices) first (more workgroups, shorter chains)
             int group = 4;
             while (group * group < p.slices) group++;
             const int ngroups = (p.slices + group - 1) / group;
@@ -449,8 +446,6 @@ int launch(WgradHParams& p, hipStream_t s) {
     return 0;
 }
 
-int g_wgrad_bf16_tile = 0;      // tuning hook: 0 heuristic, 1 = 64x64, 2 = 128x128, 4 = 256x256 (16 waves)
-
 }  // namespace
 
 // entry used by brcnn_conv2d_wgrad_nhwc_multi for dtype == BRCNN_DT_BF16
@@ -458,7 +453,7 @@ int brcnn_wgrad_bf16_dispatch(const void* x, const void* dy, void* dw, int batch
                               const int* heights_host, const int* widths_host, int cin, int cout,
                               int kh, int kw, int stride, int pad, hipStream_t stream, int f16) {
     if ((cin & 7) || (cout & 7)) return BRCNN_EINVAL;
-    if (g_wgrad_bf16_tile == 0) {       // the eight-phase 256 x 256 kernel where whole tiles and enough rows exist
+    if (brcnn::g_policy.wgrad_bf16_tile == 0) {       // the eight-phase 256 x 256 kernel where whole tiles and enough rows exist
         const int rc = brcnn_conv::wgrad_pp_bf16_try(x, dy, dw, batch, num_segments, heights_host, widths_host, cin, cout, kh, kw,
                                                      stride, pad, stream, f16);
         if (rc != 0) return rc < 0 ? rc : 0;
@@ -487,7 +482,7 @@ int brcnn_wgrad_bf16_dispatch(const void* x, const void* dy, void* dw, int batch
     p.K = kh * kw * cin;
     p.dy_bytes = (unsigned)(m_total * cout * 2);
     p.x_bytes = (unsigned)(x_off * 2);
-    int wt = g_wgrad_bf16_tile;
+    int wt = brcnn::g_policy.wgrad_bf16_tile;
     if (wt == 0) {
         wt = (cout >= 128 && p.K >= 128) ? 2 : 1;      // (K = 128, stage-2 conv3: 128 x 128 tile 42 us, 64 x 64 51 us)
         // 256 x 256 on 16 waves where the 128 x 128 tile is bound by its LDS-DMA traffic and one generation
@@ -504,27 +499,6 @@ int brcnn_wgrad_bf16_dispatch(const void* x, const void* dy, void* dw, int batch
     if (f16) return wt == 2 ? launch<2, 1>(p, stream) : launch<1, 1>(p, stream);
     return wt == 2 ? launch<2>(p, stream) : launch<1>(p, stream);
 }
-
-namespace brcnn_conv {
-int tuning_get_wgrad_slabs() { return g_wgrad_slabs; }
-int tuning_get_wgrad_generation_percent() { return g_wgrad_slot_pct; }
-}  // namespace brcnn_conv
-
-BRCNN_API int brcnn_conv_set_tile_wgrad_bf16(int wt) {
-    if (wt == 10 || wt == 11) { g_wgrad_slabs = wt - 10; return 0; }      // reduction over the M slices: atomics / slabs
-    if (wt >= 100 && wt < 1100) { g_wgrad_two_pass = wt - 100; return 0; }
-    if (wt >= 2010 && wt <= 2400) { g_wgrad_slot_pct = wt - 2000; return 0; }
-    if (wt >= 3010 && wt <= 3400) { g_wgrad_slot_pct_big = wt - 3000; return 0; }
-    // eight-phase kernel (conv_wgrad_pp_bf16.hip): 20 never / 21 heuristic / 22 wherever the shape allows; 4000 + n: n
-    // percent of the CUs per launch; 5000 + n: two reduce passes above n slices; 29: RETURNS the number of launches the
-    // eight-phase kernel took since the last query (tests); 30 / 31: its slab reduction as separate launches / inside the
-    // producing launch
-    if ((wt >= 20 && wt <= 22) || wt == 29 || wt == 30 || wt == 31 || (wt >= 4010 && wt <= 4400) || (wt >= 5001 && wt <= 5999)) return brcnn_conv::wgrad_pp_set(wt);
-    if (wt < 0 || wt == 3 || wt > 4) return BRCNN_EINVAL;
-    g_wgrad_bf16_tile = wt;
-    return 0;
-}
-
 
 // grouped variant (ResNeXt conv2): per 64-channel co tile a dense (64 x KH*KW*window) wgrad over the
 // tile's input window; called by brcnn_conv2d_wgrad_nhwc_grouped for dtype == BRCNN_DT_BF16

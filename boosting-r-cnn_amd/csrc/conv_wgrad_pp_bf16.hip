@@ -23,6 +23,7 @@
 // into dW (fixed order: reproducible), with 256-thread workgroups and eight loads in flight per thread.
 #include <type_traits>
 #include "conv_common.h"
+#include "policy.h"
 
 namespace {
 using namespace brcnn_conv;
@@ -548,12 +549,6 @@ __global__ __launch_bounds__(256) void wgrad_pp_reduce_kernel(float* __restrict_
 }
 
 constexpr int NOT_TAKEN = 1 << 20;     // launch(): the slabs would not fit the stream's workspace
-int g_wgrad_pp_mode = 1;        // tuning hook (brcnn_conv_set_tile_wgrad_bf16(20 / 21 / 22)): never / heuristic / wherever the shape allows
-int g_wgrad_pp_slot_pct = 75;   // ... (4000 + n): n percent of the CUs per launch (the launches share the device with the main stream)
-int g_wgrad_pp_two_pass = 24;
-int g_wgrad_pp_fuse = 0;         // ... (30 / 31): slab reduction as separate launches / inside the producing launch.  Measured (r04_notes.md):
-                                 // the in-launch form costs ~70 us per launch (one workgroup pulling 1-3 MB is latency-bound) -> off
-int g_wgrad_pp_launches = 0;     // launches taken so far (tests: hook 29 returns and clears it)
 
 void magic_for(unsigned d, unsigned* magic, unsigned* shift) {
     unsigned l = 0;
@@ -580,7 +575,7 @@ int launch(WgradPPParams& p, hipStream_t s) {
     const int tiles = p.tiles_co * p.tiles_k;
     // M slices: one generation of workgroups (one per CU: 128 KiB of LDS), at least 1024 reduction rows each; every
     // map is cut into its own slices (rows per slice: the smallest multiple of 64 with which the maps' slice counts fit)
-    const int slots = num_cus * g_wgrad_pp_slot_pct / 100;
+    const int slots = num_cus * brcnn::g_policy.wgrad_pp_slot_pct / 100;
     int budget = slots / tiles;
     const int max_slices = (p.M + 1023) / 1024;
     if (budget > max_slices) budget = max_slices;
@@ -607,7 +602,7 @@ int launch(WgradPPParams& p, hipStream_t s) {
     bool deferred = false;
     if (p.slices > 1) {
         if ((size_t)tiles * p.slices * TILE * TILE * sizeof(float) > ((size_t)160 << 20)) return NOT_TAKEN;
-        if (!g_wgrad_pp_fuse) {      // second stage postponed to the stream's batched reduction (wgrad_defer.hip)?
+        if (!brcnn::g_policy.wgrad_pp_fuse) {      // second stage postponed to the stream's batched reduction (wgrad_defer.hip)?
             int derr = 0;
             p.slab = wgrad_defer_slabs(s, (size_t)tiles * p.slices * TILE * TILE * sizeof(float), &derr);
             if (derr) return derr;
@@ -615,7 +610,7 @@ int launch(WgradPPParams& p, hipStream_t s) {
         }
         if (!p.slab) p.slab = conv_ws_wgrad_slabs(s);
         if (!p.slab) return BRCNN_EINVAL;
-        if (g_wgrad_pp_fuse) {      // groups of ~sqrt(slices): two serial passes of <= ~6 slabs each on the last arrivers
+        if (brcnn::g_policy.wgrad_pp_fuse) {      // groups of ~sqrt(slices): two serial passes of <= ~6 slabs each on the last arrivers
             int group = 2;
             while (group * group < p.slices) group++;
             const int ngroups = (p.slices + group - 1) / group;
@@ -627,19 +622,19 @@ int launch(WgradPPParams& p, hipStream_t s) {
             }
         }
     }
-    g_wgrad_pp_launches++;
+    brcnn::g_counters.wgrad_pp_launches++;
     hipLaunchKernelGGL((conv_wgrad_pp_bf16_kernel<ET, PLAIN>), dim3(tiles * p.slices), dim3(512), lds, s, p);
     BRCNN_LAUNCH_CHECK();
     if (deferred) {
         int group = p.slices;
-        if (p.slices > g_wgrad_pp_two_pass) {
+        if (p.slices > brcnn::g_policy.wgrad_pp_two_pass) {
             group = 4;
             while (group * group < p.slices) group++;
         }
         wgrad_defer_push(s, p.slab, p.dw, tiles, p.tiles_k, p.slices, group, p.Cout, p.K, 0);
     } else if (p.slab && p.fuse_group == 0) {
         int stride = 1, count = p.slices;
-        if (p.slices > g_wgrad_pp_two_pass) {
+        if (p.slices > brcnn::g_policy.wgrad_pp_two_pass) {
             int group = 4;
             while (group * group < p.slices) group++;
             const int ngroups = (p.slices + group - 1) / group;
@@ -664,11 +659,11 @@ namespace brcnn_conv {
 int wgrad_pp_bf16_try(const void* x, const void* dy, void* dw, int batch, int num_segments, const int* heights_host,
                       const int* widths_host, int cin, int cout, int kh, int kw, int stride, int pad, hipStream_t stream,
                       int f16) {
-    if (g_wgrad_pp_mode == 0) return 0;
+    if (brcnn::g_policy.wgrad_pp_mode == 0) return 0;
     const int K = kh * kw * cin;
     if ((cin & 63) || (cout & 7) || kh > 127 || kw > 255) return 0;
     const int tiles_co = (cout + TILE - 1) / TILE, tiles_k = (K + TILE - 1) / TILE;
-    if (g_wgrad_pp_mode == 1) {
+    if (brcnn::g_policy.wgrad_pp_mode == 1) {
         // whole 256-wide tiles on both axes (at most a seventh of the MFMA work on padding) and enough reduction rows
         if (cout < 256 || K < 256) return 0;
         if ((long long)tiles_co * TILE * tiles_k * TILE * 6 > (long long)cout * K * 7) return 0;
@@ -693,7 +688,7 @@ int wgrad_pp_bf16_try(const void* x, const void* dy, void* dw, int batch, int nu
     for (int s = num_segments; s <= BRCNN_MAX_LEVELS; s++) p.seg_m0[s] = (int)m_total;
     if (num_segments > 64) return 0;
     if (m_total * cout * 2 >= 0x7fffffffLL || x_off * 2 >= 0x7fffffffLL) return BRCNN_EINVAL;
-    if (g_wgrad_pp_mode == 1 && m_total < 4096) return 0;
+    if (brcnn::g_policy.wgrad_pp_mode == 1 && m_total < 4096) return 0;
     p.M = (int)m_total;
     p.K = K;
     p.dy_bytes = (unsigned)(m_total * cout * 2);
@@ -706,18 +701,6 @@ int wgrad_pp_bf16_try(const void* x, const void* dy, void* dw, int batch, int nu
     else rc = plain ? launch<0, true>(p, stream) : launch<0, false>(p, stream);
     if (rc == NOT_TAKEN) return 0;
     return rc ? rc : 1;
-}
-
-int tuning_get_wgrad_eight_phase() { return g_wgrad_pp_mode; }
-int tuning_get_wgrad_reduce_in_launch() { return g_wgrad_pp_fuse; }
-int tuning_get_wgrad_cu_percent() { return g_wgrad_pp_slot_pct; }
-int wgrad_pp_set(int v) {
-    if (v >= 20 && v <= 22) { g_wgrad_pp_mode = v - 20; return 0; }
-    if (v == 29) { const int n = g_wgrad_pp_launches; g_wgrad_pp_launches = 0; return n; }
-    if (v == 30 || v == 31) { g_wgrad_pp_fuse = v - 30; return 0; }
-    if (v >= 4010 && v <= 4400) { g_wgrad_pp_slot_pct = v - 4000; return 0; }
-    if (v >= 5001 && v <= 5999) { g_wgrad_pp_two_pass = v - 5000; return 0; }
-    return BRCNN_EINVAL;
 }
 
 }  // namespace brcnn_conv

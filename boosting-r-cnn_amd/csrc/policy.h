@@ -1,0 +1,63 @@
+// The library's tuning switches and test hooks as ONE table.  The integer hooks (brcnn_conv_set_tile*,
+// brcnn_roi_align_set_exact) and brcnn_get_tuning / brcnn_set_tuning (policy.hip) are the only writers; the dispatchers
+// read brcnn::g_policy.<member>.  A new switch is a member here (its default as the initialiser), a decoder line in
+// policy.hip and, if it is a product default, a brcnn_tuning field.  Process-wide, unsynchronised (include/brcnn_hip.h).
+#pragma once
+
+namespace brcnn {
+
+struct Policy {
+    // ---- fp32 conv (conv_igemm.hip): brcnn_conv_set_tile(wm, nt)
+    int use_dma = 1;                // LDS-DMA staged kernel for the FAST path; (-1, 0/1/2): register-staged / heuristic / always LDS-DMA
+    int force_wm = 0, force_nt = 0; // tuning hooks (brcnn_conv_set_tile): 0 = heuristic
+    int no_fast = 0;                // test hook (brcnn_conv_set_tile(-4, 0 / 1)): 1 = no straight-line read-out, no plain-layer set-up (every kernel, every dtype)
+    int pp_f32_n128 = 1;            // tuning hook (brcnn_conv_set_tile(-3, 0 / 1 / 2)): the 256 x 128 eight-phase tile never / heuristic / forced
+    int pp_f32_mode = 1;            // tuning hook (brcnn_conv_set_tile(-2, 0 / 1 / 2 / 128 / 256)): eight-phase fp32 kernel never / heuristic / forced (tile rows by the heuristic / 128 / 256)
+    int f32_tile_sk = 1;            // tuning hook (brcnn_conv_set_tile(-5, 0 / 1 / 2)): persistent 64 x 64 launch never / heuristic / forced
+    int f32_tile_sk_per_cu = 0;     // tuning hook ((-7, n)): workgroups per CU of the persistent launch, 0 = the occupancy query's
+
+    // ---- 16-bit conv (conv_igemm_bf16.hip, conv1x1_stream_bf16.hip): brcnn_conv_set_tile_bf16(mtnt)
+    int bf16_tile = 0;              // tuning hook: 0 heuristic, 11 / 21 / 22 = MT NT (4 waves), 42 = 256x128 (8 waves)
+    int bf16_il = 0;                // tuning hook (set_tile_bf16(-1 / -2)): spread the LDS-DMA pieces between the MFMA groups
+    int sk_mode = 1;                // tuning hook (set_tile_bf16(-3 / -4 / -5)): 0 off, 1 heuristic, 2 wherever the tile count allows
+    int sk_par = 0;                 // tuning hook (set_tile_bf16(-8 / -9 / -10)): split-K of few-tile launches off / heuristic / forced
+    int pp_mode = 1;                // eight-phase 256 x 256 kernel (set_tile_bf16(-6 / -7)): 0 never, 1 heuristic
+    int pp128_mode = 1;             // 256 x 128 two-group kernel (set_tile_bf16(-18 / -19)): 0 never, 1 heuristic
+    int pp128_min_k = 4096;         // ... (-1000 - K): shortest K the heuristic takes
+    int pp128_max_t88 = 128;        // ... (-2000 - n): N % 256 == 0 layers: 256 x 256 tiles from this count on (where pp_wins takes them)
+    int sk_spin_limit = 1 << 24;    // ~5 s of polling; test hook -11 / -12: 256 polls and heads that do not publish / back
+    int sk_drop_publish = 0;
+    int stream_mode = 1;            // persistent short-K 1x1 kernel (set_tile_bf16(-15 / -16 / -17)): never / heuristic / wherever the shape allows
+
+    // ---- 16-bit weight gradient (conv_wgrad_bf16.hip, conv_wgrad_pp_bf16.hip): brcnn_conv_set_tile_wgrad_bf16(wt)
+    int wgrad_bf16_tile = 0;        // tuning hook: 0 heuristic, 1 = 64x64, 2 = 128x128, 4 = 256x256 (16 waves)
+    int wgrad_slabs = 1;            // tuning hook (brcnn_conv_set_tile_wgrad_bf16(10 / 11)): 0 atomics, 1 slabs + second stage
+    int wgrad_slot_pct = 75;        // ... (2000 + n): n percent of a generation of workgroups per launch (75: the launches share the device with the main stream; same-box A/B 19.92 -> 19.75 ms per step, 50 % level, 35 % +0.9 ms)
+    int wgrad_slot_pct_big = 75;    // ... (3000 + n): the same for launches of more than 2^17 reduction rows on the 256 x 256 tile
+    int wgrad_two_pass = 24;        // ... (100 + n): more than n slices per tile -> the second stage runs as two passes
+    int wgrad_pp_mode = 1;          // tuning hook (brcnn_conv_set_tile_wgrad_bf16(20 / 21 / 22)): never / heuristic / wherever the shape allows
+    int wgrad_pp_slot_pct = 75;     // ... (4000 + n): n percent of the CUs per launch (the launches share the device with the main stream)
+    int wgrad_pp_two_pass = 24;     // ... (5000 + n): two reduce passes above n slices
+    int wgrad_pp_fuse = 0;          // ... (30 / 31): slab reduction as separate launches / inside the producing launch.  Measured (r04_notes.md):
+                                    // the in-launch form costs ~70 us per launch (one workgroup pulling 1-3 MB is latency-bound) -> off
+
+    // ---- RoI (roi_align.hip): brcnn_roi_align_set_exact(exact)
+    int roi_exact = 0;              // 1: exact sample-order kernel (bit-identical to the reference's CPU order)
+    int roi_stream_c = 3;           // footprint kernel: bit 0 column streaming over the bin row's patch (else the per-bin loop), bit 1 XCD-contiguous rows
+    int roi_prep = 0;               // ... (30 / 31): prepared-record form off / on where the caller provides its scratch.  OFF: measured
+                                    // slower below 1000 RoIs / image (profiles/r05_notes.md)
+    int roi_rpw = 0;                // tuning hook (set_exact(10 / 11 / 17)): rows per wave by the heuristic / 1 / all (stored 0 / 11 / 17)
+    int roi_order = 1;              // ... (20 / 21 / 22): never / where a workspace is given and the RoI count pays for the sort / always
+    int roi_gather_chunks = -1;     // tuning hook (brcnn_roi_align_set_exact(40 + n)): -1 heuristic, n chunks per coarse tile
+};
+extern Policy g_policy;
+
+// what the hooks report; the launch sites increment them
+struct Counters {
+    int f32_tile_sk_launches = 0;   // persistent launches so far (brcnn_conv_set_tile(-6, 0) reports it)
+    int f32_tile_sk_wgs = 0;        // ... and the workgroups of the last one ((-6, 1))
+    int wgrad_pp_launches = 0;      // launches taken so far (tests: hook 29 returns and clears it)
+};
+extern Counters g_counters;
+
+}  // namespace brcnn

@@ -1,0 +1,123 @@
+// The policy table (policy.h) and its two interfaces: the integer hooks decode their codes into members of g_policy,
+// brcnn_get_tuning / brcnn_set_tuning copy the public fields (include/brcnn_hip.h: brcnn_tuning).  Host code only.
+#include "common.h"
+#include "policy.h"
+
+__attribute__((require_constant_initialization)) brcnn::Policy brcnn::g_policy;
+__attribute__((require_constant_initialization)) brcnn::Counters brcnn::g_counters;
+using brcnn::g_counters, brcnn::g_policy;
+
+BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
+    if (wm == -1) { g_policy.use_dma = nt; return 0; }   // (-1, 0/1/2): register-staged / heuristic / always LDS-DMA
+    if (wm == -3) { if (nt < 0 || nt > 2) return BRCNN_EINVAL; g_policy.pp_f32_n128 = nt; return 0; }
+    if (wm == -4) { if (nt != 0 && nt != 1) return BRCNN_EINVAL; g_policy.no_fast = nt; return 0; }
+    if (wm == -5) { if (nt < 0 || nt > 2) return BRCNN_EINVAL; g_policy.f32_tile_sk = nt; return 0; }
+    if (wm == -7) { if (nt < 0 || nt > 8) return BRCNN_EINVAL; g_policy.f32_tile_sk_per_cu = nt; return 0; }
+    // (-6, 0): persistent 64 x 64 launches so far (>= 0), (-6, 1): workgroups of the last one
+    if (wm == -6) return nt == 0 ? g_counters.f32_tile_sk_launches : nt == 1 ? g_counters.f32_tile_sk_wgs : BRCNN_EINVAL;
+    if (wm == -2) { if (nt != 0 && nt != 1 && nt != 2 && nt != 128 && nt != 256) return BRCNN_EINVAL; g_policy.pp_f32_mode = nt; return 0; }
+    if ((wm != 0 && wm != 1 && wm != 2 && wm != 4) || nt < 0 || nt > 2) return BRCNN_EINVAL;
+    g_policy.force_wm = wm;
+    g_policy.force_nt = nt;
+    return 0;
+}
+
+BRCNN_API int brcnn_conv_set_tile_bf16(int mtnt) {
+    if (mtnt == -1 || mtnt == -2) { g_policy.bf16_il = (mtnt == -1); return 0; }
+    if (mtnt <= -3 && mtnt >= -5) { g_policy.sk_mode = -3 - mtnt; return 0; }       // stream-K: -3 off, -4 heuristic, -5 forced
+    if (mtnt <= -8 && mtnt >= -10) { g_policy.sk_par = -8 - mtnt; return 0; }       // split-K of few-tile launches: -8 off, -9 heuristic, -10 forced
+    if (mtnt == -6 || mtnt == -7) { g_policy.pp_mode = mtnt == -7; return 0; }      // eight-phase kernel: -6 never, -7 heuristic
+    if (mtnt == -18 || mtnt == -19) { g_policy.pp128_mode = mtnt == -19; return 0; }   // 256 x 128 two-group kernel: -18 never, -19 heuristic
+    if (mtnt <= -1000 && mtnt > -2000) { g_policy.pp128_min_k = -1000 - mtnt; return 0; }      // ... its shortest K (-1000 - K)
+    if (mtnt <= -2000 && mtnt > -3000) { g_policy.pp128_max_t88 = -2000 - mtnt; return 0; }    // ... 256 x 256 tiles from this count on
+    if (mtnt <= -15 && mtnt >= -17) { g_policy.stream_mode = -15 - mtnt; return 0; }      // persistent short-K 1x1 kernel never / heuristic / forced
+    // test hook: -11 = the K heads of the following stream-K launches do not publish and the tails give up after 256
+    // polls (a lost hand-over, to exercise BRCNN_EHANDOVER); -12 = back to normal
+    if (mtnt == -11 || mtnt == -12) { g_policy.sk_drop_publish = mtnt == -11; g_policy.sk_spin_limit = mtnt == -11 ? 256 : 1 << 24; return 0; }
+    const int ok[] = {0, 11, 21, 22, 42, 82, 81, 164, 342, 382, 3164, 322, 482, 381, 2244, 2144, 8844, 8842};
+    bool found = false;
+    for (int v : ok) found |= (v == mtnt);
+    if (!found) return BRCNN_EINVAL;
+    g_policy.bf16_tile = mtnt;
+    return 0;
+}
+
+BRCNN_API int brcnn_conv_set_tile_wgrad_bf16(int wt) {
+    if (wt == 10 || wt == 11) { g_policy.wgrad_slabs = wt - 10; return 0; }      // reduction over the M slices: atomics / slabs
+    if (wt >= 100 && wt < 1100) { g_policy.wgrad_two_pass = wt - 100; return 0; }
+    if (wt >= 2010 && wt <= 2400) { g_policy.wgrad_slot_pct = wt - 2000; return 0; }
+    if (wt >= 3010 && wt <= 3400) { g_policy.wgrad_slot_pct_big = wt - 3000; return 0; }
+    // eight-phase kernel (conv_wgrad_pp_bf16.hip): 20 never / 21 heuristic / 22 wherever the shape allows; 4000 + n: n
+    // percent of the CUs per launch; 5000 + n: two reduce passes above n slices; 29: RETURNS the number of launches the
+    // eight-phase kernel took since the last query (tests); 30 / 31: its slab reduction as separate launches / inside the
+    // producing launch
+    if (wt >= 20 && wt <= 22) { g_policy.wgrad_pp_mode = wt - 20; return 0; }
+    if (wt == 29) { const int n = g_counters.wgrad_pp_launches; g_counters.wgrad_pp_launches = 0; return n; }
+    if (wt == 30 || wt == 31) { g_policy.wgrad_pp_fuse = wt - 30; return 0; }
+    if (wt >= 4010 && wt <= 4400) { g_policy.wgrad_pp_slot_pct = wt - 4000; return 0; }
+    if (wt >= 5001 && wt <= 5999) { g_policy.wgrad_pp_two_pass = wt - 5000; return 0; }
+    if (wt < 0 || wt == 3 || wt > 4) return BRCNN_EINVAL;
+    g_policy.wgrad_bf16_tile = wt;
+    return 0;
+}
+
+BRCNN_API int brcnn_roi_align_set_exact(int exact) {
+    // 0: footprint kernel (column streaming, XCD-contiguous bin rows), 1: exact sample order, 2: footprint kernel with
+    // the per-bin loop and round-robin rows (the r02 form), 3: column streaming with round-robin rows
+    // 10 / 11 / 17: bin rows per wavefront by the heuristic / one / all seven; 20 / 21 / 22: RoI visiting order off / by the heuristic / forced
+    if (exact == 10 || exact == 11 || exact == 17) { g_policy.roi_rpw = exact == 10 ? 0 : exact; return 0; }
+    if (exact >= 20 && exact <= 22) { g_policy.roi_order = exact - 20; return 0; }
+    if (exact == 30 || exact == 31) { g_policy.roi_prep = exact - 30; return 0; }
+    if (exact >= 39 && exact <= 56) { g_policy.roi_gather_chunks = exact - 40; return 0; }    // 39: heuristic, 40 / 41: off, 42..56: chunks per coarse tile
+    g_policy.roi_exact = exact == 1 ? 1 : 0;
+    g_policy.roi_stream_c = exact == 2 ? 0 : exact == 3 ? 1 : 3;
+    return 0;
+}
+
+BRCNN_API int brcnn_get_tuning(brcnn_tuning* t) {
+    if (!t || t->size != (int)sizeof(brcnn_tuning)) return BRCNN_EINVAL;
+    t->conv_stream_k = g_policy.sk_mode;
+    t->conv_split_k = g_policy.sk_par;
+    t->conv_eight_phase_16bit = g_policy.pp_mode;
+    t->conv_persistent_1x1 = g_policy.stream_mode;
+    t->conv_eight_phase_f32 = g_policy.pp_f32_mode;
+    t->wgrad_slab_reduction = g_policy.wgrad_slabs;
+    t->wgrad_eight_phase = g_policy.wgrad_pp_mode;
+    t->wgrad_reduce_in_launch = g_policy.wgrad_pp_fuse;
+    t->wgrad_generation_percent = g_policy.wgrad_slot_pct;
+    t->wgrad_eight_phase_cu_percent = g_policy.wgrad_pp_slot_pct;
+    t->roi_exact_order = g_policy.roi_exact;
+    t->roi_rows_per_wave = g_policy.roi_rpw == 0 ? 0 : (g_policy.roi_rpw == 17 ? 7 : 1);
+    t->roi_visit_order = g_policy.roi_order;
+    t->roi_prepared_records = g_policy.roi_prep;
+    return 0;
+}
+
+BRCNN_API int brcnn_set_tuning(const brcnn_tuning* t) {
+    if (!t || t->size != (int)sizeof(brcnn_tuning)) return BRCNN_EINVAL;
+    auto in = [](int v, int lo, int hi) { return v >= lo && v <= hi; };
+    if (!in(t->conv_stream_k, 0, 2) || !in(t->conv_split_k, 0, 2) || !in(t->conv_eight_phase_16bit, 0, 1) ||
+        !in(t->conv_persistent_1x1, 0, 2) ||
+        !(in(t->conv_eight_phase_f32, 0, 2) || t->conv_eight_phase_f32 == 128 || t->conv_eight_phase_f32 == 256) ||
+        !in(t->wgrad_slab_reduction, 0, 1) || !in(t->wgrad_eight_phase, 0, 2) || !in(t->wgrad_reduce_in_launch, 0, 1) ||
+        !in(t->wgrad_generation_percent, 10, 400) || !in(t->wgrad_eight_phase_cu_percent, 10, 400) ||
+        !in(t->roi_exact_order, 0, 1) || !(t->roi_rows_per_wave == 0 || t->roi_rows_per_wave == 1 || t->roi_rows_per_wave == 7) ||
+        !in(t->roi_visit_order, 0, 2) || !in(t->roi_prepared_records, 0, 1))
+        return BRCNN_EINVAL;
+    g_policy.sk_mode = t->conv_stream_k;
+    g_policy.sk_par = t->conv_split_k;
+    g_policy.pp_mode = t->conv_eight_phase_16bit;
+    g_policy.stream_mode = t->conv_persistent_1x1;
+    g_policy.pp_f32_mode = t->conv_eight_phase_f32;
+    g_policy.wgrad_slabs = t->wgrad_slab_reduction;
+    g_policy.wgrad_pp_mode = t->wgrad_eight_phase;
+    g_policy.wgrad_pp_fuse = t->wgrad_reduce_in_launch;
+    g_policy.wgrad_slot_pct = t->wgrad_generation_percent;
+    g_policy.wgrad_pp_slot_pct = t->wgrad_eight_phase_cu_percent;
+    g_policy.roi_exact = t->roi_exact_order;
+    g_policy.roi_stream_c = 3;      // as brcnn_roi_align_set_exact(0 / 1): the struct selects the default footprint form
+    g_policy.roi_rpw = t->roi_rows_per_wave == 0 ? 0 : (t->roi_rows_per_wave == 7 ? 17 : 11);
+    g_policy.roi_order = t->roi_visit_order;
+    g_policy.roi_prep = t->roi_prepared_records;
+    return 0;
+}

@@ -13,6 +13,7 @@
 // the corner lines shared by neighbouring bins/samples are L1/L2 hits.  NCHW kernel:
 // one thread per output element (the reference's own layout; uncoalesced by nature).
 #include "common.h"
+#include "policy.h"
 
 namespace {
 
@@ -666,8 +667,6 @@ __global__ __launch_bounds__(256) void roi_align_fwd_rec_kernel(LevelTable lv, c
     }
 }
 
-int g_roi_exact = 0;     // 1: exact sample-order kernel (bit-identical to the reference's CPU order)
-int g_roi_stream_c = 3;  // footprint kernel: bit 0 column streaming over the bin row's patch (else the per-bin loop), bit 1 XCD-contiguous rows
 
 // NHWC backward (avg): same decomposition, atomicAdd of g*w/count to the four corners.
 template <bool MULTI>
@@ -802,14 +801,14 @@ BRCNN_API int brcnn_roi_align_forward(const float* input, const float* rois, flo
         if (pool_mode != 1 || (channels & 3)) return BRCNN_EINVAL;
         LevelTable lv = {};
         const long long bins = (long long)n_rois * pooled_h * pooled_w;
-        if (g_roi_exact)
+        if (brcnn::g_policy.roi_exact)
             hipLaunchKernelGGL((roi_align_fwd_nhwc_kernel<false, float>), dim3(brcnn_cdiv(bins, 4)), dim3(256), 0,
                                s, input, lv, rois, output, (int32_t*)nullptr, channels, height, width,
                                n_rois, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned);
         else
             hipLaunchKernelGGL((roi_align_fwd_nhwc_fp_kernel<false, float>), dim3(brcnn_cdiv((long long)n_rois * pooled_h, 4)), dim3(256), 0,
                                s, input, lv, rois, output, (int32_t*)nullptr, channels, height, width,
-                               n_rois, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, g_roi_stream_c, nullptr);
+                               n_rois, pooled_h, pooled_w, spatial_scale, sampling_ratio, aligned, brcnn::g_policy.roi_stream_c, nullptr);
     } else if (layout == BRCNN_LAYOUT_NCHW) {
         if (pool_mode == 0 && (!argmax_y || !argmax_x)) return BRCNN_EINVAL;
         int grid = brcnn_cdiv(total, 256);
@@ -920,10 +919,6 @@ __global__ __launch_bounds__(1024) void roi_order_kernel(const float* __restrict
 }
 
 constexpr int ROI_ORDER_MIN_ROIS = 12288;        // brcnn_roi_extract_order_min_rois(): what the caller sizes its scratch by
-int g_roi_prep = 0;      // ... (30 / 31): prepared-record form off / on where the caller provides its scratch.  OFF: measured
-                         // slower below 1000 RoIs / image (profiles/r05_notes.md)
-int g_roi_rpw = 0;       // tuning hook (set_exact(10 / 11 / 17)): rows per wave by the heuristic / 1 / all
-int g_roi_order = 1;     // ... (20 / 21 / 22): never / where a workspace is given and the RoI count pays for the sort / always
 
 template <typename T>
 static int extract_forward_impl(const void* const* feats_host, const int* heights_host, const int* widths_host,
@@ -937,7 +932,7 @@ static int extract_forward_impl(const void* const* feats_host, const int* height
         return BRCNN_EINVAL;
     if (n_rois == 0) return 0;
     if (!rois || !output) return BRCNN_EINVAL;
-    if (g_roi_exact) {
+    if (brcnn::g_policy.roi_exact) {
         const long long bins = (long long)n_rois * pooled_h * pooled_w;
         hipLaunchKernelGGL((roi_align_fwd_nhwc_kernel<true, T>), dim3(brcnn_cdiv(bins, 4)), dim3(256), 0, s, (const T*)nullptr,
                            lv, rois, (T*)output, levels_out, channels, 0, 0, n_rois, pooled_h, pooled_w, 0.f,
@@ -951,12 +946,12 @@ static int extract_forward_impl(const void* const* feats_host, const int* height
     // walks all seven rows of its RoI shares the level / geometry / x-weight arithmetic but leaves a seventh of the waves
     // to hide the gather latency -- measured 20-80 % slower (hook 17; profiles/r04_notes.md)
     const int32_t* perm = nullptr;
-    if (order_ws && batch <= BRCNN_MAX_IMAGES && (g_roi_order == 2 || (g_roi_order == 1 && n_rois >= ROI_ORDER_MIN_ROIS))) {
+    if (order_ws && batch <= BRCNN_MAX_IMAGES && (brcnn::g_policy.roi_order == 2 || (brcnn::g_policy.roi_order == 1 && n_rois >= ROI_ORDER_MIN_ROIS))) {
         hipLaunchKernelGGL(roi_order_kernel, dim3(1), dim3(1024), 0, s, rois, n_rois, lv, batch, order_ws);
         BRCNN_LAUNCH_CHECK();
         perm = order_ws;
     }
-    if (prep_ws && g_roi_prep && pooled_h <= 8 && pooled_w <= 8 && prep_bytes >= (size_t)n_rois * REC_WORDS * sizeof(int32_t)) {
+    if (prep_ws && brcnn::g_policy.roi_prep && pooled_h <= 8 && pooled_w <= 8 && prep_bytes >= (size_t)n_rois * REC_WORDS * sizeof(int32_t)) {
         // prepared records: level mapping, geometry and axis weights once per RoI (one small launch), then one wave per
         // bin row that starts from its RoI's record
         hipLaunchKernelGGL(roi_prep_kernel, dim3(brcnn_cdiv((long long)n_rois, 4)), dim3(256), 0, s, lv, rois, prep_ws, levels_out,
@@ -967,15 +962,15 @@ static int extract_forward_impl(const void* const* feats_host, const int* height
         BRCNN_LAUNCH_CHECK();
         return 0;
     }
-    const bool all_rows = pooled_h == 7 && g_roi_rpw == 17;
+    const bool all_rows = pooled_h == 7 && brcnn::g_policy.roi_rpw == 17;
     if (all_rows)
         hipLaunchKernelGGL((roi_align_fwd_nhwc_fp_kernel<true, T, 7>), dim3(brcnn_cdiv((long long)n_rois, 4)), dim3(256), 0, s,
                            (const T*)nullptr, lv, rois, (T*)output, levels_out, channels, 0, 0, n_rois, pooled_h, pooled_w,
-                           0.f, sampling_ratio, 1, g_roi_stream_c, perm);
+                           0.f, sampling_ratio, 1, brcnn::g_policy.roi_stream_c, perm);
     else
         hipLaunchKernelGGL((roi_align_fwd_nhwc_fp_kernel<true, T, 1>), dim3(brcnn_cdiv((long long)n_rois * pooled_h, 4)),
                            dim3(256), 0, s, (const T*)nullptr, lv, rois, (T*)output, levels_out, channels, 0, 0, n_rois,
-                           pooled_h, pooled_w, 0.f, sampling_ratio, 1, g_roi_stream_c, perm);
+                           pooled_h, pooled_w, 0.f, sampling_ratio, 1, brcnn::g_policy.roi_stream_c, perm);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }
@@ -1004,7 +999,7 @@ BRCNN_API int brcnn_roi_extract_forward_ordered(const void* const* feats_host, c
 // bytes of caller-owned scratch the prepared-record form wants (one 576-byte record per RoI); 0 while that form is
 // switched off (the default): the caller then passes NULL
 BRCNN_API size_t brcnn_roi_extract_prep_workspace_bytes(int n_rois) {
-    return (n_rois > 0 && g_roi_prep) ? (size_t)n_rois * REC_WORDS * sizeof(int32_t) : 0;
+    return (n_rois > 0 && brcnn::g_policy.roi_prep) ? (size_t)n_rois * REC_WORDS * sizeof(int32_t) : 0;
 }
 
 // RoI count from which the library visits the RoIs in band order when `order_ws` is given (what the caller sizes that
@@ -1366,7 +1361,6 @@ __global__ __launch_bounds__(256) void roi_grad_gather_kernel(const T* __restric
 
 // second stage of the chunked levels: one workgroup per tile, partials added in chunk order (+ the level's addend)
 BRCNN_API size_t brcnn_roi_extract_backward_workspace_bytes(int n_rois);
-static int g_roi_gather_chunks = -1;      // tuning hook (brcnn_roi_align_set_exact(40 + n)): -1 heuristic, n chunks per coarse tile
 
 template <typename T>
 __global__ __launch_bounds__(256) void roi_grad_chunk_sum_kernel(LevelTable lv, GatherLevels gl, int channels) {
@@ -1405,7 +1399,7 @@ __global__ __launch_bounds__(256) void roi_grad_chunk_sum_kernel(LevelTable lv, 
 
 // hit chunks per tile of the coarse levels for `n_rois` RoIs over `batch` images (1: the one-workgroup form)
 static int gather_chunks(int n_rois, int batch) {
-    if (g_roi_gather_chunks >= 0) return g_roi_gather_chunks < 1 ? 1 : g_roi_gather_chunks;
+    if (brcnn::g_policy.roi_gather_chunks >= 0) return brcnn::g_policy.roi_gather_chunks < 1 ? 1 : brcnn::g_policy.roi_gather_chunks;
     const int per_img = n_rois / (batch > 0 ? batch : 1);
     int ch = per_img / 48;
     if (ch > 16) ch = 16;
@@ -1534,72 +1528,4 @@ BRCNN_API int brcnn_roi_extract_backward_gather_add(void* const* grad_feats_host
         BRCNN_LAUNCH_CHECK();
     }
     return 0;
-}
-
-BRCNN_API int brcnn_roi_align_set_exact(int exact) {
-    // 0: footprint kernel (column streaming, XCD-contiguous bin rows), 1: exact sample order, 2: footprint kernel with
-    // the per-bin loop and round-robin rows (the r02 form), 3: column streaming with round-robin rows
-    // 10 / 11 / 17: bin rows per wavefront by the heuristic / one / all seven; 20 / 21 / 22: RoI visiting order off / by the heuristic / forced
-    if (exact == 10 || exact == 11 || exact == 17) { g_roi_rpw = exact == 10 ? 0 : exact; return 0; }
-    if (exact >= 20 && exact <= 22) { g_roi_order = exact - 20; return 0; }
-    if (exact == 30 || exact == 31) { g_roi_prep = exact - 30; return 0; }
-    if (exact >= 39 && exact <= 56) { g_roi_gather_chunks = exact - 40; return 0; }    // 39: heuristic, 40 / 41: off, 42..56: chunks per coarse tile
-    g_roi_exact = exact == 1 ? 1 : 0;
-    g_roi_stream_c = exact == 2 ? 0 : exact == 3 ? 1 : 3;
-    return 0;
-}
-
-// ---- the policy switches as one documented struct (include/brcnn_hip.h: brcnn_tuning) ---------------------------
-namespace brcnn_conv {
-int tuning_get_stream_k(); int tuning_get_split_k(); int tuning_get_eight_phase_16(); int tuning_get_persistent_1x1();
-int tuning_get_eight_phase_f32(); int tuning_get_wgrad_slabs(); int tuning_get_wgrad_generation_percent();
-int tuning_get_wgrad_eight_phase(); int tuning_get_wgrad_reduce_in_launch(); int tuning_get_wgrad_cu_percent();
-}  // namespace brcnn_conv
-
-BRCNN_API int brcnn_get_tuning(brcnn_tuning* t) {
-    if (!t || t->size != (int)sizeof(brcnn_tuning)) return BRCNN_EINVAL;
-    t->conv_stream_k = brcnn_conv::tuning_get_stream_k();
-    t->conv_split_k = brcnn_conv::tuning_get_split_k();
-    t->conv_eight_phase_16bit = brcnn_conv::tuning_get_eight_phase_16();
-    t->conv_persistent_1x1 = brcnn_conv::tuning_get_persistent_1x1();
-    t->conv_eight_phase_f32 = brcnn_conv::tuning_get_eight_phase_f32();
-    t->wgrad_slab_reduction = brcnn_conv::tuning_get_wgrad_slabs();
-    t->wgrad_eight_phase = brcnn_conv::tuning_get_wgrad_eight_phase();
-    t->wgrad_reduce_in_launch = brcnn_conv::tuning_get_wgrad_reduce_in_launch();
-    t->wgrad_generation_percent = brcnn_conv::tuning_get_wgrad_generation_percent();
-    t->wgrad_eight_phase_cu_percent = brcnn_conv::tuning_get_wgrad_cu_percent();
-    t->roi_exact_order = g_roi_exact;
-    t->roi_rows_per_wave = g_roi_rpw == 0 ? 0 : (g_roi_rpw == 17 ? 7 : 1);
-    t->roi_visit_order = g_roi_order;
-    t->roi_prepared_records = g_roi_prep;
-    return 0;
-}
-
-BRCNN_API int brcnn_set_tuning(const brcnn_tuning* t) {
-    if (!t || t->size != (int)sizeof(brcnn_tuning)) return BRCNN_EINVAL;
-    auto in = [](int v, int lo, int hi) { return v >= lo && v <= hi; };
-    if (!in(t->conv_stream_k, 0, 2) || !in(t->conv_split_k, 0, 2) || !in(t->conv_eight_phase_16bit, 0, 1) ||
-        !in(t->conv_persistent_1x1, 0, 2) ||
-        !(in(t->conv_eight_phase_f32, 0, 2) || t->conv_eight_phase_f32 == 128 || t->conv_eight_phase_f32 == 256) ||
-        !in(t->wgrad_slab_reduction, 0, 1) || !in(t->wgrad_eight_phase, 0, 2) || !in(t->wgrad_reduce_in_launch, 0, 1) ||
-        !in(t->wgrad_generation_percent, 10, 400) || !in(t->wgrad_eight_phase_cu_percent, 10, 400) ||
-        !in(t->roi_exact_order, 0, 1) || !(t->roi_rows_per_wave == 0 || t->roi_rows_per_wave == 1 || t->roi_rows_per_wave == 7) ||
-        !in(t->roi_visit_order, 0, 2) || !in(t->roi_prepared_records, 0, 1))
-        return BRCNN_EINVAL;
-    int rc = 0;
-    rc |= brcnn_conv_set_tile_bf16(-3 - t->conv_stream_k);
-    rc |= brcnn_conv_set_tile_bf16(-8 - t->conv_split_k);
-    rc |= brcnn_conv_set_tile_bf16(-6 - t->conv_eight_phase_16bit);
-    rc |= brcnn_conv_set_tile_bf16(-15 - t->conv_persistent_1x1);
-    rc |= brcnn_conv_set_tile(-2, t->conv_eight_phase_f32);
-    rc |= brcnn_conv_set_tile_wgrad_bf16(10 + t->wgrad_slab_reduction);
-    rc |= brcnn_conv_set_tile_wgrad_bf16(20 + t->wgrad_eight_phase);
-    rc |= brcnn_conv_set_tile_wgrad_bf16(30 + t->wgrad_reduce_in_launch);
-    rc |= brcnn_conv_set_tile_wgrad_bf16(2000 + t->wgrad_generation_percent);
-    rc |= brcnn_conv_set_tile_wgrad_bf16(4000 + t->wgrad_eight_phase_cu_percent);
-    rc |= brcnn_roi_align_set_exact(t->roi_exact_order);
-    rc |= brcnn_roi_align_set_exact(t->roi_rows_per_wave == 0 ? 10 : (t->roi_rows_per_wave == 7 ? 17 : 11));
-    rc |= brcnn_roi_align_set_exact(20 + t->roi_visit_order);
-    rc |= brcnn_roi_align_set_exact(30 + t->roi_prepared_records);
-    return rc ? BRCNN_EINVAL : 0;
 }

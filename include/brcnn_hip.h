@@ -174,7 +174,7 @@ int brcnn_roi_align_set_exact(int exact);
  * equals the exact form to fp32 round-off) and wgrad_slab_reduction = 0 (fp32 atomics: order-dependent sums).
  * `size` must be sizeof(brcnn_tuning) (a caller built against another layout gets BRCNN_EINVAL).
  * The integer hooks (brcnn_conv_set_tile*, brcnn_roi_align_set_exact) stay as the fine-grained test / tuning interface;
- * brcnn_set_tuning is expressed through them. */
+ * both interfaces write one table (csrc/policy.h), which lists every switch and its default. */
 typedef struct brcnn_tuning {
     int size;
     int conv_stream_k;                /* chained stream-K schedule of the conv kernels: 0 off, 1 by the heuristic (default), 2 wherever the tile count allows */

@@ -866,6 +866,40 @@ def test_wgrad_eight_phase_kernel_against_fp64(cfg, et):
     assert torch.equal(new, again)
 
 
+def test_wgrad_eight_phase_struct_route_selects_the_same_kernel_as_the_hook_route():
+    """brcnn_set_tuning and the integer hooks write one table (csrc/policy.h): `wgrad_eight_phase` set through the struct
+    takes / leaves the eight-phase weight-gradient kernel exactly as hook codes 22 / 20 do (hook 29 counts its launches),
+    with the same bits.  The smallest shape of test_wgrad_eight_phase_kernel_against_fp64 (taken only when forced)"""
+    import ctypes
+    from brcnn import lib
+    L = lib.load()
+    n, (h, w), ci, co, k, st, pd = 1, (33, 70), 64, 320, 3, 1, 1
+    g = torch.Generator().manual_seed(31)
+    x = torch.randn(n, h, w, ci, generator=g).to(BF).to(DEV)
+    dy = torch.randn(n, *ops.conv_out_size(h, w, k, k, st, pd), co, generator=g).to(BF).to(DEV)
+    hs, ws = (ctypes.c_int * 1)(h), (ctypes.c_int * 1)(w)
+
+    def run(select):
+        select()
+        L.brcnn_conv_set_tile_wgrad_bf16(29)
+        dw = torch.zeros(co, k, k, ci, device=DEV)
+        assert L.brcnn_conv2d_wgrad_nhwc_multi(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), n, 1, hs, ws, ci, co, k, k, st, pd, 1,
+                                               lib.stream_handle()) == 0
+        return dw, L.brcnn_conv_set_tile_wgrad_bf16(29)
+    try:
+        struct_on, launches = run(lambda: lib.set_tuning(wgrad_eight_phase=2))
+        assert launches == 1
+        struct_off, launches = run(lambda: lib.set_tuning(wgrad_eight_phase=0))
+        assert launches == 0
+        hook_on, launches = run(lambda: L.brcnn_conv_set_tile_wgrad_bf16(22))
+        assert launches == 1
+        hook_off, launches = run(lambda: L.brcnn_conv_set_tile_wgrad_bf16(20))
+        assert launches == 0
+    finally:
+        lib.set_tuning(wgrad_eight_phase=1)
+    assert torch.equal(struct_on, hook_on) and torch.equal(struct_off, hook_off)
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
 def test_straight_line_readout_and_plain_setup_keep_the_bits(dtype):
     """round 4: tiles inside the output take a read-out without guards (vector scale / shift loads, packed fp32 math,

@@ -421,6 +421,47 @@ def test_tuning_struct_round_trip_without_a_gpu():
         assert t.conv_stream_k == 1 and t.roi_visit_order == 1                  # the others keep their values
         assert L.brcnn_conv_set_tile_bf16(-10) == 0 and lib.get_tuning().conv_split_k == 2      # hook and struct: one state
         assert L.brcnn_roi_align_set_exact(31) == 0 and lib.get_tuning().roi_prepared_records == 1
+        # ... for every public field, in both directions: {value: hook call that selects it}
+        bf, wg, roi = L.brcnn_conv_set_tile_bf16, L.brcnn_conv_set_tile_wgrad_bf16, L.brcnn_roi_align_set_exact
+        routes = dict(
+            conv_stream_k={v: (bf, -3 - v) for v in (0, 1, 2)}, conv_split_k={v: (bf, -8 - v) for v in (0, 1, 2)},
+            conv_eight_phase_16bit={v: (bf, -6 - v) for v in (0, 1)}, conv_persistent_1x1={v: (bf, -15 - v) for v in (0, 1, 2)},
+            conv_eight_phase_f32={v: (L.brcnn_conv_set_tile, -2, v) for v in (0, 1, 2, 128, 256)},
+            wgrad_slab_reduction={v: (wg, 10 + v) for v in (0, 1)}, wgrad_eight_phase={v: (wg, 20 + v) for v in (0, 1, 2)},
+            wgrad_reduce_in_launch={v: (wg, 30 + v) for v in (0, 1)},
+            wgrad_generation_percent={v: (wg, 2000 + v) for v in (10, 75, 400)},
+            wgrad_eight_phase_cu_percent={v: (wg, 4000 + v) for v in (10, 75, 400)},
+            roi_exact_order={v: (roi, v) for v in (0, 1)}, roi_rows_per_wave={0: (roi, 10), 1: (roi, 11), 7: (roi, 17)},
+            roi_visit_order={v: (roi, 20 + v) for v in (0, 1, 2)}, roi_prepared_records={v: (roi, 30 + v) for v in (0, 1)})
+        assert set(routes) == set(want)
+
+        def call(route):
+            return route[0](*route[1:])
+        lib.set_tuning(**want)
+        for field, by_value in routes.items():
+            others = {k: v for k, v in want.items() if k != field}
+            for v, route in by_value.items():
+                assert call(route) == 0                                         # hook -> struct
+                t = lib.get_tuning()
+                assert getattr(t, field) == v and {k: getattr(t, k) for k in others} == others, (field, v)
+            other = 'conv_split_k' if field != 'conv_split_k' else 'conv_stream_k'
+            first = next(iter(by_value))
+            for v in by_value:
+                lib.set_tuning(**{field: v})                                    # struct -> the same state ...
+                assert getattr(lib.get_tuning(), field) == v, (field, v)
+                # ... that the hooks write: a hook call for ANOTHER switch leaves it, one for this switch replaces it
+                assert call(routes[other][2]) == 0
+                t = lib.get_tuning()
+                assert (getattr(t, field), getattr(t, other)) == (v, 2), (field, v)
+                assert call(by_value[first]) == 0 and getattr(lib.get_tuning(), field) == first
+                lib.set_tuning(**{other: want[other]})
+            lib.set_tuning(**{field: want[field]})
+        # the one hook-visible effect without a device: the scratch the prepared-record form asks for
+        lib.set_tuning(roi_prepared_records=1)
+        assert L.brcnn_roi_extract_prep_workspace_bytes(10) > 0
+        lib.set_tuning(roi_prepared_records=0)
+        assert L.brcnn_roi_extract_prep_workspace_bytes(10) == 0
+        # wgrad_eight_phase through the struct selects the kernel: tests/test_bf16_gpu.py (hook 29 counts the launches)
         with pytest.raises(lib.BrcnnHipError):
             lib.set_tuning(conv_stream_k=5)
         with pytest.raises(KeyError):
@@ -431,6 +472,61 @@ def test_tuning_struct_round_trip_without_a_gpu():
     finally:
         lib.set_tuning(**want)
     assert {k: getattr(lib.get_tuning(), k) for k in want} == want
+
+
+def _ranges(codes):
+    """sorted codes as [(first, last), ...]"""
+    out = []
+    for c in sorted(codes):
+        if out and out[-1][1] == c - 1:
+            out[-1][1] = c
+        else:
+            out.append([c, c])
+    return [tuple(r) for r in out]
+
+
+def test_integer_hooks_accept_and_refuse_exactly_their_codes():
+    """csrc/policy.hip: the four integer hooks decode the same codes as ever.  Each hook swept over its whole code range
+    (host state only, no device call): the accepted codes are exactly the sets recorded from the library before the
+    switches moved into one table; every other code is refused with BRCNN_EINVAL; every accepted call returns 0 (the two
+    reporting codes included: nothing has launched in a process without a device)"""
+    from brcnn import lib
+    L = lib.load()
+    defaults = {k: getattr(lib.get_tuning(), k) for k, _ in lib.Tuning._fields_ if k != 'size'}
+    EINVAL = -22
+    accepted = {
+        'brcnn_conv_set_tile_bf16': (-3100, 9000, [
+            (-2999, -1000), (-19, -15), (-12, 0), (11, 11), (21, 22), (42, 42), (81, 82), (164, 164), (322, 322), (342, 342),
+            (381, 382), (482, 482), (2144, 2144), (2244, 2244), (3164, 3164), (8842, 8842), (8844, 8844)]),
+        'brcnn_conv_set_tile_wgrad_bf16': (-5, 6100, [
+            (0, 2), (4, 4), (10, 11), (20, 22), (29, 31), (100, 1099), (2010, 2400), (3010, 3400), (4010, 4400), (5001, 5999)]),
+        'brcnn_roi_align_set_exact': (-5, 70, [(-5, 70)]),          # never refuses: unknown codes select the default form
+    }
+    # brcnn_conv_set_tile(wm, nt), nt in -1..257: accepted nt per wm (wm = -8, 3, 5: none)
+    accepted_nt = {-7: [(0, 8)], -6: [(0, 1)], -5: [(0, 2)], -4: [(0, 1)], -3: [(0, 2)], -2: [(0, 2), (128, 128), (256, 256)],
+                   -1: [(-1, 257)], 0: [(0, 2)], 1: [(0, 2)], 2: [(0, 2)], 4: [(0, 2)]}
+    try:
+        for name, (lo, hi, want) in accepted.items():
+            got = {c: getattr(L, name)(c) for c in range(lo, hi + 1)}
+            assert set(got.values()) <= {0, EINVAL}, (name, sorted(set(got.values())))
+            assert _ranges(c for c, r in got.items() if r == 0) == want, name
+        for wm in range(-8, 6):
+            got = {nt: L.brcnn_conv_set_tile(wm, nt) for nt in range(-1, 258)}
+            assert set(got.values()) <= {0, EINVAL}, (wm, sorted(set(got.values())))
+            assert _ranges(nt for nt, r in got.items() if r == 0) == accepted_nt.get(wm, []), wm
+    finally:
+        lib.set_tuning(**defaults)
+        # ... and the members the struct does not carry (defaults: csrc/policy.h)
+        for wm, nt in ((-1, 1), (-3, 1), (-4, 0), (-5, 1), (-7, 0), (0, 0)):
+            L.brcnn_conv_set_tile(wm, nt)
+        for code in (0, -2, -19, -1000 - 4096, -2000 - 128, -12):
+            L.brcnn_conv_set_tile_bf16(code)
+        for code in (0, 100 + 24, 3000 + 75, 5000 + 24, 29):
+            L.brcnn_conv_set_tile_wgrad_bf16(code)
+        for code in (0, 39):
+            L.brcnn_roi_align_set_exact(code)
+        lib.set_tuning(**defaults)
+    assert {k: getattr(lib.get_tuning(), k) for k in defaults} == defaults
 
 
 def test_host_thread_cap_follows_affinity_and_cgroup_quota(monkeypatch):
