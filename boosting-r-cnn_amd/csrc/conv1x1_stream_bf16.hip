@@ -294,6 +294,7 @@ int launch_stream(ConvParams& p, hipStream_t s) {
     p.st_strips = strips;
     hipLaunchKernelGGL((conv1x1_stream_kernel<KT, RES, ET>), dim3(strips * ncb), dim3(256), lds, s, p);
     BRCNN_LAUNCH_CHECK();
+    brcnn::count(brcnn::g_counters.stream1x1_launches);
     return 0;
 }
 

@@ -1094,7 +1094,8 @@ static bool sk_capturing(hipStream_t s) {
 }
 
 // a planned launch: the next epoch of the stream, its hand-over slots and flags, the item table (g_sk_mutex held)
-static void sk_fill(ConvParams& p, SkStream& st, const SkTable& tab) {
+static void sk_fill(ConvParams& p, SkStream& st, const SkTable& tab, int* counter = nullptr) {
+    if (counter) { brcnn::count(*counter); brcnn::g_counters.sk_last_wgs = tab.blocks; }
     if (++st.epoch == 0) st.epoch = 1;
     p.sk_wgs = tab.blocks;
     p.sk_items = tab.items;
@@ -1130,7 +1131,7 @@ static int sk_plan(ConvParams& p, int slots, int bm, int bn, hipStream_t s, int 
         const SkTable* tab = nullptr;
         rc = sk_table_par(tiles, nk, slots, &tab);
         if (rc) return rc == BRCNN_EINVAL ? 0 : rc;
-        sk_fill(p, *st, *tab);
+        sk_fill(p, *st, *tab, &brcnn::g_counters.sk_par_fills);
         return 0;
     }
     // every slot must own at least one whole tile's worth of iterations: a tile then straddles two ranges at most
@@ -1154,8 +1155,18 @@ static int sk_plan(ConvParams& p, int slots, int bm, int bn, hipStream_t s, int 
     const SkTable* tab = nullptr;
     rc = sk_table(tiles, nk, slots, &tab);
     if (rc) return rc == BRCNN_EINVAL ? 0 : rc;
-    sk_fill(p, *st, *tab);
+    sk_fill(p, *st, *tab, &brcnn::g_counters.sk_chain_fills);
     return 0;
+}
+
+// a launch of the tile kernel and its tile, for the tests (policy.h Counters)
+template <int MT, int NT, int WM, int WNW, int ST>
+static void count_tile_launch() {
+    brcnn::count(brcnn::g_counters.bf16_tile_launches);
+    brcnn::g_counters.bf16_tile_rows = 32 * MT * WM;
+    brcnn::g_counters.bf16_tile_cols = 32 * NT * WNW;
+    brcnn::g_counters.bf16_tile_waves = WM * WNW;
+    brcnn::g_counters.bf16_tile_stages = ST;
 }
 
 template <int MT, int NT, bool RES, bool OUTF32, int WM = 2, int WNW = 2, int ST = 2, int ET = 0, int MODE = 0>
@@ -1192,6 +1203,7 @@ int launch(ConvParams& p, hipStream_t s) {
             hipLaunchKernelGGL((conv_igemm_bf16_dma_kernel<MT, NT, RES, OUTF32, WM, WNW, ST, ET, MODE, true>), dim3(p.sk_wgs),
                                dim3(64 * WM * WNW), lds_sk, s, p);
             BRCNN_LAUNCH_CHECK();
+            count_tile_launch<MT, NT, WM, WNW, ST>();
             return 0;
         }
     }
@@ -1207,6 +1219,7 @@ int launch(ConvParams& p, hipStream_t s) {
     hipLaunchKernelGGL((conv_igemm_bf16_dma_kernel<MT, NT, RES, OUTF32, WM, WNW, ST, ET, MODE>), dim3(p.tiles_m * p.tiles_n),
                        dim3(64 * WM * WNW), lds, s, p);
     BRCNN_LAUNCH_CHECK();
+    count_tile_launch<MT, NT, WM, WNW, ST>();
     return 0;
 }
 
@@ -1256,6 +1269,10 @@ static bool pp_wins(const ConvParams& p) {
 static bool pp128_ok(const ConvParams& p) {
     return !(p.gstep || (p.Cout % 128) || p.K < 192 || (p.K % 64) || p.KH * p.KW > 32 || p.scatter || (p.tail_z && p.tail_mask));
 }
+// what brcnn_conv_set_tile_bf16(8844) needs of a shape to force the 256 x 256 eight-phase kernel (bf16 and fp16 alike)
+static bool pp_ok(const ConvParams& p) {
+    return p.Cout > 128 && p.K >= 128 && p.KH * p.KW <= 32 && !(p.tail_z && p.tail_mask);
+}
 static bool pp128_wins(const ConvParams& p) {
     if (brcnn::g_policy.pp128_mode == 0 || !pp128_ok(p) || p.K < brcnn::g_policy.pp128_min_k || p.KH * p.KW < 9) return false;     // (measured on 3x3 layers only)
     const long long tm = (p.M + 255) / 256;
@@ -1301,11 +1318,17 @@ int sk_plan_f32_tile(ConvParams& p, int per_cu, int cus, hipStream_t s) {
     return 0;
 }
 
-// fp16 operands: the production tile shapes only (the tuning-hook variants stay bf16)
+// fp16 operands: the production tile shapes only (the tuning-hook variants stay bf16, except the two eight-phase kernels:
+// 8844 / 8842 force them under bf16's shape rules, so that the tests reach their fp16 instantiations at small shapes;
+// as for bf16, any forced tile code keeps the persistent 1x1 kernel out, so that a forced tile is the tile that runs)
 static int dispatch_conv_f16(ConvParams& p, hipStream_t s) {
     p.il = 0;
-    if (const int rc = conv1x1_stream_try(p, s, 1)) return rc < 0 ? rc : 0;
+    if (brcnn::g_policy.bf16_tile == 0) {
+        if (const int rc = conv1x1_stream_try(p, s, 1)) return rc < 0 ? rc : 0;
+    }
     if (p.gstep) return launch2<1, 1, 4, 2, 2, 1>(p, s);
+    if (brcnn::g_policy.bf16_tile == 8842 && pp128_ok(p)) return dispatch_conv_pp128_bf16(p, s);
+    if (brcnn::g_policy.bf16_tile == 8844 && pp_ok(p)) return dispatch_conv_pp_bf16(p, s);
     if (pp128_wins(p)) return dispatch_conv_pp128_bf16(p, s);
     if (pp_wins(p)) return dispatch_conv_pp_bf16(p, s);
     const long long t22 = (long long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
@@ -1357,7 +1380,7 @@ int dispatch_conv_bf16(ConvParams& p, hipStream_t s) {
     }
     if (t == 8842 && pp128_ok(p)) return dispatch_conv_pp128_bf16(p, s);
     if (t == 8842) t = 82;
-    if (t == 8844 && p.Cout > 128 && p.K >= 128 && p.KH * p.KW <= 32 && !(p.tail_z && p.tail_mask)) return dispatch_conv_pp_bf16(p, s);
+    if (t == 8844 && pp_ok(p)) return dispatch_conv_pp_bf16(p, s);
     if (t == 8844) t = 82;
     if (t == 342 && p.Cout > 64) return launch2<2, 2, 4, 2, 3>(p, s);    // 3-stage ring variants
     if (t == 382 && p.Cout > 64) return launch2<1, 2, 4, 2, 3>(p, s);

@@ -20,6 +20,7 @@
 // phase's first barrier; it is overwritten in phase q+2, two barriers after the slower group's read was waited for.
 #include <type_traits>
 #include "conv_common.h"
+#include "policy.h"
 #include "conv_pp_epilogue.h"
 
 namespace {
@@ -463,6 +464,7 @@ int launch_pp2(ConvParams& p, hipStream_t s) {
         hipLaunchKernelGGL((conv_pp_bf16_kernel<RES, OUTF32, ET, DIL, MODE, false>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds, s, p);
     }
     BRCNN_LAUNCH_CHECK();
+    brcnn::count(brcnn::g_counters.pp_bf16_launches);
     return 0;
 }
 

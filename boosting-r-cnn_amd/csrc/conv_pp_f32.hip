@@ -10,6 +10,7 @@
 // (BASELINE configs[1]) is unchanged.  Plain epilogue (scale / shift, residual, ReLU); chained stream-K items.
 #include <type_traits>
 #include "conv_common.h"
+#include "policy.h"
 
 namespace {
 using namespace brcnn_conv;
@@ -561,6 +562,9 @@ int launch_pp_f32(ConvParams& p, hipStream_t s) {
     else
         hipLaunchKernelGGL((conv_pp_f32_kernel<RES, DIL, false, MT, WG>), dim3(p.tiles_m * p.tiles_n), dim3(512), lds, s, p);
     BRCNN_LAUNCH_CHECK();
+    brcnn::count(brcnn::g_counters.pp_f32_launches);
+    brcnn::g_counters.pp_f32_rows = BM;
+    brcnn::g_counters.pp_f32_cols = BN;
     return 0;
 }
 

@@ -495,9 +495,15 @@ int brcnn_wgrad_bf16_dispatch(const void* x, const void* dy, void* dw, int batch
         // stage-4 3x3 89 -> 66 us, 3x3 on the 100x168 map 204 -> 159 us; profiles/r03_notes.md)
         if (cout >= 256 && p.K >= 2048) wt = 4;
     }
-    if (wt == 4) return f16 ? launch<2, 1, 4>(p, stream) : launch<2, 0, 4>(p, stream);
-    if (f16) return wt == 2 ? launch<2, 1>(p, stream) : launch<1, 1>(p, stream);
-    return wt == 2 ? launch<2>(p, stream) : launch<1>(p, stream);
+    wt = wt == 4 ? 4 : wt == 2 ? 2 : 1;
+    const int rc = wt == 4 ? (f16 ? launch<2, 1, 4>(p, stream) : launch<2, 0, 4>(p, stream))
+                 : f16 ? (wt == 2 ? launch<2, 1>(p, stream) : launch<1, 1>(p, stream))
+                       : (wt == 2 ? launch<2>(p, stream) : launch<1>(p, stream));
+    if (rc == 0) {
+        brcnn::count(brcnn::g_counters.wgrad_bf16_tile_launches);
+        brcnn::g_counters.wgrad_bf16_last_tile = wt;
+    }
+    return rc;
 }
 
 // grouped variant (ResNeXt conv2): per 64-channel co tile a dense (64 x KH*KW*window) wgrad over the

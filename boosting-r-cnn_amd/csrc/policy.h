@@ -57,7 +57,31 @@ struct Counters {
     int f32_tile_sk_launches = 0;   // persistent launches so far (brcnn_conv_set_tile(-6, 0) reports it)
     int f32_tile_sk_wgs = 0;        // ... and the workgroups of the last one ((-6, 1))
     int wgrad_pp_launches = 0;      // launches taken so far (tests: hook 29 returns and clears it)
+    // ---- which route a launch took (tests): brcnn_conv_set_tile(-9, n) returns counter n and clears it, (-9, -1) clears all of
+    // them.  Counts wrap inside the positive ints (brcnn::count); the launch sites count after the launch
+    int pp_f32_launches = 0;        // n = 0: fp32 eight-phase launches (conv_pp_f32.hip)
+    int pp_f32_rows = 0;            // n = 1: ... tile rows of the last one (256 / 128)
+    int pp_f32_cols = 0;            // n = 2: ... and its tile columns (256 / 128)
+    int pp_bf16_launches = 0;       // n = 3: 256 x 256 eight-phase 16-bit launches (conv_pp_bf16.hip)
+    int pp128_bf16_launches = 0;    // n = 4: 256 x 128 two-group 16-bit launches (conv_pp128_bf16.hip)
+    int stream1x1_launches = 0;     // n = 5: persistent short-K 1x1 launches (conv1x1_stream_bf16.hip)
+    int sk_chain_fills = 0;         // n = 6: launches planned as chained stream-K (sk_plan -> sk_table)
+    int sk_par_fills = 0;           // n = 7: launches planned as split-K (sk_plan -> sk_table_par)
+    int sk_last_wgs = 0;            // n = 8: workgroups of the last of either (the fp32 64 x 64 persistent launch keeps f32_tile_sk_*)
+    int bf16_tile_launches = 0;     // n = 9: launches of the two-buffer / ring 16-bit tile kernel (conv_igemm_bf16.hip launch2)
+    int bf16_tile_rows = 0;         // n = 10: ... the last one's tile rows,
+    int bf16_tile_cols = 0;         // n = 11: tile columns,
+    int bf16_tile_waves = 0;        // n = 12: waves per workgroup
+    int bf16_tile_stages = 0;       // n = 13: and LDS ring stages
+    int wgrad_bf16_tile_launches = 0;   // n = 14: launches of the tile kernel of conv_wgrad_bf16.hip (not the eight-phase one)
+    int wgrad_bf16_last_tile = 0;       // n = 15: the tile code (1 / 2 / 4) of the last one
+    // brcnn_roi_align_set_exact(60 .. 63): return and clear
+    int roi_ordered_launches = 0;   // 60: RoI forward launches that visited the RoIs in band order
+    int roi_prepared_launches = 0;  // 61: RoI forward launches in the prepared-record form
+    int roi_gather_chunked = 0;     // 62: RoI gradient gathers that ran chunked (partials + chunk sum)
+    int roi_gather_last_ch = 0;     // 63: chunks per coarse tile of the last of them
 };
 extern Counters g_counters;
+inline void count(int& c) { c = (c + 1) & 0x7fffffff; }     // (a long run must not overflow a signed int)
 
 }  // namespace brcnn

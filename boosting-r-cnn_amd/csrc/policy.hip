@@ -15,6 +15,21 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
     if (wm == -7) { if (nt < 0 || nt > 8) return BRCNN_EINVAL; g_policy.f32_tile_sk_per_cu = nt; return 0; }
     // (-6, 0): persistent 64 x 64 launches so far (>= 0), (-6, 1): workgroups of the last one
     if (wm == -6) return nt == 0 ? g_counters.f32_tile_sk_launches : nt == 1 ? g_counters.f32_tile_sk_wgs : BRCNN_EINVAL;
+    // (-9, n): which route the launches took (policy.h Counters lists n = 0 .. 15): returns counter n and clears it,
+    // (-9, -1) clears them all
+    if (wm == -9) {
+        int* const c[] = {&g_counters.pp_f32_launches, &g_counters.pp_f32_rows, &g_counters.pp_f32_cols, &g_counters.pp_bf16_launches,
+                          &g_counters.pp128_bf16_launches, &g_counters.stream1x1_launches, &g_counters.sk_chain_fills,
+                          &g_counters.sk_par_fills, &g_counters.sk_last_wgs, &g_counters.bf16_tile_launches, &g_counters.bf16_tile_rows,
+                          &g_counters.bf16_tile_cols, &g_counters.bf16_tile_waves, &g_counters.bf16_tile_stages,
+                          &g_counters.wgrad_bf16_tile_launches, &g_counters.wgrad_bf16_last_tile};
+        const int count = (int)(sizeof(c) / sizeof(c[0]));
+        if (nt < -1 || nt >= count) return BRCNN_EINVAL;
+        if (nt == -1) { for (int* q : c) *q = 0; return 0; }
+        const int n = *c[nt];
+        *c[nt] = 0;
+        return n;
+    }
     if (wm == -2) { if (nt != 0 && nt != 1 && nt != 2 && nt != 128 && nt != 256) return BRCNN_EINVAL; g_policy.pp_f32_mode = nt; return 0; }
     if ((wm != 0 && wm != 1 && wm != 2 && wm != 4) || nt < 0 || nt > 2) return BRCNN_EINVAL;
     g_policy.force_wm = wm;
@@ -69,6 +84,15 @@ BRCNN_API int brcnn_roi_align_set_exact(int exact) {
     if (exact >= 20 && exact <= 22) { g_policy.roi_order = exact - 20; return 0; }
     if (exact == 30 || exact == 31) { g_policy.roi_prep = exact - 30; return 0; }
     if (exact >= 39 && exact <= 56) { g_policy.roi_gather_chunks = exact - 40; return 0; }    // 39: heuristic, 40 / 41: off, 42..56: chunks per coarse tile
+    // 60 .. 63 (tests): RETURN and clear -- forward launches that took the band order / the prepared-record form, gradient
+    // gathers that ran chunked / the chunks per coarse tile of the last of them
+    if (exact >= 60 && exact <= 63) {
+        int* const c[] = {&g_counters.roi_ordered_launches, &g_counters.roi_prepared_launches, &g_counters.roi_gather_chunked,
+                          &g_counters.roi_gather_last_ch};
+        const int n = *c[exact - 60];
+        *c[exact - 60] = 0;
+        return n;
+    }
     g_policy.roi_exact = exact == 1 ? 1 : 0;
     g_policy.roi_stream_c = exact == 2 ? 0 : exact == 3 ? 1 : 3;
     return 0;

@@ -946,10 +946,12 @@ static int extract_forward_impl(const void* const* feats_host, const int* height
     // walks all seven rows of its RoI shares the level / geometry / x-weight arithmetic but leaves a seventh of the waves
     // to hide the gather latency -- measured 20-80 % slower (hook 17; profiles/r04_notes.md)
     const int32_t* perm = nullptr;
+    bool ordered = false;
     if (order_ws && batch <= BRCNN_MAX_IMAGES && (brcnn::g_policy.roi_order == 2 || (brcnn::g_policy.roi_order == 1 && n_rois >= ROI_ORDER_MIN_ROIS))) {
         hipLaunchKernelGGL(roi_order_kernel, dim3(1), dim3(1024), 0, s, rois, n_rois, lv, batch, order_ws);
         BRCNN_LAUNCH_CHECK();
         perm = order_ws;
+        ordered = true;
     }
     if (prep_ws && brcnn::g_policy.roi_prep && pooled_h <= 8 && pooled_w <= 8 && prep_bytes >= (size_t)n_rois * REC_WORDS * sizeof(int32_t)) {
         // prepared records: level mapping, geometry and axis weights once per RoI (one small launch), then one wave per
@@ -960,6 +962,8 @@ static int extract_forward_impl(const void* const* feats_host, const int* height
         hipLaunchKernelGGL((roi_align_fwd_rec_kernel<T>), dim3(brcnn_cdiv((long long)n_rois * pooled_h, 4)), dim3(256), 0, s, lv,
                            rois, prep_ws, (T*)output, channels, n_rois, pooled_h, pooled_w, sampling_ratio, perm);
         BRCNN_LAUNCH_CHECK();
+        brcnn::count(brcnn::g_counters.roi_prepared_launches);
+        if (ordered) brcnn::count(brcnn::g_counters.roi_ordered_launches);
         return 0;
     }
     const bool all_rows = pooled_h == 7 && brcnn::g_policy.roi_rpw == 17;
@@ -972,6 +976,7 @@ static int extract_forward_impl(const void* const* feats_host, const int* height
                            dim3(256), 0, s, (const T*)nullptr, lv, rois, (T*)output, levels_out, channels, 0, 0, n_rois,
                            pooled_h, pooled_w, 0.f, sampling_ratio, 1, brcnn::g_policy.roi_stream_c, perm);
     BRCNN_LAUNCH_CHECK();
+    if (ordered) brcnn::count(brcnn::g_counters.roi_ordered_launches);
     return 0;
 }
 
@@ -1468,8 +1473,8 @@ BRCNN_API int brcnn_roi_extract_backward_gather_add(void* const* grad_feats_host
     for (int l = 0; l < BRCNN_MAX_LEVELS; l++) gl.chunks[l] = 1;
     const size_t base_bytes = (brcnn_roi_extract_backward_workspace_bytes(n_rois) + 255) & ~(size_t)255;
     int ptiles = 0;
+    const int ch = gather_chunks(n_rois, batch);
     {
-        const int ch = gather_chunks(n_rois, batch);
         size_t tiles = 0;
         for (int l = 0; l < num_levels; l++)
             if (gl.tiles_x[l] * gl.tiles_y[l] <= GT_CHUNK_TILES) tiles += (size_t)gl.tiles_x[l] * gl.tiles_y[l] * batch;
@@ -1526,6 +1531,8 @@ BRCNN_API int brcnn_roi_extract_backward_gather_add(void* const* grad_feats_host
         else
             hipLaunchKernelGGL(roi_grad_chunk_sum_kernel<f16_t>, dim3(ptiles), dim3(256), 0, s, lv, gl, channels);
         BRCNN_LAUNCH_CHECK();
+        brcnn::count(brcnn::g_counters.roi_gather_chunked);
+        brcnn::g_counters.roi_gather_last_ch = ch;
     }
     return 0;
 }

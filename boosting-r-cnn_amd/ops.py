@@ -179,10 +179,11 @@ def _roi_order_min_rois():
     return _ROI_ORDER_MIN[0]
 
 
-def roi_extract(feats_nhwc, rois, output_size, featmap_strides, finest_scale=56, sampling_ratio=0):
+def roi_extract(feats_nhwc, rois, output_size, featmap_strides, finest_scale=56, sampling_ratio=0, order_scratch=None):
     """Fused SingleRoIExtractor.forward (single_level_roi_extractor.py:57-115): level mapping
     + RoIAlign of every RoI on its own level in one launch.  `feats_nhwc`: list of (N,H,W,C)
-    contiguous fp32 tensors.  Returns ((K,ph,pw,C) features, (K,) int32 levels)."""
+    contiguous fp32 tensors.  Returns ((K,ph,pw,C) features, (K,) int32 levels).  `order_scratch`: hand the library the
+    scratch for its band-ordered visit of the RoIs (True / False; None: from the RoI count at which it orders them)."""
     _require_gpu(rois, *feats_nhwc)
     import ctypes
     L = len(feats_nhwc)
@@ -202,7 +203,9 @@ def roi_extract(feats_nhwc, rois, output_size, featmap_strides, finest_scale=56,
     lib = _L.load()
     # caller-owned scratch: the visiting order (n int32) from the RoI count at which the library orders them, and the
     # per-RoI records of the prepared form (level mapping / geometry / axis weights once per RoI instead of per bin row)
-    order = torch.empty((k,), dtype=torch.int32, device=rois.device) if k >= _roi_order_min_rois() else None
+    if order_scratch is None:
+        order_scratch = k >= _roi_order_min_rois()
+    order = torch.empty((k,), dtype=torch.int32, device=rois.device) if order_scratch and k > 0 else None
     nb = int(lib.brcnn_roi_extract_prep_workspace_bytes(k))          # 0 while the prepared form is off (the default)
     prep = torch.empty(nb, dtype=torch.uint8, device=rois.device) if nb else None
     st = lib.brcnn_roi_extract_forward_prepared(ptrs, hs, ws, sc, L, _ptr(rois), _ptr(out), _ptr(levels), n, c, k, ph, pw,

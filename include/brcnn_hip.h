@@ -164,7 +164,10 @@ int brcnn_roi_extract_backward_gather_add(void *const *grad_feats_host, const vo
  * reads every pixel of the ROW's footprint once, rows reduced first, then spread over the bins with their x weights;
  * bin rows dealt to the XCDs in contiguous eighths; equal to the reference to fp32 round-off), 1 = the reference's
  * sample-order accumulation (bit-identical to mmcv's CPU kernel; ~1.5x the L2 reads), 2 = the footprint form of
- * rounds 1-2 (per-bin loop, round-robin rows), 3 = column streaming with round-robin rows (tuning / A-B hooks). */
+ * rounds 1-2 (per-bin loop, round-robin rows), 3 = column streaming with round-robin rows (tuning / A-B hooks).
+ * 60 .. 63 (tests) RETURN a host-side count and clear it: forward launches that visited the RoIs in band order (60) /
+ * took the prepared-record form (61), gradient gathers that ran chunked (62), the chunks per coarse tile of the last
+ * of them (63). */
 int brcnn_roi_align_set_exact(int exact);
 
 /* The policy switches of the library as ONE documented struct (round 5; VERDICT r04: the integer hooks had become what
@@ -339,7 +342,13 @@ int brcnn_conv_handover_status(void);
  * launches; a launch with fewer tiles than resident workgroups runs tiles / CUs workgroups per CU).  (-6, 0) returns the
  * number of persistent launches so far (>= 0), (-6, 1) the workgroups of the last one.  (-7, n): at most n workgroups per
  * CU in the persistent launch, 0 = as many as are resident (tools/f32_tile_persistent_bench.py).
- * Every choice gives the same bits. */
+ * Every choice gives the same bits.
+ * (-9, n), tests: which route the conv launches took -- returns host-side counter n and clears it, (-9, -1) clears all:
+ * n = 0 fp32 eight-phase launches, 1 / 2 tile rows / columns of the last one; 3 / 4 / 5 launches of the 256 x 256
+ * eight-phase, 256 x 128 two-group and persistent 1x1 16-bit kernels; 6 / 7 launches planned as chained stream-K /
+ * split-K, 8 the workgroups of the last of them; 9 launches of the two-buffer / ring 16-bit tile kernel, 10 .. 13 the
+ * last one's tile rows, tile columns, waves per workgroup, ring stages; 14 launches of the 16-bit weight gradient's tile
+ * kernel (csrc/conv_wgrad_bf16.hip), 15 the tile code (1, 2, 4) of the last one (csrc/policy.h: Counters). */
 int brcnn_conv_set_tile(int wm, int nt);
 
 /* Tuning hook of the bf16 kernel: 0 heuristic; 11 / 21 / 22 = 64x64 / 128x64 / 128x128 tile on
@@ -354,7 +363,9 @@ int brcnn_conv_set_tile(int wm, int nt);
  * stop / resume publishing and tails give up after 256 polls -- a lost hand-over on demand, to exercise
  * BRCNN_EHANDOVER.  -15 / -16 / -17: the persistent kernel of the plain K = 64 / 128 1x1 layers (csrc/conv1x1_stream_bf16.hip:
  * weights resident in LDS, x / residual tiles through LDS-DMA rings) never / by the heuristic (default) / wherever the shape
- * allows; bit-identical. */
+ * allows; bit-identical.  8842: the 256x128 two-group kernel (csrc/conv_pp128_bf16.hip) wherever its shape rules allow.
+ * fp16 operands run the production tiles whatever the code, except that 8844 / 8842 force the two eight-phase kernels
+ * for fp16 as for bf16; any non-zero code keeps the persistent 1x1 kernel out (both types). */
 int brcnn_conv_set_tile_bf16(int mtnt);
 
 /* The same convolution over `num_segments` feature maps that share one set of weights (the

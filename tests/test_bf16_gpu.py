@@ -222,6 +222,12 @@ def test_conv_bn_act_one_launch_training_forward(cfg, dtype):
     bit-identical to the conv kernel followed by the bn_act kernel (the affine is applied to the stored, rounded z)
     in the forward and in every gradient (input, weight, gamma, beta, residual, the identity alias); the two-kernel
     path itself is checked against float64 in test_conv_autograd_bf16 / test_bn_eval_act"""
+    _check_conv_bn_act_forms(_conv_bn_act_forms(cfg, dtype), dtype)
+
+
+def _conv_bn_act_forms(cfg, dtype, after_form=None):
+    """{fused: [out, dx, dw, dgamma, dbeta(, dres)]} of one forward + backward pass in the fused and in the separate form;
+    `after_form(fused)` is called behind each pass (the callers read the route counters there)"""
     from brcnn.autograd import conv_bn_eval_act_autograd, conv_bn_eval_act_fusable
     N, Cin, H, W, Cout, k, stride, res, relu, with_skip = cfg
     g = torch.Generator().manual_seed(31)
@@ -251,8 +257,14 @@ def test_conv_bn_act_one_launch_training_forward(cfg, dtype):
             torch.autograd.backward(outs, [go, gs] if with_skip else [go])
             got[fused] = [outs[0].detach(), xd.grad, conv.weight.grad.clone(), bn.weight.grad.clone(), bn.bias.grad.clone()] + \
                 ([rd.grad] if res else [])
+            if after_form:
+                after_form(fused)
         finally:
             blocks.FUSE_CONV_BN_TRAIN = True
+    return got
+
+
+def _check_conv_bn_act_forms(got, dtype):
     assert got[True][0].dtype == dtype
     names = ['out', 'dx', 'dgamma', 'dbeta', 'dres']
     for i, nm in zip((0, 1, 3, 4, 5), names):
@@ -271,6 +283,11 @@ def test_bottleneck_bn_backward_inside_data_gradient_launch(cfg, dtype):
     (`brcnn_conv2d_dgrad_bn_backward_nhwc`) against the same block with the separate bn_act backward launches:
     input gradient bit for bit (dz is the same arithmetic on the same rounded values), dgamma / dbeta up to the
     summation order, weight gradients up to the order of their atomics"""
+    _check_bottleneck_forms(_bottleneck_forms(cfg, dtype))
+
+
+def _bottleneck_forms(cfg, dtype, after_form=None):
+    """{fused: (out, dx, {parameter: gradient})} of one forward + backward pass of the block in both forms"""
     from brcnn import autograd as A
     from brcnn.backbones import Bottleneck
     N, inplanes, planes, stride, H, W, down = cfg
@@ -295,8 +312,14 @@ def test_bottleneck_bn_backward_inside_data_gradient_launch(cfg, dtype):
             go = torch.randn(out.shape, device=DEV, generator=torch.Generator(DEV).manual_seed(3)).to(dtype)
             out.backward(go)
             got[fused] = (out.detach(), xd.grad.clone(), {k: p.grad.clone() for k, p in blk.named_parameters()})
+            if after_form:
+                after_form(fused)
         finally:
             A.FUSE_BN_BACKWARD_INTO_DGRAD = True
+    return got
+
+
+def _check_bottleneck_forms(got):
     assert torch.equal(got[True][0], got[False][0]) and torch.equal(got[True][1], got[False][1])
     for k, ga in got[True][2].items():
         gb = got[False][2][k]
@@ -602,14 +625,28 @@ def test_bf16_tile_shapes_agree_bit_for_bit():
     w = (torch.randn(256, 3, 3, 256, generator=g) * 0.05).bfloat16().to(DEV)
     sc = (torch.rand(256, generator=g) + 0.5).to(DEV)
     sh = torch.randn(256, generator=g).to(DEV)
+    from tests import route_util as R
+    # tile code -> (rows, columns, waves, LDS ring stages) of the tile kernel; the two eight-phase kernels have counters of their own
+    want = {11: (64, 64, 4, 2), 21: (128, 64, 4, 2), 22: (128, 128, 4, 2), 81: (128, 64, 8, 2), 82: (128, 128, 8, 2),
+            164: (128, 128, 16, 2), 42: (256, 128, 8, 2), 2244: (256, 256, 16, 2), 2144: (256, 128, 16, 2),
+            382: (128, 128, 8, 3), 342: (256, 128, 8, 3)}
     try:
         outs = {}
         for t in (11, 21, 22, 81, 82, 164, 42, 2244, 2144, 382, 342, 8844, 8842):
             assert L.brcnn_conv_set_tile_bf16(t) == 0
+            R.clear(L)
             outs[t] = ops.conv2d_nhwc(x, w, sc, sh, None, True, 1, 1)
+            c = R.take(L)
+            if t in want:       # the code's own tile, not the one a shape rule would substitute
+                assert (c['tile'], c['tile_rows'], c['tile_cols'], c['tile_waves'], c['tile_stages']) == (1,) + want[t], (t, c)
+                assert c['pp_bf16'] == 0 and c['pp128'] == 0, (t, c)
+            else:
+                assert (c['tile'], c['pp_bf16'], c['pp128']) == (0, int(t == 8844), int(t == 8842)), (t, c)
         torch.cuda.synchronize()
         for t, y in outs.items():
             assert torch.equal(y, outs[11]), t
+        # one float64 leg anchors all of them (K = 2304)
+        R.check_conv_against_fp64(outs[11], x, w, sc, sh, None, True, 1, 1, 'bf16 tile shapes 2x100x168 256->256 3x3')
     finally:
         L.brcnn_conv_set_tile_bf16(0)
 
@@ -637,14 +674,29 @@ def test_bf16_eight_phase_kernel_is_bit_identical(cfg):
     sh = torch.randn(co, generator=g).to(DEV)
     ho, wo = ops.conv_out_size(h, w_, k, k, stride, pad)
     r = torch.randn(n, ho, wo, co, generator=g).bfloat16().to(DEV) if res else None
+    from tests import route_util as R
+    K = k * k * ci
+    # dispatch_conv_bf16's shape rules: a code whose kernel does not take the shape runs the 128 x 128 (Cout <= 64: 128 x 64) tile
+    takes = {8844: co > 128 and K >= 128, 8842: co % 128 == 0 and K >= 192 and K % 64 == 0}
     try:
         assert L.brcnn_conv_set_tile_bf16(11) == 0
+        R.clear(L)
         ref = ops.conv2d_nhwc(x, w, sc, sh, r, True, stride, pad, out_f32=of32)
+        c = R.take(L)
+        assert (c['tile'], c['tile_rows'], c['tile_cols'], c['pp_bf16'], c['pp128']) == (1, 64, 64, 0, 0), c
+        R.check_conv_against_fp64(ref, x, w, sc, sh, r, True, stride, pad, f'bf16 {cfg}')
         for tile in (8844, 8842):       # 256 x 256 eight-phase; 256 x 128 two-group (conv_pp128_bf16.hip, where its shape rules allow)
             assert L.brcnn_conv_set_tile_bf16(tile) == 0
             for rep in range(3):
+                R.clear(L)
                 out = ops.conv2d_nhwc(x, w, sc, sh, r, True, stride, pad, out_f32=of32)
+                c = R.take(L)
                 assert torch.equal(out, ref), (tile, rep, (out.float() - ref.float()).abs().max().item())
+                if takes[tile]:
+                    assert (c['pp_bf16'], c['pp128'], c['tile']) == (int(tile == 8844), int(tile == 8842), 0), (tile, c)
+                else:       # the documented fall-back, as a checked fact
+                    assert (c['pp_bf16'], c['pp128'], c['tile'], c['tile_rows'], c['tile_cols']) == \
+                        (0, 0, 1, 128, 128 if co > 64 else 64), (tile, c)
     finally:
         L.brcnn_conv_set_tile_bf16(0)
 
@@ -653,8 +705,10 @@ def test_bf16_eight_phase_kernel_is_bit_identical(cfg):
 def test_bf16_256x128_kernel_every_k_tile_count(et):
     """conv_pp128_bf16.hip keeps three K tiles in nine LDS slots and unrolls six K tiles per loop iteration: every K-tile
     count 3 .. 14 (all tails of the unrolled loop), 1x1 and 3x3 taps, ragged rows, one and three column tiles, residual
-    and ReLU -- bit-identical to the two-buffer kernel, launch after launch"""
+    and ReLU -- bit-identical to the two-buffer kernel, launch after launch.  The counter says that every forced launch ran
+    this kernel (fp16 too: the fp16 dispatcher honours 8842 / 8844), the two-buffer result is pinned to float64 per shape"""
     from brcnn import lib as _lib
+    from tests import route_util as R
     L = _lib.load()
     g = torch.Generator().manual_seed(61)
     try:
@@ -667,10 +721,16 @@ def test_bf16_256x128_kernel_every_k_tile_count(et):
                 sh = torch.randn(co, generator=g).to(DEV)
                 r = torch.randn(2, 37, 53, co, generator=g).to(DEV, et) if res else None
                 assert L.brcnn_conv_set_tile_bf16(11) == 0
+                R.clear(L)
                 ref = ops.conv2d_nhwc(x, w, sc, sh, r, True, 1, k // 2)
+                c = R.take(L)
+                assert c['pp128'] == 0 and c['pp_bf16'] == 0 and c['stream'] == 0 and c['tile'] == 1, (nk, k, co, c)
+                R.check_conv_against_fp64(ref, x, w, sc, sh, r, True, 1, k // 2, f'{et} 2x37x53 nk={nk} k={k} co={co}')
                 assert L.brcnn_conv_set_tile_bf16(8842) == 0
                 for rep in range(2):
                     out = ops.conv2d_nhwc(x, w, sc, sh, r, True, 1, k // 2)
+                    c = R.take(L)
+                    assert (c['pp128'], c['tile'], c['pp_bf16']) == (1, 0, 0), (nk, k, co, rep, c)
                     assert torch.equal(out, ref), (nk, k, co, rep, (out.float() - ref.float()).abs().max().item())
     finally:
         L.brcnn_conv_set_tile_bf16(0)
@@ -682,6 +742,7 @@ def test_bf16_wgrad_slab_reduction_is_reproducible_and_equals_the_atomics_form()
     order of the additions, accumulation into an existing dW is kept, for the three tile shapes and a five-level launch"""
     import ctypes
     from brcnn import lib as _lib
+    from tests import route_util as R
     L = _lib.load()
     g = torch.Generator().manual_seed(17)
     LV = [(100, 168), (50, 84), (25, 42), (13, 21), (7, 11)]
@@ -700,8 +761,12 @@ def test_bf16_wgrad_slab_reduction_is_reproducible_and_equals_the_atomics_form()
                 for mode in (11, 11, 10):
                     assert L.brcnn_conv_set_tile_wgrad_bf16(mode) == 0
                     dw = base.clone()
+                    R.clear(L); L.brcnn_conv_set_tile_wgrad_bf16(29)
                     assert L.brcnn_conv2d_wgrad_nhwc_multi(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), N, len(lv), hs, ws, ci, co, k, k,
                                                            st, pd, 1, None) == 0
+                    # the forced tile's own kernel ran, once, and not the eight-phase one (hook 29)
+                    c = R.take(L)
+                    assert (c['wgrad'], c['wgrad_tile'], L.brcnn_conv_set_tile_wgrad_bf16(29)) == (1, tile, 0), (tile, mode, c)
                     torch.cuda.synchronize()
                     res.setdefault(mode, []).append(dw)
                 assert torch.equal(res[11][0], res[11][1]), (tile, 'slab form not reproducible')
@@ -712,23 +777,56 @@ def test_bf16_wgrad_slab_reduction_is_reproducible_and_equals_the_atomics_form()
         L.brcnn_conv_set_tile_wgrad_bf16(11)
 
 
+# conv launches per pass (forward + data gradients; the weight gradients have their own kernel) that dispatch_conv_bf16 /
+# dispatch_conv_f16 send to the forced eight-phase kernel, and the rest, which a shape rule sends to the tile kernel:
+# cfg -> {tile code: (forced kernel, tile kernel)}.  8844 needs more than 128 output channels (a data gradient's output
+# channels are the layer's input channels), 8842 a multiple of 128 and K >= 192.
+_PP_CONV_BN_ACT = {
+    (8, 256, 50, 84, 1024, 1, 1, True, True, False): {8844: (2, 0), 8842: (2, 0)},
+    (2, 256, 40, 56, 256, 3, 1, False, True, True): {8844: (2, 0), 8842: (2, 0)},
+    (2, 128, 30, 44, 512, 3, 2, False, True, False): {8844: (1, 1), 8842: (2, 0)},       # dx has 128 channels
+    (2, 128, 40, 56, 128, 3, 1, False, True, True): {8842: (2, 0)},
+}
+_PP_BOTTLENECK = {
+    (2, 1024, 256, 1, 26, 40, False): {8844: (6, 0), 8842: (6, 0)},          # conv1 .. conv3 and their three data gradients
+    (1, 1024, 512, 2, 13, 17, True): {8844: (8, 0), 8842: (8, 0)},           # ... and the downsample conv's pair
+    (2, 512, 128, 1, 26, 40, False): {8842: (4, 2)},                         # conv3 and conv1's data gradient: K = 128
+}
+
+
 @pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
 def test_bf16_eight_phase_kernel_training_epilogues(dtype):
     """the dual-store forward (MODE 1) and the data gradient + BatchNorm backward (MODE 2, incl. the zero-stuffed
-    stride-2 form) of the eight-phase kernel: the same bit-for-bit checks against the separate bn_act launches as the
-    two-buffer kernel's, with the 256 x 256 tile forced"""
+    stride-2 form) of the eight-phase kernels (8844: 256 x 256; 8842: the 256 x 128 two-group kernel, same epilogues through
+    conv_pp_epilogue.h): the same bit-for-bit checks of the fused against the separate form as the two-buffer kernel's.
+    Both forms run the forced kernel, so on top of that: the output and the input gradient equal the ones of the
+    production tiles (no code forced; that path is pinned to float64 in test_conv_autograd_bf16 / test_bn_eval_act), and
+    the counters say, per pass, how many conv launches ran the forced kernel and how many the tile kernel -- for
+    fp16 as for bf16"""
     from brcnn import lib as _lib
+    from tests import route_util as R
     L = _lib.load()
+    name = {8844: 'pp_bf16', 8842: 'pp128'}
     try:
-        for tile in (8844, 8842):       # (8842: the 256 x 128 two-group kernel, same epilogues through conv_pp_epilogue.h)
-            assert L.brcnn_conv_set_tile_bf16(tile) == 0
-            for cfg in [(8, 256, 50, 84, 1024, 1, 1, True, True, False), (2, 256, 40, 56, 256, 3, 1, False, True, True),
-                        (2, 128, 30, 44, 512, 3, 2, False, True, False)] + \
-                    ([(2, 128, 40, 56, 128, 3, 1, False, True, True)] if tile == 8842 else []):
-                test_conv_bn_act_one_launch_training_forward(cfg, dtype)
-            for cfg in [(2, 1024, 256, 1, 26, 40, False), (1, 1024, 512, 2, 13, 17, True)] + \
-                    ([(2, 512, 128, 1, 26, 40, False)] if tile == 8842 else []):
-                test_bottleneck_bn_backward_inside_data_gradient_launch(cfg, dtype)
+        for table, forms, check in ((_PP_CONV_BN_ACT, _conv_bn_act_forms, lambda g_: _check_conv_bn_act_forms(g_, dtype)),
+                                    (_PP_BOTTLENECK, _bottleneck_forms, _check_bottleneck_forms)):
+            for cfg, want in table.items():
+                assert L.brcnn_conv_set_tile_bf16(0) == 0
+                base = forms(cfg, dtype)
+                for tile, (n_forced, n_tile) in want.items():
+                    assert L.brcnn_conv_set_tile_bf16(tile) == 0
+                    counts = {}
+                    R.clear(L)
+                    got = forms(cfg, dtype, lambda fused: counts.__setitem__(fused, R.take(L)))
+                    check(got)
+                    for fused in (True, False):
+                        c = counts[fused]
+                        assert (c[name[tile]], c[name[8844 + 8842 - tile]], c['tile'], c['stream']) == (n_forced, 0, n_tile, 0), \
+                            (tile, cfg, fused, c)
+                        # (bf16 falls back to the 128 x 128 tile, code 82; fp16 to the tile its heuristic picks: 64 x 64 here)
+                        assert n_tile == 0 or (c['tile_rows'], c['tile_cols']) == ((128, 128) if dtype == BF else (64, 64)), (tile, cfg, fused, c)
+                        assert torch.equal(got[fused][0], base[fused][0]), ('out', tile, cfg, fused)
+                        assert torch.equal(got[fused][1], base[fused][1]), ('dx', tile, cfg, fused)
     finally:
         L.brcnn_conv_set_tile_bf16(0)
 
@@ -740,27 +838,44 @@ def test_bf16_eight_phase_kernel_multi_level_and_data_gradient():
     g = torch.Generator().manual_seed(34)
     sizes = [(40, 64), (20, 32), (10, 16), (5, 8), (3, 4)]
     B, C = 2, 256
-    xc = torch.cat([torch.randn(B, h, w, C, generator=g).reshape(-1, C) for h, w in sizes], 0).to(DEV, BF)
+    xs = [torch.randn(B, h, w, C, generator=g) for h, w in sizes]
+    xc = torch.cat([t_.reshape(-1, C) for t_ in xs], 0).to(DEV, BF)
     wt = (torch.randn(C, 3, 3, C, generator=g) / 48).to(DEV, BF)
     dy = torch.randn(2, 25, 42, 256, generator=g).to(DEV, BF)
     w2 = (torch.randn(256, 256, 3, 3, generator=g) / 48).to(DEV)
+    from tests import route_util as R
     try:
         outs = {}
         for t in (11, 8844, 8842):
             assert L.brcnn_conv_set_tile_bf16(t) == 0
+            R.clear(L)
             y, _ = ops.conv2d_nhwc_multi(xc, wt, B, sizes, None, None, None, False, 1, 1)
+            c = R.take(L)
+            assert (c['tile'], c['pp_bf16'], c['pp128']) == (int(t == 11), int(t == 8844), int(t == 8842)), (t, c)
             x = torch.randn(2, 50, 84, 256, generator=torch.Generator().manual_seed(35)).to(DEV, BF).requires_grad_(True)
             from brcnn.autograd import conv2d_nhwc_autograd
             z = conv2d_nhwc_autograd(x, w2.clone().requires_grad_(True), None, 2, 1)
             z.backward(dy)
-            outs[t] = (y, x.grad.clone())
+            c = R.take(L)
+            # forward and data gradient are conv launches (the weight gradient has its own kernel)
+            assert (c['tile'], c['pp_bf16'], c['pp128']) == (2 * int(t == 11), 2 * int(t == 8844), 2 * int(t == 8842)), (t, c)
+            outs[t] = (y, x.grad.clone(), z.detach())
         for t in (8844, 8842):
             assert torch.equal(outs[11][0], outs[t][0]) and torch.equal(outs[11][1], outs[t][1]), t
+        # the two-buffer results against float64: the five levels, the strided forward, its data gradient (bf16 operands:
+        # the weights as the conv rounds them)
+        want = torch.cat([R.conv_ref64(t_.to(DEV, BF), wt, pad=1).reshape(-1, C) for t_ in xs], 0)
+        assert R.excess(outs[11][0].reshape(-1, C), want, BF) <= 0
+        x64 = x.detach().double().permute(0, 3, 1, 2).requires_grad_(True)
+        z64 = F.conv2d(x64, w2.to(BF).double(), None, 2, 1)
+        assert R.excess(outs[11][2], z64.detach().permute(0, 2, 3, 1), BF) <= 0
+        z64.backward(dy.double().permute(0, 3, 1, 2))
+        assert R.excess(outs[11][1], x64.grad.permute(0, 2, 3, 1), BF) <= 0
     finally:
         L.brcnn_conv_set_tile_bf16(0)
 
 
-@pytest.mark.parametrize('shape', [
+SK_SHAPES = [
     # batch, H, W, Cin, Cout, k, residual      (8 x 50 x 84 = 33 600 rows: 263 row tiles of 128 -- the stage-3 maps)
     (8, 50, 84, 256, 256, 3, False),
     (8, 50, 84, 1024, 256, 1, False),
@@ -769,14 +884,16 @@ def test_bf16_eight_phase_kernel_multi_level_and_data_gradient():
     (3, 50, 84, 256, 256, 3, True),          # fewer tiles than resident workgroups on most tile shapes: plain launch
     (8, 100, 168, 256, 256, 3, False),       # 525 tiles of 256 x 256: the eight-phase kernel's stream-K case
     (8, 100, 168, 128, 128, 3, True),        # 525 tiles of 256 x 128: the two-group 128-column kernel's (stage 2)
-])
-def test_bf16_stream_k_schedule_is_bit_identical(shape):
-    """the chained stream-K schedule (a tile that straddles two workgroup ranges is started by one workgroup and
-    finished by another from the stored fp32 accumulators) keeps the MFMA chain over K: forced on (-5) it equals the
-    one-tile-per-workgroup launch (-3) bit for bit on every production tile shape, with and without residual / ReLU,
-    repeated (the hand-over slots and epoch flags are reused launch after launch)"""
-    from brcnn import lib as _lib
-    L = _lib.load()
+]
+SK_TILES = (0, 11, 21, 81, 82, 8844, 8842)
+SK_TILE_SHAPE = {11: (64, 64, 4), 21: (128, 64, 4), 81: (128, 64, 8), 82: (128, 128, 8)}       # rows, columns, waves
+# (tile code, shape) pairs whose launch MUST take the chained schedule when it is forced: the production cases
+SK_MUST = {(8844, SK_SHAPES[5]), (8842, SK_SHAPES[6]), (82, SK_SHAPES[0])}      # 525 / 525 / 526 (= 263 x 2) tiles
+# ... and must NOT: fewer tiles than one workgroup per CU (99 x 2 tiles of 128 x 128, 50 of 256 x 256, 50 x 2 of 256 x 128)
+SK_MUST_NOT = {(82, SK_SHAPES[4]), (8844, SK_SHAPES[4]), (8842, SK_SHAPES[4])}
+
+
+def _sk_inputs(shape):
     n, h, w_, ci, co, k, res = shape
     g = torch.Generator().manual_seed(21)
     x = torch.randn(n, h, w_, ci, generator=g).bfloat16().to(DEV)
@@ -784,18 +901,102 @@ def test_bf16_stream_k_schedule_is_bit_identical(shape):
     sc = (torch.rand(co, generator=g) + 0.5).to(DEV)
     sh = torch.randn(co, generator=g).to(DEV)
     r = torch.randn(n, h, w_, co, generator=g).bfloat16().to(DEV) if res else None
+    return x, w, sc, sh, r
+
+
+@pytest.mark.parametrize('shape', SK_SHAPES)
+def test_bf16_stream_k_schedule_is_bit_identical(shape):
+    """the chained stream-K schedule (a tile that straddles two workgroup ranges is started by one workgroup and
+    finished by another from the stored fp32 accumulators) keeps the MFMA chain over K: forced on (-5) it equals the
+    one-tile-per-workgroup launch (-3) bit for bit on every production tile shape, with and without residual / ReLU,
+    repeated (the hand-over slots and epoch flags are reused launch after launch).  The counters say which legs really
+    hand tiles over (sk_plan plans a plain launch when there are fewer tiles than resident workgroups): never under -3,
+    on all three repetitions or on none under -5, always on the production cases (SK_MUST), never on SK_MUST_NOT; the
+    whole table is in test_bf16_stream_k_every_tile_code_takes_the_schedule.  The plain result is pinned to float64."""
+    from brcnn import lib as _lib
+    from tests import route_util as R
+    L = _lib.load()
+    co, k = shape[4], shape[5]
+    x, w, sc, sh, r = _sk_inputs(shape)
+    anchored = []
     try:
-        for t in (0, 11, 21, 81, 82, 8844, 8842):
+        for t in SK_TILES:
             assert L.brcnn_conv_set_tile_bf16(t) == 0
             assert L.brcnn_conv_set_tile_bf16(-3) == 0
+            R.clear(L)
             ref = ops.conv2d_nhwc(x, w, sc, sh, r, True, 1, k // 2)
+            c = R.take(L)
+            assert c['sk_chain'] == 0 and c['sk_par'] == 0, (t, c)
+            if t in SK_TILE_SHAPE:      # the row label is the tile that ran
+                assert (c['tile'], c['tile_rows'], c['tile_cols'], c['tile_waves']) == (1,) + SK_TILE_SHAPE[t], (t, c)
+            if t == 8842 or (t == 8844 and co > 128):
+                assert (c['pp_bf16'], c['pp128'], c['tile']) == (int(t == 8844), int(t == 8842), 0), (t, c)
+            elif t == 8844:         # 128 output channels: no 256-column tile, the code runs the 128 x 128 tile (a repeat of 82)
+                assert (c['pp_bf16'], c['pp128'], c['tile'], c['tile_rows'], c['tile_cols']) == (0, 0, 1, 128, 128), (t, c)
+            if not any(torch.equal(ref, a) for a in anchored):      # one float64 leg per distinct plain result
+                R.check_conv_against_fp64(ref, x, w, sc, sh, r, True, 1, k // 2, f'bf16 stream-K {shape} tile {t}')
+                anchored.append(ref)
             assert L.brcnn_conv_set_tile_bf16(-5) == 0
             for rep in range(3):
                 out = ops.conv2d_nhwc(x, w, sc, sh, r, True, 1, k // 2)
                 assert torch.equal(out, ref), (t, rep, (out.float() - ref.float()).abs().max().item())
+            c = R.take(L)
+            took = c['sk_chain']
+            print(f'stream-K forced: tile {t} shape {shape}: {took} of 3 launches chained, {c["sk_wgs"]} workgroups')
+            assert took in (0, 3) and c['sk_par'] == 0, (t, c)
+            assert not ((t, shape) in SK_MUST and took != 3), (t, c)
+            assert not ((t, shape) in SK_MUST_NOT and took != 0), (t, c)
     finally:
         L.brcnn_conv_set_tile_bf16(0)
         L.brcnn_conv_set_tile_bf16(-4)
+
+
+def test_bf16_stream_k_every_tile_code_takes_the_schedule():
+    """which (tile code, shape) legs of test_bf16_stream_k_schedule_is_bit_identical hand tiles over when the schedule is
+    forced: one launch each, read from the counter.  sk_plan takes it when tiles >= resident workgroups (the occupancy
+    query x CUs), so the table belongs to the device; asserted here: every tile code takes it on at least one shape, the
+    production cases take it, the few-tile shape does not.  On MI355X (256 CUs; x = chained, . = plain launch, f = the code
+    fell back to the 128 x 128 tile, which chained), shapes in SK_SHAPES order:
+
+        code   8x50x84   8x50x84    8x50x84     8x25x42   3x50x84   8x100x168  8x100x168
+               256->256  1024->256  256->1024   512->512  256->256  256->256   128->128
+                  0      .         .          x           .         .         x          x
+                 11      x         x          x           .         .         x          x
+                 21      x         x          x           .         .         x          x
+                 81      x         x          x           .         .         x          x
+                 82      x         x          x           .         .         x          x
+               8844      .         .          x           .         .         x          f
+               8842      x         x          x           .         .         x          x
+
+    (the 8 x 25 x 42 and 3 x 50 x 84 legs are plain launches on every code: 8400 / 12 600 rows give fewer tiles than resident
+    workgroups; code 0, the heuristic, picks the eight-phase 256 x 256 kernel on the first two shapes -- 132 tiles, as 8844)
+    """
+    from brcnn import lib as _lib
+    from tests import route_util as R
+    L = _lib.load()
+    table = {}
+    try:
+        assert L.brcnn_conv_set_tile_bf16(-5) == 0
+        for shape in SK_SHAPES:
+            x, w, sc, sh, r = _sk_inputs(shape)
+            for t in SK_TILES:
+                assert L.brcnn_conv_set_tile_bf16(t) == 0
+                R.clear(L)
+                ops.conv2d_nhwc(x, w, sc, sh, r, True, 1, shape[5] // 2)
+                c = R.take(L)
+                own = {0: 1, 8844: c['pp_bf16'], 8842: c['pp128']}.get(t, c['tile'])      # 0: the code fell back to another kernel
+                table[(t, shape)] = c['sk_chain'] if own else 'f' * c['sk_chain']
+            del x, w, sc, sh, r
+        torch.cuda.synchronize()
+    finally:
+        L.brcnn_conv_set_tile_bf16(0)
+        L.brcnn_conv_set_tile_bf16(-4)
+    for t in SK_TILES:
+        print(f'{t:5d}  ' + ' '.join({1: 'x', 0: '.'}.get(table[(t, s_)], 'f') for s_ in SK_SHAPES))
+    assert set(table.values()) <= {0, 1, 'f', ''}
+    for t in SK_TILES:
+        assert any(table[(t, s_)] == 1 for s_ in SK_SHAPES), f'tile code {t} never takes the stream-K schedule at these shapes'
+    assert all(table[p] == 1 for p in SK_MUST) and all(table[p] == 0 for p in SK_MUST_NOT), table
 
 
 @pytest.mark.parametrize('et', [BF, torch.float16])
@@ -1094,3 +1295,71 @@ def test_fused_bottleneck_tail_16bit_equals_the_two_launches():
         assert ops.bottleneck_tail_supported(x, w2, w3, idn)
         y = ops.bottleneck_tail_nhwc(x, w2, s2, b2, w3, s3, b3, idn)
         assert y.dtype == ref.dtype and torch.equal(y, ref), (n, h, w, (y.float() - ref.float()).abs().max().item())
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+def test_persistent_1x1_kernel_against_fp64(dtype):
+    """conv1x1_stream_bf16.hip against the float64 convolution of the 16-bit operands, at the smallest shapes it accepts
+    that still have a ragged last 64-row tile and several tiles per strip: M = 1 x 67 x 63 = 4221 = 65 x 64 + 61 rows,
+    K = 64 / 128 (one / two K tiles), one and three 128-column blocks, with and without residual and ReLU.  The counter
+    says that the persistent kernel ran; bound: one rounding of the result + the suite's accumulation slack.  One result
+    with a single element moved by one ulp must be refused (the bound notices an output ulp)."""
+    from brcnn import lib as _lib
+    from tests import route_util as R
+    L = _lib.load()
+    g = torch.Generator().manual_seed(91)
+    shown = False
+    try:
+        assert L.brcnn_conv_set_tile_bf16(-17) == 0
+        for K in (64, 128):
+            for co in (128, 384):
+                x = torch.randn(1, 67, 63, K, generator=g).to(DEV, dtype)
+                w = (torch.randn(co, 1, 1, K, generator=g) / np.sqrt(K)).to(DEV, dtype)
+                sc = (torch.rand(co, generator=g) + 0.5).to(DEV)
+                sh = torch.randn(co, generator=g).to(DEV)
+                res = torch.randn(1, 67, 63, co, generator=g).to(DEV, dtype)
+                for r in (None, res):
+                    for relu in (False, True):
+                        R.clear(L)
+                        y = ops.conv2d_nhwc(x, w, sc, sh, r, relu, 1, 0)
+                        c = R.take(L)
+                        assert c['stream'] == 1 and c['tile'] == 0, (K, co, r is not None, relu, c)
+                        ref = R.conv_ref64(x, w, sc, sh, r, relu, 1, 0)
+                        e = R.excess(y, ref, dtype)
+                        assert y.dtype == dtype and e <= 0, (K, co, r is not None, relu, e)
+                        if not shown:
+                            assert R.excess(R.one_ulp_off(y, ref), ref, dtype) > 0
+                            shown = True
+    finally:
+        L.brcnn_conv_set_tile_bf16(-16)
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+def test_fused_bottleneck_tail_16bit_against_fp64(dtype):
+    """csrc/bottleneck_tail_bf16.hip against the textbook chain in float64 (conv2 3x3, bn2, ReLU, conv3 1x1, bn3, + identity,
+    ReLU) at the smallest legal sizes (rows a multiple of 128) with image borders inside a tile and two images.  The kernel
+    rounds the intermediate t to the 16-bit type by specification, the reference keeps it in float64, so the bound is
+    elementwise  h |ref| + |s3| (|W3| . (h |t64| + a mag_t)) + a mag  with h = half an ulp of the type, a = 2e-5 the
+    suite's accumulation slack, |W3| . (...) the 1x1 convolution with absolute weights (ReLU is 1-Lipschitz: no term)."""
+    from tests import route_util as R
+    g = torch.Generator().manual_seed(79)
+    h_ = R.half_ulp(dtype)
+    shown = False
+    for (n, h, w) in [(2, 8, 16), (1, 16, 24)]:
+        x = torch.randn(n, h, w, 64, generator=g).to(DEV, dtype)
+        idn = torch.randn(n, h, w, 256, generator=g).to(DEV, dtype)
+        w2 = (torch.randn(64, 3, 3, 64, generator=g) / 24).to(DEV, dtype)
+        w3 = (torch.randn(256, 1, 1, 64, generator=g) / 8).to(DEV, dtype)
+        s2, b2 = (torch.rand(64, generator=g) + 0.5).to(DEV), torch.randn(64, generator=g).to(DEV)
+        s3, b3 = (torch.rand(256, generator=g) + 0.5).to(DEV), torch.randn(256, generator=g).to(DEV)
+        assert ops.bottleneck_tail_supported(x, w2, w3, idn)
+        y = ops.bottleneck_tail_nhwc(x, w2, s2, b2, w3, s3, b3, idn)
+        t64 = R.conv_ref64(x, w2, s2, b2, None, True, 1, 1)
+        ref = R.conv_ref64(t64, w3, s3, b3, idn, True, 1, 0)
+        dt = h_ * t64.abs() * 1.001 + R.ACC_TOL * max(1.0, t64.abs().max().item())        # what the stored t may be off by
+        extra = R.conv_ref64(dt, w3.double().abs(), s3.double().abs(), None, None, False, 1, 0)
+        e = R.excess(y, ref, dtype, extra)
+        assert y.dtype == dtype and e <= 0, (n, h, w, e)
+        if not shown:
+            assert R.excess(R.one_ulp_off(y, ref, extra), ref, dtype, extra) > 0
+            shown = True

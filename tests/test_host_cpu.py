@@ -502,15 +502,15 @@ def test_integer_hooks_accept_and_refuse_exactly_their_codes():
             (0, 2), (4, 4), (10, 11), (20, 22), (29, 31), (100, 1099), (2010, 2400), (3010, 3400), (4010, 4400), (5001, 5999)]),
         'brcnn_roi_align_set_exact': (-5, 70, [(-5, 70)]),          # never refuses: unknown codes select the default form
     }
-    # brcnn_conv_set_tile(wm, nt), nt in -1..257: accepted nt per wm (wm = -8, 3, 5: none)
-    accepted_nt = {-7: [(0, 8)], -6: [(0, 1)], -5: [(0, 2)], -4: [(0, 1)], -3: [(0, 2)], -2: [(0, 2), (128, 128), (256, 256)],
+    # brcnn_conv_set_tile(wm, nt), nt in -1..257: accepted nt per wm (wm = -10, -8, 3, 5: none; -9: the 16 route counters, -1 clears)
+    accepted_nt = {-9: [(-1, 15)], -7: [(0, 8)], -6: [(0, 1)], -5: [(0, 2)], -4: [(0, 1)], -3: [(0, 2)], -2: [(0, 2), (128, 128), (256, 256)],
                    -1: [(-1, 257)], 0: [(0, 2)], 1: [(0, 2)], 2: [(0, 2)], 4: [(0, 2)]}
     try:
         for name, (lo, hi, want) in accepted.items():
             got = {c: getattr(L, name)(c) for c in range(lo, hi + 1)}
             assert set(got.values()) <= {0, EINVAL}, (name, sorted(set(got.values())))
             assert _ranges(c for c, r in got.items() if r == 0) == want, name
-        for wm in range(-8, 6):
+        for wm in range(-10, 6):
             got = {nt: L.brcnn_conv_set_tile(wm, nt) for nt in range(-1, 258)}
             assert set(got.values()) <= {0, EINVAL}, (wm, sorted(set(got.values())))
             assert _ranges(nt for nt, r in got.items() if r == 0) == accepted_nt.get(wm, []), wm

@@ -722,6 +722,29 @@ def test_fused_bottleneck_tail_equals_the_two_launches_bit_for_bit():
     assert not ops.bottleneck_tail_supported(torch.zeros(1, 5, 5, 64, device=DEV), w2, w3, torch.zeros(1, 5, 5, 256, device=DEV))
 
 
+def test_fused_bottleneck_tail_f32_against_float64():
+    """csrc/bottleneck_tail_f32.hip against the textbook chain in float64 (conv2 3x3, bn2, ReLU, conv3 1x1, bn3, + identity,
+    ReLU): the smallest legal size (rows a multiple of 64) with image borders inside a tile and two images, and one with
+    several tiles per image; bound: the suite's 2e-5 of the largest magnitude.  (An fp32 ulp is far below that bound: the
+    bit-equality test above notices it; shown here is that an error of twice the bound on one element is refused.)"""
+    from tests import route_util as R
+    g = torch.Generator().manual_seed(80)
+    for (n, h, w) in [(2, 8, 8), (3, 8, 40)]:
+        x = torch.randn(n, h, w, 64, generator=g).to(DEV)
+        idn = torch.randn(n, h, w, 256, generator=g).to(DEV)
+        w2 = (torch.randn(64, 3, 3, 64, generator=g) / 24).to(DEV)
+        w3 = (torch.randn(256, 1, 1, 64, generator=g) / 8).to(DEV)
+        s2, b2 = (torch.rand(64, generator=g) + 0.5).to(DEV), torch.randn(64, generator=g).to(DEV)
+        s3, b3 = (torch.rand(256, generator=g) + 0.5).to(DEV), torch.randn(256, generator=g).to(DEV)
+        y = ops.bottleneck_tail_nhwc(x, w2, s2, b2, w3, s3, b3, idn)
+        ref = R.conv_ref64(R.conv_ref64(x, w2, s2, b2, None, True, 1, 1), w3, s3, b3, idn, True, 1, 0)
+        e = R.excess(y, ref, torch.float32)
+        assert e <= 0, (n, h, w, e)
+        bad = y.clone()
+        bad.view(-1)[y.abs().argmax()] += 2 * R.ACC_TOL * max(1.0, ref.abs().max().item())
+        assert R.excess(bad, ref, torch.float32) > 0
+
+
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
 def test_bn_act_fused_forward_backward(dtype):
     """fused eval-BN affine (+residual) + ReLU and its backward against the torch ops it replaces"""
@@ -1053,16 +1076,21 @@ def test_roi_extract_16bit_training_path(dtype):
     # N, H, W, Cin, Cout, k, stride, pad, residual
     (2, 50, 84, 256, 256, 3, 1, 1, False),        # 72 K tiles of 32
     (2, 50, 84, 96, 256, 3, 1, 1, True),          # 27 K tiles (odd), residual
-    (3, 25, 42, 160, 512, 1, 1, 0, False),        # 5 K tiles, ragged row tiles
+    (3, 25, 42, 160, 512, 1, 1, 0, False),        # K = 160 < 256: dispatch_conv keeps the 64 x 64 kernel (asserted: a fall-back)
     (2, 51, 85, 64, 256, 3, 2, 1, False),         # stride 2
     (8, 50, 84, 256, 1024, 1, 1, 0, True),        # 528 tiles: the chained stream-K schedule in the heuristic
+    (3, 25, 42, 288, 512, 1, 1, 0, False),        # 9 K tiles (odd), ragged row tiles (3150 = 12 x 256 + 78 = 24 x 128 + 78), 1x1
 ])
 def test_f32_eight_phase_kernel_is_bit_identical(cfg):
     """the fp32 256 x 256 eight-phase kernel (conv_pp_f32.hip) keeps the two-buffer kernel's K order per accumulator:
-    identical results (plain and stream-K launches, K-tile count parities, strides, residual), launch after launch"""
+    identical results (plain and stream-K launches, K-tile count parities, strides, residual), launch after launch.
+    The route counters say which kernel each leg ran (the K = 160 case never reaches the eight-phase kernel: its leg
+    checks the fall-back), the baseline is pinned to float64 once per shape."""
     from brcnn import lib as _lib
+    from tests import route_util as R
     L = _lib.load()
     n, h, w_, ci, co, k, stride, pad, res = cfg
+    taken = k * k * ci >= 256                   # dispatch_conv's rule (Cout % 256 == 0 and Cin % 32 == 0 in every case)
     g = torch.Generator().manual_seed(35)
     x = torch.randn(n, h, w_, ci, generator=g).to(DEV)
     w = (torch.randn(co, k, k, ci, generator=g) * 0.05).to(DEV)
@@ -1072,42 +1100,86 @@ def test_f32_eight_phase_kernel_is_bit_identical(cfg):
     r = torch.randn(n, ho, wo, co, generator=g).to(DEV) if res else None
     try:
         assert L.brcnn_conv_set_tile(-2, 0) == 0
+        R.clear(L)
         ref = ops.conv2d_nhwc(x, w, sc, sh, r, True, stride, pad)
+        c = R.take(L)
+        assert c['pp_f32'] == 0 and c['sk_chain'] == 0 and c['sk_par'] == 0, c
+        ref64 = R.check_conv_against_fp64(ref, x, w, sc, sh, r, True, stride, pad, f'f32 {cfg}')
+        assert R.excess(R.twice_the_bound_off(ref, ref64), ref64, torch.float32) > 0       # the leg refuses an error of 2 x the bound
         for rows in (256, 128):                  # both tile heights forced
             assert L.brcnn_conv_set_tile(-2, rows) == 0
             for sk in (-3, -5, -4):
                 assert L.brcnn_conv_set_tile_bf16(sk) == 0
                 for rep in range(2):
+                    R.clear(L)
                     out = ops.conv2d_nhwc(x, w, sc, sh, r, True, stride, pad)
+                    c = R.take(L)
                     assert torch.equal(out, ref), (rows, sk, rep, (out - ref).abs().max().item())
+                    if taken:
+                        assert (c['pp_f32'], c['pp_f32_rows'], c['pp_f32_cols']) == (1, rows, 256), (rows, sk, c)
+                    else:
+                        assert c['pp_f32'] == 0, (rows, sk, c)
+                    assert c['sk_par'] == 0 and (sk != -3 or c['sk_chain'] == 0), (rows, sk, c)
+                    if co == 1024 and rows == 256 and sk != -3:     # 528 tiles on one workgroup per CU: forced and by the heuristic
+                        assert c['sk_chain'] == 1 and c['sk_wgs'] > 0, (rows, sk, c)
     finally:
         L.brcnn_conv_set_tile(-2, 1)
         L.brcnn_conv_set_tile_bf16(-4)
 
 
 def test_f32_eight_phase_kernel_data_gradient():
-    """the zero-stuffed data gradient of a stride-2 conv (DIL form) and the five-level launch on the fp32 eight-phase kernel"""
+    """the data gradient of a stride-2 conv and the five-level launch on the fp32 eight-phase kernel: equal bits with the
+    64 x 64 kernel; the counters say that the forced legs ran the eight-phase kernel and the baseline did not (one launch for
+    the five levels; the forward and the four phase convs autograd makes of an fp32 stride-2 data gradient -- the
+    zero-stuffed DIL form this test is named for is reached through the C entry point only, added here); baseline
+    against float64"""
     from brcnn import lib as _lib
     from brcnn.autograd import conv2d_nhwc_autograd
+    from tests import route_util as R
     L = _lib.load()
     g = torch.Generator().manual_seed(36)
     sizes = [(40, 64), (20, 32), (10, 16), (5, 8), (3, 4)]
     B, C = 2, 256
-    xc = torch.cat([torch.randn(B, h, w, C, generator=g).reshape(-1, C) for h, w in sizes], 0).to(DEV)
+    xs = [torch.randn(B, h, w, C, generator=g) for h, w in sizes]
+    xc = torch.cat([t.reshape(-1, C) for t in xs], 0).to(DEV)
     wt = (torch.randn(C, 3, 3, C, generator=g) / 48).to(DEV)
     dy = torch.randn(2, 25, 42, 256, generator=g).to(DEV)
     w2 = (torch.randn(256, 256, 3, 3, generator=g) / 48).to(DEV)
+    w2t = w2.flip(2, 3).permute(1, 2, 3, 0).contiguous()          # (Cin, KH, KW, Cout), taps flipped: the data-gradient operand
+    import ctypes
+    i50, i84, i25, i42 = ((ctypes.c_int * 1)(v) for v in (50, 84, 25, 42))
     try:
         outs = {}
         for mode in (0, 256, 128):
             assert L.brcnn_conv_set_tile(-2, mode) == 0
+            R.clear(L)
             y, _ = ops.conv2d_nhwc_multi(xc, wt, B, sizes, None, None, None, False, 1, 1)
+            c = R.take(L)
+            assert (c['pp_f32'], c['pp_f32_rows']) == ((1, mode) if mode else (0, 0)), (mode, c)
             x = torch.randn(2, 50, 84, 256, generator=torch.Generator().manual_seed(37)).to(DEV).requires_grad_(True)
             z = conv2d_nhwc_autograd(x, w2.clone().requires_grad_(True), None, 2, 1)
             z.backward(dy)
-            outs[mode] = (y, x.grad.clone())
+            c = R.take(L)
+            # conv launches: the forward and, in fp32, the data gradient of a stride-2 3x3 conv as FOUR stride-1 convs on
+            # the tap slices of the output phases (autograd._dgrad_stride2; K = 256 .. 1024) -- not the zero-stuffed form;
+            # the weight gradient has its own kernel
+            assert (c['pp_f32'], c['pp_f32_rows']) == ((5, mode) if mode else (0, 0)), (mode, c)
+            # the zero-stuffed (DIL) form itself: the C entry point, one launch
+            dx = torch.empty_like(x)
+            assert L.brcnn_conv2d_dgrad_nhwc_multi(dy.data_ptr(), w2t.data_ptr(), dx.data_ptr(), 2, 1, i50, i84, i25, i42, 256, 256, 3, 3,
+                                                   2, 1, 0, _lib.stream_handle()) == 0
+            c = R.take(L)
+            assert (c['pp_f32'], c['pp_f32_rows']) == ((1, mode) if mode else (0, 0)), (mode, c)
+            outs[mode] = (y, x.grad.clone(), dx)
         for mode in (256, 128):
-            assert torch.equal(outs[0][0], outs[mode][0]) and torch.equal(outs[0][1], outs[mode][1]), mode
+            assert all(torch.equal(outs[0][i], outs[mode][i]) for i in range(3)), mode
+        # the baseline against float64: per level, and the data gradient as autograd of the float64 conv
+        want = torch.cat([R.conv_ref64(t.to(DEV), wt, pad=1).reshape(-1, C) for t in xs], 0)
+        assert R.excess(outs[0][0].reshape(-1, C), want, torch.float32) <= 0
+        x64 = x.detach().double().permute(0, 3, 1, 2).requires_grad_(True)
+        torch.nn.functional.conv2d(x64, w2.double(), None, 2, 1).backward(dy.double().permute(0, 3, 1, 2))
+        assert R.excess(outs[0][1], x64.grad.permute(0, 2, 3, 1), torch.float32) <= 0
+        assert R.excess(outs[0][2], x64.grad.permute(0, 2, 3, 1), torch.float32) <= 0
     finally:
         L.brcnn_conv_set_tile(-2, 1)
 
@@ -1125,16 +1197,31 @@ def test_f32_split_k_option_is_reproducible_and_within_round_off():
     wb = (torch.randn(256, 3, 3, 256, generator=g) / 48).to(DEV)
     sc = (torch.rand(512, generator=g) + 0.5).to(DEV)
     sh = torch.randn(512, generator=g).to(DEV)
+    from tests import route_util as R
     try:
+        R.clear(L)
         ref = ops.conv2d_nhwc(x, w, sc, sh, None, True, 1, 1)
+        c = R.take(L)
+        assert c['sk_par'] == 0, c                      # off by default
         refb = ops.conv2d_nhwc(xb, wb, None, None, None, False, 1, 1)
+        cb = R.take(L)
+        assert cb['sk_par'] == 0, cb
+        # the unsplit results against float64 (K = 4608 / 2304)
+        R.check_conv_against_fp64(ref, x, w, sc, sh, None, True, 1, 1, 'f32 split-K layer 8x25x42 512->512 3x3')
+        R.check_conv_against_fp64(refb, xb, wb, None, None, None, False, 1, 1, 'f32 enough-tiles layer 8x50x84 256->256 3x3')
         assert L.brcnn_conv_set_tile_bf16(-9) == 0
         a = ops.conv2d_nhwc(x, w, sc, sh, None, True, 1, 1)
         b = ops.conv2d_nhwc(x, w, sc, sh, None, True, 1, 1)
+        c2 = R.take(L)
+        # both launches: the eight-phase kernel on 128-row tiles, split-K (66 x 2 tiles of 128 x 256 on 256 CUs)
+        assert (c2['pp_f32'], c2['pp_f32_rows'], c2['sk_par'], c2['sk_chain']) == (2, 128, 2, 0) and c2['sk_wgs'] > 132, c2
         assert torch.equal(a, b)
         assert not torch.equal(a, ref)          # the layer IS split (66 x 2 tiles of 128 x 256 on 256 CUs)
         assert (a - ref).abs().max().item() <= 1e-5 * ref.abs().max().item()
+        R.clear(L)
         assert torch.equal(ops.conv2d_nhwc(xb, wb, None, None, None, False, 1, 1), refb)
+        c3 = R.take(L)
+        assert c3['sk_par'] == 0 and c3['pp_f32'] == cb['pp_f32'] and c3['sk_chain'] == cb['sk_chain'], (c3, cb)   # untouched: the route it had
     finally:
         L.brcnn_conv_set_tile_bf16(-8)
 
@@ -1153,14 +1240,21 @@ def test_roi_extract_visiting_order_and_rows_per_wave_keep_the_bits():
     feats = [torch.randn(B, h, w, 256, generator=g).to(DEV) for h, w in sizes]
     rois = util.rand_rois(7000, B, 672., 400., seed=4, min_size=4., max_size=500.).to(DEV)     # unsorted images, tiny and huge RoIs
     try:
+        # (ops.roi_extract hands the library an order scratch only from 12 288 RoIs on unless told to: without one a forced
+        # order falls back to the unordered visit -- the counter (hook 60) says which legs were ordered)
         L.brcnn_roi_align_set_exact(30)      # the footprint form itself (round 5's prepared records off)
         L.brcnn_roi_align_set_exact(11); L.brcnn_roi_align_set_exact(20)
-        ref, lref = ops.roi_extract(feats, rois, 7, strides, 56, 0)
+        L.brcnn_roi_align_set_exact(60)
+        ref, lref = ops.roi_extract(feats, rois, 7, strides, 56, 0, order_scratch=True)
+        assert L.brcnn_roi_align_set_exact(60) == 0
         for rpw in (11, 17):
             for od in (20, 22):
                 L.brcnn_roi_align_set_exact(rpw); L.brcnn_roi_align_set_exact(od)
-                out, lv = ops.roi_extract(feats, rois, 7, strides, 56, 0)
+                out, lv = ops.roi_extract(feats, rois, 7, strides, 56, 0, order_scratch=True)
+                assert L.brcnn_roi_align_set_exact(60) == int(od == 22), (rpw, od)
                 assert torch.equal(out, ref) and torch.equal(lv, lref), (rpw, od)
+        out, lv = ops.roi_extract(feats, rois, 7, strides, 56, 0)       # 7000 RoIs, no scratch: the documented fall-back
+        assert L.brcnn_roi_align_set_exact(60) == 0 and torch.equal(out, ref)
         # raw C ABI: the order scratch is written (a permutation of 0..n-1) only when given
         L.brcnn_roi_align_set_exact(22)
         n = rois.shape[0]
@@ -1171,7 +1265,7 @@ def test_roi_extract_visiting_order_and_rows_per_wave_keep_the_bits():
         sc = (ctypes.c_float * 5)(*[1.0 / s for s in strides])
         st = L.brcnn_roi_extract_forward_ordered(ptrs, hs, ws, sc, 5, rois.data_ptr(), out.data_ptr(), None, B, 256, n, 7, 7, 0,
                                                  56.0, 0, order.data_ptr(), lib.stream_handle())
-        assert st == 0
+        assert st == 0 and L.brcnn_roi_align_set_exact(60) == 1
         torch.cuda.synchronize()
         assert torch.equal(out, ref) and torch.equal(order.sort().values, torch.arange(n, dtype=torch.int32, device=DEV))
     finally:
@@ -1201,10 +1295,14 @@ def test_roi_extract_prepared_records_equal_the_footprint_form(dtype):
     rois = torch.cat([rois, extra]).to(DEV)
     try:
         L.brcnn_roi_align_set_exact(30)
+        L.brcnn_roi_align_set_exact(60); L.brcnn_roi_align_set_exact(61)
         ref, lref = ops.roi_extract(feats, rois, 7, strides, 56, 0)
+        assert (L.brcnn_roi_align_set_exact(60), L.brcnn_roi_align_set_exact(61)) == (0, 0)       # the footprint form, unordered
         for od in (20, 22):
             L.brcnn_roi_align_set_exact(31); L.brcnn_roi_align_set_exact(od)
-            out, lv = ops.roi_extract(feats, rois, 7, strides, 56, 0)
+            # (an order scratch at this RoI count too: the forced order is then taken -- hook 60)
+            out, lv = ops.roi_extract(feats, rois, 7, strides, 56, 0, order_scratch=True)
+            assert (L.brcnn_roi_align_set_exact(60), L.brcnn_roi_align_set_exact(61)) == (int(od == 22), 1), od
             assert torch.equal(lv, lref)
             differ = (out != ref).flatten(1).any(1)
             assert differ.float().mean().item() < 0.2, differ.float().mean().item()      # most RoIs: the streaming form, same bits
@@ -1231,6 +1329,7 @@ def test_roi_extract_prepared_records_equal_the_footprint_form(dtype):
                                                   56.0, dt, None, None, 0, lib.raw_stream_handle())
         torch.cuda.synchronize()
         assert st == 0 and torch.equal(o2, ref)
+        assert (L.brcnn_roi_align_set_exact(60), L.brcnn_roi_align_set_exact(61)) == (0, 0)       # NULL scratch: the footprint form
         nb = L.brcnn_roi_extract_prep_workspace_bytes(n)
         assert nb == n * 576
         L.brcnn_roi_align_set_exact(30)
@@ -1268,9 +1367,13 @@ def test_f32_eight_phase_256x128_tile_is_bit_identical(cfg):
     sh = torch.randn(co, generator=g).to(DEV)
     ho, wo = ops.conv_out_size(h, w_, k, k, stride, pad)
     r = torch.randn(n, ho, wo, co, generator=g).to(DEV) if res else None
+    from tests import route_util as R
     try:
         assert L.brcnn_conv_set_tile(-3, 0) == 0
+        R.clear(L)
         ref = ops.conv2d_nhwc(x, w, sc, sh, r, True, stride, pad)
+        c = R.take(L)
+        assert c['pp_f32'] == 0 and c['sk_chain'] == 0, c
         y64 = ref.double()
         xd, wd = x.double().permute(0, 3, 1, 2), w.double().permute(0, 3, 1, 2)
         want = torch.nn.functional.conv2d(xd, wd, None, stride, pad).permute(0, 2, 3, 1) * sc.double() + sh.double()
@@ -1281,8 +1384,195 @@ def test_f32_eight_phase_256x128_tile_is_bit_identical(cfg):
         for sk in (-3, -5, -4):
             assert L.brcnn_conv_set_tile_bf16(sk) == 0
             for rep in range(2):
+                R.clear(L)
                 out = ops.conv2d_nhwc(x, w, sc, sh, r, True, stride, pad)
+                c = R.take(L)
                 assert torch.equal(out, ref), (sk, rep, (out - ref).abs().max().item())
+                assert (c['pp_f32'], c['pp_f32_rows'], c['pp_f32_cols']) == (1, 256, 128), (sk, c)
+                assert c['sk_par'] == 0 and (sk != -3 or c['sk_chain'] == 0), (sk, c)
     finally:
         L.brcnn_conv_set_tile(-3, 1)
         L.brcnn_conv_set_tile_bf16(-4)
+
+
+_DT_CODE = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 3}
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
+def test_packed_conv_operands_equal_the_torch_expression(dtype):
+    """brcnn_pack_conv_weights_batch through the raw C ABI, by exact equality: the forward operand is
+    w.permute(0, 2, 3, 1) and the data-gradient operand w.flip(2, 3).permute(1, 2, 3, 0), cast once -- ragged 32 x 32
+    blocks, 1x1 / 3x3 / 7x7 taps, contiguous and channels-last sources, a NULL data-gradient entry, 70 tensors in one
+    call (a second table of 64), and a skipped step (ctl[2] = 1) that leaves both operands untouched"""
+    import ctypes
+    from brcnn import lib
+    L = lib.load()
+    g = torch.Generator().manual_seed(51)
+    shapes = [(54, 70, 3), (33, 31, 1), (64, 3, 7), (128, 64, 3)]
+    ws, want_f, want_d = [], [], []
+    for i in range(70):
+        co, ci, k = shapes[i % 4]
+        w = torch.randn(co, ci, k, k, generator=g).to(DEV)
+        if (i // 4) % 2:        # channels-last source (same values, other strides)
+            w = w.contiguous(memory_format=torch.channels_last)
+        ws.append(w)
+        want_f.append(w.permute(0, 2, 3, 1).contiguous().to(dtype))
+        want_d.append(w.flip(2, 3).permute(1, 2, 3, 0).contiguous().to(dtype))
+    no_dgrad = 66                                     # in the second table
+    fwd = [torch.full_like(t, 7.0) for t in want_f]
+    dg = [torch.full_like(t, 7.0) for t in want_d]
+    n = len(ws)
+    wp = (ctypes.c_void_p * n)(*[w.data_ptr() for w in ws])
+    fp = (ctypes.c_void_p * n)(*[t.data_ptr() for t in fwd])
+    dp = (ctypes.c_void_p * n)(*[None if i == no_dgrad else t.data_ptr() for i, t in enumerate(dg)])
+    dims = (ctypes.c_int * (4 * n))(*[int(v) for w in ws for v in w.shape])
+    cl = (ctypes.c_int * n)(*[int(not w.is_contiguous()) for w in ws])
+    assert any(cl) and not all(cl)
+    ctl = torch.tensor([0., 1., 1.], device=DEV)     # [norm, factor, skipped]: the step was skipped -> nothing is written
+    assert L.brcnn_pack_conv_weights_batch(wp, fp, dp, dims, cl, n, _DT_CODE[dtype], ctl.data_ptr(), lib.raw_stream_handle()) == 0
+    torch.cuda.synchronize()
+    assert all(bool((t == 7.0).all()) for t in fwd + dg)
+    ctl[2] = 0.
+    assert L.brcnn_pack_conv_weights_batch(wp, fp, dp, dims, cl, n, _DT_CODE[dtype], ctl.data_ptr(), lib.raw_stream_handle()) == 0
+    torch.cuda.synchronize()
+    for i in range(n):
+        assert torch.equal(fwd[i], want_f[i]), ('forward operand', i, tuple(ws[i].shape), cl[i])
+        if i == no_dgrad:
+            assert bool((dg[i] == 7.0).all())
+        else:
+            assert torch.equal(dg[i], want_d[i]), ('data-gradient operand', i, tuple(ws[i].shape), cl[i])
+    # without a control block
+    f0, d0 = torch.empty_like(want_f[0]), torch.empty_like(want_d[0])
+    assert L.brcnn_pack_conv_weights_batch((ctypes.c_void_p * 1)(ws[0].data_ptr()), (ctypes.c_void_p * 1)(f0.data_ptr()),
+                                           (ctypes.c_void_p * 1)(d0.data_ptr()), (ctypes.c_int * 4)(*ws[0].shape), None, 1,
+                                           _DT_CODE[dtype], None, lib.raw_stream_handle()) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(f0, want_f[0]) and torch.equal(d0, want_d[0])
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16, torch.float16])
+def test_permuted_fc_operands_equal_the_torch_expression(dtype):
+    """brcnn_pack_fc_weight_permuted (fc_perm_kernel + transpose16_kernel), by exact equality: the forward operand is
+    w.view(out, C, P).permute(0, 2, 1) -- the (C, P) columns of the first FC in the (P, C) order of the NHWC features --
+    and the data-gradient operand its transpose, cast once; ragged 64 x 64 transpose tiles, P = 1 and the largest P,
+    without the transposed operand, a skipped step, and the refusals (C % 64 != 0, P > 255)"""
+    from brcnn import lib
+    L = lib.load()
+    g = torch.Generator().manual_seed(52)
+    code, st = _DT_CODE[dtype], lib.raw_stream_handle()
+    for (out, C, P) in [(70, 128, 49), (64, 64, 1), (130, 64, 255)]:
+        w = torch.randn(out, C * P, generator=g).to(DEV)
+        want = w.view(out, C, P).permute(0, 2, 1).contiguous().to(dtype)
+        for with_t in (True, False):
+            f = torch.full((out, P, C), 7.0, dtype=dtype, device=DEV)
+            d = torch.full((P * C, out), 7.0, dtype=dtype, device=DEV)
+            skipped = torch.tensor([0., 1., 1.], device=DEV)
+            assert L.brcnn_pack_fc_weight_permuted(w.data_ptr(), f.data_ptr(), d.data_ptr() if with_t else None, out, C, P, code,
+                                                   skipped.data_ptr(), st) == 0
+            torch.cuda.synchronize()
+            assert bool((f == 7.0).all()) and bool((d == 7.0).all())
+            assert L.brcnn_pack_fc_weight_permuted(w.data_ptr(), f.data_ptr(), d.data_ptr() if with_t else None, out, C, P, code,
+                                                   None, st) == 0
+            torch.cuda.synchronize()
+            assert torch.equal(f, want), (out, C, P)
+            if with_t:
+                assert torch.equal(d, want.reshape(out, P * C).t().contiguous()), (out, C, P)
+            else:
+                assert bool((d == 7.0).all())
+    w = torch.zeros(8, 96 * 4, device=DEV)
+    f = torch.zeros(8, 256 * 96, dtype=dtype, device=DEV)
+    assert L.brcnn_pack_fc_weight_permuted(w.data_ptr(), f.data_ptr(), None, 8, 96, 4, code, None, st) == -22       # C % 64
+    assert L.brcnn_pack_fc_weight_permuted(w.data_ptr(), f.data_ptr(), None, 8, 64, 256, code, None, st) == -22     # P > 255
+
+
+_GATHER_CASES = {}
+
+
+def _gather_case(C, dtype):
+    """RoIs, dY (rounded to `dtype`) and the float64 adjoint per level of the chunked-gather case, computed once per (C, dtype)"""
+    from tests import roi_ref64 as RR
+    if (C, dtype) not in _GATHER_CASES:
+        rois, dy = RR.gather_case(C, RR.PILE[dtype])
+        dy = dy.to(dtype).float()
+        _GATHER_CASES[(C, dtype)] = (rois, dy, RR.roi_extract_adjoint_f64(dy, rois, 3, device=DEV))
+    return _GATHER_CASES[(C, dtype)]
+
+
+def _gather_leg(L, hook, want_ch, rois, dy, C, dtype, addends=None):
+    """one backward pass of the RoI extractor in the gather form under chunk hook `hook`; asserts the chunked-launch
+    counter (62) and its chunk count (63): `want_ch` chunks per coarse tile, 0 = the one-workgroup form"""
+    from brcnn import autograd as ag
+    from tests import roi_ref64 as RR
+    assert ag.ROI_BACKWARD_GATHER
+    assert L.brcnn_roi_align_set_exact(hook) == 0
+    L.brcnn_roi_align_set_exact(62); L.brcnn_roi_align_set_exact(63)
+    fg = [torch.zeros(3, h, w, C, device=DEV, dtype=dtype).requires_grad_() for h, w in RR.SIZES]
+    if addends is None:
+        out = ag.roi_extract_autograd(fg, rois.to(DEV), 7, RR.STRIDES, 56, 0)
+    else:
+        out = ag.RoIExtractFunction.apply(rois.to(DEV), 7, RR.STRIDES, 56, 0, list(addends), *fg)
+    out.backward(dy.to(DEV, dtype))
+    torch.cuda.synchronize()
+    got = (L.brcnn_roi_align_set_exact(62), L.brcnn_roi_align_set_exact(63))
+    assert got == ((1, want_ch) if want_ch else (0, 0)), (hook, got)
+    return [f.grad for f in fg]
+
+
+def _gather_check(grads, ref, dtype, what, addends=None):
+    from tests import roi_ref64 as RR
+    from tests import route_util as R
+    for l, g in enumerate(grads):
+        S = ref[l] if addends is None else ref[l] + addends[l].double().abs()          # the addend is one more term of the sum
+        want = ref[l] if addends is None else ref[l] + addends[l].double()
+        # K_KERNEL (tests/roi_ref64.py): 4 x the fp32 C oracle's own measured ratio on these inputs, per level
+        # (oracle at most 7441 / 114 / 24 / 61 / 0 at C = 32 and 260, taken as 7500 / 120 / 25 / 65 / 0 -> kernel 30000 / 480 / 100 / 260 / 0)
+        bound = RR.gather_bound(RR.K_KERNEL[l], S, want, R.half_ulp(dtype))
+        over = ((g.double() - want).abs() - bound).max().item()
+        assert g.dtype == dtype and over <= 0, (what, l, over)
+
+
+@pytest.mark.parametrize('C', [32, 260])
+def test_roi_gather_chunked_against_the_float64_adjoint(C):
+    """roi_grad_gather_kernel with chunks + roi_grad_chunk_sum_kernel against the float64 adjoint of RoIAlign
+    (tests/roi_ref64.py; the inputs and why they resolve one lost hit: gather_case and tests/test_roi_ref64_cpu.py): one
+    launch over a fine level (77 tiles per image) and chunked coarse ones; image 0 with 520 RoIs piled on both tiles of
+    the 7 x 11 map (a second collection batch), image 1 without RoIs (chunk 0 writes the zeros), image 2 with few-hit
+    tiles (the direct path) beside a pile; C = 260: a second 256-channel pass with a partial wave.  2 chunks, the
+    heuristic's 5 and 16, and chunking off (the counter stays 0) all meet the same elementwise bound
+    K_KERNEL 2^-24 S, S = the float64 adjoint of |dY|; with per-level addends; with RoIs not grouped by image."""
+    from brcnn import lib
+    from tests import roi_ref64 as RR
+    L = lib.load()
+    rois, dy, ref = _gather_case(C, torch.float32)
+    try:
+        for hook, ch in ((39, 5), (42, 2), (56, 16), (40, 0)):
+            _gather_check(_gather_leg(L, hook, ch, rois, dy, C, torch.float32), ref, torch.float32, (C, hook))
+        g = torch.Generator().manual_seed(31)
+        adds = [(torch.rand(3, h, w, C, generator=g) + 0.5).to(DEV) for h, w in RR.SIZES]
+        for hook, ch in ((39, 5), (40, 0)):
+            _gather_check(_gather_leg(L, hook, ch, rois, dy, C, torch.float32, adds), ref, torch.float32, (C, hook, 'addends'), adds)
+        if C == 32:     # RoIs of the images interleaved: "only widens the range" of RoIs a tile looks at
+            perm = torch.randperm(rois.shape[0], generator=g)
+            _gather_check(_gather_leg(L, 39, 5, rois[perm], dy[perm], C, torch.float32), ref, torch.float32, (C, 'ungrouped'))
+    finally:
+        L.brcnn_roi_align_set_exact(39)
+
+
+@pytest.mark.parametrize('dtype', [torch.bfloat16, torch.float16])
+def test_roi_gather_chunked_16bit_against_the_float64_adjoint(dtype):
+    """the same with 16-bit gradient maps (fp32 accumulation, one rounding at the store): the bound gains half an ulp of
+    the result, and the pile is as large as that rounding still resolves one hit of (12 RoIs for bf16, 120 for fp16:
+    tests/test_roi_ref64_cpu.py); dY and the addends are the 16-bit values"""
+    from brcnn import lib
+    from tests import roi_ref64 as RR
+    L = lib.load()
+    C = 32
+    rois, dy, ref = _gather_case(C, dtype)
+    g = torch.Generator().manual_seed(32)
+    adds = [(torch.rand(3, h, w, C, generator=g) + 0.5).to(DEV, dtype) for h, w in RR.SIZES]
+    try:
+        for hook, ch in ((39, 5), (42, 2), (56, 16), (40, 0)):
+            _gather_check(_gather_leg(L, hook, ch, rois, dy, C, dtype), ref, dtype, (dtype, hook))
+        _gather_check(_gather_leg(L, 39, 5, rois, dy, C, dtype, adds), ref, dtype, (dtype, 'addends'), adds)
+    finally:
+        L.brcnn_roi_align_set_exact(39)

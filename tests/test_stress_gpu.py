@@ -116,18 +116,31 @@ def test_stream_k_200_repetitions_under_load_equal_the_plain_launch(shape):
     sc = (torch.rand(co, generator=g) + 0.5).to(DEV)
     sh = torch.randn(co, generator=g).to(DEV)
     load = _Load()
+    from tests import route_util as R
+    tiles = (0, 82, 8844, 21)
+    chained = {t: 0 for t in tiles}
     try:
         assert L.brcnn_conv_set_tile_bf16(-3) == 0
+        R.clear(L)
         ref = ops.conv2d_nhwc(x, w, sc, sh, None, True, 1, k // 2)
+        c = R.take(L)
+        assert c['sk_chain'] == 0 and c['sk_par'] == 0, c          # the plain launch
+        R.check_conv_against_fp64(ref, x, w, sc, sh, None, True, 1, k // 2, f'bf16 stream-K stress {shape}')
         assert L.brcnn_conv_set_tile_bf16(-5) == 0
         for rep in range(REPS):
             load.push(rep)
             # alternate the tile shapes that take the schedule: the hand-over slots and epoch flags are shared
-            assert L.brcnn_conv_set_tile_bf16((0, 82, 8844, 21)[rep % 4]) == 0
+            assert L.brcnn_conv_set_tile_bf16(tiles[rep % 4]) == 0
             out = ops.conv2d_nhwc(x, w, sc, sh, None, True, 1, k // 2)
+            chained[tiles[rep % 4]] += L.brcnn_conv_set_tile(-9, 6)
             assert torch.equal(out, ref), (rep, (out.float() - ref.float()).abs().max().item())
         torch.cuda.synchronize()
         _lib.handover_status()
+        # a tile shape hands tiles over on every repetition or on none (fewer tiles than resident workgroups: 132 tiles
+        # of 256 x 256 on the 33 600-row maps); the 128 x 128 tile (526 / 2100 / 1052 tiles for 512 slots) always does
+        print(f'stream-K stress {shape}: chained launches per tile code {chained} of {REPS // 4} each')
+        assert all(v in (0, REPS // 4) for v in chained.values()), chained
+        assert chained[82] == REPS // 4, chained
     finally:
         L.brcnn_conv_set_tile_bf16(0)
         L.brcnn_conv_set_tile_bf16(-4)
@@ -277,6 +290,7 @@ def test_persistent_short_k_kernel_equals_the_tile_kernels_under_repetition(dtyp
     around it.  100 repetitions per shape against the one-tile-per-workgroup kernel, bit for bit -- a wait that let a tile
     through early would read a stale ring slot in some repetition"""
     from brcnn import lib, ops
+    from tests import route_util as R
     L = lib.load()
     g = torch.Generator().manual_seed(9)
     try:
@@ -287,7 +301,11 @@ def test_persistent_short_k_kernel_equals_the_tile_kernels_under_repetition(dtyp
             sc = (torch.rand(co, generator=g) + 0.5).cuda(); sh = torch.randn(co, generator=g).cuda()
             r = torch.randn(n, h, w_, co, generator=g).to(dtype).cuda() if res else None
             assert L.brcnn_conv_set_tile_bf16(-15) == 0
+            R.clear(L)
             ref = ops.conv2d_nhwc(x, wt, scale=sc, shift=sh, residual=r, relu=relu)
+            c = R.take(L)
+            assert c['stream'] == 0 and c['tile'] == 1, c           # the one-tile-per-workgroup kernel
+            R.check_conv_against_fp64(ref, x, wt, sc, sh, r, relu, 1, 0, f'{dtype} 1x1 {(n, h, w_, k, co, res, relu)}')
             assert L.brcnn_conv_set_tile_bf16(-17) == 0
             other = torch.randn(4096, 4096, device='cuda')          # a co-running load on a second stream
             side = torch.cuda.Stream()
@@ -296,6 +314,7 @@ def test_persistent_short_k_kernel_equals_the_tile_kernels_under_repetition(dtyp
                     with torch.cuda.stream(side):
                         other @ other
                 got = ops.conv2d_nhwc(x, wt, scale=sc, shift=sh, residual=r, relu=relu)
+                assert L.brcnn_conv_set_tile(-9, 5) == 1, 'the persistent kernel declined the launch'
                 assert torch.equal(got, ref), (rep, (n, h, w_, k, co, res, relu), int((got != ref).sum()))
             torch.cuda.synchronize()
     finally:
