@@ -355,15 +355,17 @@ class ConvModule(nn.Module):
         # GroupNorm needs the statistics of the whole conv output: conv, then fused GN(+ReLU)
         assert residual is None and not with_skip
         y = conv_bn_act_nhwc(x, self.conv, None, self._cache, False)
-        if y.requires_grad:
-            from . import autograd as ag
-            if y.shape[3] <= 256 and y.shape[3] % 4 == 0:
-                return ag.groupnorm_nhwc_autograd(y, norm.weight, norm.bias, norm.num_groups, norm.eps,
-                                                  self.with_activation)
+        if y.shape[3] > 256 or y.shape[3] % 4:
+            # wider than the kernels' one-workgroup row (256 channels) or no whole channel quads: torch's GroupNorm, in
+            # training and at inference alike
             import torch.nn.functional as F
             z = F.group_norm(y.permute(0, 3, 1, 2).float(), norm.num_groups, norm.weight, norm.bias, norm.eps)
             z = z.permute(0, 2, 3, 1).to(y.dtype)
             return (z.relu() if self.with_activation else z).contiguous()
+        if y.requires_grad:
+            from . import autograd as ag
+            return ag.groupnorm_nhwc_autograd(y, norm.weight, norm.bias, norm.num_groups, norm.eps,
+                                              self.with_activation)
         return ops.groupnorm_nhwc(y, norm.weight.detach(), norm.bias.detach(), norm.num_groups,
                                   norm.eps, self.with_activation)
 

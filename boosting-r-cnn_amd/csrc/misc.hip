@@ -338,15 +338,15 @@ __global__ void gn_finalize_kernel(double* __restrict__ stats, GnSegs sg, int N,
     reinterpret_cast<float2*>(stats + (size_t)i * 2)[0] = make_float2((float)mean, rstd);
 }
 
-// pass 3: y = (x - mean) * rstd * gamma + beta (+ReLU); Q channel quads (16 bytes) per thread
-template <typename T, int Q>
+// pass 3: y = (x - mean) * rstd * gamma + beta (+ReLU); one channel quad per thread (the flat form: C % 8 == 4)
+template <typename T>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x,
                                                       const double* __restrict__ stats,
                                                       const float* __restrict__ gamma,
                                                       const float* __restrict__ beta,
                                                       T* __restrict__ y, GnSegs sg, int N, int C,
                                                       int G, int relu) {
-    const int cvn = C / (4 * Q), cpg = C / G;
+    const int cvn = C / 4, cpg = C / G;
     // 32-bit index arithmetic (the host checks rows * C < 2^31): the row -> (segment, image) decode
     // was two 64-bit divisions per thread and iteration
     const unsigned total = (unsigned)(sg.row0[sg.nseg] * cvn);
@@ -359,27 +359,19 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x,
             if (t < sg.nseg && row >= (unsigned)sg.row0[t]) seg = t;
         const int n = (int)((row - (unsigned)sg.row0[seg]) / (unsigned)sg.hw[seg]);
         const size_t sbase = ((size_t)(seg * N + n)) * G;
-        static_assert(Q == 1 || Q == 2, "one or two channel quads per thread");
-        float4 v[2];
-        if constexpr (Q == 2) ld8(x + (size_t)idx * 8, v[0], v[1]);
-        else v[0] = ld4(x + (size_t)idx * 4);
+        const float4 v = ld4(x + (size_t)idx * 4);
+        const int c0 = cv * 4;
+        const float in[4] = {v.x, v.y, v.z, v.w};
+        float out[4];
 #pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const int c0 = (cv * Q + q) * 4;
-            const float in[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
-            float out[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int c = c0 + e;
-                const float2 mr = reinterpret_cast<const float2*>(stats + (sbase + c / cpg) * 2)[0];
-                float o = (in[e] - mr.x) * mr.y * gamma[c] + beta[c];
-                if (relu) o = fmaxf(o, 0.f);
-                out[e] = o;
-            }
-            v[q] = make_float4(out[0], out[1], out[2], out[3]);
+        for (int e = 0; e < 4; e++) {
+            const int c = c0 + e;
+            const float2 mr = reinterpret_cast<const float2*>(stats + (sbase + c / cpg) * 2)[0];
+            float o = (in[e] - mr.x) * mr.y * gamma[c] + beta[c];
+            if (relu) o = fmaxf(o, 0.f);
+            out[e] = o;
         }
-        if constexpr (Q == 2) st8(y + (size_t)idx * 8, v[0], v[1]);
-        else st4(y + (size_t)idx * 4, v[0]);
+        st4(y + (size_t)idx * 4, make_float4(out[0], out[1], out[2], out[3]));
     }
 }
 
@@ -485,16 +477,18 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_rows_kernel(const T* __restr
 // B = sum g*xh) of its row chunk; they go to a partial buffer [workgroup][2][C] for the
 // deterministic second stage (dgamma / dbeta), and, weighted by gamma, as two double atomics per
 // group into gsum (s1, s2).
-template <typename T>
+template <typename T, int V>
 __global__ __launch_bounds__(256) void gn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                            const double* __restrict__ stats,
                                                            const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, double* __restrict__ gsum,
                                                            float* __restrict__ part, GnSegs sg, int N, int C, int G,
                                                            int rows_per_block, int relu) {
-    // V channels per lane: 16-byte loads for both element widths (8 x 16-bit / 4 x fp32); LPR lanes cover 256 channels
-    // of a row, RL rows are in flight per pass over the block's row strip
-    constexpr int V = sizeof(T) == 2 ? 8 : 4, LPR = 256 / V, RL = 256 / LPR;
+    // V channels per lane as in gn_stats_kernel: 16-byte loads for both element widths where C % 8 == 0 (8 x 16-bit /
+    // 4 x fp32), 8-byte loads of a 16-bit tensor with C % 8 == 4 (V = 4); LPR lanes cover 256 channels of a row, RL rows
+    // are in flight per pass over the block's row strip
+    static_assert(V == 4 || (V == 8 && sizeof(T) == 2), "one 16-byte load per lane, or half of one for 16-bit rows");
+    constexpr int LPR = 256 / V, RL = 256 / LPR;
     __shared__ float red[RL][256][2];
     const int seg = blockIdx.y / N, n = blockIdx.y - seg * N;
     const int HW = sg.hw[seg];
@@ -617,16 +611,16 @@ __global__ __launch_bounds__(256) void gn_bwd_param_final_kernel(const float* __
     else dgamma[col - C] = t;
 }
 
-// Q channel quads (16 bytes of a 16-bit tensor with Q = 2) per thread; the group statistics are fetched once per
-// quad when the quad lies inside one group (channels per group a multiple of 4: every GroupNorm of the recipes)
-template <typename T, int Q>
+// one channel quad per thread (the flat form: C % 8 == 4); the group statistics are fetched once per quad when the
+// quad lies inside one group (channels per group a multiple of 4), per channel when it straddles two
+template <typename T>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                           const double* __restrict__ stats,
                                                           const double* __restrict__ gsum,
                                                           const float* __restrict__ gamma,
                                                           const float* __restrict__ beta, T* __restrict__ dx,
                                                           GnSegs sg, int N, int C, int G, int relu) {
-    const int cvn = C / (4 * Q), cpg = C / G;
+    const int cvn = C / 4, cpg = C / G;
     const unsigned total = (unsigned)(sg.row0[sg.nseg] * cvn);      // rows * C < 2^31 checked by the host
     for (unsigned idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
         const unsigned row = idx / (unsigned)cvn;
@@ -638,40 +632,28 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const T* __restrict__
         const int n = (int)((row - (unsigned)sg.row0[seg]) / (unsigned)sg.hw[seg]);
         const size_t sbase = ((size_t)(seg * N + n)) * G;
         const float inv_d = 1.f / ((float)sg.hw[seg] * (float)cpg);
-        float4 xq[2], dq[2];
-        if constexpr (Q == 2) {
-            ld8(x + (size_t)idx * 8, xq[0], xq[1]);
-            ld8(dy + (size_t)idx * 8, dq[0], dq[1]);
-        } else {
-            xq[0] = ld4(x + (size_t)idx * 4);
-            dq[0] = ld4(dy + (size_t)idx * 4);
-        }
+        const float4 xq = ld4(x + (size_t)idx * 4), dq = ld4(dy + (size_t)idx * 4);
+        const int c0 = cv * 4;
+        const float xi[4] = {xq.x, xq.y, xq.z, xq.w}, di[4] = {dq.x, dq.y, dq.z, dq.w};
+        const bool one = (c0 + 3) / cpg == c0 / cpg;
+        size_t gi = (sbase + c0 / cpg) * 2;
+        float2 mr = reinterpret_cast<const float2*>(stats + gi)[0];
+        float s1 = (float)gsum[gi], s2 = (float)gsum[gi + 1];
+        float out[4];
 #pragma unroll
-        for (int q = 0; q < Q; q++) {
-            const int c0 = (cv * Q + q) * 4;
-            const float xi[4] = {xq[q].x, xq[q].y, xq[q].z, xq[q].w}, di[4] = {dq[q].x, dq[q].y, dq[q].z, dq[q].w};
-            const bool one = (c0 + 3) / cpg == c0 / cpg;
-            size_t gi = (sbase + c0 / cpg) * 2;
-            float2 mr = reinterpret_cast<const float2*>(stats + gi)[0];
-            float s1 = (float)gsum[gi], s2 = (float)gsum[gi + 1];
-            float out[4];
-#pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int c = c0 + e;
-                if (!one) {
-                    gi = (sbase + c / cpg) * 2;
-                    mr = reinterpret_cast<const float2*>(stats + gi)[0];
-                    s1 = (float)gsum[gi]; s2 = (float)gsum[gi + 1];
-                }
-                const float xh = (xi[e] - mr.x) * mr.y;
-                const float gmm = gamma[c];
-                const float g = (relu && xh * gmm + beta[c] <= 0.f) ? 0.f : di[e];
-                out[e] = mr.y * (g * gmm - (s1 + xh * s2) * inv_d);
+        for (int e = 0; e < 4; e++) {
+            const int c = c0 + e;
+            if (!one) {
+                gi = (sbase + c / cpg) * 2;
+                mr = reinterpret_cast<const float2*>(stats + gi)[0];
+                s1 = (float)gsum[gi]; s2 = (float)gsum[gi + 1];
             }
-            xq[q] = make_float4(out[0], out[1], out[2], out[3]);
+            const float xh = (xi[e] - mr.x) * mr.y;
+            const float gmm = gamma[c];
+            const float g = (relu && xh * gmm + beta[c] <= 0.f) ? 0.f : di[e];
+            out[e] = mr.y * (g * gmm - (s1 + xh * s2) * inv_d);
         }
-        if constexpr (Q == 2) st8(dx + (size_t)idx * 8, xq[0], xq[1]);
-        else st4(dx + (size_t)idx * 4, xq[0]);
+        st4(dx + (size_t)idx * 4, make_float4(out[0], out[1], out[2], out[3]));
     }
 }
 
@@ -947,7 +929,7 @@ static int gn_forward_16(const void* x, const float* gamma, const float* beta, v
                        channels, groups, eps);
     BRCNN_LAUNCH_CHECK();
     if (channels & 7) {
-        hipLaunchKernelGGL((gn_apply_kernel<T, 1>), dim3(stream_grid(total)), dim3(256), 0, s, (const T*)x,
+        hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(stream_grid(total)), dim3(256), 0, s, (const T*)x,
                            (const double*)stats_ws, gamma, beta, (T*)y, sg, batch, channels, groups, relu);
     } else {
         int max_hw = 0;
@@ -1002,7 +984,7 @@ BRCNN_API int brcnn_groupnorm_nhwc_multi(const void* x, const float* gamma, cons
                                dim3(256), 0, s, (const float*)x, (const double*)stats_ws, gamma, beta, (float*)y, sg, batch, channels,
                                groups, GN_APPLY_ROWS, relu);
         else
-        hipLaunchKernelGGL((gn_apply_kernel<float, 1>), dim3(stream_grid(total)), dim3(256), 0, s,
+        hipLaunchKernelGGL(gn_apply_kernel<float>, dim3(stream_grid(total)), dim3(256), 0, s,
                            (const float*)x, (const double*)stats_ws, gamma, beta, (float*)y, sg, batch,
                            channels, groups, relu);
     } else if (dtype == BRCNN_DT_BF16) {
@@ -1061,8 +1043,7 @@ BRCNN_API int brcnn_groupnorm_nhwc_multi_backward(const void* dy, const void* x,
                                                   int relu, int dtype, void* stream) {
     if (!dy || !x || !stats || !gamma || !beta || !dx || !dgamma || !dbeta || !workspace || batch <= 0 ||
         num_segments <= 0 || num_segments > BRCNN_MAX_LEVELS || !hw_host || channels <= 0 || channels > 256 ||
-        groups <= 0 || channels % groups || (channels & 3) || !brcnn_elem_ok(dtype) ||
-        (dtype != BRCNN_DT_F32 && (channels & 7)))          // 16-bit rows are read 8 channels (16 bytes) per lane
+        groups <= 0 || channels % groups || (channels & 3) || !brcnn_elem_ok(dtype))
         return BRCNN_EINVAL;
     if (workspace_bytes < brcnn_groupnorm_nhwc_multi_backward_workspace_bytes(batch, num_segments, hw_host, channels, groups))
         return BRCNN_EINVAL;
@@ -1080,18 +1061,22 @@ BRCNN_API int brcnn_groupnorm_nhwc_multi_backward(const void* dy, const void* x,
     BRCNN_HIP_CHECK(hipMemsetAsync(gsum, 0, gbytes, s));
     const long long total = rows * (channels >> 2);
     const int num_parts = batch * num_segments * chunks;
+    const dim3 rgrid(chunks, batch * num_segments);
     if (dtype == BRCNN_DT_F32)
-        hipLaunchKernelGGL(gn_bwd_reduce_kernel<float>, dim3(chunks, batch * num_segments), dim3(256), 0, s,
-                           (const float*)x, (const float*)dy, (const double*)stats, gamma, beta, gsum, part, sg, batch,
-                           channels, groups, rpb, relu);
-    else if (dtype == BRCNN_DT_BF16)
-        hipLaunchKernelGGL(gn_bwd_reduce_kernel<bf16_t>, dim3(chunks, batch * num_segments), dim3(256), 0, s,
-                           (const bf16_t*)x, (const bf16_t*)dy, (const double*)stats, gamma, beta, gsum, part, sg,
-                           batch, channels, groups, rpb, relu);
+        hipLaunchKernelGGL((gn_bwd_reduce_kernel<float, 4>), rgrid, dim3(256), 0, s, (const float*)x, (const float*)dy,
+                           (const double*)stats, gamma, beta, gsum, part, sg, batch, channels, groups, rpb, relu);
+    else if (dtype == BRCNN_DT_BF16 && !(channels & 7))
+        hipLaunchKernelGGL((gn_bwd_reduce_kernel<bf16_t, 8>), rgrid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy,
+                           (const double*)stats, gamma, beta, gsum, part, sg, batch, channels, groups, rpb, relu);
+    else if (dtype == BRCNN_DT_BF16)            // C % 8 == 4: a 16-bit row is not a whole number of 16-byte vectors
+        hipLaunchKernelGGL((gn_bwd_reduce_kernel<bf16_t, 4>), rgrid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)dy,
+                           (const double*)stats, gamma, beta, gsum, part, sg, batch, channels, groups, rpb, relu);
+    else if (!(channels & 7))
+        hipLaunchKernelGGL((gn_bwd_reduce_kernel<f16_t, 8>), rgrid, dim3(256), 0, s, (const f16_t*)x, (const f16_t*)dy,
+                           (const double*)stats, gamma, beta, gsum, part, sg, batch, channels, groups, rpb, relu);
     else
-        hipLaunchKernelGGL(gn_bwd_reduce_kernel<f16_t>, dim3(chunks, batch * num_segments), dim3(256), 0, s,
-                           (const f16_t*)x, (const f16_t*)dy, (const double*)stats, gamma, beta, gsum, part, sg,
-                           batch, channels, groups, rpb, relu);
+        hipLaunchKernelGGL((gn_bwd_reduce_kernel<f16_t, 4>), rgrid, dim3(256), 0, s, (const f16_t*)x, (const f16_t*)dy,
+                           (const double*)stats, gamma, beta, gsum, part, sg, batch, channels, groups, rpb, relu);
     BRCNN_LAUNCH_CHECK();
     float* part2 = part + (size_t)num_parts * 2 * channels;
     hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((2 * channels + 31) / 32, GN_PARAM_SLICES), dim3(256), 0, s, part, part2,
@@ -1100,14 +1085,12 @@ BRCNN_API int brcnn_groupnorm_nhwc_multi_backward(const void* dy, const void* x,
     hipLaunchKernelGGL(gn_bwd_param_final_kernel, dim3((2 * channels + 255) / 256), dim3(256), 0, s, part2, dgamma, dbeta,
                        channels);
     BRCNN_LAUNCH_CHECK();
-    // one channel quad per thread: the two-quad (16-byte) form measured 35 % SLOWER here (295 vs 208 us per
-    // backward of the tower tensor in bf16), although it is the faster one in the forward apply kernel
     if (dtype == BRCNN_DT_F32 && !(channels & 7))
         hipLaunchKernelGGL(gn_bwd_apply_rows_kernel<float>, dim3((max_hw + GN_APPLY_ROWS - 1) / GN_APPLY_ROWS, batch * num_segments), dim3(256), 0, s, (const float*)x, (const float*)dy,
                                (const double*)stats, gsum, gamma, beta, (float*)dx, sg, batch, channels, groups,
                                GN_APPLY_ROWS, relu);
     else if (dtype == BRCNN_DT_F32)
-        hipLaunchKernelGGL((gn_bwd_apply_kernel<float, 1>), dim3(stream_grid(total)), dim3(256), 0, s, (const float*)x,
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, dim3(stream_grid(total)), dim3(256), 0, s, (const float*)x,
                            (const float*)dy, (const double*)stats, gsum, gamma, beta, (float*)dx, sg, batch, channels,
                            groups, relu);
     else if ((channels & 7) == 0) {      // 16-bit, whole 16-byte channel vectors: the row-strip form
@@ -1121,11 +1104,11 @@ BRCNN_API int brcnn_groupnorm_nhwc_multi_backward(const void* dy, const void* x,
                                (const double*)stats, gsum, gamma, beta, (f16_t*)dx, sg, batch, channels, groups,
                                GN_APPLY_ROWS, relu);
     } else if (dtype == BRCNN_DT_BF16)
-        hipLaunchKernelGGL((gn_bwd_apply_kernel<bf16_t, 1>), dim3(stream_grid(total)), dim3(256), 0, s, (const bf16_t*)x,
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<bf16_t>, dim3(stream_grid(total)), dim3(256), 0, s, (const bf16_t*)x,
                            (const bf16_t*)dy, (const double*)stats, gsum, gamma, beta, (bf16_t*)dx, sg, batch, channels,
                            groups, relu);
     else
-        hipLaunchKernelGGL((gn_bwd_apply_kernel<f16_t, 1>), dim3(stream_grid(total)), dim3(256), 0, s, (const f16_t*)x,
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<f16_t>, dim3(stream_grid(total)), dim3(256), 0, s, (const f16_t*)x,
                            (const f16_t*)dy, (const double*)stats, gsum, gamma, beta, (f16_t*)dx, sg, batch, channels,
                            groups, relu);
     BRCNN_LAUNCH_CHECK();

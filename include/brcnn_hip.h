@@ -493,7 +493,9 @@ int brcnn_groupnorm_nhwc_multi(const void *x, const float *gamma, const float *b
  * forward's stats_ws (mean / rstd per (segment, image, group) after the forward call), `relu`
  * the forward's flag (the clipped positions are recomputed from x).  Writes dx (same layout and
  * dtype as x), dgamma / dbeta (channels, fp32, overwritten).  Deterministic except for the
- * double-precision group sums (atomics). */
+ * double-precision group sums (atomics).  Accepts what the forward accepts, in every dtype:
+ * channels <= 256, channels % 4 == 0, channels % groups == 0; anything else is BRCNN_EINVAL
+ * and writes nothing. */
 size_t brcnn_groupnorm_nhwc_multi_backward_workspace_bytes(int batch, int num_segments, const int *hw_host,
                                                            int channels, int groups);
 int brcnn_groupnorm_nhwc_multi_backward(const void *dy, const void *x, const void *stats, const float *gamma,

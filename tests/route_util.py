@@ -66,12 +66,12 @@ def check_conv_against_fp64(y, x, w, scale, shift, residual, relu, stride, pad, 
     return ref
 
 
-def twice_the_bound_off(y, ref):
+def twice_the_bound_off(y, ref, extra=None):
     """`y` with its largest element moved by twice the bound: what an fp32 leg must refuse (an fp32 ulp, 6e-8 of the value,
     is below the suite's fp32 bound by construction; there the bit-equality legs notice an ulp)"""
     out = y.clone().contiguous()
     i = out.abs().view(-1).argmax()
-    out.view(-1)[i] += 2 * bound(ref, y.dtype).reshape(-1)[i].to(y.dtype)
+    out.view(-1)[i] += 2 * bound(ref, y.dtype, extra).reshape(-1)[i].to(y.dtype)
     return out
 
 
