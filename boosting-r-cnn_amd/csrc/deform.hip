@@ -234,10 +234,23 @@ __global__ __launch_bounds__(256) void deform_im2col_nhwc16_kernel(const unsigne
 }
 
 // torch AvgPool2d output size (the last window must start inside the input in ceil mode)
+// (the division rounds towards minus infinity, as torch's does: a map smaller than the window has no output, where
+// C's truncation would give it one)
 inline int brcnn_avgpool_out(int in, int kernel, int stride, int pad, int ceil_mode) {
-    int o = ceil_mode ? (in + 2 * pad - kernel + stride - 1) / stride + 1 : (in + 2 * pad - kernel) / stride + 1;
+    const int num = in + 2 * pad - kernel + (ceil_mode ? stride - 1 : 0);
+    if (num < 0) return 0;
+    int o = num / stride + 1;
     if (ceil_mode && (o - 1) * stride >= in + pad) o--;
     return o;
+}
+
+// a kernel extent the padded map does not hold has no output either (C's truncating division would give it one row)
+inline bool deform_out_size(int height, int width, int kh, int kw, int stride, int pad, int dilation, int* Ho, int* Wo) {
+    const int eh = height + 2 * pad - (dilation * (kh - 1) + 1), ew = width + 2 * pad - (dilation * (kw - 1) + 1);
+    if (eh < 0 || ew < 0) return false;
+    *Ho = eh / stride + 1;
+    *Wo = ew / stride + 1;
+    return true;
 }
 
 inline int stream_grid(long long total) {
@@ -253,12 +266,8 @@ BRCNN_API int brcnn_avgpool_nhwc(const float* x, float* y, int batch, int height
     if (!x || !y || batch <= 0 || height <= 0 || width <= 0 || channels <= 0 || (channels & 3) || kernel <= 0 ||
         stride <= 0 || pad < 0 || pad > kernel / 2)
         return BRCNN_EINVAL;
-    auto osz = [&](int in) {
-        int o = ceil_mode ? (in + 2 * pad - kernel + stride - 1) / stride + 1 : (in + 2 * pad - kernel) / stride + 1;
-        if (ceil_mode && (o - 1) * stride >= in + pad) o--;      // last window must start inside the input
-        return o;
-    };
-    const int Ho = osz(height), Wo = osz(width);
+    const int Ho = brcnn_avgpool_out(height, kernel, stride, pad, ceil_mode);
+    const int Wo = brcnn_avgpool_out(width, kernel, stride, pad, ceil_mode);
     if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
     const long long total = (long long)batch * Ho * Wo * (channels >> 2);
     hipLaunchKernelGGL(avgpool_nhwc_kernel<BRCNN_DT_F32>, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x, y, batch,
@@ -274,9 +283,8 @@ BRCNN_API int brcnn_deform_im2col_nhwc(const float* x, const float* offset_mask,
         kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dilation <= 0 || om_stride < 3 * kh * kw ||
         channels_padded < channels || (channels_padded & 3))
         return BRCNN_EINVAL;
-    const int Ho = (height + 2 * pad - (dilation * (kh - 1) + 1)) / stride + 1;
-    const int Wo = (width + 2 * pad - (dilation * (kw - 1) + 1)) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
+    int Ho, Wo;
+    if (!deform_out_size(height, width, kh, kw, stride, pad, dilation, &Ho, &Wo)) return BRCNN_EINVAL;
     const long long total = (long long)batch * Ho * Wo * kh * kw * (channels_padded >> 2);
     hipLaunchKernelGGL(deform_im2col_nhwc_kernel, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x,
                        offset_mask, col, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation,
@@ -294,9 +302,8 @@ BRCNN_API int brcnn_deform_col2im_nhwc(const float* x, const float* offset_mask,
         channels <= 0 || (channels & 3) || kh <= 0 || kw <= 0 || stride <= 0 || pad < 0 || dilation <= 0 ||
         om_stride != 3 * kh * kw || channels_padded < channels || (channels_padded & 3))
         return BRCNN_EINVAL;
-    const int Ho = (height + 2 * pad - (dilation * (kh - 1) + 1)) / stride + 1;
-    const int Wo = (width + 2 * pad - (dilation * (kw - 1) + 1)) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
+    int Ho, Wo;
+    if (!deform_out_size(height, width, kh, kw, stride, pad, dilation, &Ho, &Wo)) return BRCNN_EINVAL;
     const long long items = (long long)batch * Ho * Wo * kh * kw;
     hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_F32>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        x, offset_mask, dcol, dx, d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride,
@@ -340,9 +347,8 @@ BRCNN_API int brcnn_deform_im2col_nhwc_ex(const void* x, const float* offset_mas
         channels_padded < channels || (channels_padded & 7) || (dtype != BRCNN_DT_BF16 && dtype != BRCNN_DT_F16) ||
         (long long)batch * height * width * channels >= 0x7fffffffLL)
         return BRCNN_EINVAL;
-    const int Ho = (height + 2 * pad - (dilation * (kh - 1) + 1)) / stride + 1;
-    const int Wo = (width + 2 * pad - (dilation * (kw - 1) + 1)) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
+    int Ho, Wo;
+    if (!deform_out_size(height, width, kh, kw, stride, pad, dilation, &Ho, &Wo)) return BRCNN_EINVAL;
     const long long total = (long long)batch * Ho * Wo * kh * kw * (channels_padded >> 3);
     if (dtype == BRCNN_DT_F16)
         hipLaunchKernelGGL(deform_im2col_nhwc16_kernel<BRCNN_DT_F16>, dim3(stream_grid(total)), dim3(256), 0,
@@ -368,9 +374,8 @@ BRCNN_API int brcnn_deform_col2im_nhwc_ex(const void* x, const float* offset_mas
         om_stride != 3 * kh * kw || channels_padded < channels || (channels_padded & 3) ||
         (dtype != BRCNN_DT_BF16 && dtype != BRCNN_DT_F16))
         return BRCNN_EINVAL;
-    const int Ho = (height + 2 * pad - (dilation * (kh - 1) + 1)) / stride + 1;
-    const int Wo = (width + 2 * pad - (dilation * (kw - 1) + 1)) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
+    int Ho, Wo;
+    if (!deform_out_size(height, width, kh, kw, stride, pad, dilation, &Ho, &Wo)) return BRCNN_EINVAL;
     const long long items = (long long)batch * Ho * Wo * kh * kw;
     if (dtype == BRCNN_DT_F16)
         hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_F16>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0,

@@ -254,8 +254,9 @@ BRCNN_API int brcnn_deform_conv_nhwc(const void* x, const float* offset_mask, co
         (cout != 64 && cout != 128 && cout != 256) || (stride != 1 && stride != 2) || pad < 0 || pad > 2 ||
         om_stride < 27 || (dtype != BRCNN_DT_BF16 && dtype != BRCNN_DT_F16))
         return BRCNN_EINVAL;
+    // (a padded map smaller than the kernel has no output: C's truncating division would give it one row)
+    if (height + 2 * pad < 3 || width + 2 * pad < 3) return BRCNN_EINVAL;
     const int Ho = (height + 2 * pad - 3) / stride + 1, Wo = (width + 2 * pad - 3) / stride + 1;
-    if (Ho <= 0 || Wo <= 0) return BRCNN_EINVAL;
     const long long M = (long long)batch * Ho * Wo;
     // every element offset (x, y, the weights' byte range of the buffer descriptor) fits 32 bits
     if ((long long)batch * height * width * channels >= 0x7fffffffLL || M * cout >= 0x7fffffffLL ||

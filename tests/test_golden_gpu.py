@@ -428,33 +428,14 @@ def test_grouped_conv_and_resnext_golden():
 
 
 def _deform_ref(x, om, w, stride, pad):
-    """modulated deformable 3x3 conv in fp64 torch, straight from the published algorithm
-    (mmcv modulated_deform_conv: taps displaced by (dy, dx), zero outside (-1, H) x (-1, W),
-    bilinear with per-corner validity, times sigmoid(mask))"""
-    n, c, h, wd = x.shape
-    ho, wo = om.shape[2], om.shape[3]
-    x, om, w = x.double(), om.double(), w.double()
-    out = torch.zeros(n, w.shape[0], ho, wo, dtype=torch.float64)
-    ys = (torch.arange(ho) * stride - pad).view(1, ho, 1).double()
-    xs = (torch.arange(wo) * stride - pad).view(1, 1, wo).double()
-    for t in range(9):
-        i, j = t // 3, t % 3
-        hy = ys + i + om[:, 2 * t]
-        wx = xs + j + om[:, 2 * t + 1]
-        mask = torch.sigmoid(om[:, 18 + t])
-        inside = (hy > -1) & (wx > -1) & (hy < h) & (wx < wd)
-        hl, wl = torch.floor(hy), torch.floor(wx)
-        lh, lw = hy - hl, wx - wl
-        val = torch.zeros(n, c, ho, wo, dtype=torch.float64)
-        for (hh, ww, wt) in ((hl, wl, (1 - lh) * (1 - lw)), (hl, wl + 1, (1 - lh) * lw),
-                             (hl + 1, wl, lh * (1 - lw)), (hl + 1, wl + 1, lh * lw)):
-            ok = inside & (hh >= 0) & (hh <= h - 1) & (ww >= 0) & (ww <= wd - 1)
-            hi, wi = hh.clamp(0, h - 1).long(), ww.clamp(0, wd - 1).long()
-            g = x[torch.arange(n).view(n, 1, 1), :, hi, wi].permute(0, 3, 1, 2)      # (n,c,ho,wo)
-            val += g * (wt * ok).unsqueeze(1)
-        val = val * mask.unsqueeze(1)
-        out += torch.einsum('nchw,oc->nohw', val, w[:, :, i, j])
-    return out
+    """modulated deformable 3x3 conv in fp64 torch, straight from the published algorithm (mmcv modulated_deform_conv:
+    taps displaced by (dy, dx), zero outside (-1, H) x (-1, W), bilinear with per-corner validity, times sigmoid(mask)):
+    NCHW x, om (N, 27, Ho, Wo) and w (Cout, C, 3, 3) in, (N, Cout, Ho, Wo) out -- a thin wrapper over
+    tests/deform_ref64.py (differentiable in x, om and w as before)"""
+    from tests import deform_ref64
+    y = deform_ref64.deform_conv64(x.double().permute(0, 2, 3, 1), om.double().permute(0, 2, 3, 1),
+                                   w.double().permute(0, 2, 3, 1), 3, 3, stride, pad, 1)
+    return y.permute(0, 3, 1, 2)
 
 
 def test_avgpool_deform_res2net_golden():
