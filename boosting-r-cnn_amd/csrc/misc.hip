@@ -1017,6 +1017,35 @@ static int gn_setup(GnSegs& sg, long long& rows, int& max_hw, int batch, int num
     return 0;
 }
 
+// The statistics half of brcnn_groupnorm_nhwc_multi alone (fp32): the same two launches with the same arguments, so
+// stats_ws holds the same (mean, rstd) bits; the apply pass is left to a consumer that folds it into its operand load
+// (conv_winograd_f32.hip)
+BRCNN_API int brcnn_groupnorm_nhwc_multi_stats(const void* x, void* stats_ws, int batch, int num_segments, const int* hw_host,
+                                               int channels, int groups, float eps, int dtype, void* stream) {
+    if (!x || !stats_ws || batch <= 0 || num_segments <= 0 || num_segments > BRCNN_MAX_LEVELS || !hw_host || channels <= 0 ||
+        channels > 256 || groups <= 0 || channels % groups || (channels & 3) || dtype != BRCNN_DT_F32)
+        return BRCNN_EINVAL;
+    GnSegs sg;
+    long long rows;
+    int max_hw;
+    if (gn_setup(sg, rows, max_hw, batch, num_segments, hw_host)) return BRCNN_EINVAL;
+    if (rows * channels >= 0x7fffffffLL) return BRCNN_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    BRCNN_HIP_CHECK(hipMemsetAsync(stats_ws, 0, (size_t)batch * num_segments * groups * 2 * sizeof(double), s));
+    int chunks = (max_hw + 255) / 256;
+    if (chunks > 512) chunks = 512;
+    const int rpb = (max_hw + chunks - 1) / chunks;
+    chunks = (max_hw + rpb - 1) / rpb;
+    const int nstat = num_segments * batch * groups;
+    hipLaunchKernelGGL((gn_stats_kernel<float, 4>), dim3(chunks, batch * num_segments), dim3(256), 0, s, (const float*)x,
+                       (double*)stats_ws, sg, batch, channels, groups, rpb);
+    BRCNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3((nstat + 255) / 256), dim3(256), 0, s, (double*)stats_ws, sg, batch, channels,
+                       groups, eps);
+    BRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
 static void gn_bwd_chunks(int max_hw, int* chunks, int* rpb) {
     int c = (max_hw + 255) / 256;
     if (c > 64) c = 64;

@@ -15,6 +15,9 @@ struct Policy {
     int pp_f32_mode = 1;            // tuning hook (brcnn_conv_set_tile(-2, 0 / 1 / 2 / 128 / 256)): eight-phase fp32 kernel never / heuristic / forced (tile rows by the heuristic / 128 / 256)
     int f32_tile_sk = 1;            // tuning hook (brcnn_conv_set_tile(-5, 0 / 1 / 2)): persistent 64 x 64 launch never / heuristic / forced
     int f32_tile_sk_per_cu = 0;     // tuning hook ((-7, n)): workgroups per CU of the persistent launch, 0 = the occupancy query's
+    // ---- fp32 Winograd F(2x2,3x3) (conv_winograd_f32.hip): brcnn_conv_set_tile(-11, n); read by the CALLER that prepares filters
+    int f32_winograd = 1;           // (-11, 0 / 1): never / where the caller prepared the transformed filter; (-11, 2) returns it
+    int f32_winograd_chunks = 1;    // tuning hook ((-11, 10 + n), n = 1 .. 8): transform + GEMM launch pairs per call
 
     // ---- 16-bit conv (conv_igemm_bf16.hip, conv1x1_stream_bf16.hip): brcnn_conv_set_tile_bf16(mtnt)
     int bf16_tile = 0;              // tuning hook: 0 heuristic, 11 / 21 / 22 = MT NT (4 waves), 42 = 256x128 (8 waves)
@@ -75,6 +78,9 @@ struct Counters {
     int bf16_tile_stages = 0;       // n = 13: and LDS ring stages
     int wgrad_bf16_tile_launches = 0;   // n = 14: launches of the tile kernel of conv_wgrad_bf16.hip (not the eight-phase one)
     int wgrad_bf16_last_tile = 0;       // n = 15: the tile code (1 / 2 / 4) of the last one
+    // brcnn_conv_set_tile(-12, 0 / 1): return and clear ((-9, -1) clears them too)
+    int f32_winograd_launches = 0;      // (-12, 0): calls of brcnn_conv3x3_winograd_f32_multi that launched
+    int f32_winograd_tiles = 0;         // (-12, 1): 2x2 output tiles of the last one
     // brcnn_roi_align_set_exact(60 .. 63): return and clear
     int roi_ordered_launches = 0;   // 60: RoI forward launches that visited the RoIs in band order
     int roi_prepared_launches = 0;  // 61: RoI forward launches in the prepared-record form

@@ -25,9 +25,29 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
                           &g_counters.wgrad_bf16_tile_launches, &g_counters.wgrad_bf16_last_tile};
         const int count = (int)(sizeof(c) / sizeof(c[0]));
         if (nt < -1 || nt >= count) return BRCNN_EINVAL;
-        if (nt == -1) { for (int* q : c) *q = 0; return 0; }
+        if (nt == -1) {
+            for (int* q : c) *q = 0;
+            g_counters.f32_winograd_launches = g_counters.f32_winograd_tiles = 0;
+            return 0;
+        }
         const int n = *c[nt];
         *c[nt] = 0;
+        return n;
+    }
+    // Winograd F(2x2,3x3) for the fp32 3x3 layers whose caller prepared the filter: (-11, 0 / 1) never / yes, (-11, 2) RETURNS
+    // the setting (the caller decides: the entry point itself never falls back), (-11, 10 + n): n launch pairs per call
+    if (wm == -11) {
+        if (nt == 0 || nt == 1) { g_policy.f32_winograd = nt; return 0; }
+        if (nt == 2) return g_policy.f32_winograd;
+        if (nt >= 11 && nt <= 18) { g_policy.f32_winograd_chunks = nt - 10; return 0; }
+        return BRCNN_EINVAL;
+    }
+    // (-12, 0): Winograd calls so far, (-12, 1): tiles of the last one; return and clear
+    if (wm == -12) {
+        if (nt != 0 && nt != 1) return BRCNN_EINVAL;
+        int& c = nt == 0 ? g_counters.f32_winograd_launches : g_counters.f32_winograd_tiles;
+        const int n = c;
+        c = 0;
         return n;
     }
     if (wm == -2) { if (nt != 0 && nt != 1 && nt != 2 && nt != 128 && nt != 256) return BRCNN_EINVAL; g_policy.pp_f32_mode = nt; return 0; }

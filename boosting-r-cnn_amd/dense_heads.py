@@ -157,6 +157,10 @@ class ATSSRPNHead(AnchorHead):
         self._head_caches = [PackedCache() for _ in range(8)]
         self._tower_caches = [PackedCache() for _ in range(stacked_convs)]
         self._fused_head_cache = PackedCache()
+        # Winograd-transformed tower filters (prepare_winograd: inference with frozen weights, fp32), keyed on the weight
+        # like the caches above
+        self._wino_caches = [PackedCache() for _ in range(stacked_convs)]
+        self._wino_prepared = False
         self._base_anchor_cache = {}
         self.init_weights()
 
@@ -267,6 +271,9 @@ class ATSSRPNHead(AnchorHead):
         B = feats[0].shape[0]
         sizes = [tuple(f.shape[1:3]) for f in feats]
         x = cat_rows(feats)        # (a view when the neck wrote the levels back to back: ops.output_into)
+        if self._wino_prepared and x.dtype == torch.float32 and self._winograd_ok() and ops.winograd_enabled():
+            x = self._tower_winograd(x, B, sizes)
+            return self._fused_heads(x, B, sizes)
         for i, conv in enumerate(self.rpn_convs):
             assert isinstance(conv.norm, nn.GroupNorm) and conv.conv.bias is None
             w = self._tower_caches[i].get([conv.conv.weight],
@@ -275,6 +282,43 @@ class ATSSRPNHead(AnchorHead):
             x = ops.groupnorm_nhwc_multi(x, conv.norm.weight.detach(), conv.norm.bias.detach(),
                                          conv.norm.num_groups, B, sizes, conv.norm.eps,
                                          conv.with_activation)
+        return self._fused_heads(x, B, sizes)
+
+    def prepare_winograd(self):
+        """Inference with frozen weights: the tower's four 3x3 convs may run in the Winograd F(2x2,3x3) form (fp32 compute
+        only, and only while the library's switch is on: ops.winograd_enabled).  The transformed filters are built here
+        when the weights already live on the device, else on the first pass; a later load_state_dict rebuilds them."""
+        self._wino_prepared = True
+        if self._winograd_ok() and self.rpn_convs[0].conv.weight.is_cuda and ops.winograd_enabled():
+            for i, conv in enumerate(self.rpn_convs):
+                self._wino_filter(i, conv)
+        return self
+
+    def _winograd_ok(self):
+        return all(isinstance(c.norm, nn.GroupNorm) and c.conv.bias is None and c.conv.groups == 1 and
+                   c.conv.kernel_size == (3, 3) and c.conv.stride == (1, 1) and c.conv.padding == (1, 1) and
+                   c.conv.dilation == (1, 1) and c.conv.in_channels % 32 == 0 and c.conv.out_channels % 64 == 0 and
+                   c.conv.out_channels <= 256 for c in self.rpn_convs)
+
+    def _wino_filter(self, i, conv):
+        return self._wino_caches[i].get([conv.conv.weight], lambda: ops.winograd_filter(pack_weight(conv.conv.weight)))
+
+    def _tower_winograd(self, x, B, sizes):
+        """the tower with each layer's GroupNorm + ReLU applied by the NEXT conv's input transform: per layer the Winograd
+        conv and the GroupNorm statistics of its raw output; the last layer's GroupNorm runs as the usual pass (the
+        54-channel head conv stays direct)"""
+        ws = ops.winograd_workspace(B, sizes, max(c.conv.in_channels for c in self.rpn_convs), x.device)    # one for the four layers
+        gn, last = None, len(self.rpn_convs) - 1
+        for i, conv in enumerate(self.rpn_convs):
+            x = ops.conv3x3_winograd_multi(x, self._wino_filter(i, conv), B, sizes, gn=gn, workspace=ws)
+            norm = conv.norm
+            if i == last:
+                return ops.groupnorm_nhwc_multi(x, norm.weight.detach(), norm.bias.detach(), norm.num_groups, B, sizes,
+                                                norm.eps, conv.with_activation)
+            gn = (ops.groupnorm_stats_multi(x, norm.num_groups, B, sizes, norm.eps), norm.weight.detach(),
+                  norm.bias.detach(), norm.num_groups, conv.with_activation)
+
+    def _fused_heads(self, x, B, sizes):
         heads = (self.rpn_cls, self.rpn_reg, self.rpn_iou)
 
         def builder():

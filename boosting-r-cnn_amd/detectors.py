@@ -213,8 +213,11 @@ class TwoStageDetector(BaseDetector):
 
     def freeze_for_inference(self):
         """read the (tiny) host-side constants once so that `simple_test_device` issues no
-        device->host copies: the five learnable rpn_reg scales."""
+        device->host copies: the five learnable rpn_reg scales.  The weights are frozen from here on, so the RPN tower
+        may also keep Winograd-transformed filters (fp32 compute only; ATSSRPNHead.prepare_winograd)."""
         self._rpn_scale_cache = [float(m.scale.detach().cpu()) for m in self.rpn_head.scales]
+        if hasattr(self.rpn_head, 'prepare_winograd'):
+            self.rpn_head.prepare_winograd()
         return self
 
     # ---- features ----------------------------------------------------------------------

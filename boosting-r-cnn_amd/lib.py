@@ -55,6 +55,11 @@ SIGNATURES = {
     'brcnn_conv2d_nhwc_scatter2': (c_int, [c_ptr] * 3 + [c_int] * 14 + [c_ptr]),
     'brcnn_conv2d_nhwc_multi': (c_int, [c_ptr] * 6 + [c_int, c_int, c_ptr, c_ptr] + [c_int] * 8 +
                                 [c_ptr]),
+    'brcnn_winograd_filter_f32': (c_int, [c_ptr, c_ptr] + [c_int] * 5 + [c_ptr]),
+    'brcnn_conv3x3_winograd_f32_multi_workspace_bytes': (c_size, [c_int, c_int, c_ptr, c_ptr, c_int]),
+    'brcnn_conv3x3_winograd_f32_multi': (c_int, [c_ptr] * 5 + [c_int, c_int, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_size,
+                                                 c_int, c_int, c_ptr, c_ptr] + [c_int] * 7 + [c_ptr]),
+    'brcnn_groupnorm_nhwc_multi_stats': (c_int, [c_ptr, c_ptr, c_int, c_int, c_ptr, c_int, c_int, c_f32, c_int, c_ptr]),
     'brcnn_conv2d_dgrad_nhwc_multi': (c_int, [c_ptr] * 3 + [c_int, c_int] + [c_ptr] * 4 + [c_int] * 7 +
                                       [c_ptr]),
     'brcnn_conv2d_wgrad_nhwc_multi': (c_int, [c_ptr] * 3 + [c_int, c_int] + [c_ptr] * 2 + [c_int] * 7 +

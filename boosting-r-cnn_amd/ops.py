@@ -674,6 +674,79 @@ def groupnorm_nhwc_multi(x_cat, gamma, beta, groups, batch, sizes, eps=1e-5, rel
     return (y, ws) if return_stats else y
 
 
+def groupnorm_stats_multi(x_cat, groups, batch, sizes, eps=1e-5):
+    """the (mean, rstd) buffer of groupnorm_nhwc_multi without its apply pass (fp32): for conv3x3_winograd_multi's `gn`"""
+    import ctypes
+    _require_gpu(x_cat)
+    L = len(sizes)
+    ws = torch.empty((batch * L * groups * 2,), dtype=torch.float64, device=x_cat.device)
+    hw = (ctypes.c_int * L)(*[h * w for h, w in sizes])
+    st = _L.load().brcnn_groupnorm_nhwc_multi_stats(_ptr(x_cat), _ptr(ws), batch, L, hw, x_cat.shape[1], int(groups),
+                                                    float(eps), _dt(x_cat), _stream())
+    _L.check(st, 'brcnn_groupnorm_nhwc_multi_stats')
+    return ws
+
+
+def winograd_enabled():
+    """the library's switch for the Winograd form of the fp32 3x3 layers (csrc/policy.h: f32_winograd); the CALLER reads
+    it when it decides whether to prepare transformed filters -- the Winograd entry points never fall back by themselves"""
+    return _L.load().brcnn_conv_set_tile(-11, 2) == 1
+
+
+def winograd_filter(w):
+    """packed fp32 weight (Cout,3,3,Cin) -> the transformed filter (16,Cout,Cin) of conv3x3_winograd_multi; once per weight"""
+    _require_gpu(w)
+    assert w.dim() == 4 and w.is_contiguous()
+    cout, kh, kw, cin = w.shape
+    u = torch.empty((16, cout, cin), dtype=torch.float32, device=w.device)
+    st = _L.load().brcnn_winograd_filter_f32(_ptr(w), _ptr(u), cout, cin, kh, kw, _dt(w), _stream())
+    _L.check(st, 'brcnn_winograd_filter_f32')
+    return u
+
+
+_WINO_WS = {}       # (device, stream) -> the V workspace of that stream's Winograd convs (grow-only; launches of one stream are ordered)
+
+
+def winograd_workspace(batch, sizes, cin, device):
+    """the V workspace of conv3x3_winograd_multi for this geometry: one buffer per (device, stream), shared by all layers"""
+    import ctypes
+    L = len(sizes)
+    hs = (ctypes.c_int * L)(*[h for h, _ in sizes])
+    ws = (ctypes.c_int * L)(*[ww for _, ww in sizes])
+    nbytes = _L.load().brcnn_conv3x3_winograd_f32_multi_workspace_bytes(batch, L, hs, ws, cin)
+    key = (str(torch.device(device)), _stream())
+    t = _WINO_WS.get(key)
+    if t is None or t.numel() < nbytes:
+        t = _WINO_WS[key] = _ws(nbytes, device)
+    return t
+
+
+def conv3x3_winograd_multi(x_cat, u, batch, sizes, gn=None, scale=None, shift=None, relu=False, workspace=None,
+                           kernel=3, stride=1, pad=1):
+    """3x3 stride-1 pad-1 fp32 conv over back-to-back segments in the Winograd F(2x2,3x3) form; `u` from winograd_filter.
+    gn = (stats, gamma, beta, groups, relu_in): the input is [relu_in](groupnorm(x_cat)) with the statistics of
+    groupnorm_stats_multi / groupnorm_nhwc_multi(return_stats=True) over the same segments, applied while the operand is
+    loaded.  Returns y_cat (rows, Cout).  Anything but that layer form raises (there is no fall-back)."""
+    import ctypes
+    stats, gamma, beta, groups, relu_in = gn if gn is not None else (None, None, None, 0, False)
+    _require_gpu(x_cat, u, scale, shift, stats, gamma, beta)
+    assert x_cat.dim() == 2 and x_cat.is_contiguous() and u.is_contiguous() and u.dim() == 3 and u.shape[0] == 16
+    _, cout, cin = u.shape
+    assert x_cat.shape[1] == cin and x_cat.shape[0] == sum(batch * h * ww for h, ww in sizes)
+    if workspace is None:
+        workspace = winograd_workspace(batch, sizes, cin, x_cat.device)
+    y = _alloc_out((x_cat.shape[0], cout), torch.float32, x_cat.device)
+    L = len(sizes)
+    hs = (ctypes.c_int * L)(*[h for h, _ in sizes])
+    ws = (ctypes.c_int * L)(*[ww for _, ww in sizes])
+    st = _L.load().brcnn_conv3x3_winograd_f32_multi(
+        _ptr(x_cat), _ptr(u), _ptr(stats), _ptr(gamma), _ptr(beta), int(groups), int(bool(relu_in)), _ptr(scale), _ptr(shift),
+        int(bool(relu)), _ptr(y), _ptr(workspace), workspace.numel() * workspace.element_size(), batch, L, hs, ws, cin, cout,
+        int(kernel), int(kernel), int(stride), int(pad), _dt(x_cat), _stream())
+    _L.check(st, 'brcnn_conv3x3_winograd_f32_multi')
+    return y
+
+
 def groupnorm_nhwc_multi_backward(dy, x_cat, stats, gamma, beta, groups, batch, sizes, relu):
     """(dx, dgamma, dbeta) of groupnorm_nhwc_multi; `stats` from its return_stats"""
     import ctypes

@@ -348,7 +348,11 @@ int brcnn_conv_handover_status(void);
  * eight-phase, 256 x 128 two-group and persistent 1x1 16-bit kernels; 6 / 7 launches planned as chained stream-K /
  * split-K, 8 the workgroups of the last of them; 9 launches of the two-buffer / ring 16-bit tile kernel, 10 .. 13 the
  * last one's tile rows, tile columns, waves per workgroup, ring stages; 14 launches of the 16-bit weight gradient's tile
- * kernel (csrc/conv_wgrad_bf16.hip), 15 the tile code (1, 2, 4) of the last one (csrc/policy.h: Counters). */
+ * kernel (csrc/conv_wgrad_bf16.hip), 15 the tile code (1, 2, 4) of the last one (csrc/policy.h: Counters).
+ * (-11, 0 / 1): Winograd F(2x2,3x3) for the fp32 3x3 layers whose caller prepared the transformed filter never / yes;
+ * (-11, 2) RETURNS the setting (the caller reads it: the Winograd entry point never falls back by itself); (-11, 11 .. 18):
+ * 1 .. 8 transform + GEMM launch pairs per call.  (-12, 0) returns and clears the number of Winograd calls that launched,
+ * (-12, 1) the 2x2 tiles of the last one; (-9, -1) clears both as well. */
 int brcnn_conv_set_tile(int wm, int nt);
 
 /* Tuning hook of the bf16 kernel: 0 heuristic; 11 / 21 / 22 = 64x64 / 128x64 / 128x128 tile on
@@ -376,6 +380,28 @@ int brcnn_conv2d_nhwc_multi(const void *x, const void *w, const float *scale, co
                             const int *heights_host, const int *widths_host, int cin, int cout,
                             int kh, int kw, int stride, int pad, int relu, int dtype,
                             void *stream);
+
+/* Winograd F(2x2,3x3) form of the fp32 3x3 stride-1 pad-1 convolution over the same segment table
+ * (csrc/conv_winograd_f32.hip): 4 multiplies per output and input channel instead of 9.
+ *   brcnn_winograd_filter_f32: w (Cout,3,3,Cin) packed fp32 -> u (16,Cout,Cin) = G g G^T, once per weight.
+ *   ..._workspace_bytes: the V planes (16, tiles, cin) of the input transform, tiles = sum over the segments of
+ *     batch * ceil(H/2) * ceil(W/2); 0 for arguments the conv would refuse (host arithmetic only, no device call).
+ *   brcnn_conv3x3_winograd_f32_multi: y (rows, cout) = [relu](conv3x3(x') * scale + shift), scale / shift NULL = none;
+ *     x' = x, or with gn_stats != NULL x' = [relu_in](groupnorm(x)) from the finalized (mean, rstd) pairs a GroupNorm
+ *     call over the same segments left in its stats_ws, with gamma / beta (cin) and `groups` -- the expression of the
+ *     GroupNorm apply pass, so the result has the bits of GroupNorm launch -> this call without gn_stats; the zero
+ *     padding surrounds the NORMALISED tensor.
+ * fp32 only (dtype BRCNN_DT_F32), kh = kw = 3, stride 1, pad 1, cin % 32 == 0, cout % 64 == 0, a workspace of at least
+ * ..._workspace_bytes: anything else is BRCNN_EINVAL and launches nothing (no fall-back inside the entry point).
+ * Results differ from brcnn_conv2d_nhwc_multi by fp32 round-off (about 2.5x its error against float64). */
+int brcnn_winograd_filter_f32(const void *w, void *u, int cout, int cin, int kh, int kw, int dtype, void *stream);
+size_t brcnn_conv3x3_winograd_f32_multi_workspace_bytes(int batch, int num_segments, const int *heights_host,
+                                                        const int *widths_host, int cin);
+int brcnn_conv3x3_winograd_f32_multi(const void *x, const void *u, const void *gn_stats, const float *gamma,
+                                     const float *beta, int groups, int relu_in, const float *scale,
+                                     const float *shift, int relu, void *y, void *workspace, size_t workspace_bytes,
+                                     int batch, int num_segments, const int *heights_host, const int *widths_host,
+                                     int cin, int cout, int kh, int kw, int stride, int pad, int dtype, void *stream);
 
 /* Grouped convolution (ResNeXt bottleneck conv2, mmdet/models/backbones/resnext.py:10-84).
  * x (N,H,W,Cin) fp32; w_tiles (Cout,KH,KW,window) block-diagonal per 64-channel output tile
@@ -486,6 +512,10 @@ int brcnn_groupnorm_nhwc_multi(const void *x, const float *gamma, const float *b
                                void *stats_ws /* batch*num_segments*groups*2 doubles */,
                                int batch, int num_segments, const int *hw_host, int channels,
                                int groups, float eps, int relu, int dtype, void *stream);
+/* its statistics alone (fp32 only): stats_ws as the full call leaves it, no y -- for a consumer that applies the
+ * normalisation while it loads its operand (the gn_stats argument of the Winograd conv above) */
+int brcnn_groupnorm_nhwc_multi_stats(const void *x, void *stats_ws, int batch, int num_segments, const int *hw_host,
+                                     int channels, int groups, float eps, int dtype, void *stream);
 
 /* Backward of brcnn_groupnorm_nhwc_multi (training of the RPN tower: GroupNorm(32) + ReLU of
  * mmcv's ConvModule, atss_rpn_head.py:150-170; torch's native group-norm backward needs NCHW
