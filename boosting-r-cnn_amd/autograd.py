@@ -1017,64 +1017,76 @@ def grouped_conv_autograd(x, weight, groups, stride, pad):
 
 
 class DeformIm2colFunction(Function):
-    """modulated deformable im2col (DCNv2, deform_groups 1) with its backward: x (N,H,W,C),
-    offset_mask (N,Ho,Wo,27) raw conv_offset output -> columns (N*Ho*Wo, 9*C)"""
+    """(modulated) deformable im2col with its backward: x (N,H,W,C), offset_mask (N,Ho,Wo,(3 | 2) * 9 * G) raw conv_offset
+    output -> columns (N*Ho*Wo, 9*C).  G = 1, modulated (DCNv2 of the Res2Net recipes): the original entry points;
+    deform groups / v1 (`modulated=False`, no mask): the `_g` entries.  x fp32, or 16-bit (16-bit columns; dx is
+    accumulated in fp32 and rounded once)"""
 
     @staticmethod
-    def forward(ctx, x, om, stride, pad):
+    def forward(ctx, x, om, stride, pad, deform_groups=1, modulated=True):
         _require_gpu(x, om)
         x, om = x.contiguous(), om.contiguous()
-        assert om.shape[3] == 27
-        col, (ho, wo) = ops.deform_im2col_nhwc(x, om, 3, stride, pad, 1)
+        assert om.shape[3] == (27 if modulated else 18) * deform_groups and om.dtype == torch.float32
+        col, (ho, wo) = ops.deform_im2col_nhwc(x, om, 3, stride, pad, 1, None, deform_groups, modulated)
         ctx.save_for_backward(x, om)
-        ctx.cfg = (stride, pad)
+        ctx.cfg = (stride, pad, deform_groups, modulated)
         return col
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dcol):
         x, om = ctx.saved_tensors
-        stride, pad = ctx.cfg
+        stride, pad, groups, modulated = ctx.cfg
         n, h, w, c = x.shape
         dcol = dcol.float().contiguous()
+        if groups != 1 or not modulated or x.dtype != torch.float32:
+            dx, dom = ops.deform_col2im_nhwc(x, om, dcol, stride, pad, groups, modulated)
+            return dx.to(x.dtype), dom, None, None, None, None
         dx = torch.zeros_like(x)
         dom = torch.empty_like(om)
         st = _L.load().brcnn_deform_col2im_nhwc(_ptr(x), _ptr(om), _ptr(dcol), _ptr(dx), _ptr(dom), n, h, w, c, 3, 3,
                                                 int(stride), int(pad), 1, 27, c, _stream())
         _L.check(st, 'brcnn_deform_col2im_nhwc')
-        return dx, dom, None, None
+        return dx, dom, None, None, None, None
 
 
-def deform_im2col_autograd(x, om, stride, pad):
-    return DeformIm2colFunction.apply(x, om, stride, pad)
+def deform_im2col_autograd(x, om, stride, pad, deform_groups=1, modulated=True):
+    return DeformIm2colFunction.apply(x, om, stride, pad, deform_groups, modulated)
 
 
 class DeformConvFunction(Function):
-    """modulated deformable 3x3 conv (DCNv2, deform_groups 1) in the 16-bit compute dtypes: x (N,H,W,Cp) bf16 / fp16,
-    om (N,Ho,Wo,27) fp32 raw conv_offset output, weight (Cout,Cp,3,3) in the parameter layout -> the raw conv output
-    (N,Ho,Wo,Cout) in x's dtype, from the fused kernel (the columns are never stored).  Backward: dcol = dY . W on the
-    16-bit GEMM with an fp32 result, dx / d_om from the 16-bit col2im (dx accumulated in fp32, rounded once), dW from the
-    recomputed 16-bit columns on the weight-gradient kernel.  (fp32 keeps DeformIm2colFunction + linear_autograd.)"""
+    """(modulated) deformable 3x3 conv in the 16-bit compute dtypes: x (N,H,W,Cp) bf16 / fp16, om (N,Ho,Wo,(27 | 18) * G)
+    fp32 raw conv_offset output, weight (Cout,Cp,3,3) in the parameter layout -> the raw conv output (N,Ho,Wo,Cout) in x's
+    dtype, from the fused kernel (the columns are never stored).  `route=True` (the ResNet DCN bottlenecks): from the fused
+    kernel where `ops.deform_conv_route` sends the shape there, else from the 16-bit im2col + GEMM; without it (the Res2Net
+    recipes, as ever) the fused kernel runs whatever the policy table says, and a shape it refuses is an error.  Backward: dcol = dY . W on the 16-bit GEMM with an fp32 result, dx / d_om from the
+    16-bit col2im (dx accumulated in fp32, rounded once), dW from the recomputed 16-bit columns on the weight-gradient
+    kernel.  (fp32 keeps DeformIm2colFunction + linear_autograd.)"""
 
     @staticmethod
-    def forward(ctx, x, om, weight, stride, pad):
+    def forward(ctx, x, om, weight, stride, pad, deform_groups=1, modulated=True, route=False):
         _require_gpu(x, om, weight)
         if x.dtype not in (torch.bfloat16, torch.float16):
             raise _L.BrcnnHipError(f'DeformConvFunction: bf16 / fp16 activations (got {x.dtype})')
         x, om = x.contiguous(), om.contiguous()
-        assert om.shape[3] == 27 and om.dtype == torch.float32
+        assert om.shape[3] == (27 if modulated else 18) * deform_groups and om.dtype == torch.float32
         w_p = weight.detach().permute(0, 2, 3, 1).to(x.dtype).contiguous()        # (Cout,3,3,Cp), K order (tap, c)
-        y = ops.deform_conv_nhwc(x, om, w_p, None, None, False, stride, pad)
+        cout, cp = w_p.shape[0], w_p.shape[3]
+        if not route or ops.deform_conv_route(x, cout, stride, pad, deform_groups):
+            y = ops.deform_conv_nhwc(x, om, w_p, None, None, False, stride, pad, deform_groups, modulated)
+        else:
+            col, (ho, wo) = ops.deform_im2col_nhwc(x, om, 3, stride, pad, 1, None, deform_groups, modulated)
+            y = ops.linear_nhwc(col, w_p.view(cout, 9 * cp)).view(x.shape[0], ho, wo, cout)
         ctx.save_for_backward(x, om)
         ctx.w_p = w_p
-        ctx.cfg = (stride, pad)
+        ctx.cfg = (stride, pad, deform_groups, modulated)
         return y
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
         x, om = ctx.saved_tensors
-        stride, pad = ctx.cfg
+        stride, pad, groups, modulated = ctx.cfg
         w_p = ctx.w_p
         n, h, w, cp = x.shape
         _, ho, wo, cout = dy.shape
@@ -1084,25 +1096,28 @@ class DeformConvFunction(Function):
         dx = dom = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             dcol = ops.linear_nhwc(dy, w_p.view(cout, 9 * cp).t().contiguous(), out_f32=True)      # (M, 9 Cp) fp32
-            dx32 = torch.zeros((n, h, w, cp), dtype=torch.float32, device=x.device)
-            dom = torch.empty_like(om)
-            st = lib.brcnn_deform_col2im_nhwc_ex(_ptr(x), _ptr(om), _ptr(dcol), _ptr(dx32), _ptr(dom), n, h, w, cp, 3, 3,
-                                                 int(stride), int(pad), 1, 27, cp, ops._dt(x), _stream())
-            _L.check(st, 'brcnn_deform_col2im_nhwc_ex')
+            if groups != 1 or not modulated:
+                dx32, dom = ops.deform_col2im_nhwc(x, om, dcol, stride, pad, groups, modulated)
+            else:
+                dx32 = torch.zeros((n, h, w, cp), dtype=torch.float32, device=x.device)
+                dom = torch.empty_like(om)
+                st = lib.brcnn_deform_col2im_nhwc_ex(_ptr(x), _ptr(om), _ptr(dcol), _ptr(dx32), _ptr(dom), n, h, w, cp, 3, 3,
+                                                     int(stride), int(pad), 1, 27, cp, ops._dt(x), _stream())
+                _L.check(st, 'brcnn_deform_col2im_nhwc_ex')
             dx = dx32.to(x.dtype)
         if ctx.needs_input_grad[2]:
-            col, _ = ops.deform_im2col_nhwc(x, om, 3, stride, pad, 1)                 # recomputed, 16-bit
+            col, _ = ops.deform_im2col_nhwc(x, om, 3, stride, pad, 1, None, groups, modulated)     # recomputed, 16-bit
             dwp = torch.zeros((cout, 1, 1, 9 * cp), dtype=torch.float32, device=x.device)
             one = _ints([1])
             st = lib.brcnn_conv2d_wgrad_nhwc_multi(_ptr(col), _ptr(dy), _ptr(dwp), m, 1, one, one, 9 * cp, cout, 1, 1, 1, 0,
                                                    ops._dt(x), _conv_stream())
             _L.check(st, 'brcnn_conv2d_wgrad_nhwc_multi')
             dw = dwp.view(cout, 3, 3, cp).permute(0, 3, 1, 2)
-        return dx, dom, dw, None, None
+        return dx, dom, dw, None, None, None, None, None
 
 
-def deform_conv_autograd(x, om, weight, stride, pad):
-    return DeformConvFunction.apply(x, om, weight, stride, pad)
+def deform_conv_autograd(x, om, weight, stride, pad, deform_groups=1, modulated=True, route=False):
+    return DeformConvFunction.apply(x, om, weight, stride, pad, deform_groups, modulated, route)
 
 
 class BnActFunction(Function):

@@ -13,8 +13,8 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .blocks import (PackedCache, build_norm_layer, compute_dtype, conv_bn_act_nhwc, folded_conv_operands, to_nchw_view,
-                     to_nhwc)
+from .blocks import (PackedCache, build_norm_layer, compute_dtype, conv_bn_act_nhwc, conv_bn_act_tail, folded_conv_operands,
+                     to_nchw_view, to_nhwc)
 from .registry import BACKBONES
 
 
@@ -22,7 +22,7 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, style='pytorch',
-                 norm_cfg=dict(type='BN')):
+                 norm_cfg=dict(type='BN'), dcn=None):
         super().__init__()
         assert style in ('pytorch', 'caffe')
         self.inplanes, self.planes, self.stride, self.style = inplanes, planes, stride, style
@@ -32,13 +32,19 @@ class Bottleneck(nn.Module):
             self.conv1_stride, self.conv2_stride = stride, 1
         self.conv1 = nn.Conv2d(inplanes, planes, 1, stride=self.conv1_stride, bias=False)
         self.add_module('bn1', build_norm_layer(norm_cfg, planes, 1)[1])
-        self.conv2 = nn.Conv2d(planes, planes, 3, stride=self.conv2_stride, padding=1, bias=False)
+        self.with_dcn = dcn is not None
+        if self.with_dcn:
+            # resnet.py:160-180: conv2 becomes mmcv's DeformConv2dPack ('DCN') / ModulatedDeformConv2dPack ('DCNv2')
+            self.conv2 = build_dcn(dcn, planes, planes, stride=self.conv2_stride)
+        else:
+            self.conv2 = nn.Conv2d(planes, planes, 3, stride=self.conv2_stride, padding=1, bias=False)
         self.add_module('bn2', build_norm_layer(norm_cfg, planes, 2)[1])
         self.conv3 = nn.Conv2d(planes, planes * self.expansion, 1, bias=False)
         self.add_module('bn3', build_norm_layer(norm_cfg, planes * self.expansion, 3)[1])
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self._c = [PackedCache() for _ in range(4)]
+        self._c_dcn = {}            # activation dtype -> PackedCache of the deformable stage's operands
 
     chain_fusion = True        # ResLayer may pass `out_single_use` / `in_from_prev`
 
@@ -49,6 +55,8 @@ class Bottleneck(nn.Module):
         stride 1) -> 256 shape of stage 1"""
         from .autograd import wants_grad
         c2, c3 = self.conv2, self.conv3
+        if self.with_dcn:           # a deformable conv2 is no nn.Conv2d: it has its own path (_dcn_tail)
+            return False
         if not (self.FUSE_TAIL and type(self) is Bottleneck and out.is_cuda and identity.dtype == out.dtype and
                 out.dtype in (torch.float32, torch.bfloat16, torch.float16) and not self.bn2.training and not self.bn3.training):
             return False
@@ -65,16 +73,24 @@ class Bottleneck(nn.Module):
     def forward_nhwc(self, x, out_single_use=False, in_from_prev=False):
         """`out_single_use`: the caller promises that the result feeds only the next block of the stage (whose
         conv1 then runs bn3's backward inside its data-gradient launch); `in_from_prev`: x is such a result"""
+        # a DCN block's conv1 output has TWO consumers (the offset conv and the sampling): the single-use promise, which
+        # lets the next launch run bn1's backward inside its data-gradient kernel, is not made on that edge
+        single = not self.with_dcn
         if self.downsample is None:
             # the identity branch leaves through conv1's autograd node: its gradient is added in
             # conv1's data-gradient kernel instead of by a separate add over the whole tensor
             out, identity = conv_bn_act_nhwc(x, self.conv1, self.bn1, self._c[0], True, with_skip=True,
-                                             sole_consumer=in_from_prev, single_use_output=True)
+                                             sole_consumer=in_from_prev, single_use_output=single)
         else:
             # the downsample branch reads conv1's input through the same alias: its data gradient is added in
             # conv1's data-gradient epilogue too (stride-1 conv1, the 'pytorch' style) instead of by an autograd add
-            out, xs = conv_bn_act_nhwc(x, self.conv1, self.bn1, self._c[0], True, with_skip=True, single_use_output=True)
+            out, xs = conv_bn_act_nhwc(x, self.conv1, self.bn1, self._c[0], True, with_skip=True, single_use_output=single)
             identity = conv_bn_act_nhwc(xs, self.downsample[0], self.downsample[1], self._c[3], False)
+        if self.with_dcn:
+            out = self._dcn_bn_act(out)
+            # (bn2's output comes from the deformable path: there is no BatchNorm backward to run in conv3's launch)
+            return conv_bn_act_nhwc(out, self.conv3, self.bn3, self._c[2], True, residual=identity,
+                                    single_use_output=out_single_use)
         if self._tail_fusable(out, identity):
             # frozen / inference block with 64 -> 64 -> 256 channels (stage 1): conv2 .. the block's ReLU in ONE launch,
             # the 64-channel intermediate stays in LDS (csrc/bottleneck_tail_f32.hip / _bf16.hip; equal to the two launches)
@@ -86,6 +102,48 @@ class Bottleneck(nn.Module):
         # relu(bn3(conv3(out)) + identity) in one epilogue (resnet.py:288-300)
         return conv_bn_act_nhwc(out, self.conv3, self.bn3, self._c[2], True, residual=identity, sole_consumer=True,
                                 single_use_output=out_single_use)
+
+    def _dcn_bn_act(self, x):
+        """relu(bn2(deformable conv2(x))) on conv1's (N,h,w,planes) output.  The offset conv has an fp32 result in every
+        compute dtype (an offset rounded to 16 bits is off by up to half a pixel at a coordinate of ~100).  Inference:
+        16-bit on the fused kernel with bn2 + ReLU in its epilogue where `ops.deform_conv_route` sends the shape, else
+        im2col + the 1x1 GEMM with that epilogue (fp32 always).  Training: the autograd forms of the same kernels;
+        gradients reach conv2.weight, conv_offset.{weight,bias} and x through both the sampling and the offset conv."""
+        from .autograd import (conv2d_nhwc_autograd, deform_conv_autograd, deform_im2col_autograd, linear_autograd,
+                               wants_grad)
+        c2, co, bn = self.conv2, self.conv2.conv_offset, self.bn2
+        G, mod, stride, p = c2.deform_groups, c2.modulated, self.conv2_stride, self.planes
+        sixteen = x.dtype != torch.float32
+        n = x.shape[0]
+        if wants_grad(x, c2.weight, co.weight, co.bias, bn.weight, bn.bias):
+            om = conv2d_nhwc_autograd(x, co.weight, co.bias, stride, 1, out_f32=sixteen)
+            if sixteen:
+                y = deform_conv_autograd(x, om, c2.weight, stride, 1, G, mod, route=True)
+            else:
+                col = deform_im2col_autograd(x, om, stride, 1, G, mod)
+                y = linear_autograd(col, c2.weight.permute(0, 2, 3, 1).reshape(p, 9 * p), None)
+                y = y.view(n, om.shape[1], om.shape[2], p)
+            return conv_bn_act_tail(y, bn, True, None)
+        rows = c2.offset_rows
+        pad_rows = (-rows) % 64 if sixteen else 0       # the 16-bit conv kernels take Cout % 64 == 0; the row is read in place
+
+        def builder():
+            F = torch.nn.functional
+            from .blocks import fold_bn, pack_weight
+            scale, shift = fold_bn(bn)
+            wo = F.pad(pack_weight(co.weight), (0, 0, 0, 0, 0, 0, 0, pad_rows)).to(x.dtype).contiguous()
+            bo = F.pad(co.bias.detach().float(), (0, pad_rows)).contiguous()
+            return pack_weight(c2.weight).to(x.dtype).contiguous(), scale, shift, wo, bo
+        # (one cache per activation dtype: the packed dtype and the row padding follow x, not the process-wide compute dtype)
+        w, scale, shift, wo, bo = self._c_dcn.setdefault(x.dtype, PackedCache()).get(
+            [c2.weight, co.weight, co.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var], builder)
+        om = ops.conv2d_nhwc(x, wo, None, bo, None, False, stride, 1, out_f32=True) if sixteen else \
+            ops.conv2d_nhwc(x, wo, None, bo, None, False, stride, 1)
+        if sixteen and ops.deform_conv_route(x, p, stride, 1, G):
+            return ops.deform_conv_nhwc(x, om, w, scale, shift, True, stride, 1, G, mod)
+        col, (ho, wo_) = ops.deform_im2col_nhwc(x, om, 3, stride, 1, 1, None, G, mod)
+        y = ops.conv2d_nhwc(col.view(n * ho * wo_, 1, 1, 9 * p), w.reshape(p, 1, 1, 9 * p), scale, shift, None, True, 1, 0)
+        return y.view(n, ho, wo_, p)
 
     def forward(self, x):
         return to_nchw_view(self.forward_nhwc(to_nhwc(x)))
@@ -132,8 +190,12 @@ class ResNet(nn.Module):
         super().__init__()
         if depth not in self.arch_settings:
             raise KeyError(f'invalid depth {depth} for resnet (hot path: 50/101/152)')
-        assert not deep_stem and not avg_down and dcn is None and plugins is None and \
-            conv_cfg is None, 'ResNetV1d / DCN / plugin variants are outside the hot path'
+        assert not deep_stem and not avg_down and plugins is None and \
+            conv_cfg is None, 'ResNetV1d / plugin variants are outside the hot path'
+        if dcn is not None:
+            assert len(stage_with_dcn) == num_stages
+            parse_dcn(dcn)                  # a bad `dcn` entry fails here, whatever stage_with_dcn says
+        self.dcn, self.stage_with_dcn = dcn, stage_with_dcn
         assert all(d == 1 for d in dilations)
         assert 1 <= num_stages <= 4 and max(out_indices) < num_stages
         self.depth, self.num_stages, self.out_indices = depth, num_stages, out_indices
@@ -152,8 +214,10 @@ class ResNet(nn.Module):
         self.res_layers = []
         for i, num_blocks in enumerate(self.stage_blocks):
             planes = base_channels * 2 ** i
-            layer = ResLayer(self.block, self.inplanes, planes, num_blocks, strides[i], style,
-                             norm_cfg, **self.block_kwargs())
+            kw = self.block_kwargs()
+            if dcn is not None and stage_with_dcn[i]:
+                kw['dcn'] = dcn
+            layer = ResLayer(self.block, self.inplanes, planes, num_blocks, strides[i], style, norm_cfg, **kw)
             self.inplanes = planes * self.block.expansion
             name = f'layer{i + 1}'
             self.add_module(name, layer)
@@ -179,6 +243,10 @@ class ResNet(nn.Module):
             elif isinstance(m, (nn.BatchNorm2d, nn.GroupNorm)):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
+        for m in self.modules():            # the loop above ran over conv_offset too (resnet.py:639-642 re-zeroes it)
+            if isinstance(m, DCNv2):
+                nn.init.constant_(m.conv_offset.weight, 0)
+                nn.init.constant_(m.conv_offset.bias, 0)
         if self.zero_init_residual and not (isinstance(self.init_cfg, dict) and
                                             self.init_cfg.get('type') == 'Pretrained'):
             for m in self.modules():
@@ -295,6 +363,9 @@ class ResNeXt(ResNet):
                      152: (BottleneckX, (3, 8, 36, 3))}
 
     def __init__(self, groups=1, base_width=4, **kwargs):
+        if kwargs.get('dcn') is not None:
+            raise NotImplementedError('ResNeXt + DCN: a deformable conv with groups > 1 needs a grouped GEMM over the '
+                                      'columns; only ResNet / Res2Net backbones take `dcn`')
         self.groups, self.base_width = groups, base_width
         self._base_channels = kwargs.get('base_channels', 64)
         super().__init__(**kwargs)
@@ -305,22 +376,58 @@ class ResNeXt(ResNet):
 
 # --------------------------------------------------------------------------- Res2Net (+ DCNv2)
 class DCNv2(nn.Module):
-    """mmcv.ops.ModulatedDeformConv2dPack (the `dcn=dict(type='DCNv2', deform_groups=1)` of the
-    r2_101 recipes): a 3x3 conv whose taps are displaced by learned offsets and scaled by a
-    learned mask, both predicted by `conv_offset` (zero-initialised).  Parameter names as mmcv's:
-    `weight`, `conv_offset.{weight,bias}`."""
+    """mmcv.ops.ModulatedDeformConv2dPack (`dcn=dict(type='DCNv2', deform_groups=G)`): a 3x3 conv whose taps are displaced
+    by learned offsets and scaled by a learned mask, both predicted by `conv_offset` (zero-initialised, 3 * 9 * G
+    outputs; same stride / padding / dilation as the conv).  Each of the G deform groups (in_channels / G consecutive
+    channels) has its own offsets and masks.  Parameter names as mmcv's: `weight`, `conv_offset.{weight,bias}`.
+    `groups > 1` (ResNeXt + DCN) is not built."""
+    modulated = True
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, dilation=1, groups=1,
                  deform_groups=1, bias=False):
         super().__init__()
-        assert groups == 1 and deform_groups == 1 and kernel_size == 3 and not bias
-        self.in_channels, self.out_channels = in_channels, out_channels
+        assert groups == 1, 'deformable conv with groups > 1 (ResNeXt + DCN) is not built'
+        assert deform_groups >= 1 and in_channels % deform_groups == 0 and kernel_size == 3 and not bias
+        self.in_channels, self.out_channels, self.deform_groups = in_channels, out_channels, deform_groups
         self.kernel_size, self.stride, self.padding, self.dilation = (3, 3), stride, padding, dilation
+        self.offset_rows = (3 if self.modulated else 2) * 9 * deform_groups
         self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 3, 3))
-        self.conv_offset = nn.Conv2d(in_channels, 27, 3, stride=stride, padding=padding, dilation=dilation, bias=True)
+        self.conv_offset = nn.Conv2d(in_channels, self.offset_rows, 3, stride=stride, padding=padding, dilation=dilation,
+                                     bias=True)
         nn.init.kaiming_uniform_(self.weight, nonlinearity='relu')
         nn.init.constant_(self.conv_offset.weight, 0)
         nn.init.constant_(self.conv_offset.bias, 0)
+
+
+class DCN(DCNv2):
+    """mmcv.ops.DeformConv2dPack (`dcn=dict(type='DCN', deform_groups=G)`): the unmodulated form -- the same sampling with
+    the mask factor identically 1; `conv_offset` has 2 * 9 * G outputs"""
+    modulated = False
+
+
+def parse_dcn(dcn):
+    """(module class, deform_groups) of a config's `dcn=dict(type='DCN' | 'DCNv2', deform_groups=G,
+    fallback_on_stride=False)`; anything else in it is refused"""
+    cfg = dict(dcn)
+    if cfg.pop('fallback_on_stride', False):
+        # (the reference pops the key from a dict all blocks share, so its meaning there depends on the block order;
+        # no shipped config sets it)
+        raise NotImplementedError('dcn: fallback_on_stride=True is not supported')
+    kind = cfg.pop('type')
+    if kind not in ('DCN', 'DCNv2'):
+        raise KeyError(f"dcn type {kind!r}: 'DCN' or 'DCNv2'")
+    groups = cfg.pop('deform_groups', 1)
+    if cfg:
+        raise NotImplementedError(f'dcn: unsupported keys {sorted(cfg)}')
+    if not (isinstance(groups, int) and groups >= 1):
+        raise ValueError(f'dcn: deform_groups {groups!r}')
+    return (DCN if kind == 'DCN' else DCNv2), groups
+
+
+def build_dcn(dcn, in_channels, out_channels, stride=1):
+    """the deformable conv2 of a block from a config's `dcn` entry"""
+    cls, groups = parse_dcn(dcn)
+    return cls(in_channels, out_channels, 3, stride=stride, padding=1, deform_groups=groups)
 
 
 def _pad_to(n, mult=32):

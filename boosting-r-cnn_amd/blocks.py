@@ -136,6 +136,13 @@ def load_pretrained(module, init_cfg, prefixes=('backbone.', 'module.')):
         out[k] = v
     missing, unexpected = module.load_state_dict(out, strict=False)
     missing = [k for k in missing if not k.endswith('num_batches_tracked')]
+    # a plain (torchvision) ResNet checkpoint under a DCN backbone: `conv2.weight` has the plain conv's shape and loads, the
+    # offset branch is not in the file and keeps its zero initialisation -- reported, not fatal
+    offset = [k for k in missing if '.conv_offset.' in k]
+    if offset:
+        missing = [k for k in missing if '.conv_offset.' not in k]
+        log.info(f'pretrained {ckpt}: {len(offset)} conv_offset tensors are not in the checkpoint and stay zero-initialised '
+                 f'({offset[0]} ...)')
     log.info(f'loaded pretrained {ckpt} from {path}: {len(out) - len(unexpected)} tensors, missing {missing[:6]}'
              f'{"..." if len(missing) > 6 else ""}, unexpected {list(unexpected)[:6]}{"..." if len(unexpected) > 6 else ""}')
     return True

@@ -11,6 +11,7 @@
 // Both are HBM-bound streams, 16 bytes of channels per lane.
 #include "common.h"
 #include "deform_common.h"
+#include "policy.h"
 
 namespace {
 
@@ -83,8 +84,11 @@ __global__ __launch_bounds__(256) void deform_im2col_nhwc_kernel(const float* __
                                                                 const float* __restrict__ om,
                                                                 float* __restrict__ col, int N, int H, int W,
                                                                 int C, int Ho, int Wo, int KH, int KW, int stride,
-                                                                int pad, int dilation, int om_stride, int Cpad) {
-    const int c4n = Cpad >> 2, taps = KH * KW;
+                                                                int pad, int dilation, int om_stride, int Cpad, int G,
+                                                                int modulated) {
+    // deform groups: channel c takes the offsets (and mask logit) of group c / (C / G); the offset row of a pixel is
+    // [2 T g + 2 t] dy, [2 T g + 2 t + 1] dx, [2 T G + T g + t] mask logit (modulated only; v1: the factor is 1)
+    const int c4n = Cpad >> 2, taps = KH * KW, cg = C / G;
     const long long total = (long long)N * Ho * Wo * taps * c4n;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
@@ -99,8 +103,9 @@ __global__ __launch_bounds__(256) void deform_im2col_nhwc_kernel(const float* __
         if (c < C) {
             const int i = tap / KW, j = tap - i * KW;
             const float* o = om + (size_t)m * om_stride;
-            const float off_h = o[2 * tap], off_w = o[2 * tap + 1];
-            const float mask = 1.f / (1.f + expf(-o[2 * taps + tap]));
+            const int grp = c / cg;
+            const float off_h = o[2 * taps * grp + 2 * tap], off_w = o[2 * taps * grp + 2 * tap + 1];
+            const float mask = modulated ? 1.f / (1.f + expf(-o[2 * taps * G + taps * grp + tap])) : 1.f;
             const float h_im = (float)(ho * stride - pad + i * dilation) + off_h;
             const float w_im = (float)(wo * stride - pad + j * dilation) + off_w;
             if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
@@ -124,8 +129,8 @@ __global__ __launch_bounds__(256) void deform_im2col_nhwc_kernel(const float* __
 }
 
 // Backward of the modulated deformable im2col (mmcv modulated_deformable_col2im_gpu_kernel and
-// modulated_deformable_col2im_coord_gpu_kernel): one wavefront per (output pixel, tap), lanes over
-// channels.  dx gets dcol * mask * corner weight (fp32 atomics, like the RoIAlign backward); the
+// modulated_deformable_col2im_coord_gpu_kernel): one wavefront per (output pixel, tap, deform group), lanes over
+// the group's channels.  dx gets dcol * mask * corner weight (fp32 atomics, like the RoIAlign backward); the
 // offset / mask gradients are channel sums, reduced across the wave and written once:
 //   d off_h = mask * sum_c dcol_c * d val_c / d h,   d off_w likewise,
 //   d mask_logit = mask (1 - mask) * sum_c dcol_c * val_c          (sigmoid applied in the forward)
@@ -137,21 +142,23 @@ __global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const void* __r
                                                                 float* __restrict__ dx, float* __restrict__ dom,
                                                                 int N, int H, int W, int C, int Ho, int Wo, int KH,
                                                                 int KW, int stride, int pad, int dilation,
-                                                                int om_stride, int Cpad) {
+                                                                int om_stride, int Cpad, int G, int modulated) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int taps = KH * KW;
+    const int taps = KH * KW, cg = C / G;
     const long long item = (long long)blockIdx.x * 4 + wave;
-    if (item >= (long long)N * Ho * Wo * taps) return;
-    const int tap = (int)(item % taps);
-    const long long m = item / taps;
+    if (item >= (long long)N * Ho * Wo * taps * G) return;
+    const int grp = (int)(item % G);
+    const long long mt = item / G;
+    const int tap = (int)(mt % taps);
+    const long long m = mt / taps;
     const int wo = (int)(m % Wo);
     const int ho = (int)((m / Wo) % Ho);
     const int n = (int)(m / ((long long)Wo * Ho));
     const int i = tap / KW, j = tap - i * KW;
     const float* o = om + (size_t)m * om_stride;
-    const float off_h = o[2 * tap], off_w = o[2 * tap + 1];
-    const float mask = 1.f / (1.f + expf(-o[2 * taps + tap]));
+    const float off_h = o[2 * taps * grp + 2 * tap], off_w = o[2 * taps * grp + 2 * tap + 1];
+    const float mask = modulated ? 1.f / (1.f + expf(-o[2 * taps * G + taps * grp + tap])) : 1.f;
     const float h_im = (float)(ho * stride - pad + i * dilation) + off_h;
     const float w_im = (float)(wo * stride - pad + j * dilation) + off_w;
     const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
@@ -164,7 +171,7 @@ __global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const void* __r
         const bool ok1 = h_low >= 0 && w_low >= 0, ok2 = h_low >= 0 && w_high <= W - 1;
         const bool ok3 = h_high <= H - 1 && w_low >= 0, ok4 = h_high <= H - 1 && w_high <= W - 1;
         const float* dc = dcol + ((size_t)m * taps + tap) * Cpad;
-        for (int c = lane * 4; c < C; c += 256) {
+        for (int c = grp * cg + lane * 4; c < (grp + 1) * cg; c += 256) {
             const float4 g = *reinterpret_cast<const float4*>(dc + c);
             const float4 v1 = ld4z_t<DT>(x, H, W, C, n, h_low, w_low, c, ok1);
             const float4 v2 = ld4z_t<DT>(x, H, W, C, n, h_low, w_high, c, ok2);
@@ -195,9 +202,9 @@ __global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const void* __r
     }
     if (lane == 0) {
         float* go = dom + (size_t)m * om_stride;
-        go[2 * tap] = g_h * mask;
-        go[2 * tap + 1] = g_w * mask;
-        go[2 * taps + tap] = g_m * mask * (1.f - mask);
+        go[2 * taps * grp + 2 * tap] = g_h * mask;
+        go[2 * taps * grp + 2 * tap + 1] = g_w * mask;
+        if (modulated) go[2 * taps * G + taps * grp + tap] = g_m * mask * (1.f - mask);
     }
 }
 
@@ -208,8 +215,9 @@ __global__ __launch_bounds__(256) void deform_im2col_nhwc16_kernel(const unsigne
                                                                   const float* __restrict__ om,
                                                                   unsigned short* __restrict__ col, int N, int H, int W,
                                                                   int C, int Ho, int Wo, int KH, int KW, int stride,
-                                                                  int pad, int dilation, int om_stride, int Cpad) {
-    const int c8n = Cpad >> 3, taps = KH * KW;
+                                                                  int pad, int dilation, int om_stride, int Cpad, int G,
+                                                                  int modulated) {
+    const int c8n = Cpad >> 3, taps = KH * KW, cg = C / G;      // cg % 8 == 0: a thread's eight channels share a group
     const long long total = (long long)N * Ho * Wo * taps * c8n;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
@@ -222,8 +230,11 @@ __global__ __launch_bounds__(256) void deform_im2col_nhwc16_kernel(const unsigne
         const int n = (int)(m / ((long long)Wo * Ho));
         const int i = tap / KW, j = tap - i * KW;
         const float* o = om + (size_t)m * om_stride;
-        const DeformTapGeom g = deform_tap_geom(o[2 * tap], o[2 * tap + 1], o[2 * taps + tap], ho * stride - pad + i * dilation,
-                                                wo * stride - pad + j * dilation, H, W, C, c < C);
+        const int grp = c < C ? c / cg : 0;                     // (a pad channel belongs to no group: it reads group 0's row and stays 0)
+        const float lg = modulated ? o[2 * taps * G + taps * grp + tap] : 0.f;
+        const DeformTapGeom g = deform_tap_geom(o[2 * taps * grp + 2 * tap], o[2 * taps * grp + 2 * tap + 1], lg,
+                                                ho * stride - pad + i * dilation, wo * stride - pad + j * dilation, H, W, C, c < C,
+                                                modulated != 0);
         const unsigned short* xc = x + (size_t)n * H * W * C + (c < C ? c : 0);
         const uint4 v1 = *reinterpret_cast<const uint4*>(xc + g.off1);
         const uint4 v2 = *reinterpret_cast<const uint4*>(xc + g.off2);
@@ -288,8 +299,9 @@ BRCNN_API int brcnn_deform_im2col_nhwc(const float* x, const float* offset_mask,
     const long long total = (long long)batch * Ho * Wo * kh * kw * (channels_padded >> 2);
     hipLaunchKernelGGL(deform_im2col_nhwc_kernel, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, x,
                        offset_mask, col, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation,
-                       om_stride, channels_padded);
+                       om_stride, channels_padded, 1, 1);
     BRCNN_LAUNCH_CHECK();
+    brcnn::count(brcnn::g_counters.dcn_im2col_launches);
     return 0;
 }
 
@@ -307,7 +319,7 @@ BRCNN_API int brcnn_deform_col2im_nhwc(const float* x, const float* offset_mask,
     const long long items = (long long)batch * Ho * Wo * kh * kw;
     hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_F32>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        x, offset_mask, dcol, dx, d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride,
-                       pad, dilation, om_stride, channels_padded);
+                       pad, dilation, om_stride, channels_padded, 1, 1);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }
@@ -353,12 +365,13 @@ BRCNN_API int brcnn_deform_im2col_nhwc_ex(const void* x, const float* offset_mas
     if (dtype == BRCNN_DT_F16)
         hipLaunchKernelGGL(deform_im2col_nhwc16_kernel<BRCNN_DT_F16>, dim3(stream_grid(total)), dim3(256), 0,
                            (hipStream_t)stream, (const unsigned short*)x, offset_mask, (unsigned short*)col, batch, height,
-                           width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded);
+                           width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded, 1, 1);
     else
         hipLaunchKernelGGL(deform_im2col_nhwc16_kernel<BRCNN_DT_BF16>, dim3(stream_grid(total)), dim3(256), 0,
                            (hipStream_t)stream, (const unsigned short*)x, offset_mask, (unsigned short*)col, batch, height,
-                           width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded);
+                           width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded, 1, 1);
     BRCNN_LAUNCH_CHECK();
+    brcnn::count(brcnn::g_counters.dcn_im2col_launches);
     return 0;
 }
 
@@ -380,11 +393,89 @@ BRCNN_API int brcnn_deform_col2im_nhwc_ex(const void* x, const float* offset_mas
     if (dtype == BRCNN_DT_F16)
         hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_F16>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0,
                            (hipStream_t)stream, x, offset_mask, dcol, dx, d_offset_mask, batch, height, width, channels, Ho,
-                           Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded);
+                           Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded, 1, 1);
     else
         hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_BF16>, dim3((unsigned)((items + 3) / 4)), dim3(256), 0,
                            (hipStream_t)stream, x, offset_mask, dcol, dx, d_offset_mask, batch, height, width, channels, Ho,
-                           Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded);
+                           Wo, kh, kw, stride, pad, dilation, om_stride, channels_padded, 1, 1);
+    BRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- deform groups and the unmodulated form (DCN v1): offset rows of (modulated ? 3 : 2) * KH * KW * deform_groups floats
+// in the layout of deform_im2col_nhwc_kernel; the entries above are these with deform_groups 1, modulated 1 ---------------
+namespace {
+bool deform_g_args_ok(const void* x, const float* om, int batch, int height, int width, int channels, int kh, int kw,
+                      int stride, int pad, int dilation, int channels_padded, int groups, int modulated, int dtype) {
+    if (!x || !om || batch <= 0 || height <= 0 || width <= 0 || channels <= 0 || kh <= 0 || kw <= 0 || stride <= 0 ||
+        pad < 0 || dilation <= 0 || channels_padded < channels || groups <= 0 || channels % groups ||
+        (modulated != 0 && modulated != 1) || (long long)kh * kw * groups > 4096)
+        return false;
+    if (dtype != BRCNN_DT_F32 && dtype != BRCNN_DT_BF16 && dtype != BRCNN_DT_F16) return false;
+    // a thread's 4 (fp32) / 8 (16-bit) channels lie inside one group
+    const int q = dtype == BRCNN_DT_F32 ? 3 : 7;
+    return !((channels / groups) & q) && !(channels_padded & q);
+}
+}  // namespace
+
+BRCNN_API int brcnn_deform_im2col_nhwc_g(const void* x, const float* offset_mask, void* col, int batch, int height,
+                                         int width, int channels, int kh, int kw, int stride, int pad, int dilation,
+                                         int om_stride, int channels_padded, int deform_groups, int modulated, int dtype,
+                                         void* stream) {
+    if (!col || !deform_g_args_ok(x, offset_mask, batch, height, width, channels, kh, kw, stride, pad, dilation,
+                                  channels_padded, deform_groups, modulated, dtype))
+        return BRCNN_EINVAL;
+    if (om_stride < (modulated ? 3 : 2) * kh * kw * deform_groups) return BRCNN_EINVAL;
+    if (dtype != BRCNN_DT_F32 && (long long)batch * height * width * channels >= 0x7fffffffLL) return BRCNN_EINVAL;
+    int Ho, Wo;
+    if (!deform_out_size(height, width, kh, kw, stride, pad, dilation, &Ho, &Wo)) return BRCNN_EINVAL;
+    const long long total = (long long)batch * Ho * Wo * kh * kw * (channels_padded >> (dtype == BRCNN_DT_F32 ? 2 : 3));
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == BRCNN_DT_F32)
+        hipLaunchKernelGGL(deform_im2col_nhwc_kernel, dim3(stream_grid(total)), dim3(256), 0, s, (const float*)x, offset_mask,
+                           (float*)col, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride,
+                           channels_padded, deform_groups, modulated);
+    else if (dtype == BRCNN_DT_F16)
+        hipLaunchKernelGGL(deform_im2col_nhwc16_kernel<BRCNN_DT_F16>, dim3(stream_grid(total)), dim3(256), 0, s,
+                           (const unsigned short*)x, offset_mask, (unsigned short*)col, batch, height, width, channels, Ho, Wo,
+                           kh, kw, stride, pad, dilation, om_stride, channels_padded, deform_groups, modulated);
+    else
+        hipLaunchKernelGGL(deform_im2col_nhwc16_kernel<BRCNN_DT_BF16>, dim3(stream_grid(total)), dim3(256), 0, s,
+                           (const unsigned short*)x, offset_mask, (unsigned short*)col, batch, height, width, channels, Ho, Wo,
+                           kh, kw, stride, pad, dilation, om_stride, channels_padded, deform_groups, modulated);
+    BRCNN_LAUNCH_CHECK();
+    brcnn::count(brcnn::g_counters.dcn_im2col_launches);
+    return 0;
+}
+
+BRCNN_API int brcnn_deform_col2im_nhwc_g(const void* x, const float* offset_mask, const float* dcol, float* dx,
+                                         float* d_offset_mask, int batch, int height, int width, int channels, int kh,
+                                         int kw, int stride, int pad, int dilation, int om_stride, int channels_padded,
+                                         int deform_groups, int modulated, int dtype, void* stream) {
+    if (!dcol || !dx || !d_offset_mask ||
+        !deform_g_args_ok(x, offset_mask, batch, height, width, channels, kh, kw, stride, pad, dilation, channels_padded,
+                          deform_groups, modulated, dtype))
+        return BRCNN_EINVAL;
+    // every entry of a d_offset_mask row is written: the row is exactly the layout
+    if (om_stride != (modulated ? 3 : 2) * kh * kw * deform_groups) return BRCNN_EINVAL;
+    int Ho, Wo;
+    if (!deform_out_size(height, width, kh, kw, stride, pad, dilation, &Ho, &Wo)) return BRCNN_EINVAL;
+    const long long items = (long long)batch * Ho * Wo * kh * kw * deform_groups;
+    if ((items + 3) / 4 >= 0x7fffffffLL) return BRCNN_EINVAL;
+    const dim3 grid((unsigned)((items + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == BRCNN_DT_F32)
+        hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_F32>, grid, dim3(256), 0, s, x, offset_mask, dcol, dx,
+                           d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride,
+                           channels_padded, deform_groups, modulated);
+    else if (dtype == BRCNN_DT_F16)
+        hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_F16>, grid, dim3(256), 0, s, x, offset_mask, dcol, dx,
+                           d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride,
+                           channels_padded, deform_groups, modulated);
+    else
+        hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_BF16>, grid, dim3(256), 0, s, x, offset_mask, dcol, dx,
+                           d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride,
+                           channels_padded, deform_groups, modulated);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }

@@ -1,4 +1,4 @@
-// The sampled value of a modulated deformable 3x3 conv (DCNv2, deform_groups 1) in the 16-bit modes, shared by the
+// The sampled value of a deformable 3x3 conv (DCNv2, or DCN v1 = the mask factor identically 1) in the 16-bit modes, shared by the
 // 16-bit im2col (deform.hip) and the fused conv (deform_conv_bf16.hip): the same fp32 arithmetic in the same order as
 // deform_im2col_nhwc_kernel (the library is built with -ffp-contract=off, so neither form fuses a multiply-add the
 // other does not), then ONE round to nearest even.  The fused kernel's A operand is therefore the 16-bit column matrix
@@ -10,6 +10,8 @@
 // one (output pixel, tap): four corner pixels (element offset of channel 0 inside the image, 0 where the corner is
 // outside the map), which of them are inside (bits 0..3), the bilinear corner weights and sigmoid(mask logit).
 // A tap whose sample point lies outside (-1, H) x (-1, W) gets no corners, zero weights and a zero mask.
+// modulated = false (DCN v1): the mask factor is 1 and no sigmoid is evaluated (x * 1.f is exact, so the blend below is
+// the v2 arithmetic with that factor).  With deform groups the caller passes the offsets / logit of the channels' group.
 struct DeformTapGeom {
     int off1, off2, off3, off4;
     unsigned ok;
@@ -19,9 +21,9 @@ struct DeformTapGeom {
 
 // hb / wb: ho * stride - pad + i * dilation and its column counterpart (the integer base of the tap's sample point)
 __device__ __forceinline__ DeformTapGeom deform_tap_geom(float off_h, float off_w, float mask_logit, int hb, int wb,
-                                                         int H, int W, int C, bool pixel_ok) {
+                                                         int H, int W, int C, bool pixel_ok, bool modulated = true) {
     DeformTapGeom g;
-    const float mask = 1.f / (1.f + expf(-mask_logit));
+    const float mask = modulated ? 1.f / (1.f + expf(-mask_logit)) : 1.f;
     const float h_im = (float)hb + off_h;
     const float w_im = (float)wb + off_w;
     g.ok = 0u;

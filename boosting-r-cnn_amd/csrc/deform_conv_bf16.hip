@@ -1,10 +1,13 @@
-// Fused modulated deformable 3x3 conv (DCNv2, deform_groups 1) of the r2_101 recipes in the 16-bit modes:
+// Fused deformable 3x3 conv (DCNv2 of the r2_101 recipes; DCN v1 / DCNv2 with deform groups of the ResNet dconv_c3-c5
+// backbones) in the 16-bit modes:
 //     y = act(scale * (sum_k col[m,k] * W[co,k]) + shift)
 // in ONE launch, the column matrix never written to memory (the two-launch form writes (N*Ho*Wo, 9*Cp) columns and the
 // GEMM reads them back: ~155 MB per stage-3 conv at batch 8 x 800 x 1344 in 16 bits).
 //   x (N,H,W,Cp) bf16 / fp16, Cp % 64 == 0; offset_mask (N,Ho,Wo,om_stride >= 27) fp32, the raw conv_offset output (the
 //   offsets are not rounded to 16 bits: at a coordinate of ~100 a bf16 offset is off by up to half a pixel);
-//   w (Cout,3,3,Cp) in the K order (tap, c) of the columns; Cout in {64, 128, 256}; y (N,Ho,Wo,Cout) 16-bit.
+//   w (Cout,3,3,Cp) in the K order (tap, c) of the columns; Cout % 64 == 0 (output-channel blocks in grid.y); y (N,Ho,Wo,Cout)
+//   16-bit.  Deform groups G: (Cp / G) % 64 == 0, so every K step lies inside one group; the geometry is rebuilt at every
+//   (tap, group) unit and its offsets are requested one unit ahead.  MOD = false (v1): no mask load, no sigmoid.
 // A workgroup (4 waves, 2 x 2) computes 128 output pixels x BN = 64 * NB output channels on v_mfma_f32_32x32x16 with fp32
 // accumulation; one K step = one tap x 64 channels.  Per step every thread gathers four 16-byte chunks (32 channels) of
 // the four bilinear corners of one (pixel, tap), blends them in fp32 through deform_sample8 (deform_common.h: the 16-bit
@@ -15,6 +18,7 @@
 // offset / mask values of the next tap are requested one tap ahead.
 #include "common.h"
 #include "deform_common.h"
+#include "policy.h"
 
 namespace {
 
@@ -34,14 +38,16 @@ struct DcnParams {
     const float* shift;
     unsigned short* y;
     int H, W, Cp, Ho, Wo, M, stride, pad, om_stride, Cout, relu, tiles_m;
+    int G, cbg;                     // deform groups, 64-channel blocks per group
     unsigned w_bytes;
 };
 
-// the three fp32 offset / mask values of one tap of a pixel's offset_mask row
-__device__ __forceinline__ void dcn_load_om(float (&om_n)[3], const float* omg, int tap) {
-    om_n[0] = omg[2 * tap];
-    om_n[1] = omg[2 * tap + 1];
-    om_n[2] = omg[18 + tap];
+// the three fp32 offset / mask values of one (tap, group) of a pixel's offset_mask row
+template <bool MOD>
+__device__ __forceinline__ void dcn_load_om(float (&om_n)[3], const float* omg, int tap, int grp, int G) {
+    om_n[0] = omg[18 * grp + 2 * tap];
+    om_n[1] = omg[18 * grp + 2 * tap + 1];
+    om_n[2] = MOD ? omg[18 * G + 9 * grp + tap] : 0.f;
 }
 
 // the four corners x four 16-byte chunks of one step (clamped offsets: every load is issued)
@@ -79,7 +85,7 @@ __device__ __forceinline__ void dcn_dma_w(const unsigned short* w, unsigned w_by
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (lds_ptr_t)(dst + (wave * 2 * NB + j) * 1024), 16, b_off[j] + k_off, 0, 0, 0);
 }
 
-template <int DT, int NB>       // NB: 32-channel MFMA tiles per wave; the workgroup covers BN = 64 * NB output channels
+template <int DT, int NB, bool MOD>     // NB: 32-channel MFMA tiles per wave; the workgroup covers BN = 64 * NB output channels
 __global__ __launch_bounds__(256, 2) void deform_conv16_kernel(DcnParams p) {
     constexpr int BN = 64 * NB, B_BUF = BN * 128;
     // LDS: A buffers [0, 32K), B buffers [32K, 32K + 2 * B_BUF); step s uses buffers s & 1
@@ -167,12 +173,14 @@ __global__ __launch_bounds__(256, 2) void deform_conv16_kernel(DcnParams p) {
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
 
-    // prologue: tap 0's geometry, step 0's corners and weights, tap 1's offsets
-    dcn_load_om(om_n, omg, 0);
-    g = deform_tap_geom(om_n[0], om_n[1], om_n[2], hb0, wb0, p.H, p.W, p.Cp, gvalid);
+    // prologue: the geometry of unit 0 = (tap 0, group 0), step 0's corners and weights, unit 1's offsets
+    // (unit u = tap * G + group, in the order the K loop meets them)
+    const int G = p.G, cbg = p.cbg;
+    dcn_load_om<MOD>(om_n, omg, 0, 0, G);
+    g = deform_tap_geom(om_n[0], om_n[1], om_n[2], hb0, wb0, p.H, p.W, p.Cp, gvalid, MOD);
     dcn_load_corners(cv, g, xg, 0);
     dcn_dma_w<NB>(p.w, p.w_bytes, Bs, b_off, wave, 0, CB, p.Cp);
-    dcn_load_om(om_n, omg, 1);
+    dcn_load_om<MOD>(om_n, omg, G > 1 ? 0 : 1, G > 1 ? 1 : 0, G);
 
     for (int s = 0; s < S; s++) {
         const int cur = s & 1;
@@ -183,10 +191,15 @@ __global__ __launch_bounds__(256, 2) void deform_conv16_kernel(DcnParams p) {
         __syncthreads();
         if (s + 1 < S) {
             const int tap = (s + 1) / CB, cb = (s + 1) - tap * CB;
-            if (cb == 0) {
+            const int grp = cb / cbg;
+            if (cb - grp * cbg == 0) {      // the channel chunk enters the next group (or tap): its geometry, and the next unit's offsets
                 const int ti = tap / 3, tj = tap - ti * 3;
-                g = deform_tap_geom(om_n[0], om_n[1], om_n[2], hb0 + ti, wb0 + tj, p.H, p.W, p.Cp, gvalid);
-                if (tap + 1 < 9) dcn_load_om(om_n, omg, tap + 1);
+                g = deform_tap_geom(om_n[0], om_n[1], om_n[2], hb0 + ti, wb0 + tj, p.H, p.W, p.Cp, gvalid, MOD);
+                const int un = tap * G + grp + 1;
+                if (un < 9 * G) {
+                    const int tn = un / G;
+                    dcn_load_om<MOD>(om_n, omg, tn, un - tn * G, G);
+                }
             }
             dcn_load_corners(cv, g, xg, cb);
             dcn_dma_w<NB>(p.w, p.w_bytes, Bs + (cur ^ 1) * B_BUF, b_off, wave, s + 1, CB, p.Cp);
@@ -237,12 +250,49 @@ __global__ __launch_bounds__(256, 2) void deform_conv16_kernel(DcnParams p) {
     }
 }
 
-template <int DT, int NB>
+template <int DT, int NB, bool MOD>
 int launch_dcn16(const DcnParams& p, hipStream_t s) {
     const size_t lds = (size_t)2 * A_BUF + 2 * (64 * NB) * 128;
-    hipLaunchKernelGGL((deform_conv16_kernel<DT, NB>), dim3(p.tiles_m, p.Cout / (64 * NB)), dim3(256), lds, s, p);
+    hipLaunchKernelGGL((deform_conv16_kernel<DT, NB, MOD>), dim3(p.tiles_m, p.Cout / (64 * NB)), dim3(256), lds, s, p);
     BRCNN_LAUNCH_CHECK();
+    brcnn::count(brcnn::g_counters.dcn_fused_launches);
     return 0;
+}
+
+// what the fused kernel takes: 64-channel K steps inside one deform group, whole 64-channel output blocks
+bool dcn16_shape_ok(int channels, int cout, int stride, int pad, int groups, int dtype) {
+    return channels > 0 && !(channels & 63) && groups > 0 && !(channels % groups) && !((channels / groups) & 63) && cout > 0 &&
+           !(cout & 63) && (stride == 1 || stride == 2) && pad >= 0 && pad <= 2 && (dtype == BRCNN_DT_BF16 || dtype == BRCNN_DT_F16);
+}
+
+int dcn16_run(const void* x, const float* offset_mask, const void* w, const float* scale, const float* shift, void* y,
+              int batch, int height, int width, int channels, int cout, int stride, int pad, int relu, int om_stride,
+              int groups, int modulated, int dtype, void* stream) {
+    // (a padded map smaller than the kernel has no output: C's truncating division would give it one row)
+    if (height + 2 * pad < 3 || width + 2 * pad < 3) return BRCNN_EINVAL;
+    const int Ho = (height + 2 * pad - 3) / stride + 1, Wo = (width + 2 * pad - 3) / stride + 1;
+    const long long M = (long long)batch * Ho * Wo;
+    // every element offset (x, y, the weights' byte range of the buffer descriptor) fits 32 bits
+    if ((long long)batch * height * width * channels >= 0x7fffffffLL || M * cout >= 0x7fffffffLL ||
+        M * om_stride >= 0x7fffffffLL || (long long)cout * 9 * channels * 2 >= 0x7fffffffLL)
+        return BRCNN_EINVAL;
+    DcnParams p;
+    p.x = (const unsigned short*)x; p.om = offset_mask; p.w = (const unsigned short*)w; p.scale = scale; p.shift = shift;
+    p.y = (unsigned short*)y;
+    p.H = height; p.W = width; p.Cp = channels; p.Ho = Ho; p.Wo = Wo; p.M = (int)M; p.stride = stride; p.pad = pad;
+    p.om_stride = om_stride; p.Cout = cout; p.relu = relu ? 1 : 0; p.tiles_m = (int)((M + BM - 1) / BM);
+    p.w_bytes = (unsigned)((long long)cout * 9 * channels * 2);
+    p.G = groups; p.cbg = (channels >> 6) / groups;
+    hipStream_t s = (hipStream_t)stream;
+    // 128-channel workgroups wherever Cout is a multiple of 128: one gather per two 64-channel slices.  (64-channel workgroups
+    // on the short stage-4 maps -- twice the workgroups, each gathering its own A tiles -- measured slower: the gather is the bound)
+    const bool wide = !(cout & 127);
+    if (modulated) {
+        if (dtype == BRCNN_DT_F16) return wide ? launch_dcn16<BRCNN_DT_F16, 2, true>(p, s) : launch_dcn16<BRCNN_DT_F16, 1, true>(p, s);
+        return wide ? launch_dcn16<BRCNN_DT_BF16, 2, true>(p, s) : launch_dcn16<BRCNN_DT_BF16, 1, true>(p, s);
+    }
+    if (dtype == BRCNN_DT_F16) return wide ? launch_dcn16<BRCNN_DT_F16, 2, false>(p, s) : launch_dcn16<BRCNN_DT_F16, 1, false>(p, s);
+    return wide ? launch_dcn16<BRCNN_DT_BF16, 2, false>(p, s) : launch_dcn16<BRCNN_DT_BF16, 1, false>(p, s);
 }
 
 }  // namespace
@@ -254,24 +304,35 @@ BRCNN_API int brcnn_deform_conv_nhwc(const void* x, const float* offset_mask, co
         (cout != 64 && cout != 128 && cout != 256) || (stride != 1 && stride != 2) || pad < 0 || pad > 2 ||
         om_stride < 27 || (dtype != BRCNN_DT_BF16 && dtype != BRCNN_DT_F16))
         return BRCNN_EINVAL;
-    // (a padded map smaller than the kernel has no output: C's truncating division would give it one row)
-    if (height + 2 * pad < 3 || width + 2 * pad < 3) return BRCNN_EINVAL;
-    const int Ho = (height + 2 * pad - 3) / stride + 1, Wo = (width + 2 * pad - 3) / stride + 1;
-    const long long M = (long long)batch * Ho * Wo;
-    // every element offset (x, y, the weights' byte range of the buffer descriptor) fits 32 bits
-    if ((long long)batch * height * width * channels >= 0x7fffffffLL || M * cout >= 0x7fffffffLL ||
-        M * om_stride >= 0x7fffffffLL)
+    return dcn16_run(x, offset_mask, w, scale, shift, y, batch, height, width, channels, cout, stride, pad, relu, om_stride, 1, 1,
+                     dtype, stream);
+}
+
+// deform groups, the unmodulated form (DCN v1: offset rows of 18 * deform_groups floats, no mask) and any cout % 64 == 0.
+// Refuses (BRCNN_EINVAL) what the kernel does not take -- (channels / deform_groups) % 64 != 0 above all: the caller then
+// runs brcnn_deform_im2col_nhwc_g + the GEMM (brcnn_deform_conv_route answers beforehand).
+BRCNN_API int brcnn_deform_conv_nhwc_g(const void* x, const float* offset_mask, const void* w, const float* scale,
+                                       const float* shift, void* y, int batch, int height, int width, int channels,
+                                       int cout, int stride, int pad, int relu, int om_stride, int deform_groups,
+                                       int modulated, int dtype, void* stream) {
+    if (!x || !offset_mask || !w || !y || batch <= 0 || height <= 0 || width <= 0 || (modulated != 0 && modulated != 1) ||
+        !dcn16_shape_ok(channels, cout, stride, pad, deform_groups, dtype) ||
+        om_stride < (modulated ? 27 : 18) * (long long)deform_groups)
         return BRCNN_EINVAL;
-    DcnParams p;
-    p.x = (const unsigned short*)x; p.om = offset_mask; p.w = (const unsigned short*)w; p.scale = scale; p.shift = shift;
-    p.y = (unsigned short*)y;
-    p.H = height; p.W = width; p.Cp = channels; p.Ho = Ho; p.Wo = Wo; p.M = (int)M; p.stride = stride; p.pad = pad;
-    p.om_stride = om_stride; p.Cout = cout; p.relu = relu ? 1 : 0; p.tiles_m = (int)((M + BM - 1) / BM);
-    p.w_bytes = (unsigned)((long long)cout * 9 * channels * 2);
-    hipStream_t s = (hipStream_t)stream;
-    // 128-channel workgroups for Cout 128 / 256: one gather per two 64-channel slices.  (64-channel workgroups on the short
-    // stage-4 maps -- twice the workgroups, each gathering its own A tiles -- measured slower: the gather is the bound)
-    const bool wide = cout > 64;
-    if (dtype == BRCNN_DT_F16) return wide ? launch_dcn16<BRCNN_DT_F16, 2>(p, s) : launch_dcn16<BRCNN_DT_F16, 1>(p, s);
-    return wide ? launch_dcn16<BRCNN_DT_BF16, 2>(p, s) : launch_dcn16<BRCNN_DT_BF16, 1>(p, s);
+    return dcn16_run(x, offset_mask, w, scale, shift, y, batch, height, width, channels, cout, stride, pad, relu, om_stride,
+                     deform_groups, modulated, dtype, stream);
+}
+
+// 1: the 16-bit deformable conv of this shape runs on the fused kernel, 0: as im2col + GEMM.  policy dcn_fused
+// (brcnn_conv_set_tile(-13, n)): 0 never fused, 2 wherever brcnn_deform_conv_nhwc_g accepts the shape, 1 (default) the
+// rule measured on the ResNet c3-c5 and Res2Net shapes (profiles/resnet_dcn_bench_*.txt).
+BRCNN_API int brcnn_deform_conv_route(int batch, int height, int width, int channels, int cout, int stride, int pad,
+                                      int deform_groups, int dtype) {
+    if (batch <= 0 || height <= 0 || width <= 0 || !dcn16_shape_ok(channels, cout, stride, pad, deform_groups, dtype)) return 0;
+    if (brcnn::g_policy.dcn_fused != 1) return brcnn::g_policy.dcn_fused == 2;
+    // The measured rule (profiles/resnet_dcn_bench_*.txt, res2net16_deform_bench_*.txt): a workgroup column covers at most 128
+    // output channels, and every column gathers and blends the A tiles again.  With one column (cout <= 128) the fused
+    // kernel took 0.6-0.9 of the time of im2col + GEMM on every shape measured; with two or four columns (cout 256 / 512:
+    // the gather done two / four times) 1.3-2.2 of it.
+    return cout <= 128;
 }

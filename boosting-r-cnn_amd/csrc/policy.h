@@ -19,6 +19,9 @@ struct Policy {
     int f32_winograd = 1;           // (-11, 0 / 1): never / where the caller prepared the transformed filter; (-11, 2) returns it
     int f32_winograd_chunks = 1;    // tuning hook ((-11, 10 + n), n = 1 .. 8): transform + GEMM launch pairs per call
 
+    // ---- 16-bit deformable conv (deform_conv_bf16.hip): brcnn_conv_set_tile(-13, n); read by brcnn_deform_conv_route
+    int dcn_fused = 1;              // (-13, 0 / 1 / 2): im2col + GEMM always / the measured rule / fused wherever the kernel accepts the shape
+
     // ---- 16-bit conv (conv_igemm_bf16.hip, conv1x1_stream_bf16.hip): brcnn_conv_set_tile_bf16(mtnt)
     int bf16_tile = 0;              // tuning hook: 0 heuristic, 11 / 21 / 22 = MT NT (4 waves), 42 = 256x128 (8 waves)
     int bf16_il = 0;                // tuning hook (set_tile_bf16(-1 / -2)): spread the LDS-DMA pieces between the MFMA groups
@@ -81,6 +84,9 @@ struct Counters {
     // brcnn_conv_set_tile(-12, 0 / 1): return and clear ((-9, -1) clears them too)
     int f32_winograd_launches = 0;      // (-12, 0): calls of brcnn_conv3x3_winograd_f32_multi that launched
     int f32_winograd_tiles = 0;         // (-12, 1): 2x2 output tiles of the last one
+    // brcnn_conv_set_tile(-13, 10 / 11): return and clear ((-9, -1) clears them too)
+    int dcn_fused_launches = 0;         // (-13, 10): launches of the fused deformable conv (deform_conv_bf16.hip), every entry
+    int dcn_im2col_launches = 0;        // (-13, 11): launches of the deformable im2col kernels (deform.hip), every entry
     // brcnn_roi_align_set_exact(60 .. 63): return and clear
     int roi_ordered_launches = 0;   // 60: RoI forward launches that visited the RoIs in band order
     int roi_prepared_launches = 0;  // 61: RoI forward launches in the prepared-record form

@@ -28,6 +28,7 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
         if (nt == -1) {
             for (int* q : c) *q = 0;
             g_counters.f32_winograd_launches = g_counters.f32_winograd_tiles = 0;
+            g_counters.dcn_fused_launches = g_counters.dcn_im2col_launches = 0;
             return 0;
         }
         const int n = *c[nt];
@@ -46,6 +47,18 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
     if (wm == -12) {
         if (nt != 0 && nt != 1) return BRCNN_EINVAL;
         int& c = nt == 0 ? g_counters.f32_winograd_launches : g_counters.f32_winograd_tiles;
+        const int n = c;
+        c = 0;
+        return n;
+    }
+    // deformable conv route (brcnn_deform_conv_route): (-13, 0 / 1 / 2) im2col + GEMM always / by the measured rule / the
+    // fused kernel wherever it accepts the shape; (-13, 3) RETURNS the setting; (-13, 10 / 11) return and clear the
+    // launches of the fused kernel / of the im2col kernels
+    if (wm == -13) {
+        if (nt >= 0 && nt <= 2) { g_policy.dcn_fused = nt; return 0; }
+        if (nt == 3) return g_policy.dcn_fused;
+        if (nt != 10 && nt != 11) return BRCNN_EINVAL;
+        int& c = nt == 10 ? g_counters.dcn_fused_launches : g_counters.dcn_im2col_launches;
         const int n = c;
         c = 0;
         return n;

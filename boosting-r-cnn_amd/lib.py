@@ -127,6 +127,10 @@ SIGNATURES = {
     'brcnn_deform_im2col_nhwc_ex': (c_int, [c_ptr] * 3 + [c_int] * 12 + [c_ptr]),
     'brcnn_deform_col2im_nhwc_ex': (c_int, [c_ptr] * 5 + [c_int] * 12 + [c_ptr]),
     'brcnn_deform_conv_nhwc': (c_int, [c_ptr] * 6 + [c_int] * 10 + [c_ptr]),
+    'brcnn_deform_im2col_nhwc_g': (c_int, [c_ptr] * 3 + [c_int] * 14 + [c_ptr]),
+    'brcnn_deform_col2im_nhwc_g': (c_int, [c_ptr] * 5 + [c_int] * 14 + [c_ptr]),
+    'brcnn_deform_conv_nhwc_g': (c_int, [c_ptr] * 6 + [c_int] * 12 + [c_ptr]),
+    'brcnn_deform_conv_route': (c_int, [c_int] * 9),
     'brcnn_pack_conv_weights': (c_int, [c_ptr] * 3 + [c_int] * 5 + [c_ptr]),
     'brcnn_rpn_topk_workspace_bytes': (ctypes.c_size_t, [c_ptr, c_int, c_int, c_int]),
     'brcnn_rpn_topk': (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, ctypes.c_size_t, c_ptr]),

@@ -1368,16 +1368,26 @@ def avgpool_nhwc(x, kernel, stride, pad=0, ceil_mode=False, count_include_pad=Tr
     return y
 
 
-def deform_im2col_nhwc(x, offset_mask, kernel=3, stride=1, pad=1, dilation=1, channels_padded=None):
-    """mmcv modulated deformable im2col (deform_groups 1): x (N,H,W,C), offset_mask (N,Ho,Wo,>=27)
+def deform_im2col_nhwc(x, offset_mask, kernel=3, stride=1, pad=1, dilation=1, channels_padded=None, deform_groups=1,
+                       modulated=True):
+    """mmcv (modulated) deformable im2col: x (N,H,W,C), offset_mask (N,Ho,Wo,>=(3 | 2) k k G)
     raw conv_offset output -> columns (N*Ho*Wo, k*k*Cp), K order (tap, c), zero in the pad channels.
-    bf16 / fp16 x: 16-bit columns, each the fp32 sample of the widened input rounded once (offset_mask stays fp32)"""
+    bf16 / fp16 x: 16-bit columns, each the fp32 sample of the widened input rounded once (offset_mask stays fp32).
+    `deform_groups` G > 1 / `modulated=False` (DCN v1: no mask): the row layout of brcnn_deform_im2col_nhwc_g"""
     _require_gpu(x, offset_mask)
     assert x.dim() == 4 and x.is_contiguous()
     n, h, w, c = x.shape
     cp = c if channels_padded is None else channels_padded
     ho, wo = conv_out_size(h, w, dilation * (kernel - 1) + 1, dilation * (kernel - 1) + 1, stride, pad)
     assert tuple(offset_mask.shape[:3]) == (n, ho, wo) and offset_mask.is_contiguous()
+    if deform_groups != 1 or not modulated:
+        assert offset_mask.dtype == torch.float32, 'deform_im2col_nhwc: offset_mask stays fp32'
+        col = torch.empty((n * ho * wo, kernel * kernel * cp), dtype=x.dtype, device=x.device)
+        st = _L.load().brcnn_deform_im2col_nhwc_g(_ptr(x), _ptr(offset_mask), _ptr(col), n, h, w, c, kernel, kernel,
+                                                  int(stride), int(pad), int(dilation), offset_mask.shape[3], cp,
+                                                  int(deform_groups), int(bool(modulated)), _dt(x), _stream())
+        _L.check(st, 'brcnn_deform_im2col_nhwc_g')
+        return col, (ho, wo)
     if x.dtype != torch.float32:
         assert offset_mask.dtype == torch.float32, 'deform_im2col_nhwc: offset_mask stays fp32'
         col = torch.empty((n * ho * wo, kernel * kernel * cp), dtype=x.dtype, device=x.device)
@@ -1393,11 +1403,39 @@ def deform_im2col_nhwc(x, offset_mask, kernel=3, stride=1, pad=1, dilation=1, ch
     return col, (ho, wo)
 
 
-def deform_conv_nhwc(x, offset_mask, w, scale=None, shift=None, relu=False, stride=1, pad=1):
-    """fused modulated deformable 3x3 conv, 16-bit only: y = [relu](scale * (im2col(x, offset_mask) . w^T) + shift) in
-    one launch.  x (N,H,W,Cp) bf16 / fp16 with Cp % 64 == 0; offset_mask (N,Ho,Wo,>=27) fp32 raw conv_offset output
-    (a padded row, e.g. the 64-channel output of the offset conv, is read in place); w (Cout,3,3,Cp) in x's dtype,
-    Cout in {64, 128, 256}; scale / shift (Cout) fp32 or None.  Returns y (N,Ho,Wo,Cout) in x's dtype."""
+def deform_col2im_nhwc(x, offset_mask, dcol, stride=1, pad=1, deform_groups=1, modulated=True):
+    """backward of the 3x3 deformable im2col: dcol (N*Ho*Wo, 9*C) fp32 -> (dx fp32 (N,H,W,C), d_offset_mask like offset_mask);
+    x fp32 / bf16 / fp16, offset_mask (N,Ho,Wo,(3 | 2) * 9 * G) exactly the layout (every entry of its gradient is written)"""
+    _require_gpu(x, offset_mask, dcol)
+    assert x.is_contiguous() and offset_mask.is_contiguous() and dcol.is_contiguous() and dcol.dtype == torch.float32
+    n, h, w, c = x.shape
+    dx = torch.zeros((n, h, w, c), dtype=torch.float32, device=x.device)
+    dom = torch.empty_like(offset_mask)
+    st = _L.load().brcnn_deform_col2im_nhwc_g(_ptr(x), _ptr(offset_mask), _ptr(dcol), _ptr(dx), _ptr(dom), n, h, w, c, 3, 3,
+                                              int(stride), int(pad), 1, offset_mask.shape[3], c, int(deform_groups),
+                                              int(bool(modulated)), _dt(x), _stream())
+    _L.check(st, 'brcnn_deform_col2im_nhwc_g')
+    return dx, dom
+
+
+def deform_conv_route(x, cout, stride=1, pad=1, deform_groups=1):
+    """True: the 16-bit deformable conv of x (N,H,W,Cp) runs on the fused kernel (`deform_conv_nhwc`); False: as
+    `deform_im2col_nhwc` + the GEMM -- every shape the fused kernel refuses ((Cp / G) % 64, cout % 64) and whatever the
+    policy table sends there (brcnn_deform_conv_route; brcnn_conv_set_tile(-13, n))"""
+    if x.dtype not in (torch.bfloat16, torch.float16):
+        return False
+    n, h, w, cp = x.shape
+    return _L.load().brcnn_deform_conv_route(n, h, w, cp, int(cout), int(stride), int(pad), int(deform_groups), _dt(x)) == 1
+
+
+def deform_conv_nhwc(x, offset_mask, w, scale=None, shift=None, relu=False, stride=1, pad=1, deform_groups=1,
+                     modulated=True):
+    """fused deformable 3x3 conv, 16-bit only: y = [relu](scale * (im2col(x, offset_mask) . w^T) + shift) in one launch.
+    x (N,H,W,Cp) bf16 / fp16 with (Cp / G) % 64 == 0 for G = `deform_groups`; offset_mask (N,Ho,Wo, >= 27 G, or >= 18 G with
+    `modulated=False`: DCN v1, no mask) fp32 raw conv_offset output in the layout of brcnn_deform_im2col_nhwc_g (a padded
+    row, e.g. the 64-channel output of the offset conv, is read in place); w (Cout,3,3,Cp) in x's dtype, Cout % 64 == 0;
+    scale / shift (Cout) fp32 or None.  Returns y (N,Ho,Wo,Cout) in x's dtype.  A shape the kernel does not take raises
+    (`deform_conv_route` answers beforehand).  G = 1, modulated, Cout in {64, 128, 256} runs the original entry point."""
     _require_gpu(x, offset_mask, w, scale, shift)
     assert x.dim() == 4 and x.is_contiguous() and w.is_contiguous() and offset_mask.is_contiguous()
     if x.dtype not in (torch.bfloat16, torch.float16) or w.dtype != x.dtype:
@@ -1410,6 +1448,12 @@ def deform_conv_nhwc(x, offset_mask, w, scale=None, shift=None, relu=False, stri
     ho, wo = conv_out_size(h, wd, 3, 3, stride, pad)
     assert tuple(offset_mask.shape[:3]) == (n, ho, wo)
     y = torch.empty((n, ho, wo, cout), dtype=x.dtype, device=x.device)
+    if deform_groups != 1 or not modulated or cout not in (64, 128, 256):
+        st = _L.load().brcnn_deform_conv_nhwc_g(_ptr(x), _ptr(offset_mask), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), n, h,
+                                                wd, cp, cout, int(stride), int(pad), int(bool(relu)), offset_mask.shape[3],
+                                                int(deform_groups), int(bool(modulated)), _dt(x), _stream())
+        _L.check(st, 'brcnn_deform_conv_nhwc_g')
+        return y
     st = _L.load().brcnn_deform_conv_nhwc(_ptr(x), _ptr(offset_mask), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), n, h,
                                           wd, cp, cout, int(stride), int(pad), int(bool(relu)), offset_mask.shape[3],
                                           _dt(x), _stream())

@@ -352,7 +352,10 @@ int brcnn_conv_handover_status(void);
  * (-11, 0 / 1): Winograd F(2x2,3x3) for the fp32 3x3 layers whose caller prepared the transformed filter never / yes;
  * (-11, 2) RETURNS the setting (the caller reads it: the Winograd entry point never falls back by itself); (-11, 11 .. 18):
  * 1 .. 8 transform + GEMM launch pairs per call.  (-12, 0) returns and clears the number of Winograd calls that launched,
- * (-12, 1) the 2x2 tiles of the last one; (-9, -1) clears both as well. */
+ * (-12, 1) the 2x2 tiles of the last one; (-9, -1) clears both as well.
+ * (-13, 0 / 1 / 2): route of the 16-bit deformable convs (brcnn_deform_conv_route) im2col + GEMM always / the measured
+ * rule / fused wherever accepted; (-13, 3) RETURNS the setting; (-13, 10) / (-13, 11) return and clear the launches of the
+ * fused deformable kernel / of the deformable im2col kernels ((-9, -1) clears them too). */
 int brcnn_conv_set_tile(int wm, int nt);
 
 /* Tuning hook of the bf16 kernel: 0 heuristic; 11 / 21 / 22 = 64x64 / 128x64 / 128x128 tile on
@@ -657,6 +660,37 @@ int brcnn_deform_col2im_nhwc_ex(const void *x, const float *offset_mask, const f
 int brcnn_deform_conv_nhwc(const void *x, const float *offset_mask, const void *w, const float *scale,
                            const float *shift, void *y, int batch, int height, int width, int channels, int cout,
                            int stride, int pad, int relu, int om_stride, int dtype, void *stream);
+/* Deform groups and the unmodulated form (mmcv DeformConv2dPack, `type='DCN'`; ResNet dconv_c3-c5 backbones).  With
+ * T = KH*KW taps and G = deform_groups (channels % G == 0; channel c belongs to group c / (channels / G); the pad
+ * channels c >= channels stay zero and belong to no group) an offset row of a pixel holds [2 T g + 2 t] = dy and
+ * [2 T g + 2 t + 1] = dx of tap t in group g and, when `modulated`, the mask logit at [2 T G + T g + t] -- mmcv's
+ * `o1, o2, mask = chunk(out, 3); offset = cat(o1, o2)`; G = 1 is the layout of the entries above.  modulated = 0: the
+ * mask factor is identically 1, no sigmoid is evaluated, rows have 2 T G entries (v1 is DEFINED as the v2
+ * restatement with that factor).  dtype BRCNN_DT_F32 | _BF16 | _F16; (channels / G) % 4 == 0 in fp32, % 8 == 0 in 16 bits.
+ * im2col: om_stride >= (modulated ? 3 : 2) T G; col2im: om_stride equal to it, every entry of d_offset_mask written.
+ * With G = 1, modulated = 1 they equal the entries above bit for bit (dx: up to the order of its atomics). */
+int brcnn_deform_im2col_nhwc_g(const void *x, const float *offset_mask, void *col, int batch, int height, int width,
+                               int channels, int kh, int kw, int stride, int pad, int dilation, int om_stride,
+                               int channels_padded, int deform_groups, int modulated, int dtype, void *stream);
+int brcnn_deform_col2im_nhwc_g(const void *x, const float *offset_mask, const float *dcol, float *dx,
+                               float *d_offset_mask, int batch, int height, int width, int channels, int kh, int kw,
+                               int stride, int pad, int dilation, int om_stride, int channels_padded, int deform_groups,
+                               int modulated, int dtype, void *stream);
+/* The fused 16-bit deformable 3x3 conv with deform groups, modulated or not, any cout % 64 == 0 (output-channel blocks in
+ * the grid).  Requires (channels / deform_groups) % 64 == 0 (a K step -- one tap x 64 channels -- then lies inside one
+ * group) and om_stride >= (modulated ? 27 : 18) * deform_groups; anything else is refused with BRCNN_EINVAL and the
+ * caller runs brcnn_deform_im2col_nhwc_g + the GEMM.  The A operand equals brcnn_deform_im2col_nhwc_g's 16-bit columns
+ * bit for bit; modulated = 0 loads no mask and evaluates no sigmoid. */
+int brcnn_deform_conv_nhwc_g(const void *x, const float *offset_mask, const void *w, const float *scale,
+                             const float *shift, void *y, int batch, int height, int width, int channels, int cout,
+                             int stride, int pad, int relu, int om_stride, int deform_groups, int modulated, int dtype,
+                             void *stream);
+/* Which route a caller takes for a 16-bit deformable conv of this shape: 1 = brcnn_deform_conv_nhwc_g, 0 = im2col + GEMM
+ * (also for every shape the fused entry refuses).  Reads the policy switch brcnn_conv_set_tile(-13, 0 / 1 / 2): im2col +
+ * GEMM always / the measured rule (default) / fused wherever accepted; (-13, 3) returns the setting; (-13, 10) and
+ * (-13, 11) return and clear the launches of the fused kernel and of the deformable im2col kernels (tests). */
+int brcnn_deform_conv_route(int batch, int height, int width, int channels, int cout, int stride, int pad,
+                            int deform_groups, int dtype);
 
 /* FPN top-down path: dst[n,y,x,c] += src[n, y*Hs/Hd, x*Ws/Wd, c]  (nearest,
  * F.interpolate(size=...) at necks/pafpn.py:113-115, fpn.py:178-181) */
