@@ -59,6 +59,7 @@ class PackedCache:
     def __init__(self):
         self.key = None
         self.val = None
+        self.wino = None        # a PackedCache of the Winograd-transformed filter once prepare_winograd_layer accepted the layer
 
     def get(self, sources, builder):
         key = tuple((s.data_ptr(), s._version, s.device) for s in sources if s is not None) + \
@@ -246,8 +247,37 @@ def conv_bn_act_nhwc(x, conv, bn, cache, relu, residual=None, with_skip=False, s
             y = y + residual
         return y.relu() if relu else y
     w, scale, shift = folded_conv_operands(conv, bn, cache, x.dtype)
+    wino = getattr(cache, 'wino', None)
+    if wino is not None and residual is None and not with_skip and ops.winograd_layer_route(x, conv):
+        # frozen fp32 3x3 stride-1 layer of a size the policy table sends to the Winograd form (prepare_winograd_layer);
+        # the folded BN / bias and the ReLU go to its GEMM's read-out
+        u = wino.get([conv.weight], lambda: ops.winograd_filter(pack_weight(conv.weight)))
+        return ops.conv3x3_winograd_layer(x, u, scale, shift, relu)
     out = ops.conv2d_nhwc(x, w, scale, shift, residual, relu, conv.stride[0], conv.padding[0])
     return (out, x) if with_skip else out
+
+
+def winograd_layer_form(conv):
+    """the layer form of the Winograd single-layer route: a plain 3x3 stride-1 pad-1 nn.Conv2d with Cin % 32 == 0 and
+    Cout % 64 == 0 (what brcnn_winograd_layer_route accepts before it looks at the size)"""
+    return (type(conv) is nn.Conv2d and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and
+            conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == 'zeros' and conv.in_channels % 32 == 0 and
+            conv.out_channels % 64 == 0)
+
+
+def prepare_winograd_layer(conv, cache):
+    """Inference with frozen weights (freeze_for_inference): from here on the no-grad tail of conv_bn_act_nhwc may run this
+    layer in the Winograd F(2x2,3x3) form where `ops.winograd_layer_route` sends its size there (fp32 operands only).  The
+    transformed filter lives beside the layer's packed operands, keyed on the weight's version like them; it is built now
+    when the weight is on the device and the rule can accept the layer's channels at some size, else on first use.  A layer
+    that was not prepared never takes the route.  Returns whether the layer has the form."""
+    if not winograd_layer_form(conv):
+        return False
+    if getattr(cache, 'wino', None) is None:
+        cache.wino = PackedCache()
+    if conv.weight.is_cuda and compute_dtype() == torch.float32 and ops.winograd_layer_channels_ok(conv):
+        cache.wino.get([conv.weight], lambda: ops.winograd_filter(pack_weight(conv.weight)))
+    return True
 
 
 def folded_conv_operands(conv, bn, cache, dtype):

@@ -6,7 +6,8 @@
 //              the finalized (mean, rstd) of brcnn_groupnorm_nhwc_multi in gn_apply_rows_kernel's expression (misc.hip) --
 //              the operand is then bit for bit the transform of what that kernel would have written; the halo is zero
 //              AFTER the prologue (the conv pads the normalised tensor)
-//   gemm       per workgroup 64 tiles x 128 channels: for each xi a K = Cin product into one temporary accumulator set
+//   gemm       per workgroup 64 tiles x 128 channels (the tower; 32 x 128 and 64 x 64 for the single-layer entry, see
+//              wino_gemm_kernel): for each xi a K = Cin product into one temporary accumulator set
 //              (v_mfma_f32_32x32x2_f32, LDS-DMA staging of step s + 1 under the MFMAs of step s, the 16 x Cin / 32 steps
 //              run as ONE pipelined loop), then tmp is added / subtracted into y00 y01 y10 y11 by A^T M A (per-lane VALU:
 //              the 16 products share one lane mapping); read-out with scale / shift / ReLU to the pixels of each
@@ -151,22 +152,35 @@ struct WinoGemmParams {
     WinoSegs sg;
 };
 
-constexpr int WBM = 64, WBN = 128;      // tiles x output channels of a workgroup; a wave owns 32 x 64
+// Workgroup tile variants (WBM tiles x WBN output channels, four waves as WMW x WNW, a wave owns 32 x 32 NB):
+//   1  64 x 128, 2 x 2 waves of 32 x 64: the tower's (the only one until the single-layer route; its code is unchanged)
+//   2  32 x 128, four waves side by side, 32 x 32 each
+//   3  64 x 64, 2 x 2 waves of 32 x 32
+// The 32 x 32 wave tiles double the waves of a launch: the layers of 2 184 .. 8 400 tiles leave most CUs with ONE 64 x 128
+// workgroup.  Every variant sums the K loop of an output in the same order, so the results are equal bit for bit.
+constexpr int WBM_MAX = 64;             // launch chunks are whole row blocks of every variant
 
 // A^T = [1 1 1 0; 0 1 -1 -1]: coefficient of M[i][j] (xi = 4 i + j) in y[a][b] is AT[a][i] AT[b][j]
 __device__ __forceinline__ constexpr int wino_at(int a, int i) { return a == 0 ? (i < 3 ? 1 : 0) : (i == 0 ? 0 : (i == 1 ? 1 : -1)); }
 
+// (the body exists in the device pass only: the host pass would instantiate the inline assembly, whose operand types depend on
+// the template's parameters, against the host's constraints and drop the launch stub)
+template <int WBM, int WBN, int WNW>
 __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
-    __shared__ __attribute__((aligned(16))) float smem[2 * WBM * 32 + 2 * WBN * 32];      // 48 KiB: two stages of A and B
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int NB = WBN / (32 * WNW);        // 32-column blocks of a wave
+    static_assert(WBM % 32 == 0 && (WBM / 32) * WNW == 4 && NB * 32 * WNW == WBN && (NB == 1 || NB == 2), "four waves of 32 x 32 NB");
+    static_assert(2 * WBM * 32 + 2 * WBN * 32 >= 4 * 1024, "the read-out slabs live in the staging buffers");
+    __shared__ __attribute__((aligned(16))) float smem[2 * WBM * 32 + 2 * WBN * 32];      // 64 x 128: 48 KiB, two stages of A and B
     float* As = smem;
     float* Bs = smem + 2 * WBM * 32;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
+    const int wm = wave / WNW, wn = wave % WNW;
     const int li = lane & 31, lh = lane >> 5;
 
-    // the Cout / 128 column tiles of one row block side by side on one XCD: V is fetched from HBM once
+    // the Cout / WBN column tiles of one row block side by side on one XCD: V is fetched from HBM once
     const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_m = tile / p.tiles_n, tile_n = tile - tile_m * p.tiles_n;
     const int m0 = tile_m * WBM, n0 = tile_n * WBN;
@@ -175,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
     const __amdgpu_buffer_rsrc_t rsrc_u = __builtin_amdgcn_make_buffer_rsrc((void*)p.u, 0, (int)p.u_bytes, 0x00020000);
 
     // ---- DMA assignment (conv_igemm_f32_dma_kernel's): a wave moves 8-row groups, lane -> (row in group, physical chunk)
-    constexpr int AG = WBM / 8 / 4, BG = WBN / 8 / 4;       // 2, 4
+    constexpr int AG = WBM / 8 / 4, BG = WBN / 8 / 4;       // 64 x 128: 2, 4
     const int rg = lane >> 3, pc = lane & 7;
     int a_off[AG], b_off[BG];
 #pragma unroll
@@ -215,22 +229,25 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
 #pragma unroll
     for (int kk = 0; kk < 4; kk++) chb[kk] = (unsigned)(((2 * kk + lh) ^ sw) * 16);
     const unsigned a_lane = (unsigned)(size_t)(lds_ptr_t)(As + (wm * 32 + li) * 32);
-    const unsigned b_lane = (unsigned)(size_t)(lds_ptr_t)(Bs + (wn * 64 + li) * 32);
-    f32x4 av[2], bv[2][2];
+    const unsigned b_lane = (unsigned)(size_t)(lds_ptr_t)(Bs + (wn * 32 * NB + li) * 32);
+    f32x4 av[2], bv[2][NB];
     auto frag_read = [&](int slot, unsigned a_addr, unsigned b_addr) {
         asm volatile("ds_read_b128 %0, %1" : "=v"(av[slot]) : "v"(a_addr) : "memory");
         asm volatile("ds_read_b128 %0, %1" : "=v"(bv[slot][0]) : "v"(b_addr) : "memory");
-        asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(bv[slot][1]) : "v"(b_addr) : "memory");
+        if constexpr (NB == 2) asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(bv[slot][NB - 1]) : "v"(b_addr) : "memory");
     };
     auto frag_wait = [&](int slot) {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(av[slot]), "+v"(bv[slot][0]), "+v"(bv[slot][1]) :: "memory");
+        if constexpr (NB == 2)
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(av[slot]), "+v"(bv[slot][0]), "+v"(bv[slot][NB - 1]) :: "memory");
+        else
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(av[slot]), "+v"(bv[slot][0]) :: "memory");
     };
 
-    f32x16 yacc[4][2], tmp[2];          // y00 y01 y10 y11 and the product of the current xi, two 32-column blocks each
+    f32x16 yacc[4][NB], tmp[NB];        // y00 y01 y10 y11 and the product of the current xi, NB 32-column blocks each
 #pragma unroll
     for (int q = 0; q < 4; q++)
 #pragma unroll
-        for (int b = 0; b < 2; b++)
+        for (int b = 0; b < NB; b++)
 #pragma unroll
             for (int r = 0; r < 16; r++) yacc[q][b][r] = 0.f;
 
@@ -240,7 +257,7 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
     int cur = 0;
     for (int xi = 0; xi < 16; xi++) {
 #pragma unroll
-        for (int b = 0; b < 2; b++)
+        for (int b = 0; b < NB; b++)
 #pragma unroll
             for (int r = 0; r < 16; r++) tmp[b][r] = 0.f;
         for (int kc = 0; kc < nk; kc++) {
@@ -256,7 +273,7 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
 #pragma unroll
                 for (int e = 0; e < 4; e++)
 #pragma unroll
-                    for (int b = 0; b < 2; b++)
+                    for (int b = 0; b < NB; b++)
                         tmp[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[sl][e], bv[sl][b][e], tmp[b], 0, 0, 0);
                 if (kk + 1 < 4) frag_wait(sl ^ 1);
             }
@@ -274,7 +291,7 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
             for (int bq = 0; bq < 2; bq++) {
                 const float c = (float)(wino_at(a, i) * wino_at(bq, j));
 #pragma unroll
-                for (int b = 0; b < 2; b++)
+                for (int b = 0; b < NB; b++)
 #pragma unroll
                     for (int r = 0; r < 16; r++) yacc[a * 2 + bq][b][r] = __builtin_fmaf(c, tmp[b][r], yacc[a * 2 + bq][b][r]);
             }
@@ -301,12 +318,12 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
     }
     float* __restrict__ yout = p.y;
 #pragma unroll
-    for (int b = 0; b < 2; b++) {
-        const int co = n0 + wn * 64 + b * 32 + li;
+    for (int b = 0; b < NB; b++) {
+        const int co = n0 + wn * 32 * NB + b * 32 + li;
         const bool cok = co < p.Cout;
         const float sc = (p.scale && cok) ? p.scale[co] : 1.f;
         const float sh = (p.shift && cok) ? p.shift[co] : 0.f;
-        const int cv = n0 + wn * 64 + b * 32 + vcol;
+        const int cv = n0 + wn * 32 * NB + b * 32 + vcol;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
 #pragma unroll
@@ -329,6 +346,7 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
             __builtin_amdgcn_wave_barrier();
         }
     }
+#endif
 }
 
 // host side: the tile table of a segment list; 0 or BRCNN_EINVAL
@@ -371,6 +389,46 @@ BRCNN_API int brcnn_winograd_filter_f32(const void* w, void* u, int cout, int ci
     return 0;
 }
 
+namespace {
+
+// transform + GEMM launch pairs of one call; `variant` 1 / 2 / 3 as listed at wino_gemm_kernel.  0 or BRCNN_EINVAL; the caller
+// has checked the layer form and counts the launch
+int wino_run(const void* x, const void* u, const void* gn_stats, const float* gamma, const float* beta, int groups, int relu_in,
+             const float* scale, const float* shift, int relu, void* y, void* workspace, size_t workspace_bytes, WinoGemmParams& p,
+             int num_segments, int cin, int cout, int variant, void* stream) {
+    const int tiles = p.sg.t0[num_segments];
+    if ((long long)p.sg.r0[num_segments] * (cin > cout ? cin : cout) * 4 >= 0x7fffffffLL) return BRCNN_EINVAL;
+    if (workspace_bytes < (size_t)16 * tiles * cin * sizeof(float)) return BRCNN_EINVAL;
+    const int wbm = variant == 2 ? 32 : 64, wbn = variant == 3 ? 64 : 128;
+    // chunks of whole workgroup row blocks; more of them where the V planes of one would pass the 2 GiB of a buffer descriptor
+    int chunks = brcnn::g_policy.f32_winograd_chunks;
+    while ((long long)16 * ((tiles + chunks - 1) / chunks + WBM_MAX) * cin * 4 >= 0x7fffffffLL) chunks *= 2;
+    const int per = ((tiles + chunks - 1) / chunks + WBM_MAX - 1) / WBM_MAX * WBM_MAX;
+    hipStream_t s = (hipStream_t)stream;
+    p.v = (const float*)workspace; p.u = (const float*)u; p.scale = scale; p.shift = shift; p.y = (float*)y;
+    p.u_bytes = (unsigned)((long long)cout * cin * 64);
+    p.Cin = cin; p.Cout = cout; p.relu = relu;
+    p.tiles_n = (cout + wbn - 1) / wbn;
+    for (int t0 = 0; t0 < tiles; t0 += per) {
+        const int nt = tiles - t0 < per ? tiles - t0 : per;
+        const long long th = (long long)nt * (cin >> 2);
+        hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, (const float*)x, (float*)workspace,
+                           p.sg, t0, nt, cin, (const double*)gn_stats, gamma, beta, groups, relu_in);
+        BRCNN_LAUNCH_CHECK();
+        p.tile0 = t0; p.nt = nt;
+        p.v_bytes = (unsigned)((long long)16 * nt * cin * 4);
+        p.tiles_m = (nt + wbm - 1) / wbm;
+        const dim3 grid(p.tiles_m * p.tiles_n);
+        if (variant == 2) hipLaunchKernelGGL((wino_gemm_kernel<32, 128, 4>), grid, dim3(256), 0, s, p);
+        else if (variant == 3) hipLaunchKernelGGL((wino_gemm_kernel<64, 64, 2>), grid, dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((wino_gemm_kernel<64, 128, 2>), grid, dim3(256), 0, s, p);
+        BRCNN_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+}  // namespace
+
 BRCNN_API int brcnn_conv3x3_winograd_f32_multi(const void* x, const void* u, const void* gn_stats, const float* gamma,
                                                const float* beta, int groups, int relu_in, const float* scale,
                                                const float* shift, int relu, void* y, void* workspace, size_t workspace_bytes,
@@ -382,31 +440,33 @@ BRCNN_API int brcnn_conv3x3_winograd_f32_multi(const void* x, const void* u, con
     if (gn_stats && (!gamma || !beta || groups <= 0 || cin % groups)) return BRCNN_EINVAL;
     WinoGemmParams p = {};
     if (wino_segs(p.sg, batch, num_segments, heights_host, widths_host)) return BRCNN_EINVAL;
-    const int tiles = p.sg.t0[num_segments];
-    if ((long long)p.sg.r0[num_segments] * (cin > cout ? cin : cout) * 4 >= 0x7fffffffLL) return BRCNN_EINVAL;
-    if (workspace_bytes < (size_t)16 * tiles * cin * sizeof(float)) return BRCNN_EINVAL;
-    // chunks of whole workgroup row blocks; more of them where the V planes of one would pass the 2 GiB of a buffer descriptor
-    int chunks = brcnn::g_policy.f32_winograd_chunks;
-    while ((long long)16 * ((tiles + chunks - 1) / chunks + WBM) * cin * 4 >= 0x7fffffffLL) chunks *= 2;
-    const int per = ((tiles + chunks - 1) / chunks + WBM - 1) / WBM * WBM;
-    hipStream_t s = (hipStream_t)stream;
-    p.v = (const float*)workspace; p.u = (const float*)u; p.scale = scale; p.shift = shift; p.y = (float*)y;
-    p.u_bytes = (unsigned)((long long)cout * cin * 64);
-    p.Cin = cin; p.Cout = cout; p.relu = relu;
-    p.tiles_n = (cout + WBN - 1) / WBN;
-    for (int t0 = 0; t0 < tiles; t0 += per) {
-        const int nt = tiles - t0 < per ? tiles - t0 : per;
-        const long long th = (long long)nt * (cin >> 2);
-        hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)((th + 255) / 256)), dim3(256), 0, s, (const float*)x, (float*)workspace,
-                           p.sg, t0, nt, cin, (const double*)gn_stats, gamma, beta, groups, relu_in);
-        BRCNN_LAUNCH_CHECK();
-        p.tile0 = t0; p.nt = nt;
-        p.v_bytes = (unsigned)((long long)16 * nt * cin * 4);
-        p.tiles_m = (nt + WBM - 1) / WBM;
-        hipLaunchKernelGGL(wino_gemm_kernel, dim3(p.tiles_m * p.tiles_n), dim3(256), 0, s, p);
-        BRCNN_LAUNCH_CHECK();
-    }
+    // the tower's launches stay on the 64 x 128 tile
+    const int st = wino_run(x, u, gn_stats, gamma, beta, groups, relu_in, scale, shift, relu, y, workspace, workspace_bytes, p,
+                            num_segments, cin, cout, 1, stream);
+    if (st) return st;
     brcnn::count(brcnn::g_counters.f32_winograd_launches);
-    brcnn::g_counters.f32_winograd_tiles = tiles;
+    brcnn::g_counters.f32_winograd_tiles = p.sg.t0[num_segments];
+    return 0;
+}
+
+// One frozen conv + folded-BN / bias (+ ReLU) layer, (batch, height, width, cin) -> (batch, height, width, cout), in the same
+// form: the single-layer route of blocks.conv_bn_act_nhwc.  The GEMM tile comes from brcnn::wino_gemm_variant (policy.hip:
+// the measured rule or the forcing hook (-14, 20 + v)).  Like the entry above it accepts every shape of the layer form and
+// never falls back: brcnn_winograd_layer_route says beforehand whether the policy sends a layer here.  Counted apart from the
+// tower's launches ((-14, 10): launches, (-14, 11): GEMM variant of the last one).
+BRCNN_API int brcnn_conv3x3_winograd_f32_layer(const void* x, const void* u, const float* scale, const float* shift, int relu,
+                                               void* y, void* workspace, size_t workspace_bytes, int batch, int height, int width,
+                                               int cin, int cout, int kh, int kw, int stride, int pad, int dtype, void* stream) {
+    if (!x || !u || !y || !workspace || dtype != BRCNN_DT_F32 || kh != 3 || kw != 3 || stride != 1 || pad != 1 || cin <= 0 ||
+        cout <= 0 || (cin % 32) || (cout % 64) || (long long)cout * cin * 64 >= 0x7fffffffLL)
+        return BRCNN_EINVAL;
+    WinoGemmParams p = {};
+    if (wino_segs(p.sg, batch, 1, &height, &width)) return BRCNN_EINVAL;
+    const int variant = brcnn::wino_gemm_variant(p.sg.t0[1], cout);
+    const int st = wino_run(x, u, nullptr, nullptr, nullptr, 0, 0, scale, shift, relu, y, workspace, workspace_bytes, p, 1, cin,
+                            cout, variant, stream);
+    if (st) return st;
+    brcnn::count(brcnn::g_counters.f32_winograd_layer_launches);
+    brcnn::g_counters.f32_winograd_layer_variant = variant;
     return 0;
 }

@@ -18,6 +18,10 @@ struct Policy {
     // ---- fp32 Winograd F(2x2,3x3) (conv_winograd_f32.hip): brcnn_conv_set_tile(-11, n); read by the CALLER that prepares filters
     int f32_winograd = 1;           // (-11, 0 / 1): never / where the caller prepared the transformed filter; (-11, 2) returns it
     int f32_winograd_chunks = 1;    // tuning hook ((-11, 10 + n), n = 1 .. 8): transform + GEMM launch pairs per call
+    // ... the single-layer route of the frozen backbone / neck 3x3 convs: brcnn_conv_set_tile(-14, n); read by
+    // brcnn_winograd_layer_route (f32_winograd = 0 switches it off as well) and by brcnn_conv3x3_winograd_f32_layer
+    int f32_winograd_layer = 1;     // (-14, 0 / 1 / 2): never / the measured rule (wino_layer_rule) / wherever the entry accepts the shape; (-14, 3) returns it
+    int f32_winograd_gemm = 0;      // tuning hook ((-14, 20 + v)): GEMM tile of the layer entry, 0 = the measured rule (wino_gemm_rule), 1 = 64 x 128, 2 = 32 x 128, 3 = 64 x 64; (-14, 24) returns it
 
     // ---- 16-bit deformable conv (deform_conv_bf16.hip): brcnn_conv_set_tile(-13, n); read by brcnn_deform_conv_route
     int dcn_fused = 1;              // (-13, 0 / 1 / 2): im2col + GEMM always / the measured rule / fused wherever the kernel accepts the shape
@@ -84,6 +88,9 @@ struct Counters {
     // brcnn_conv_set_tile(-12, 0 / 1): return and clear ((-9, -1) clears them too)
     int f32_winograd_launches = 0;      // (-12, 0): calls of brcnn_conv3x3_winograd_f32_multi that launched
     int f32_winograd_tiles = 0;         // (-12, 1): 2x2 output tiles of the last one
+    // brcnn_conv_set_tile(-14, 10 / 11): return and clear ((-9, -1) clears them too)
+    int f32_winograd_layer_launches = 0;    // (-14, 10): calls of brcnn_conv3x3_winograd_f32_layer that launched (the tower's are not in it)
+    int f32_winograd_layer_variant = 0;     // (-14, 11): GEMM tile of the last one (1 = 64 x 128, 2 = 32 x 128, 3 = 64 x 64)
     // brcnn_conv_set_tile(-13, 10 / 11): return and clear ((-9, -1) clears them too)
     int dcn_fused_launches = 0;         // (-13, 10): launches of the fused deformable conv (deform_conv_bf16.hip), every entry
     int dcn_im2col_launches = 0;        // (-13, 11): launches of the deformable im2col kernels (deform.hip), every entry
@@ -95,5 +102,12 @@ struct Counters {
 };
 extern Counters g_counters;
 inline void count(int& c) { c = (c + 1) & 0x7fffffff; }     // (a long run must not overflow a signed int)
+
+// The measured rules of the Winograd single-layer route (policy.hip; host only, no launch): does a frozen 3x3 stride-1 layer
+// of `tiles` 2x2 output tiles gain from the Winograd form (1) or stay on the direct kernels (0); and the GEMM tile of such a
+// launch (1 / 2 / 3, or the forced one)
+int wino_layer_rule(int tiles, int cin, int cout);
+int wino_gemm_rule(int tiles, int cout);
+int wino_gemm_variant(int tiles, int cout);
 
 }  // namespace brcnn

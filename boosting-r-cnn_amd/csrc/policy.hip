@@ -29,6 +29,7 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
             for (int* q : c) *q = 0;
             g_counters.f32_winograd_launches = g_counters.f32_winograd_tiles = 0;
             g_counters.dcn_fused_launches = g_counters.dcn_im2col_launches = 0;
+            g_counters.f32_winograd_layer_launches = g_counters.f32_winograd_layer_variant = 0;
             return 0;
         }
         const int n = *c[nt];
@@ -63,12 +64,71 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
         c = 0;
         return n;
     }
+    // Winograd single-layer route (brcnn_winograd_layer_route): (-14, 0 / 1 / 2) never / by the measured rule / wherever the
+    // entry accepts the shape, (-14, 3) RETURNS the setting; (-14, 10 / 11) return and clear the launches of the layer entry /
+    // the GEMM tile of the last one; (-14, 20 + v): GEMM tile by the rule (v = 0) or forced (1 = 64 x 128, 2 = 32 x 128,
+    // 3 = 64 x 64), (-14, 24) RETURNS that setting
+    if (wm == -14) {
+        if (nt >= 0 && nt <= 2) { g_policy.f32_winograd_layer = nt; return 0; }
+        if (nt == 3) return g_policy.f32_winograd_layer;
+        if (nt >= 20 && nt <= 23) { g_policy.f32_winograd_gemm = nt - 20; return 0; }
+        if (nt == 24) return g_policy.f32_winograd_gemm;
+        if (nt != 10 && nt != 11) return BRCNN_EINVAL;
+        int& c = nt == 10 ? g_counters.f32_winograd_layer_launches : g_counters.f32_winograd_layer_variant;
+        const int n = c;
+        c = 0;
+        return n;
+    }
     if (wm == -2) { if (nt != 0 && nt != 1 && nt != 2 && nt != 128 && nt != 256) return BRCNN_EINVAL; g_policy.pp_f32_mode = nt; return 0; }
     if ((wm != 0 && wm != 1 && wm != 2 && wm != 4) || nt < 0 || nt > 2) return BRCNN_EINVAL;
     g_policy.force_wm = wm;
     g_policy.force_nt = nt;
     return 0;
 }
+
+// ---- the Winograd single-layer route: the measured rules (profiles/f32_winograd_layers.txt: MI355X, the production launch
+// of each layer against the Winograd entry per GEMM tile, batch 8 and batch 1 of the flagship pass's maps and probes
+// between them; a point wins where the gain exceeds the spread of the direct rounds)
+int brcnn::wino_gemm_rule(int tiles, int cout) {
+    // 64 x 64 was the fastest tile on every row of the table, from 616 to 33 600 tiles and 128 to 512 channels (the 32 x 32
+    // wave tiles run four waves per SIMD where 64 x 128 runs two; at 8 400 tiles 243 us against 299 us)
+    (void)tiles; (void)cout;
+    return 3;
+}
+
+int brcnn::wino_layer_rule(int tiles, int cin, int cout) {
+    // per channel class the threshold lies midway between the nearest losing (or not proven) and the nearest winning
+    // measured tile count; classes that were not measured stay on the direct kernels
+    if (cin != cout) return 0;
+    // 128 -> 128 (stage-2 conv2) is NOT wired although it wins from about 3 200 tiles on (2 184: -14 us of 49; 4 200: +4 us of
+    // 69; 33 600: +62 us of 326, three launches per pass): with it the flagship pass's detections keep their values to
+    // round-off, but two of them whose scores are 4e-7 apart change places in the result list (profiles/r09_notes.md), and
+    // the pass has to return what it returned before
+    if (cin == 256) return tiles >= 5250;       // 4 200: +12 us of 177 inside the spread (18); 6 300: +107 us of 281, 8 400: +65 us of 308
+    if (cin == 512) return tiles >= 444;        // 273: -62 us of 112; 616: +3 us of 180 (spread 3), 2 184: +45 us of 344
+    return 0;
+}
+
+int brcnn::wino_gemm_variant(int tiles, int cout) {
+    return g_policy.f32_winograd_gemm ? g_policy.f32_winograd_gemm : wino_gemm_rule(tiles, cout);
+}
+
+// 1: the frozen fp32 conv layer of this form and size runs brcnn_conv3x3_winograd_f32_layer, 0: the launches it ran before.
+// Host only, launches nothing.  0 for anything but 3x3, stride 1, pad 1, dilation 1, groups 1, Cin % 32 == 0, Cout % 64 == 0,
+// fp32; 0 while the library's Winograd switch ((-11, 0)) or the route ((-14, 0)) is off; (-14, 2): 1 for every such layer;
+// (-14, 1), the default: brcnn::wino_layer_rule.
+BRCNN_API int brcnn_winograd_layer_route(int tiles, int cin, int cout, int kh, int kw, int stride, int pad, int dilation,
+                                         int groups, int dtype) {
+    if (tiles <= 0 || cin <= 0 || cout <= 0 || kh != 3 || kw != 3 || stride != 1 || pad != 1 || dilation != 1 || groups != 1 ||
+        (cin % 32) || (cout % 64) || dtype != BRCNN_DT_F32 || (long long)cout * cin * 64 >= 0x7fffffffLL)
+        return 0;
+    if (!g_policy.f32_winograd || !g_policy.f32_winograd_layer) return 0;
+    if (g_policy.f32_winograd_layer == 2) return 1;
+    return brcnn::wino_layer_rule(tiles, cin, cout);
+}
+
+// the GEMM tile brcnn_conv3x3_winograd_f32_layer would launch for (tiles, cout): 1 / 2 / 3 (tools, tests)
+BRCNN_API int brcnn_winograd_layer_gemm_variant(int tiles, int cout) { return brcnn::wino_gemm_variant(tiles, cout); }
 
 BRCNN_API int brcnn_conv_set_tile_bf16(int mtnt) {
     if (mtnt == -1 || mtnt == -2) { g_policy.bf16_il = (mtnt == -1); return 0; }

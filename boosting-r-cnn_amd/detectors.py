@@ -218,7 +218,23 @@ class TwoStageDetector(BaseDetector):
         self._rpn_scale_cache = [float(m.scale.detach().cpu()) for m in self.rpn_head.scales]
         if hasattr(self.rpn_head, 'prepare_winograd'):
             self.rpn_head.prepare_winograd()
+        self.prepare_winograd_layers()
         return self
+
+    def prepare_winograd_layers(self):
+        """the frozen 3x3 stride-1 conv + BatchNorm / bias layers of the backbone and the neck (a Bottleneck's conv2, the
+        neck's plain ConvModules) may take the Winograd single-layer route (blocks.prepare_winograd_layer; the policy
+        table decides per layer size, ops.winograd_layer_route).  Returns the number of layers prepared."""
+        from .backbones import Bottleneck
+        from .blocks import ConvModule, prepare_winograd_layer
+        n = 0
+        for part in (self.backbone, self.neck if self.with_neck else None):
+            for m in (part.modules() if part is not None else ()):
+                if isinstance(m, Bottleneck) and not m.with_dcn:
+                    n += prepare_winograd_layer(m.conv2, m._c[1])
+                elif isinstance(m, ConvModule) and (m.norm is None or isinstance(m.norm, nn.BatchNorm2d)):
+                    n += prepare_winograd_layer(m.conv, m._cache)
+        return n
 
     # ---- features ----------------------------------------------------------------------
     def extract_feat_nhwc(self, img):

@@ -747,6 +747,44 @@ def conv3x3_winograd_multi(x_cat, u, batch, sizes, gn=None, scale=None, shift=No
     return y
 
 
+def winograd_layer_route(x, conv):
+    """whether the policy table sends this frozen conv layer on the (N,H,W,Cin) operand `x` to conv3x3_winograd_layer
+    (brcnn_winograd_layer_route: host arithmetic, no launch; brcnn_conv_set_tile(-14, n)).  The caller holds the layer's
+    transformed filter (blocks.prepare_winograd_layer) and checks for a residual / gradient alias itself."""
+    if conv.kernel_size != (3, 3) or x.dtype != torch.float32 or not x.is_cuda:
+        return False
+    n, h, w, _ = x.shape
+    return _L.load().brcnn_winograd_layer_route(
+        n * ((h + 1) // 2) * ((w + 1) // 2), conv.in_channels, conv.out_channels, 3, 3, conv.stride[0] if
+        conv.stride[0] == conv.stride[1] else 0, conv.padding[0] if conv.padding[0] == conv.padding[1] else -1,
+        conv.dilation[0] if conv.dilation[0] == conv.dilation[1] else 0, conv.groups, _dt(x)) == 1
+
+
+def winograd_layer_channels_ok(conv):
+    """whether the policy table sends a layer of these channels to the Winograd form at SOME size (the largest the entry
+    takes is asked): freeze_for_inference builds the transformed filters of such layers ahead of the first pass"""
+    return _L.load().brcnn_winograd_layer_route(1 << 24, conv.in_channels, conv.out_channels, 3, 3, 1, 1, 1, 1, DT_F32) == 1
+
+
+def conv3x3_winograd_layer(x, u, scale=None, shift=None, relu=False, kernel=3, stride=1, pad=1):
+    """y = act(conv3x3(x) * scale + shift) of one frozen fp32 layer in the Winograd F(2x2,3x3) form: x (N,H,W,Cin), `u` from
+    winograd_filter, y (N,H,W,Cout) -- in the caller's buffer under `output_into`.  The V workspace is the stream's
+    (winograd_workspace).  Anything but that layer form raises (there is no fall-back)."""
+    _require_gpu(x, u, scale, shift)
+    assert x.dim() == 4 and x.is_contiguous() and u.is_contiguous() and u.dim() == 3 and u.shape[0] == 16
+    n, h, w, cin = x.shape
+    _, cout, cin2 = u.shape
+    assert cin == cin2, f'conv3x3_winograd_layer: Cin mismatch {cin} vs {cin2}'
+    workspace = winograd_workspace(n, ((h, w),), cin, x.device)
+    y = _alloc_out((n, h, w, cout), torch.float32, x.device)
+    st = _L.load().brcnn_conv3x3_winograd_f32_layer(
+        _ptr(x), _ptr(u), _ptr(scale), _ptr(shift), int(bool(relu)), _ptr(y), _ptr(workspace),
+        workspace.numel() * workspace.element_size(), n, h, w, cin, cout, int(kernel), int(kernel), int(stride), int(pad),
+        _dt(x), _stream())
+    _L.check(st, 'brcnn_conv3x3_winograd_f32_layer')
+    return y
+
+
 def groupnorm_nhwc_multi_backward(dy, x_cat, stats, gamma, beta, groups, batch, sizes, relu):
     """(dx, dgamma, dbeta) of groupnorm_nhwc_multi; `stats` from its return_stats"""
     import ctypes

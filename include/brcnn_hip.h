@@ -355,7 +355,12 @@ int brcnn_conv_handover_status(void);
  * (-12, 1) the 2x2 tiles of the last one; (-9, -1) clears both as well.
  * (-13, 0 / 1 / 2): route of the 16-bit deformable convs (brcnn_deform_conv_route) im2col + GEMM always / the measured
  * rule / fused wherever accepted; (-13, 3) RETURNS the setting; (-13, 10) / (-13, 11) return and clear the launches of the
- * fused deformable kernel / of the deformable im2col kernels ((-9, -1) clears them too). */
+ * fused deformable kernel / of the deformable im2col kernels ((-9, -1) clears them too).
+ * (-14, 0 / 1 / 2): Winograd single-layer route of the frozen fp32 3x3 layers (brcnn_winograd_layer_route) never / the
+ * measured rule / wherever the entry accepts the shape; (-14, 3) RETURNS the setting; (-14, 10) / (-14, 11) return and clear
+ * the launches of brcnn_conv3x3_winograd_f32_layer / the GEMM tile of the last one (1 = 64 x 128, 2 = 32 x 128,
+ * 3 = 64 x 64; (-9, -1) clears them too); (-14, 20 + v): that entry's GEMM tile by the measured rule (v = 0) or forced
+ * (v = 1 .. 3), (-14, 24) RETURNS it.  (-11, 0) switches this route off as well.  Every tile gives the same bits. */
 int brcnn_conv_set_tile(int wm, int nt);
 
 /* Tuning hook of the bf16 kernel: 0 heuristic; 11 / 21 / 22 = 64x64 / 128x64 / 128x128 tile on
@@ -405,6 +410,23 @@ int brcnn_conv3x3_winograd_f32_multi(const void *x, const void *u, const void *g
                                      const float *shift, int relu, void *y, void *workspace, size_t workspace_bytes,
                                      int batch, int num_segments, const int *heights_host, const int *widths_host,
                                      int cin, int cout, int kh, int kw, int stride, int pad, int dtype, void *stream);
+
+/* The same form for ONE frozen conv + folded-BN / bias (+ ReLU) layer: x (batch, height, width, cin) -> y (batch, height,
+ * width, cout) = [relu](conv3x3(x) * scale + shift), u from brcnn_winograd_filter_f32, the workspace of
+ * ..._multi_workspace_bytes(batch, 1, &height, &width, cin).  The GEMM's workgroup tile (64 x 128, 32 x 128 or 64 x 64 tiles x
+ * channels; equal bits) follows the measured rule or the hook (-14, 20 + v).  Same refusals as the entry above, no fall-back.
+ *   brcnn_winograd_layer_route: host arithmetic only, launches nothing.  1 when the policy sends a layer of `tiles` =
+ *     batch * ceil(H/2) * ceil(W/2) output tiles and this form to brcnn_conv3x3_winograd_f32_layer, else 0: always 0 for
+ *     anything but 3x3, stride 1, pad 1, dilation 1, groups 1, cin % 32 == 0, cout % 64 == 0, BRCNN_DT_F32, and while
+ *     (-11, 0) or (-14, 0) is set; (-14, 2): 1 for every such layer; (-14, 1), the default: the rule measured on MI355X
+ *     (profiles/f32_winograd_layers.txt).  The caller must hold the transformed filter of the layer.
+ *   brcnn_winograd_layer_gemm_variant: the GEMM tile (1 / 2 / 3) the layer entry would launch for (tiles, cout). */
+int brcnn_conv3x3_winograd_f32_layer(const void *x, const void *u, const float *scale, const float *shift, int relu,
+                                     void *y, void *workspace, size_t workspace_bytes, int batch, int height, int width,
+                                     int cin, int cout, int kh, int kw, int stride, int pad, int dtype, void *stream);
+int brcnn_winograd_layer_route(int tiles, int cin, int cout, int kh, int kw, int stride, int pad, int dilation,
+                               int groups, int dtype);
+int brcnn_winograd_layer_gemm_variant(int tiles, int cout);
 
 /* Grouped convolution (ResNeXt bottleneck conv2, mmdet/models/backbones/resnext.py:10-84).
  * x (N,H,W,Cin) fp32; w_tiles (Cout,KH,KW,window) block-diagonal per 64-channel output tile
