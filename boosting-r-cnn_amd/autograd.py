@@ -1387,6 +1387,105 @@ def bn_eval_act_autograd(z, bn, res=None, relu=True):
     return BnEvalActFunction.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, res, relu)
 
 
+class BnTrainActFunction(Function):
+    """out = [relu](bn_train(z) [+ res]): training-mode BatchNorm over the rows of z (`brcnn_bn_train_stats`: batch
+    statistics, scale / shift, running statistics updated in place), the apply pass of the eval path
+    (`brcnn_bn_act_forward`), and `brcnn_bn_train_backward`.  Everything the backward needs goes through
+    save_for_backward; the node keeps no reference to its own output (no BnTail: a training BatchNorm's backward needs
+    sums over the whole gradient before the first dz can leave, so no consumer's data-gradient launch can run it)."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, running_mean, running_var, eps, momentum, res, relu):
+        _require_gpu(z, gamma, beta, running_mean, running_var, res)
+        z = z.contiguous()
+        c = z.shape[-1]
+        rows = z.numel() // c
+        if rows == 1:
+            raise ValueError(f'Expected more than 1 value per channel when training, got input size {tuple(z.shape)}')
+        for t in (running_mean, running_var):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == c, 'running statistics: fp32 (C,)'
+        dt = _dt(z)
+        g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
+        r = res.contiguous() if res is not None else None
+        assert r is None or (r.shape == z.shape and r.dtype == z.dtype)
+        lib = _L.load()
+        st4 = torch.empty((4, c), dtype=torch.float32, device=z.device)
+        mean, rstd, scale, shift = st4[0], st4[1], st4[2], st4[3]
+        nb = lib.brcnn_bn_train_workspace_bytes(rows, c, dt)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=z.device)
+        h = _stream()
+        st = lib.brcnn_bn_train_stats(_ptr(z), _ptr(g32), _ptr(b32), float(eps), float(momentum), _ptr(running_mean),
+                                      _ptr(running_var), _ptr(mean), _ptr(rstd), None, _ptr(scale), _ptr(shift), _ptr(ws), nb,
+                                      rows, c, dt, h)
+        _L.check(st, 'brcnn_bn_train_stats')
+        # the kernel wrote the buffers through raw pointers: the packed-operand caches of the eval / inference paths
+        # (blocks.PackedCache) key on their versions
+        torch.autograd.graph.increment_version(running_mean)
+        torch.autograd.graph.increment_version(running_var)
+        out = torch.empty_like(z)
+        st = lib.brcnn_bn_act_forward(_ptr(z), _ptr(scale), _ptr(shift), _ptr(r), _ptr(out), rows, c, int(relu), dt, h)
+        _L.check(st, 'brcnn_bn_act_forward')
+        ctx.save_for_backward(z, g32, mean, rstd, out if relu else None)
+        ctx.cfg = (bool(relu), res is not None, dt, rows, c, gamma.dtype, beta.dtype)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        z, g32, mean, rstd, out = ctx.saved_tensors
+        relu, has_res, dt, rows, c, gdt, bdt = ctx.cfg
+        dout = dout.to(z.dtype).contiguous()
+        dz = torch.empty_like(z)
+        dres = torch.empty_like(z) if has_res and ctx.needs_input_grad[7] else None
+        dgamma = torch.empty(c, dtype=torch.float32, device=z.device)
+        dbeta = torch.empty(c, dtype=torch.float32, device=z.device)
+        lib = _L.load()
+        nb = lib.brcnn_bn_train_workspace_bytes(rows, c, dt)
+        ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=z.device)
+        st = lib.brcnn_bn_train_backward(_ptr(dout), _ptr(out), _ptr(z), _ptr(g32), _ptr(mean), _ptr(rstd), _ptr(dz), _ptr(dres),
+                                         _ptr(dgamma), _ptr(dbeta), _ptr(ws), nb, rows, c, int(relu), dt, _stream())
+        _L.check(st, 'brcnn_bn_train_backward')
+        return dz, dgamma.to(gdt), dbeta.to(bdt), None, None, None, None, dres, None
+
+
+def bn_train_refuse(bn):
+    """the forms of a training-mode BatchNorm that are not on the HIP path, each with its own error"""
+    if not bn.track_running_stats:
+        raise NotImplementedError('training-mode BatchNorm with track_running_stats=False is not on the HIP path')
+    if not bn.affine:
+        raise NotImplementedError('training-mode BatchNorm with affine=False is not on the HIP path')
+    if sync_bn_across_ranks(bn):
+        raise NotImplementedError('SyncBN in training mode under a process group of more than one rank is not on the HIP '
+                                  'path: the batch statistics would be per-rank (use norm_eval=True, or type=\'BN\' for '
+                                  'per-rank statistics)')
+
+
+def sync_bn_across_ranks(bn):
+    """`bn` was configured as SyncBN (blocks.build_norm_layer remembers the type) and more than one rank is up"""
+    if getattr(bn, 'brcnn_norm_type', 'BN') != 'SyncBN':
+        return False
+    import torch.distributed as dist
+    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+
+
+def bn_train_act_autograd(z, bn, res=None, relu=True):
+    """z through the training-mode BatchNorm module `bn` (+ residual, + ReLU): batch statistics of z, the module's running
+    statistics and num_batches_tracked updated as torch.nn.BatchNorm2d.forward does -- also under no_grad"""
+    bn_train_refuse(bn)
+    if not (z.is_cuda and bn_act_supported(z)):
+        raise NotImplementedError(f'training-mode BatchNorm: {z.shape[-1]} channels of {z.dtype} on {z.device.type} are not '
+                                  f'on the HIP path (whole 16-byte vectors, a power of two of them, on the device)')
+    if z.numel() == z.shape[-1]:
+        raise ValueError(f'Expected more than 1 value per channel when training, got input size {tuple(z.shape)}')
+    momentum = bn.momentum
+    bn.num_batches_tracked.add_(1)
+    if momentum is None:            # cumulative moving average (the count comes to the host: one sync per layer and step)
+        momentum = 1.0 / float(bn.num_batches_tracked)
+    if res is not None:
+        res = res.reshape(z.shape).to(z.dtype)
+    return BnTrainActFunction.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, momentum, res, relu)
+
+
 def bn_act_supported(z):
     """channel-vector count a power of two (every BatchNorm width of the ResNet family)"""
     c = z.shape[-1]

@@ -60,6 +60,7 @@ class PackedCache:
         self.key = None
         self.val = None
         self.wino = None        # a PackedCache of the Winograd-transformed filter once prepare_winograd_layer accepted the layer
+        self.raw = None         # a PackedCache of the conv alone (no fold): the forward under a training-mode BatchNorm
 
     def get(self, sources, builder):
         key = tuple((s.data_ptr(), s._version, s.device) for s in sources if s is not None) + \
@@ -157,6 +158,8 @@ def build_norm_layer(cfg, num_features, postfix=''):
     cfg.setdefault('eps', 1e-5)
     if layer_type in ('BN', 'BN2d', 'SyncBN'):
         name, layer = 'bn', nn.BatchNorm2d(num_features, **cfg)
+        # (SyncBN in training mode needs cross-rank statistics: autograd.bn_train_refuse asks for the configured type)
+        layer.brcnn_norm_type = 'SyncBN' if layer_type == 'SyncBN' else 'BN'
     elif layer_type == 'GN':
         assert 'num_groups' in cfg
         name, layer = 'gn', nn.GroupNorm(num_channels=num_features, **cfg)
@@ -191,6 +194,8 @@ FUSE_CONV_BN_TRAIN = True
 
 def conv_bn_act_tail(y, bn, relu, residual):
     """eval-BN affine (+residual, +ReLU) behind a differentiable conv (fused kernel when it applies)"""
+    if bn is not None and bn.training:
+        return bn_train_act_tail(y, bn, relu, residual)
     if bn is not None:
         from .autograd import bn_act_supported, bn_eval_act_autograd
         if y.is_cuda and bn_act_supported(y) and (residual is None or residual.dtype == y.dtype):
@@ -203,14 +208,36 @@ def conv_bn_act_tail(y, bn, relu, residual):
     return y.relu() if relu else y
 
 
+def _raw_cache(cache):
+    if getattr(cache, 'raw', None) is None:
+        cache.raw = PackedCache()
+    return cache.raw
+
+
+def bn_train_act_tail(y, bn, relu, residual):
+    """training-mode BatchNorm (+residual, +ReLU) over a raw conv output: batch statistics on the device, running
+    statistics and num_batches_tracked updated; differentiable, and the same launches without the graph under no_grad"""
+    from .autograd import bn_train_act_autograd
+    return bn_train_act_autograd(y, bn, residual, relu)
+
+
 def conv_bn_act_nhwc(x, conv, bn, cache, relu, residual=None, with_skip=False, sole_consumer=False,
                      single_use_output=False):
     """act(bn(conv(x)) + residual).  Inference / frozen layers: everything folded into one
     kernel launch.  Trainable layers under grad mode: the differentiable conv kernel followed
-    by the (cheap, element-wise) eval-BN affine / add / ReLU as torch ops."""
+    by the (cheap, element-wise) eval-BN affine / add / ReLU as torch ops.  A BatchNorm in training mode
+    (norm_eval=False): the raw conv, then batch statistics + affine / add / ReLU on the device (bn_train_act_tail)."""
     if bn is not None and bn.training:
-        raise NotImplementedError('training-mode BatchNorm is not on the HIP path '
-                                  '(the reference runs BN in eval mode: norm_eval=True)')
+        # norm_eval=False: the raw conv (the differentiable kernel, or the plain one when nothing wants a gradient -- the
+        # dispatch below with bn=None), then the training BatchNorm tail over its stored output.  No BnTail leaves here
+        # and none is consumed: `sole_consumer` / `single_use_output` are promises about eval-mode producers, and a
+        # producer whose tail nobody runs does its own BatchNorm backward (ConvBnEvalActFunction.backward).
+        # (the raw conv's operands live beside the fold: going between train() and eval() rebuilds neither, and the fold is
+        # rebuilt when -- and only when -- the running statistics changed version)
+        y = conv_bn_act_nhwc(x, conv, None, _raw_cache(cache), False, None, with_skip)
+        y, skip = y if with_skip else (y, None)
+        out = bn_train_act_tail(y, bn, relu, residual)
+        return (out, skip) if with_skip else out
     from .autograd import conv2d_nhwc_autograd, wants_grad
     if conv.groups > 1:
         out = _grouped_conv_bn_act_nhwc(x, conv, bn, cache, relu, residual)
@@ -301,6 +328,8 @@ def folded_conv_operands(conv, bn, cache, dtype):
 def _grouped_conv_bn_act_nhwc(x, conv, bn, cache, relu, residual):
     """grouped conv (ResNeXt conv2) + folded eval-BN + ReLU in one launch; inference / frozen only"""
     from .autograd import bn_act_autograd, bn_act_supported, grouped_conv_autograd, wants_grad
+    if bn is not None and bn.training:
+        return bn_train_act_tail(_grouped_conv_bn_act_nhwc(x, conv, None, _raw_cache(cache), False, None), bn, relu, residual)
     cg_in, cg_out = conv.in_channels // conv.groups, conv.out_channels // conv.groups
     if x.dtype != torch.float32 and ((64 // cg_out) * cg_in) % 64:
         # bf16 tiles need a 64-channel input window per 64-channel output tile; other group shapes

@@ -175,7 +175,15 @@ class GraphedTrunk:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and not _A._OWN_REDUCER[0]:
             return False            # (possibly) DistributedDataParallel: its reducer wants every gradient through its hooks
+        if self._bn_training():
+            # a training-mode BatchNorm updates its running statistics and num_batches_tracked once per forward: the warm-up
+            # passes of a capture would count as steps, and momentum=None needs the count on the host.  Eager launches.
+            return False
         return any(p.requires_grad for p in self._params())
+
+    def _bn_training(self):
+        return any(s.training and isinstance(s, torch.nn.modules.batchnorm._BatchNorm)
+                   for m in self._modules() for s in m.modules())
 
     # ---- capture ---------------------------------------------------------------------------------
     def _capture(self, img, key):

@@ -119,6 +119,9 @@ SIGNATURES = {
                                                                                    c_int, c_ptr, c_int]),
     'brcnn_bn_reduce_flush': (c_int, [c_ptr]),
     'brcnn_bn_reduce_pending': (c_int, []),
+    'brcnn_bn_train_workspace_bytes': (c_size, [c_i64, c_int, c_int]),
+    'brcnn_bn_train_stats': (c_int, [c_ptr] * 3 + [c_f32, c_f32] + [c_ptr] * 8 + [c_size, c_i64, c_int, c_int, c_ptr]),
+    'brcnn_bn_train_backward': (c_int, [c_ptr] * 11 + [c_size, c_i64, c_int, c_int, c_int, c_ptr]),
     'brcnn_conv2d_nhwc_grouped': (c_int, [c_ptr] * 6 + [c_int] * 12 + [c_ptr]),
     'brcnn_avgpool_nhwc': (c_int, [c_ptr, c_ptr] + [c_int] * 9 + [c_ptr]),
     'brcnn_deform_im2col_nhwc': (c_int, [c_ptr] * 3 + [c_int] * 11 + [c_ptr]),

@@ -643,6 +643,32 @@ int brcnn_conv2d_dgrad_bn_backward_nhwc_ex(const void *dy, const void *w_t, cons
 int brcnn_bn_reduce_flush(void *stream);
 int brcnn_bn_reduce_pending(void);
 
+/* Training-mode BatchNorm (norm_eval=False: F.batch_norm(training=True)) over (rows, C) NHWC rows in fp32 / bf16 /
+ * fp16; gamma, beta, the statistics and the running buffers are fp32 (C each).
+ *   brcnn_bn_train_stats: per channel mean and biased var over the rows of the STORED z (two stages: per-strip partial
+ *     sums as doubles in `workspace`, then one launch that adds them in a fixed order and finalizes); writes
+ *       save_mean, save_rstd = 1 / sqrt(var + eps)           (for the backward)
+ *       scale = gamma save_rstd, shift = beta - mean scale    (the apply pass is brcnn_bn_act_forward on these)
+ *       batch_var (may be NULL): the biased variance
+ *     and updates in place  running_mean <- (1 - momentum) running_mean + momentum mean,
+ *                           running_var  <- (1 - momentum) running_var  + momentum var rows / (rows - 1).
+ *   brcnn_bn_train_backward: dpre = dout * (out > 0) (relu; `out` = the saved forward output, ignored without relu),
+ *       dbeta = sum dpre,  dgamma = save_rstd sum dpre (z - save_mean)    (same two stages, same workspace size)
+ *       dz = gamma save_rstd (dpre - dbeta / rows - xh dgamma / rows),  xh = (z - save_mean) save_rstd
+ *       dres = dpre (optional: NULL without a residual)
+ * No atomics: results are bit-identical from run to run.  C % 4 == 0 (fp32) / C % 8 == 0 (16-bit) and C / vec a power of
+ * two (what brcnn_bn_act_backward takes below 256 vectors); rows >= 2 (one value per channel has no variance); rows * C * 16
+ * must fit int64.  Anything else: BRCNN_EINVAL, and the workspace query returns 0.  `workspace` 8-byte aligned. */
+size_t brcnn_bn_train_workspace_bytes(int64_t rows, int channels, int dtype);
+int brcnn_bn_train_stats(const void *z, const float *gamma, const float *beta, float eps, float momentum,
+                         float *running_mean, float *running_var, float *save_mean, float *save_rstd,
+                         float *batch_var, float *scale, float *shift, void *workspace, size_t workspace_bytes,
+                         int64_t rows, int channels, int dtype, void *stream);
+int brcnn_bn_train_backward(const void *dout, const void *out, const void *z, const float *gamma,
+                            const float *save_mean, const float *save_rstd, void *dz, void *dres, float *dgamma,
+                            float *dbeta, void *workspace, size_t workspace_bytes, int64_t rows, int channels,
+                            int relu, int dtype, void *stream);
+
 /* Res2Net / DCNv2 rows (the r2_101 recipes): NHWC average pooling with torch.nn.AvgPool2d's
  * window / divisor rules (res2net.py:52-54, 173-178), and mmcv's modulated deformable im2col
  * (ModulatedDeformConv2dPack, deform_groups 1): col (N*Ho*Wo, KH*KW*channels_padded) with K
