@@ -169,6 +169,11 @@ int sk_plan_pp_f32(ConvParams& p, int slots, int bm, int bn, hipStream_t s);
 // [sk_wgs x (first item, count, 0, 0) | items (tile, first K tile, end K tile, hand-over slot)]; p.sk_wgs = 0: take the
 // plain launch (stream capture, fewer than two tiles per CU, a one-K-tile layer)
 int sk_plan_f32_tile(ConvParams& p, int per_cu, int cus, hipStream_t s);
+// the same schedule for a kernel with its own parameter block (the Winograd GEMM, conv_winograd_f32.hip: tiles x nk = 16 xi
+// planes): `slots` workgroups, `slot_bytes` of hand-over each.  wgs = 0: take the plain launch (stream capture, stream-K
+// switched off, fewer tiles than slots, a hand-over area beyond the stream's workspace)
+struct SkRangePlan { int wgs; const int4* items; float* ws; unsigned* flags; unsigned epoch; unsigned* err; int spin_limit; };
+int sk_plan_ranges(SkRangePlan& k, long long tiles, int nk, int slots, size_t slot_bytes, hipStream_t s);
 float* conv_ws_wgrad_slabs(hipStream_t s);          // the weight-gradient slab part of the stream's conv workspace (160 MiB)
 // deferred second stage of the sliced weight gradients (wgrad_defer.hip): slabs from the stream's deferral arena (nullptr:
 // deferral off / request larger than the arena; *err < 0: the flush it had to launch first failed), and the item of a

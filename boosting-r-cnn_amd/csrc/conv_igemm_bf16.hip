@@ -1318,6 +1318,30 @@ int sk_plan_f32_tile(ConvParams& p, int per_cu, int cus, hipStream_t s) {
     return 0;
 }
 
+// persistent launch of the Winograd GEMM (conv_winograd_f32.hip): the same range table over tiles x `nk` units, `slots`
+// workgroups (the caller has settled the count: at most the resident ones) that hand over `slot_bytes` each
+int sk_plan_ranges(SkRangePlan& k, long long tiles, int nk, int slots, size_t slot_bytes, hipStream_t s) {
+    k = {};
+    if (int e = sk_take_error()) return e;          // a tail of an EARLIER launch gave up waiting for its head
+    if (brcnn::g_policy.sk_mode == 0 || slots <= 0 || slots > SK_MAX_SLOTS) return 0;
+    if (sk_capturing(s)) return 0;
+    // (tiles >= slots: a range never lies inside one tile -- no three-way split)
+    if (nk < 2 || tiles < slots || tiles * nk >= 0x7fffffffLL) return 0;
+    if ((size_t)slots * slot_bytes > SK_WS_BYTES) return 0;
+    std::lock_guard<std::mutex> lock(g_sk_mutex);
+    SkStream* st = nullptr;
+    int rc = sk_stream_state(s, &st);
+    if (rc) return rc;
+    const SkTable* tab = nullptr;
+    rc = sk_table_ranges(tiles, nk, slots, &tab);
+    if (rc) return rc == BRCNN_EINVAL ? 0 : rc;
+    ConvParams p = {};
+    sk_fill(p, *st, *tab);
+    k.wgs = p.sk_wgs; k.items = p.sk_items; k.ws = p.sk_ws; k.flags = p.sk_flags; k.epoch = p.sk_epoch; k.err = p.sk_err;
+    k.spin_limit = p.sk_spin_limit;
+    return 0;
+}
+
 // fp16 operands: the production tile shapes only (the tuning-hook variants stay bf16, except the two eight-phase kernels:
 // 8844 / 8842 force them under bf16's shape rules, so that the tests reach their fp16 instantiations at small shapes;
 // as for bf16, any forced tile code keeps the persistent 1x1 kernel out, so that a forced tile is the tile that runs)

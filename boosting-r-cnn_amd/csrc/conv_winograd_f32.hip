@@ -150,6 +150,16 @@ struct WinoGemmParams {
     int tile0, nt, Cin, Cout, relu;
     int tiles_m, tiles_n;
     WinoSegs sg;
+    // persistent launch (wino_gemm_kernel<.., true>; appended: the plain kernels read what they read before): the range table
+    // [sk_wgs x (first item, count, 0, 0) | items (workgroup tile, first xi, end xi, hand-over slot)] of sk_plan_ranges, the
+    // stream's hand-over slots (the four y accumulator sets of one workgroup tile each) and flags, the launch's epoch, the
+    // host-mapped error word and the poll bound of a tail that waits for its head
+    const int4* sk_items;
+    float* sk_ws;
+    unsigned* sk_flags;
+    unsigned sk_epoch;
+    unsigned* sk_err;
+    int sk_spin_limit;
 };
 
 // Workgroup tile variants (WBM tiles x WBN output channels, four waves as WMW x WNW, a wave owns 32 x 32 NB):
@@ -163,25 +173,33 @@ constexpr int WBM_MAX = 64;             // launch chunks are whole row blocks of
 // A^T = [1 1 1 0; 0 1 -1 -1]: coefficient of M[i][j] (xi = 4 i + j) in y[a][b] is AT[a][i] AT[b][j]
 __device__ __forceinline__ constexpr int wino_at(int a, int i) { return a == 0 ? (i < 3 ? 1 : 0) : (i == 0 ? 0 : (i == 1 ? 1 : -1)); }
 
+// One work item: xi planes [xb, xe) of workgroup tile `tile` (the 16 x Cin / 32 steps of a tile are cut on xi boundaries
+// only, so tmp is never handed over).  The plain launch runs one item per workgroup, all 16 planes of its tile (PERS = false:
+// xb = 0, xe = 16 fold away and the code is the one-tile kernel's).  The persistent launch (PERS = true, wino_gemm_kernel)
+// hands a workgroup a list of items: an item that stops short of xi = 16 stores its four y accumulator sets to
+// sk_ws[slot] and publishes sk_flags[slot] = sk_epoch instead of reading out; an item that starts past xi = 0 waits for
+// that flag (bounded poll, conv_igemm.hip's) and continues from those accumulators.  Every output sees its 16 products,
+// each the same MFMA chain over Cin, folded into y in the order xi = 0 .. 15 either way: the two forms give the same bits.
+// RING: stages of the LDS ring.  2 is the loop as it was: the DMA of step s + 1 is issued under the MFMAs of step s and drained
+// (vmcnt(0)) before the barrier that ends the step.  3 keeps TWO steps in flight: step s waits only until its own operands
+// have landed (counted vmcnt: the AG + BG loads of step s + 1 may still be out), takes the barrier, issues step s + 2 into
+// the stage that step s - 1 has just left, and runs the same fragment reads and MFMAs in the same order.
 // (the body exists in the device pass only: the host pass would instantiate the inline assembly, whose operand types depend on
 // the template's parameters, against the host's constraints and drop the launch stub)
-template <int WBM, int WBN, int WNW>
-__global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
+template <int WBM, int WBN, int WNW, bool PERS, int RING>
+__device__ __forceinline__ void wino_gemm_item(const WinoGemmParams& p, float* smem, const int tile, const int xb_, const int xe_,
+                                               const int slot) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int NB = WBN / (32 * WNW);        // 32-column blocks of a wave
-    static_assert(WBM % 32 == 0 && (WBM / 32) * WNW == 4 && NB * 32 * WNW == WBN && (NB == 1 || NB == 2), "four waves of 32 x 32 NB");
-    static_assert(2 * WBM * 32 + 2 * WBN * 32 >= 4 * 1024, "the read-out slabs live in the staging buffers");
-    __shared__ __attribute__((aligned(16))) float smem[2 * WBM * 32 + 2 * WBN * 32];      // 64 x 128: 48 KiB, two stages of A and B
+    const int xb = PERS ? xb_ : 0, xe = PERS ? xe_ : 16;
     float* As = smem;
-    float* Bs = smem + 2 * WBM * 32;
+    float* Bs = smem + RING * WBM * 32;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WNW, wn = wave % WNW;
     const int li = lane & 31, lh = lane >> 5;
 
-    // the Cout / WBN column tiles of one row block side by side on one XCD: V is fetched from HBM once
-    const int tile = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
     const int tile_m = tile / p.tiles_n, tile_n = tile - tile_m * p.tiles_n;
     const int m0 = tile_m * WBM, n0 = tile_n * WBN;
 
@@ -206,7 +224,7 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
     }
     const int nk = p.Cin / 32;
     const int a_xi = p.nt * p.Cin * 4, b_xi = p.Cout * p.Cin * 4;      // bytes between two xi planes (< 2^31 / 16: the host checks)
-    int s_xi = 0, s_kc = 0;             // (xi, K chunk) of the step staged next
+    int s_xi = xb, s_kc = 0;            // (xi, K chunk) of the step staged next
     auto dma_step = [&](int buf) {
         const int ao = s_xi * a_xi + s_kc * 128, bo = s_xi * b_xi + s_kc * 128;
         if (++s_kc == nk) { s_kc = 0; s_xi++; }
@@ -252,19 +270,85 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
             for (int r = 0; r < 16; r++) yacc[q][b][r] = 0.f;
 
     dma_step(0);
+    if constexpr (RING == 3) {
+        if ((xe - xb) * nk > 1) dma_step(1);
+    }
+    if constexpr (PERS) {
+        if (xb > 0) {
+            // the planes below xb of this tile, published by the workgroup of the range below as its FIRST item: one lane
+            // polls (bounded), one agent-scope acquire, then plain loads into the accumulators in their register layout
+            // (the DMA above stays in flight under them)
+            if (tid == 0) {
+                int spins = 0;
+                while (__hip_atomic_load(p.sk_flags + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != p.sk_epoch &&
+                       ++spins < p.sk_spin_limit)
+                    __builtin_amdgcn_s_sleep(4);
+                // a hand-over that never arrives must not end as a silent wrong result: the host-mapped error word
+                // makes the next launch on any stream (and brcnn_conv_handover_status) return BRCNN_EHANDOVER
+                if (spins >= p.sk_spin_limit)
+                    __hip_atomic_store(p.sk_err, p.sk_epoch | 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            }
+            __syncthreads();
+            const f32x4* src = reinterpret_cast<const f32x4*>(p.sk_ws) + (size_t)slot * (WBM * WBN) + wave * 64 + lane;
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int b = 0; b < NB; b++)
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        const f32x4 v = src[((q * NB + b) * 4 + g) * 256];
+                        yacc[q][b][4 * g + 0] = v.x; yacc[q][b][4 * g + 1] = v.y;
+                        yacc[q][b][4 * g + 2] = v.z; yacc[q][b][4 * g + 3] = v.w;
+                    }
+            // the compiler's own wait for these loads belongs HERE, in front of the drain below, not in front of their first
+            // use at the end of the first plane, where it would drain the ring once per plane
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int b = 0; b < NB; b++) asm volatile("" : "+v"(yacc[q][b]));
+        }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int cur = 0;
-    for (int xi = 0; xi < 16; xi++) {
+    [[maybe_unused]] int left = (xe - xb) * nk;     // RING 3: steps from the current one to the end of the item
+    for (int xi = xb; xi < xe; xi++) {
 #pragma unroll
         for (int b = 0; b < NB; b++)
 #pragma unroll
             for (int r = 0; r < 16; r++) tmp[b][r] = 0.f;
+        if constexpr (RING == 3) {
+            for (int kc = 0; kc < nk; kc++, left--) {
+                // this step's operands have landed (the loads of the step after it may still be out), and every wave is past
+                // its reads of the step before: its stage takes step s + 2
+                if (left > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AG + BG) : "memory");
+                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
+                const unsigned a_cur = a_lane + cur * (WBM * 32 * 4);
+                const unsigned b_cur = b_lane + cur * (WBN * 32 * 4);
+                frag_read(0, a_cur + chb[0], b_cur + chb[0]);
+                if (left > 2) dma_step(cur == 0 ? 2 : cur - 1);     // (cur + 2) % 3, under the latency of the first fragment read
+                frag_wait(0);
+#pragma unroll
+                for (int kk = 0; kk < 4; kk++) {
+                    const int sl = kk & 1;
+                    if (kk + 1 < 4) frag_read(sl ^ 1, a_cur + chb[kk + 1], b_cur + chb[kk + 1]);
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+#pragma unroll
+                        for (int b = 0; b < NB; b++)
+                            tmp[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[sl][e], bv[sl][b][e], tmp[b], 0, 0, 0);
+                    if (kk + 1 < 4) frag_wait(sl ^ 1);
+                }
+                cur = cur == 2 ? 0 : cur + 1;
+            }
+        } else
         for (int kc = 0; kc < nk; kc++) {
             const unsigned a_cur = a_lane + cur * (WBM * 32 * 4);
             const unsigned b_cur = b_lane + cur * (WBN * 32 * 4);
             frag_read(0, a_cur + chb[0], b_cur + chb[0]);
-            if (xi < 15 || kc + 1 < nk) dma_step(cur ^ 1);      // issued under the latency of the first fragment read
+            if (xi < xe - 1 || kc + 1 < nk) dma_step(cur ^ 1);  // issued under the latency of the first fragment read
             frag_wait(0);
 #pragma unroll
             for (int kk = 0; kk < 4; kk++) {
@@ -295,6 +379,35 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
 #pragma unroll
                     for (int r = 0; r < 16; r++) yacc[a * 2 + bq][b][r] = __builtin_fmaf(c, tmp[b][r], yacc[a * 2 + bq][b][r]);
             }
+    }
+
+    // RING 3: the last step took its barrier BEFORE its reads; the read-out slabs (and the next item's first stages) lie in
+    // stages that another wave may still be reading
+    if constexpr (RING == 3) __syncthreads();
+    if constexpr (PERS) {
+        if (xe < 16) {
+            // head of a tile: the four accumulator sets in their register layout (16-byte stores), then the flag
+            f32x4* dst = reinterpret_cast<f32x4*>(p.sk_ws) + (size_t)slot * (WBM * WBN) + wave * 64 + lane;
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+#pragma unroll
+                for (int b = 0; b < NB; b++)
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        f32x4 v;
+                        v.x = yacc[q][b][4 * g + 0]; v.y = yacc[q][b][4 * g + 1];
+                        v.z = yacc[q][b][4 * g + 2]; v.w = yacc[q][b][4 * g + 3];
+                        dst[((q * NB + b) * 4 + g) * 256] = v;
+                    }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __hip_atomic_store(p.sk_flags + slot, p.sk_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            return;
+        }
     }
 
     // ---- read-out.  Accumulator layout: column = lane & 31 = channel, rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5) = tiles; a
@@ -349,6 +462,37 @@ __global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
 #endif
 }
 
+// PERS = false: one workgroup per workgroup tile.  PERS = true: the persistent launch of at most the resident workgroups;
+// workgroup b owns one contiguous range of the launch's (workgroup tile x xi plane) iteration space, cut into the items
+// sk_items[first .. first + count), (first, count) = sk_items[b] (sk_table_ranges, conv_igemm_bf16.hip: the ranges follow
+// xcd_remap like the plain launch's tiles, so the column tiles of a row block stay on one XCD): the head of the tile the
+// range ends in (published at once: nobody waits long for it), its whole tiles, and last the tail of the tile it starts in.
+template <int WBM, int WBN, int WNW, bool PERS = false, int RING = 2>
+__global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(WBM % 32 == 0 && (WBM / 32) * WNW == 4 && (WBN == 32 * WNW || WBN == 64 * WNW), "four waves of 32 x 32 NB");
+    static_assert(RING == 2 || RING == 3, "two or three LDS stages");
+    static_assert(RING * (WBM * 32 + WBN * 32) >= 4 * 1024, "the read-out slabs live in the staging buffers");
+    __shared__ __attribute__((aligned(16))) float smem[RING * (WBM * 32 + WBN * 32)];     // 64 x 128: 48 KiB with two stages of A and B
+    if constexpr (PERS) {
+        const int4 range = p.sk_items[blockIdx.x];      // wave-uniform: scalar loads
+        const int first = __builtin_amdgcn_readfirstlane(range.x), count = __builtin_amdgcn_readfirstlane(range.y);
+        for (int i = 0; i < count; i++) {
+            // the read-out slabs and the last step of the item before live in the staging buffers: every wave is past
+            // them before the next item's first DMA lands
+            if (i > 0) __syncthreads();
+            const int4 item = p.sk_items[first + i];
+            wino_gemm_item<WBM, WBN, WNW, true, RING>(p, smem, __builtin_amdgcn_readfirstlane(item.x),
+                                                __builtin_amdgcn_readfirstlane(item.y), __builtin_amdgcn_readfirstlane(item.z),
+                                                __builtin_amdgcn_readfirstlane(item.w));
+        }
+    } else {
+        // the Cout / WBN column tiles of one row block side by side on one XCD: V is fetched from HBM once
+        wino_gemm_item<WBM, WBN, WNW, false, RING>(p, smem, xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n), 0, 16, 0);
+    }
+#endif
+}
+
 // host side: the tile table of a segment list; 0 or BRCNN_EINVAL
 int wino_segs(WinoSegs& sg, int batch, int num_segments, const int* heights_host, const int* widths_host) {
     if (batch <= 0 || num_segments <= 0 || num_segments > BRCNN_MAX_LEVELS || !heights_host || !widths_host) return BRCNN_EINVAL;
@@ -391,6 +535,70 @@ BRCNN_API int brcnn_winograd_filter_f32(const void* w, void* u, int cout, int ci
 
 namespace {
 
+// The persistent form of one GEMM launch, or wgs = 0: the plain launch.  The grid is at most the resident workgroups of the
+// persistent kernel (occupancy query x CUs, queried once per tile), fewer per CU where the launch has fewer workgroup tiles
+// than that (floor(tiles / CUs), one at least: every range then still holds a whole tile's worth of planes), under the
+// hooks' caps; policy (-16, 1) asks the measured rule, (-16, 2) takes whatever the schedule allows.  Stream capture, fewer
+// workgroup tiles than workgroups and a hand-over area beyond the stream's workspace all give the plain launch
+// (sk_plan_ranges).  0, or the error of an earlier launch's lost hand-over
+int g_wino_cus = 0;
+template <int WBM, int WBN, int WNW, int RING>
+int wino_occupancy(int& occ) {
+    static int cached = -1;
+    if (cached < 0) {
+        int n = 0;
+        BRCNN_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)wino_gemm_kernel<WBM, WBN, WNW, true, RING>, 256, 0));
+        if (g_wino_cus == 0) {
+            int dev = 0;
+            hipDeviceProp_t prop;
+            BRCNN_HIP_CHECK(hipGetDevice(&dev));
+            BRCNN_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+            g_wino_cus = prop.multiProcessorCount;
+        }
+        cached = n;
+    }
+    occ = cached;
+    return 0;
+}
+
+template <int RING>
+int wino_occupancy_of(int variant, int& occ) {
+    return variant == 2 ? wino_occupancy<32, 128, 4, RING>(occ) : variant == 3 ? wino_occupancy<64, 64, 2, RING>(occ)
+                                                                               : wino_occupancy<64, 128, 2, RING>(occ);
+}
+
+int wino_plan(WinoGemmParams& p, int variant, int ring, hipStream_t s, int& wgs) {
+    wgs = 0;
+    const int mode = brcnn::g_policy.f32_winograd_sk;
+    if (mode == 0) return 0;
+    int occ = 0;
+    if (const int rc = ring == 3 ? wino_occupancy_of<3>(variant, occ) : wino_occupancy_of<2>(variant, occ)) return rc;
+    const int cus = g_wino_cus;
+    const long long tiles = (long long)p.tiles_m * p.tiles_n;
+    int per_cu = occ;
+    if (brcnn::g_policy.f32_winograd_sk_per_cu > 0 && brcnn::g_policy.f32_winograd_sk_per_cu < per_cu) per_cu = brcnn::g_policy.f32_winograd_sk_per_cu;
+    if (per_cu <= 0 || cus <= 0) return 0;
+    if (tiles < (long long)per_cu * cus) per_cu = tiles / cus > 1 ? (int)(tiles / cus) : 1;
+    if (mode == 1 && !brcnn::wino_persistent_rule(tiles > 0x7fffffffLL ? 0x7fffffff : (int)tiles, 16, cus, per_cu)) return 0;
+    long long slots = (long long)per_cu * cus;
+    if (brcnn::g_policy.f32_winograd_sk_wgs > 0 && brcnn::g_policy.f32_winograd_sk_wgs < slots) slots = brcnn::g_policy.f32_winograd_sk_wgs;
+    const int wbm = variant == 2 ? 32 : 64, wbn = variant == 3 ? 64 : 128;
+    SkRangePlan k;
+    if (const int rc = sk_plan_ranges(k, tiles, 16, (int)slots, (size_t)4 * wbm * wbn * sizeof(float), s)) return rc;
+    if (k.wgs <= 0) return 0;
+    p.sk_items = k.items; p.sk_ws = k.ws; p.sk_flags = k.flags; p.sk_epoch = k.epoch; p.sk_err = k.err;
+    p.sk_spin_limit = k.spin_limit;
+    wgs = k.wgs;
+    return 0;
+}
+
+template <bool PERS, int RING>
+void wino_launch(int variant, const dim3& grid, hipStream_t s, const WinoGemmParams& p) {
+    if (variant == 2) hipLaunchKernelGGL((wino_gemm_kernel<32, 128, 4, PERS, RING>), grid, dim3(256), 0, s, p);
+    else if (variant == 3) hipLaunchKernelGGL((wino_gemm_kernel<64, 64, 2, PERS, RING>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((wino_gemm_kernel<64, 128, 2, PERS, RING>), grid, dim3(256), 0, s, p);
+}
+
 // transform + GEMM launch pairs of one call; `variant` 1 / 2 / 3 as listed at wino_gemm_kernel.  0 or BRCNN_EINVAL; the caller
 // has checked the layer form and counts the launch
 int wino_run(const void* x, const void* u, const void* gn_stats, const float* gamma, const float* beta, int groups, int relu_in,
@@ -418,10 +626,24 @@ int wino_run(const void* x, const void* u, const void* gn_stats, const float* ga
         p.tile0 = t0; p.nt = nt;
         p.v_bytes = (unsigned)((long long)16 * nt * cin * 4);
         p.tiles_m = (nt + wbm - 1) / wbm;
+        // the LDS ring: the measured rule or the hook (-16, 42 / 43)
+        const int ring = brcnn::g_policy.f32_winograd_ring ? brcnn::g_policy.f32_winograd_ring
+                                                           : brcnn::wino_ring_rule(p.tiles_m * p.tiles_n, cin);
+        brcnn::g_counters.f32_winograd_last_ring = ring;
+        // each launch pair plans for itself: its own epoch of the stream's flags, its own range table
+        int wgs = 0;
+        if (const int rc = wino_plan(p, variant, ring, s, wgs)) return rc;
+        if (wgs > 0) {
+            if (ring == 3) wino_launch<true, 3>(variant, dim3(wgs), s, p);
+            else wino_launch<true, 2>(variant, dim3(wgs), s, p);
+            BRCNN_LAUNCH_CHECK();
+            brcnn::count(brcnn::g_counters.f32_winograd_sk_launches);
+            brcnn::g_counters.f32_winograd_sk_last_wgs = wgs;
+            continue;
+        }
         const dim3 grid(p.tiles_m * p.tiles_n);
-        if (variant == 2) hipLaunchKernelGGL((wino_gemm_kernel<32, 128, 4>), grid, dim3(256), 0, s, p);
-        else if (variant == 3) hipLaunchKernelGGL((wino_gemm_kernel<64, 64, 2>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((wino_gemm_kernel<64, 128, 2>), grid, dim3(256), 0, s, p);
+        if (ring == 3) wino_launch<false, 3>(variant, grid, s, p);
+        else wino_launch<false, 2>(variant, grid, s, p);
         BRCNN_LAUNCH_CHECK();
     }
     return 0;
@@ -440,12 +662,15 @@ BRCNN_API int brcnn_conv3x3_winograd_f32_multi(const void* x, const void* u, con
     if (gn_stats && (!gamma || !beta || groups <= 0 || cin % groups)) return BRCNN_EINVAL;
     WinoGemmParams p = {};
     if (wino_segs(p.sg, batch, num_segments, heights_host, widths_host)) return BRCNN_EINVAL;
-    // the tower's launches stay on the 64 x 128 tile
+    // the tower's tile: the measured rule (64 x 128) or the hook (-16, 20 + v)
+    const int variant = brcnn::g_policy.f32_winograd_tower_gemm ? brcnn::g_policy.f32_winograd_tower_gemm
+                                                                : brcnn::wino_tower_gemm_rule(p.sg.t0[num_segments], cout);
     const int st = wino_run(x, u, gn_stats, gamma, beta, groups, relu_in, scale, shift, relu, y, workspace, workspace_bytes, p,
-                            num_segments, cin, cout, 1, stream);
+                            num_segments, cin, cout, variant, stream);
     if (st) return st;
     brcnn::count(brcnn::g_counters.f32_winograd_launches);
     brcnn::g_counters.f32_winograd_tiles = p.sg.t0[num_segments];
+    brcnn::g_counters.f32_winograd_tower_variant = variant;
     return 0;
 }
 

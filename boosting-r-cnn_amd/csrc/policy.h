@@ -22,6 +22,12 @@ struct Policy {
     // brcnn_winograd_layer_route (f32_winograd = 0 switches it off as well) and by brcnn_conv3x3_winograd_f32_layer
     int f32_winograd_layer = 1;     // (-14, 0 / 1 / 2): never / the measured rule (wino_layer_rule) / wherever the entry accepts the shape; (-14, 3) returns it
     int f32_winograd_gemm = 0;      // tuning hook ((-14, 20 + v)): GEMM tile of the layer entry, 0 = the measured rule (wino_gemm_rule), 1 = 64 x 128, 2 = 32 x 128, 3 = 64 x 64; (-14, 24) returns it
+    // ... the persistent, balanced launch of the Winograd GEMM (both entries): brcnn_conv_set_tile(-16, n)
+    int f32_winograd_sk = 1;        // (-16, 0 / 1 / 2): never / the measured rule (wino_persistent_rule) / wherever the schedule allows; (-16, 3) returns it
+    int f32_winograd_sk_per_cu = 0; // tuning hook ((-16, 30 + n), n = 0 .. 8): workgroups per CU of the persistent launch at most, 0 = the occupancy query's; (-16, 39) returns it
+    int f32_winograd_sk_wgs = 0;    // test hook ((-16, 1000 + n), n = 0 .. 2048): workgroups of the persistent launch at most (small maps then straddle tiles), 0 = no cap; (-16, 999) returns it
+    int f32_winograd_ring = 0;      // tuning hook ((-16, 40 / 42 / 43)): LDS ring stages of the GEMM's K loop by the measured rule (wino_ring_rule) / 2 / 3; (-16, 49) returns it
+    int f32_winograd_tower_gemm = 0;    // tuning hook ((-16, 20 + v)): GEMM tile of the tower entry, 0 = the measured rule (wino_tower_gemm_rule), 1 = 64 x 128, 3 = 64 x 64; (-16, 24) returns it
 
     // ---- 16-bit deformable conv (deform_conv_bf16.hip): brcnn_conv_set_tile(-13, n); read by brcnn_deform_conv_route
     int dcn_fused = 1;              // (-13, 0 / 1 / 2): im2col + GEMM always / the measured rule / fused wherever the kernel accepts the shape
@@ -91,6 +97,11 @@ struct Counters {
     // brcnn_conv_set_tile(-14, 10 / 11): return and clear ((-9, -1) clears them too)
     int f32_winograd_layer_launches = 0;    // (-14, 10): calls of brcnn_conv3x3_winograd_f32_layer that launched (the tower's are not in it)
     int f32_winograd_layer_variant = 0;     // (-14, 11): GEMM tile of the last one (1 = 64 x 128, 2 = 32 x 128, 3 = 64 x 64)
+    // brcnn_conv_set_tile(-16, 10 .. 13): return and clear ((-9, -1) clears them too)
+    int f32_winograd_sk_launches = 0;       // (-16, 10): persistent Winograd GEMM launches (either entry; a call of n launch pairs counts up to n)
+    int f32_winograd_sk_last_wgs = 0;       // (-16, 11): workgroups of the last one
+    int f32_winograd_tower_variant = 0;     // (-16, 12): GEMM tile of the last tower call (1 = 64 x 128, 3 = 64 x 64)
+    int f32_winograd_last_ring = 0;         // (-16, 13): LDS ring stages of the last Winograd GEMM launch (2 / 3)
     // brcnn_conv_set_tile(-13, 10 / 11): return and clear ((-9, -1) clears them too)
     int dcn_fused_launches = 0;         // (-13, 10): launches of the fused deformable conv (deform_conv_bf16.hip), every entry
     int dcn_im2col_launches = 0;        // (-13, 11): launches of the deformable im2col kernels (deform.hip), every entry
@@ -109,5 +120,10 @@ inline void count(int& c) { c = (c + 1) & 0x7fffffff; }     // (a long run must 
 int wino_layer_rule(int tiles, int cin, int cout);
 int wino_gemm_rule(int tiles, int cout);
 int wino_gemm_variant(int tiles, int cout);
+// ... of the persistent launch of the Winograd GEMM: does a launch of `workgroup_tiles` GEMM tiles of `units` xi planes each
+// gain from `per_cu` balanced workgroups on each of `cus` CUs (1) or stay one workgroup per tile (0); and the tower's tile
+int wino_persistent_rule(int workgroup_tiles, int units, int cus, int per_cu);
+int wino_tower_gemm_rule(int tiles, int cout);
+int wino_ring_rule(int workgroup_tiles, int cin);       // LDS ring stages (2 / 3) of a GEMM launch
 
 }  // namespace brcnn

@@ -30,6 +30,8 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
             g_counters.f32_winograd_launches = g_counters.f32_winograd_tiles = 0;
             g_counters.dcn_fused_launches = g_counters.dcn_im2col_launches = 0;
             g_counters.f32_winograd_layer_launches = g_counters.f32_winograd_layer_variant = 0;
+            g_counters.f32_winograd_sk_launches = g_counters.f32_winograd_sk_last_wgs = g_counters.f32_winograd_tower_variant = 0;
+            g_counters.f32_winograd_last_ring = 0;
             return 0;
         }
         const int n = *c[nt];
@@ -79,6 +81,31 @@ BRCNN_API int brcnn_conv_set_tile(int wm, int nt) {
         c = 0;
         return n;
     }
+    // persistent launch of the Winograd GEMM: (-16, 0 / 1 / 2) never / by the measured rule / wherever the schedule allows,
+    // (-16, 3) RETURNS the setting; (-16, 10 .. 13) return and clear the persistent launches / the workgroups of the last
+    // one / the GEMM tile of the last tower call / the LDS ring stages of the last GEMM launch; (-16, 40 / 42 / 43): ring
+    // stages by the rule / 2 / 3, (-16, 49) RETURNS it; (-16, 20 + v): the tower's GEMM tile by the rule (v = 0) or forced (1 =
+    // 64 x 128, 3 = 64 x 64), (-16, 24) RETURNS it; (-16, 30 + n), n = 0 .. 8: at most n workgroups per CU (0: the occupancy
+    // query's), (-16, 39) RETURNS it; (-16, 1000 + n), n = 0 .. 2048: at most n workgroups in all (0: no cap), (-16, 999)
+    // RETURNS it
+    if (wm == -16) {
+        if (nt >= 0 && nt <= 2) { g_policy.f32_winograd_sk = nt; return 0; }
+        if (nt == 3) return g_policy.f32_winograd_sk;
+        if (nt == 20 || nt == 21 || nt == 23) { g_policy.f32_winograd_tower_gemm = nt - 20; return 0; }
+        if (nt == 24) return g_policy.f32_winograd_tower_gemm;
+        if (nt >= 30 && nt <= 38) { g_policy.f32_winograd_sk_per_cu = nt - 30; return 0; }
+        if (nt == 39) return g_policy.f32_winograd_sk_per_cu;
+        if (nt == 40 || nt == 42 || nt == 43) { g_policy.f32_winograd_ring = nt - 40; return 0; }
+        if (nt == 49) return g_policy.f32_winograd_ring;
+        if (nt >= 1000 && nt <= 1000 + 2048) { g_policy.f32_winograd_sk_wgs = nt - 1000; return 0; }
+        if (nt == 999) return g_policy.f32_winograd_sk_wgs;
+        if (nt < 10 || nt > 13) return BRCNN_EINVAL;
+        int& c = nt == 10 ? g_counters.f32_winograd_sk_launches : nt == 11 ? g_counters.f32_winograd_sk_last_wgs
+                 : nt == 12 ? g_counters.f32_winograd_tower_variant : g_counters.f32_winograd_last_ring;
+        const int n = c;
+        c = 0;
+        return n;
+    }
     if (wm == -2) { if (nt != 0 && nt != 1 && nt != 2 && nt != 128 && nt != 256) return BRCNN_EINVAL; g_policy.pp_f32_mode = nt; return 0; }
     if ((wm != 0 && wm != 1 && wm != 2 && wm != 4) || nt < 0 || nt > 2) return BRCNN_EINVAL;
     g_policy.force_wm = wm;
@@ -111,6 +138,48 @@ int brcnn::wino_layer_rule(int tiles, int cin, int cout) {
 
 int brcnn::wino_gemm_variant(int tiles, int cout) {
     return g_policy.f32_winograd_gemm ? g_policy.f32_winograd_gemm : wino_gemm_rule(tiles, cout);
+}
+
+// ---- the persistent launch of the Winograd GEMM: the measured rules (profiles/f32_winograd_persistent.txt: MI355X, 256
+// CUs, transform + GEMM per shape, plain against forced persistent, 7 alternating rounds of 10 launches; a class takes a
+// form where its gain exceeds the spread of the plain rounds).  `per_cu` is what the launch would run: the resident count,
+// or floor(workgroup_tiles / cus), one at least, where the launch has fewer GEMM tiles than that (conv_winograd_f32.hip:
+// wino_plan).  The thresholds are the midpoints between the nearest losing and the nearest winning measured tile count of a
+// class, as tiles per CU (x / 256).
+int brcnn::wino_persistent_rule(int workgroup_tiles, int units, int cus, int per_cu) {
+    if (workgroup_tiles <= 0 || units < 16 || cus <= 0 || per_cu <= 0) return 0;
+    const long long t256 = (long long)workgroup_tiles * 256;
+    // ONE balanced workgroup per CU, 1.03 - 1.25 chains each, where the plain launch leaves a few CUs with two whole chains:
+    // 264 GEMM tiles 164 -> 124 us, 280 (512 channels) 297 -> 219 us, 320 166 -> 143 us (spreads 6 - 8 us); at 396 the
+    // second workgroup is on more than half of the CUs and nearly free there: 174 -> 175 us
+    if (per_cu == 1) return workgroup_tiles >= cus && t256 < 358LL * cus;
+    // TWO per CU, 2.06 chains each, where the plain launch puts a third workgroup on a few CUs: 528 GEMM tiles 241 -> 200 us
+    // (spread 13 us).  512 is two whole chains per CU either way (182 -> 183 us), and at 640 the plain launch's third
+    // workgroups are on half of the CUs: 252 -> 239 us, inside the spread of 20 us
+    if (per_cu == 2) return t256 >= 520LL * cus && t256 < 584LL * cus;
+    // more GEMM tiles than places (33 600 tiles: 2 100 GEMM tiles on four per CU, 793 -> 775 us inside the spread of 59 us,
+    // -73 us on two per CU) and the tower (1 406: 1006 -> 991 us, a gain the size of the persistent rounds' own spread; its
+    // 64 x 64 tile -95 us): plain.  Three and more whole chains per CU were not measured
+    return 0;
+}
+
+// LDS ring stages of the GEMM's K loop.  Three stages lost 3 - 10 us on every plain launch of the table but the 33 600-tile
+// one (+21 us inside its spread of 59 us) and moved the persistent ones by -3 .. +6 us, inside or at the edge of their
+// spreads: two everywhere
+int brcnn::wino_ring_rule(int workgroup_tiles, int cin) {
+    (void)workgroup_tiles; (void)cin;
+    return 2;
+}
+
+// the tower's GEMM tile: 64 x 128 (1) or 64 x 64 (3).  64 x 64 measured 973 against 1006 us, inside its own spread of 61 us
+int brcnn::wino_tower_gemm_rule(int tiles, int cout) {
+    (void)tiles; (void)cout;
+    return 1;
+}
+
+// host arithmetic only (tests, tools): brcnn::wino_persistent_rule
+BRCNN_API int brcnn_winograd_persistent_rule(int workgroup_tiles, int units, int cus, int per_cu) {
+    return brcnn::wino_persistent_rule(workgroup_tiles, units, cus, per_cu);
 }
 
 // 1: the frozen fp32 conv layer of this form and size runs brcnn_conv3x3_winograd_f32_layer, 0: the launches it ran before.

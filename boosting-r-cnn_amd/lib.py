@@ -62,6 +62,7 @@ SIGNATURES = {
     'brcnn_conv3x3_winograd_f32_layer': (c_int, [c_ptr] * 4 + [c_int, c_ptr, c_ptr, c_size] + [c_int] * 10 + [c_ptr]),
     'brcnn_winograd_layer_route': (c_int, [c_int] * 10),
     'brcnn_winograd_layer_gemm_variant': (c_int, [c_int, c_int]),
+    'brcnn_winograd_persistent_rule': (c_int, [c_int] * 4),
     'brcnn_groupnorm_nhwc_multi_stats': (c_int, [c_ptr, c_ptr, c_int, c_int, c_ptr, c_int, c_int, c_f32, c_int, c_ptr]),
     'brcnn_conv2d_dgrad_nhwc_multi': (c_int, [c_ptr] * 3 + [c_int, c_int] + [c_ptr] * 4 + [c_int] * 7 +
                                       [c_ptr]),

@@ -360,7 +360,15 @@ int brcnn_conv_handover_status(void);
  * measured rule / wherever the entry accepts the shape; (-14, 3) RETURNS the setting; (-14, 10) / (-14, 11) return and clear
  * the launches of brcnn_conv3x3_winograd_f32_layer / the GEMM tile of the last one (1 = 64 x 128, 2 = 32 x 128,
  * 3 = 64 x 64; (-9, -1) clears them too); (-14, 20 + v): that entry's GEMM tile by the measured rule (v = 0) or forced
- * (v = 1 .. 3), (-14, 24) RETURNS it.  (-11, 0) switches this route off as well.  Every tile gives the same bits. */
+ * (v = 1 .. 3), (-14, 24) RETURNS it.  (-11, 0) switches this route off as well.  Every tile gives the same bits.
+ * (-16, 0 / 1 / 2): persistent, balanced launch of the Winograd GEMM (both Winograd entries) never / by the measured rule
+ * (brcnn_winograd_persistent_rule) / wherever the schedule allows; (-16, 3) RETURNS the setting; (-16, 10) / (-16, 11) /
+ * (-16, 12) / (-16, 13) return and clear the persistent launches / the workgroups of the last one / the GEMM tile of the
+ * last tower call / the LDS ring stages of the last GEMM launch ((-9, -1) clears them too); (-16, 40 / 42 / 43): LDS ring
+ * stages of the GEMM's K loop by the measured rule / 2 / 3, (-16, 49) RETURNS it; (-16, 20 + v): the tower entry's GEMM tile by the measured rule (v = 0) or forced (1 = 64 x 128,
+ * 3 = 64 x 64), (-16, 24) RETURNS it; (-16, 30 + n), n = 0 .. 8: at most n workgroups per CU in a persistent launch (0: the
+ * occupancy query's), (-16, 39) RETURNS it; (-16, 1000 + n), n = 0 .. 2048: at most n workgroups in all (a test hook: small
+ * maps then straddle tiles; 0: no cap), (-16, 999) RETURNS it.  Both launch forms give the same bits. */
 int brcnn_conv_set_tile(int wm, int nt);
 
 /* Tuning hook of the bf16 kernel: 0 heuristic; 11 / 21 / 22 = 64x64 / 128x64 / 128x128 tile on
@@ -427,6 +435,10 @@ int brcnn_conv3x3_winograd_f32_layer(const void *x, const void *u, const float *
 int brcnn_winograd_layer_route(int tiles, int cin, int cout, int kh, int kw, int stride, int pad, int dilation,
                                int groups, int dtype);
 int brcnn_winograd_layer_gemm_variant(int tiles, int cout);
+/* The measured rule of the persistent launch of the Winograd GEMM (host arithmetic only): 1 when a launch of
+ * `workgroup_tiles` GEMM tiles of `units` xi planes each runs as `per_cu` balanced workgroups on each of `cus` CUs, 0 when it
+ * stays one workgroup per tile (profiles/f32_winograd_persistent.txt). */
+int brcnn_winograd_persistent_rule(int workgroup_tiles, int units, int cus, int per_cu);
 
 /* Grouped convolution (ResNeXt bottleneck conv2, mmdet/models/backbones/resnext.py:10-84).
  * x (N,H,W,Cin) fp32; w_tiles (Cout,KH,KW,window) block-diagonal per 64-channel output tile
