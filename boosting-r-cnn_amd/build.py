@@ -29,7 +29,8 @@ FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-ffp-contract=
 # are latency- or HBM-bound, the scalar form costs nothing measurable
 EXTRA_FLAGS = {'roi_align.hip': ['-fno-slp-vectorize'], 'focal_loss.hip': ['-fno-slp-vectorize'],
                'train_loss.hip': ['-fno-slp-vectorize'], 'deform.hip': ['-fno-slp-vectorize'],
-               'deform_conv_bf16.hip': ['-fno-slp-vectorize'], 'tta.hip': ['-fno-slp-vectorize']}
+               'deform_conv_bf16.hip': ['-fno-slp-vectorize'], 'tta.hip': ['-fno-slp-vectorize'],
+               'rpn_sampled.hip': ['-fno-slp-vectorize']}
 
 
 def hipcc():

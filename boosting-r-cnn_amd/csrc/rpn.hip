@@ -143,10 +143,14 @@ __global__ __launch_bounds__(256) void rpn_decode_levels_kernel(DecodeLevels lv,
 //     score = sqrt(softmax_c * prior),  box = delta2bbox(proposal, deltas[4c:4c+4]) clipped to the
 //     image and divided by its scale factor,  valid = score > thr and the proposal row is real.
 // `probs` are the softmax outputs (all C+1 columns, the background column is not emitted).
+// PLAIN (BBoxHead.get_bboxes, bbox_head.py:317-379, the standard head): score = softmax_c alone, and a
+// class-agnostic head (`reg_cols` == 4) hands its one box to every class.  The fused form is untouched:
+// the template only selects the score expression and the delta row.
+template <bool PLAIN>
 __global__ __launch_bounds__(256) void rcnn_decode_kernel(const float* __restrict__ probs, const float* __restrict__ bbox_pred,
                                                          const float* __restrict__ props, const int* __restrict__ num,
                                                          const float* __restrict__ max_shape, const float* __restrict__ scale,
-                                                         int B, int K, int C, float score_thr, DecodeParams dp,
+                                                         int B, int K, int C, int reg_cols, float score_thr, DecodeParams dp,
                                                          float* __restrict__ boxes, float* __restrict__ scores,
                                                          int64_t* __restrict__ labels, uint8_t* __restrict__ valid) {
     const long long total = (long long)B * K * C;
@@ -156,8 +160,8 @@ __global__ __launch_bounds__(256) void rcnn_decode_kernel(const float* __restric
         const long long bk = t / C;
         const int b = (int)(bk / K), k = (int)(bk - (long long)b * K);
         const float* pr = props + bk * 5;            // x1, y1, x2, y2, prior
-        const float s = sqrtf(probs[bk * (C + 1) + c] * pr[4]);
-        const float4 d = *reinterpret_cast<const float4*>(bbox_pred + bk * 4 * C + 4 * c);
+        const float s = PLAIN ? probs[bk * (C + 1) + c] : sqrtf(probs[bk * (C + 1) + c] * pr[4]);
+        const float4 d = *reinterpret_cast<const float4*>(bbox_pred + bk * reg_cols + (reg_cols == 4 ? 0 : 4 * c));
         const float x1 = pr[0], y1 = pr[1], x2 = pr[2], y2 = pr[3];
         const float dx = d.x * dp.std[0] + dp.mean[0];
         const float dy = d.y * dp.std[1] + dp.mean[1];
@@ -418,9 +422,30 @@ BRCNN_API int brcnn_rcnn_decode(const float* probs, const float* bbox_pred, cons
     const long long total = (long long)batch * per_image * num_classes;
     long long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(rcnn_decode_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, probs, bbox_pred, proposals,
-                       num, max_shape, scale_factor, batch, per_image, num_classes, score_thr, dp, boxes, scores, labels,
-                       valid);
+    hipLaunchKernelGGL(rcnn_decode_kernel<false>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, probs, bbox_pred, proposals,
+                       num, max_shape, scale_factor, batch, per_image, num_classes, 4 * num_classes, score_thr, dp, boxes,
+                       scores, labels, valid);
+    BRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+BRCNN_API int brcnn_rcnn_decode_plain(const float* probs, const float* bbox_pred, const float* proposals, const int32_t* num,
+                                      const float* max_shape, const float* scale_factor, int batch, int per_image,
+                                      int num_classes, int reg_class_agnostic, float score_thr, const float* means4_host,
+                                      const float* stds4_host, double wh_ratio_clip, float* boxes, float* scores,
+                                      int64_t* labels, uint8_t* valid, void* stream) {
+    if (!probs || !bbox_pred || !proposals || !num || !max_shape || !boxes || !scores || !labels || !valid ||
+        batch <= 0 || per_image <= 0 || num_classes <= 0 || !means4_host || !stds4_host || !(wh_ratio_clip > 0.0))
+        return BRCNN_EINVAL;
+    DecodeParams dp = {};
+    for (int i = 0; i < 4; i++) { dp.mean[i] = means4_host[i]; dp.std[i] = stds4_host[i]; }
+    dp.max_ratio = (float)fabs(log(wh_ratio_clip));
+    const long long total = (long long)batch * per_image * num_classes;
+    long long g = (total + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(rcnn_decode_kernel<true>, dim3((int)g), dim3(256), 0, (hipStream_t)stream, probs, bbox_pred, proposals,
+                       num, max_shape, scale_factor, batch, per_image, num_classes,
+                       reg_class_agnostic ? 4 : 4 * num_classes, score_thr, dp, boxes, scores, labels, valid);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }

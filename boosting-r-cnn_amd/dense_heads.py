@@ -591,7 +591,7 @@ class ATSSRPNHead(AnchorHead):
             cache[key] = (anchors, (starts, [w for _, w in sizes], self.num_anchors))
         return cache[key]
 
-    def assign_targets_device(self, sizes, img_metas, gts, gt_offsets, device):
+    def assign_targets_device(self, sizes, img_metas, gts, gt_offsets, device, want_counts=False):
         """AnchorHead._get_targets_single's assignment for the whole batch on the device: gt_inds
         (B, anchors per image) int32 (-1 ignore / outside, 0 negative, k matched to gt k-1)"""
         import numpy as np
@@ -614,7 +614,7 @@ class ATSSRPNHead(AnchorHead):
         a = self.assigner
         return train_ops.assign_max_iou(anchors, gts, gt_offsets, a.pos_iou_thr, a.neg_iou_thr, a.min_pos_iou,
                                         a.match_low_quality, batch=B, geom=geom, valid_hw=valid_hw, img_hw=img_hw,
-                                        allowed_border=border)
+                                        allowed_border=border, want_counts=want_counts)
 
     def loss_fused(self, y, sizes, gt_bboxes, img_metas, gt_flat=None, scales=None):
         """ATSSRPNHead.loss on the fused head output: assignment + every loss term in HIP kernels, no
@@ -657,6 +657,9 @@ class ATSSRPNHead(AnchorHead):
         return self.get_bboxes_padded(cls, reg, iou, img_metas, cfg=cfg, reg_scales=scales)
 
     # ------------------------------------------------------------------ proposals
+    def _proposal_scores(self, cls, iou):
+        return ops.rpn_score(cls, iou)
+
     def _base_anchors(self, level, device):
         key = (level, str(device))
         if key not in self._base_anchor_cache:
@@ -679,7 +682,8 @@ class ATSSRPNHead(AnchorHead):
         shapes = {tuple(m['img_shape'][:2]) for m in img_metas}
         A = self.num_anchors
         sc_l, pr_l, va_l, id_l = [], [], [], []
-        raw = [ops.rpn_score(cls_nhwc[lvl], iou_nhwc[lvl]).view(B, -1) for lvl in range(len(cls_nhwc))]
+        raw = [self._proposal_scores(cls_nhwc[lvl], None if iou_nhwc is None else iou_nhwc[lvl]).view(B, -1)
+               for lvl in range(len(cls_nhwc))]
         if 0 < cfg.nms_pre <= 4096:
             # descending, ties by ascending index (the shared tie rule), all levels in one launch
             picked = ops.rpn_topk(raw, cfg.nms_pre)
@@ -806,3 +810,281 @@ class ATSSRPNHead(AnchorHead):
         merged, _, num = batched_nms_images(boxes, scores, torch.zeros_like(scores, dtype=torch.long), valid,
                                             nms_cfg['iou_threshold'], cfg.max_per_img, nms_cfg.get('offset', 0))
         return merged, num, geom
+
+
+# ----------------------------------------------------------------------------- Faster R-CNN baseline
+@HEADS.register_module()
+class RPNHead(AnchorHead):
+    """The plain RPN of the Faster R-CNN baseline (mmdet/models/dense_heads/rpn_head.py:16-249 over
+    anchor_head.py:37-497): `rpn_conv` (one 3x3 Conv2d, or `rpn_conv.{i}.conv` for num_convs > 1) + ReLU, then the 1x1
+    `rpn_cls` / `rpn_reg`; sigmoid objectness, 256 anchors drawn per image for the loss.  Parameter names and shapes
+    are the reference's.  Execution: the 3x3 conv and the two 1x1 heads (as ONE launch, [cls A | reg 4A]) run over
+    all pyramid levels at once on the NHWC conv kernels; the proposal stage and the whole-batch assignment are the
+    head-agnostic ones ATSSRPNHead uses; the sampled loss has its own kernels (csrc/rpn_sampled.hip)."""
+
+    plain_rpn = True        # (detectors.py: no IoU branch, no per-level Scale, no early RPN backward pass)
+    supports_tta = False
+    # nms_pre / candidate limits of the device proposal stage (include/brcnn_hip.h: brcnn_rpn_topk, brcnn_nms_prepare_levels)
+    MAX_NMS_PRE, MAX_CANDIDATES, MAX_LEVELS = 4096, 16384, 8
+
+    def __init__(self, in_channels, num_classes=1, init_cfg=None, num_convs=1, **kwargs):
+        if not kwargs.get('loss_cls', dict(use_sigmoid=True)).get('use_sigmoid', False):
+            raise NotImplementedError('RPNHead: loss_cls.use_sigmoid=False (two-channel softmax objectness) is not '
+                                      'supported; the device proposal stage and the sampled loss score with a sigmoid')
+        self.num_convs = num_convs
+        super().__init__(num_classes, in_channels, init_cfg=init_cfg, **kwargs)
+        if self.cls_out_channels != 1:
+            raise NotImplementedError(f'RPNHead: num_classes={num_classes}; the RPN scores one objectness per anchor')
+        self._conv_caches = [PackedCache() for _ in range(max(num_convs, 1))]
+        self._fused_head_cache = PackedCache()
+        self._base_anchor_cache = {}
+        self.init_weights()
+
+    def _init_layers(self):
+        if self.num_convs > 1:
+            self.rpn_conv = nn.Sequential(*[
+                ConvModule(self.in_channels if i == 0 else self.feat_channels, self.feat_channels, 3, padding=1,
+                           inplace=False) for i in range(self.num_convs)])
+        else:
+            self.rpn_conv = nn.Conv2d(self.in_channels, self.feat_channels, 3, padding=1)
+        self.rpn_cls = nn.Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 1)
+        self.rpn_reg = nn.Conv2d(self.feat_channels, self.num_anchors * 4, 1)
+
+    def init_weights(self):
+        """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01) (rpn_head.py:28)"""
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.normal_(m.weight, 0, 0.01)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+
+    def _tower_convs(self):
+        return [self.rpn_conv] if self.num_convs <= 1 else [m.conv for m in self.rpn_conv]
+
+    # ------------------------------------------------------------------ forward
+    def forward_fused(self, feats):
+        """inference: list of (B,h,w,C) NHWC maps -> per level a (B,h,w,5A) fp32 tensor [cls A | reg 4A]; every layer
+        is one launch over all levels (the weights are shared across them)"""
+        B = feats[0].shape[0]
+        sizes = [tuple(f.shape[1:3]) for f in feats]
+        x = cat_rows(feats)
+        for conv, cache in zip(self._tower_convs(), self._conv_caches):
+            w, b = cache.get([conv.weight, conv.bias], lambda c=conv: (pack_weight(c.weight).to(x.dtype),
+                                                                      c.bias.detach().float().contiguous()))
+            x, _ = ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, True, 1, 1)      # bias + ReLU in the read-out
+        heads = (self.rpn_cls, self.rpn_reg)
+
+        def builder():
+            return (torch.cat([pack_weight(h.weight) for h in heads], 0).to(x.dtype).contiguous(),
+                    torch.cat([h.bias.detach().float() for h in heads], 0).contiguous())
+        w, b = self._fused_head_cache.get([t for h in heads for t in (h.weight, h.bias)], builder)
+        y, _ = ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, False, 1, 0, out_f32=True)
+        outs, r0 = [], 0
+        for (h, wd) in sizes:
+            n = B * h * wd
+            outs.append(y[r0:r0 + n].view(B, h, wd, y.shape[1]))
+            r0 += n
+        return outs
+
+    def split_fused(self, fused):
+        a = self.num_anchors
+        return [f[..., :a] for f in fused], [f[..., a:5 * a] for f in fused]
+
+    def forward_head_fused(self, feats):
+        """training forward over all levels; returns the fused head output y (rows, Cpad) fp32
+        [cls A | reg 4A | zero padding], level-major rows, differentiable"""
+        from .autograd import ConvNHWCFunction, conv2d_nhwc_multi_autograd, fused_head_weights
+        B = feats[0].shape[0]
+        sizes = tuple(tuple(int(v) for v in f.shape[1:3]) for f in feats)
+        x = cat_rows(feats)
+        mult = 32 if x.dtype == torch.float32 else 64
+        for conv in self._tower_convs():
+            if conv.out_channels % mult == 0:       # ReLU in the kernel's read-out
+                x = ConvNHWCFunction.apply(x, conv.weight, conv.bias, B, sizes, 1, 1, False, True, False)
+            else:
+                x = conv2d_nhwc_multi_autograd(x, conv.weight, conv.bias, B, sizes, 1, 1).relu()
+        w, b = fused_head_weights((self.rpn_cls, self.rpn_reg), mult)
+        y = ConvNHWCFunction.apply(x, w, b, B, sizes, 1, 0, False, False, True)
+        return y, sizes
+
+    def forward_nhwc(self, feats):
+        """list of (B,h,w,C) -> (cls (B,h,w,A), reg (B,h,w,4A)) lists, fp32"""
+        from .autograd import wants_grad
+        if wants_grad(feats[0], self.rpn_cls.weight, self._tower_convs()[0].weight):
+            y, sizes = self.forward_head_fused(list(feats))
+            B, fused, r0 = feats[0].shape[0], [], 0
+            for (h, w) in sizes:
+                fused.append(y[r0:r0 + B * h * w].view(B, h, w, y.shape[1]))
+                r0 += B * h * w
+        else:
+            fused = self.forward_fused(list(feats))
+        return self.split_fused(fused)
+
+    def forward(self, feats):
+        """reference signature: list of (N,C,h,w) -> lists of (N,A,h,w), (N,4A,h,w)"""
+        cls, reg = self.forward_nhwc([to_nhwc(f) for f in feats])
+        v = lambda lst: [t.permute(0, 3, 1, 2) for t in lst]  # noqa: E731
+        return v(cls), v(reg)
+
+    # ------------------------------------------------------------------ proposals
+    _base_anchors = ATSSRPNHead._base_anchors
+    _proposals_from_candidates = staticmethod(ATSSRPNHead._proposals_from_candidates)
+    _atss_get_bboxes_padded = ATSSRPNHead.get_bboxes_padded
+
+    def _check_proposal_limits(self, cfg, sizes):
+        """the sizes the device proposal stage serves (brcnn_rpn_topk: k <= 4096; brcnn_nms_prepare_levels: <= 8 levels,
+        <= 16384 candidates per image); anything beyond is refused, not served some slower way"""
+        if not 0 < cfg.nms_pre <= self.MAX_NMS_PRE:
+            raise ValueError(f'RPNHead: nms_pre={cfg.nms_pre} outside (0, {self.MAX_NMS_PRE}] (brcnn_rpn_topk)')
+        if len(sizes) > self.MAX_LEVELS:
+            raise ValueError(f'RPNHead: {len(sizes)} pyramid levels, at most {self.MAX_LEVELS} are supported')
+        total = sum(min(cfg.nms_pre, h * w * self.num_anchors) for h, w in sizes)
+        if total > self.MAX_CANDIDATES:
+            raise ValueError(f'RPNHead: {total} NMS candidates per image, at most {self.MAX_CANDIDATES} are supported '
+                             '(brcnn_nms_prepare_levels)')
+        if cfg.nms.get('type', 'nms') != 'nms':
+            raise ValueError('RPNHead: proposals use greedy NMS')
+
+    def _proposal_scores(self, cls, iou):
+        """rpn_head.py:203-205: the sigmoid alone (ATSSRPNHead: sqrt(sigmoid(cls) * sigmoid(iou)))"""
+        return cls.float().sigmoid().contiguous()
+
+    def get_bboxes_padded(self, cls_nhwc, reg_nhwc, img_metas, cfg=None, per_image_shapes=False):
+        """rpn_head.py:159-249 for the whole batch on the device, no host sync: sigmoid scores, per-level top-k, decode
+        (`per_image_shapes`: the clip border from a device table, training batches of differently sized images),
+        min_bbox_size filter, level-aware NMS, max_per_img.  Returns (dets (B, max_per_img, 5) zero padded, num (B,))"""
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_proposal_limits(cfg, [tuple(c.shape[1:3]) for c in cls_nhwc])
+        scales = None
+        if per_image_shapes and len({tuple(m['img_shape'][:2]) for m in img_metas}) > 1:
+            scales = torch.ones(len(cls_nhwc), dtype=torch.float32, device=cls_nhwc[0].device)
+        return self._atss_get_bboxes_padded(cls_nhwc, reg_nhwc, None, img_metas, cfg=cfg, reg_scales=scales)
+
+    def proposals_fused(self, y, sizes, img_metas, cfg):
+        """proposal stage straight from the fused training head output (channel-slice views, no copies)"""
+        yd = y.detach()
+        B, a = len(img_metas), self.num_anchors
+        cls, reg, r0 = [], [], 0
+        for (h, w) in sizes:
+            n = B * h * w
+            t = yd[r0:r0 + n].view(B, h, w, yd.shape[1])
+            cls.append(t[..., :a])
+            reg.append(t[..., a:5 * a])
+            r0 += n
+        return self.get_bboxes_padded(cls, reg, img_metas, cfg=cfg, per_image_shapes=True)
+
+    def simple_test_padded(self, feats_nhwc, img_metas):
+        cls, reg = self.split_fused(self.forward_fused(list(feats_nhwc)))
+        return self.get_bboxes_padded(cls, reg, img_metas)
+
+    def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False, with_nms=True):
+        """reference signature (rpn_head.py:104-157): per-level (N,A,h,w) / (N,4A,h,w) -> list of (k,5) per image"""
+        assert with_nms, '``with_nms`` in RPNHead should always True'
+        assert len(cls_scores) == len(bbox_preds)
+        f = lambda lst: [to_nhwc(t.detach()).contiguous() for t in lst]  # noqa: E731
+        dets, num = self.get_bboxes_padded(f(cls_scores), f(bbox_preds), img_metas, cfg, per_image_shapes=True)
+        num = num.tolist()   # the one host sync of the proposal stage
+        return [dets[i, :num[i]] for i in range(len(img_metas))]
+
+    def simple_test_rpn(self, x, img_metas):
+        cls_scores, bbox_preds = self(x)
+        return self.get_bboxes(cls_scores, bbox_preds, img_metas)
+
+    # ------------------------------------------------------------------ train
+    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
+        outs = self(x)
+        losses = self.loss(*outs, gt_bboxes, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+        if proposal_cfg is None:
+            return losses
+        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
+
+    def loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights,
+                    num_total_samples):
+        """anchor_head.py:373-421"""
+        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
+        loss_cls = self.loss_cls(cls_score, labels.reshape(-1), label_weights.reshape(-1), avg_factor=num_total_samples)
+        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4)
+        if self.reg_decoded_bbox:
+            bbox_pred = self.bbox_coder.decode(anchors.reshape(-1, 4), bbox_pred)
+        loss_bbox = self.loss_bbox(bbox_pred, bbox_targets.reshape(-1, 4), bbox_weights.reshape(-1, 4),
+                                   avg_factor=num_total_samples)
+        return loss_cls, loss_bbox
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=None):
+        """rpn_head.py:70-101 / anchor_head.py:423-497.  Device tensors of a covered configuration go to the HIP
+        kernels (`loss_fused`); otherwise the reference's per-image chain in torch (the host path: `self.last_drawn`
+        keeps the drawn (pos_inds, neg_inds) per image)."""
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        device = cls_scores[0].device
+        if device.type == 'cuda' and gt_bboxes_ignore is None and self.device_train_ok():
+            sizes = tuple(tuple(int(v) for v in s_) for s_ in featmap_sizes)
+            rows = [torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in (c_, r_)], 1)
+                    for c_, r_ in zip(cls_scores, bbox_preds)]
+            return self.loss_fused(torch.cat(rows, 0).float().contiguous(), sizes, gt_bboxes, img_metas)
+        num_imgs = len(img_metas)
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
+        num_level_anchors = [a.size(0) for a in anchor_list[0]]
+        flat_anchors = [torch.cat(a) for a in anchor_list]
+        flat_flags = [torch.cat(v) for v in valid_flag_list]
+        ignore = gt_bboxes_ignore if gt_bboxes_ignore is not None else [None] * num_imgs
+        all_valid = self._all_valid
+        self._all_valid = None
+        (labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds, _) = multi_apply(
+            self._get_targets_single, flat_anchors, flat_flags, gt_bboxes, ignore, [None] * num_imgs, img_metas, all_valid)
+        if any(l is None for l in labels):
+            return None
+        self.last_drawn = list(zip(pos_inds, neg_inds))
+        num_total_samples = sum(max(p.numel(), 1) for p in pos_inds) + sum(max(n.numel(), 1) for n in neg_inds)
+        losses_cls, losses_bbox = multi_apply(
+            self.loss_single, cls_scores, bbox_preds, images_to_levels(flat_anchors, num_level_anchors),
+            images_to_levels(labels, num_level_anchors), images_to_levels(label_weights, num_level_anchors),
+            images_to_levels(bbox_targets, num_level_anchors), images_to_levels(bbox_weights, num_level_anchors),
+            num_total_samples=num_total_samples)
+        return dict(loss_rpn_cls=losses_cls, loss_rpn_bbox=losses_bbox)
+
+    # ------------------------------------------------------------------ device-resident train step
+    _anchor_table = ATSSRPNHead._anchor_table
+    assign_targets_device = ATSSRPNHead.assign_targets_device
+
+    def _tower_fusable(self):
+        return True
+
+    def device_train_ok(self):
+        """what the sampled-loss kernels cover: sigmoid cross-entropy without class weights, L1 / SmoothL1 on encoded
+        deltas, MaxIoU assignment without ignore regions, the RandomSampler without added ground truths"""
+        from .core import MaxIoUAssigner, RandomSampler
+        from .losses import CrossEntropyLoss, L1Loss, SmoothL1Loss
+        tc = self.train_cfg
+        return bool(
+            tc is not None and type(self.loss_cls) is CrossEntropyLoss and self.loss_cls.use_sigmoid and
+            self.loss_cls.class_weight is None and self.loss_cls.reduction == 'mean' and
+            type(self.loss_bbox) in (L1Loss, SmoothL1Loss) and self.loss_bbox.reduction == 'mean' and
+            not self.reg_decoded_bbox and type(self.assigner) is MaxIoUAssigner and self.assigner.ignore_iof_thr <= 0 and
+            self.assigner.gt_max_assign_all and type(self.sampler) is RandomSampler and
+            not self.sampler.add_gt_as_proposals and 0 < self.sampler.num <= 2048 and
+            not getattr(self.bbox_coder, 'add_ctr_clamp', False))
+
+    def loss_fused(self, y, sizes, gt_bboxes, img_metas, gt_flat=None):
+        """RPNHead.loss on the fused head output: whole-batch assignment, then the RandomSampler's draw -- the device
+        compacts the candidates, the host reads the (B, 2) counts (this head's one host read) and draws the
+        permutations with the reference's calls in the reference's order -- then the sampled loss kernels.
+        `self.last_rpn_targets` keeps (gt_inds, drawn (B, num) int32, num_total_samples)."""
+        from . import train_ops
+        device = y.device
+        gts, _, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes)
+        B, sp = len(img_metas), self.sampler
+        gt_inds, counts = self.assign_targets_device(sizes, img_metas, gts, offs, device, want_counts=True)
+        num_pos = int(sp.num * sp.pos_fraction)
+        cnt = [tuple(c) for c in counts.tolist()]            # the host read: (B, 2) candidate counts
+        perm, _ = train_ops.draw_sampler_perms(cnt, sp.num, num_pos, sp.neg_pos_ub)
+        total = train_ops.rpn_num_total_samples(cnt, sp.num, num_pos, sp.neg_pos_ub)
+        meta = train_ops.RPNSampledMeta(
+            B, sizes, self.anchor_generator.strides, [self._base_anchors(l, device) for l in range(len(sizes))],
+            self.num_anchors, offs, sp.num, num_pos, sp.neg_pos_ub, self.train_cfg.pos_weight,
+            getattr(self.loss_bbox, 'beta', 0.0), self.bbox_coder.means, self.bbox_coder.stds,
+            self.loss_cls.loss_weight, self.loss_bbox.loss_weight)
+        drawn, ws = train_ops.rpn_sampled_draw(gt_inds, perm.to(device, non_blocking=True), meta)
+        losses2 = train_ops.rpn_sampled_loss(y, gt_inds, gts, drawn, meta, total, workspace=ws)
+        self.last_rpn_targets = (gt_inds, drawn, total)
+        return dict(loss_rpn_cls=[losses2[0]], loss_rpn_bbox=[losses2[1]])

@@ -215,7 +215,8 @@ class TwoStageDetector(BaseDetector):
         """read the (tiny) host-side constants once so that `simple_test_device` issues no
         device->host copies: the five learnable rpn_reg scales.  The weights are frozen from here on, so the RPN tower
         may also keep Winograd-transformed filters (fp32 compute only; ATSSRPNHead.prepare_winograd)."""
-        self._rpn_scale_cache = [float(m.scale.detach().cpu()) for m in self.rpn_head.scales]
+        if hasattr(self.rpn_head, 'scales'):
+            self._rpn_scale_cache = [float(m.scale.detach().cpu()) for m in self.rpn_head.scales]
         if hasattr(self.rpn_head, 'prepare_winograd'):
             self.rpn_head.prepare_winograd()
         self.prepare_winograd_layers()
@@ -309,8 +310,10 @@ class TwoStageDetector(BaseDetector):
     graph_trunk = False
 
     def _early_rpn_backward_ok(self, feats):
+        # (RPNHead: switched off -- its loss reads the sampler counts back on the host, which would stall the stream the
+        # early backward pass is queued on)
         return bool(self.early_rpn_backward) and torch.is_grad_enabled() and feats[0].is_cuda and \
-            any(p.requires_grad for p in self.rpn_head.parameters())
+            not getattr(self.rpn_head, 'plain_rpn', False) and any(p.requires_grad for p in self.rpn_head.parameters())
 
     def _forward_train_device_early(self, feats, img_metas, gt_bboxes, gt_labels):
         from . import autograd as _A, train_ops
@@ -402,6 +405,12 @@ class TwoStageDetector(BaseDetector):
         (det_bboxes (B,M,5), det_labels (B,M), num_dets (B,))."""
         feats = self.extract_feat_nhwc(img)
         rpn = self.rpn_head
+        if getattr(rpn, 'plain_rpn', False):        # RPNHead (the Faster R-CNN baseline): no IoU branch, no Scale
+            dets, num = rpn.simple_test_padded(feats, img_metas)
+            stage_mark('rpn_postprocess')
+            out = self.roi_head.simple_test_padded(feats, dets, num, img_metas, rescale=rescale)
+            stage_mark('rcnn_decode_nms')
+            return out
         cls, reg, iou = rpn.split_fused(rpn.forward_fused(list(feats)))
         stage_mark('rpn_tower')
         scales = [float(s) for s in torch.stack([m.scale.detach() for m in rpn.scales]).tolist()] \
@@ -458,6 +467,9 @@ class TwoStageDetector(BaseDetector):
         Without `rescale` the boxes fit the frame of imgs[0]."""
         assert self.with_roi_head, 'Bbox head must be implemented.'
         self._check_augs(imgs, img_metas)
+        for head in (self.roi_head, self.rpn_head):
+            if not getattr(head, 'supports_tta', True):      # (the Faster R-CNN baseline heads)
+                raise NotImplementedError(f'{type(head).__name__} has no test-time augmentation')
         if self._device_path_ok() and self.roi_head.tta_device_ok():
             det, lab, nd = self.aug_test_device(imgs, img_metas, rescale)
             B, M = lab.shape

@@ -172,6 +172,14 @@ SIGNATURES = {
     'brcnn_tta_gather_proposals': (c_int, [c_ptr] * 3 + [c_int, c_ptr, c_int] + [c_ptr] * 5),
     'brcnn_tta_map_rois': (c_int, [c_ptr, c_ptr, c_int, c_int, c_int, c_ptr, c_ptr]),
     'brcnn_rcnn_decode_tta': (c_int, [c_ptr] * 6 + [c_int] * 5 + [c_f32, c_ptr, c_ptr, c_f64] + [c_ptr] * 5),
+    'brcnn_rcnn_decode_plain': (c_int, [c_ptr] * 6 + [c_int, c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_f64] + [c_ptr] * 5),
+    'brcnn_rpn_sampled_workspace_bytes': (c_size, [c_int, c_int, c_int]),
+    'brcnn_rpn_sampled_draw': (c_int, [c_ptr, c_int, c_int, c_int, c_int, c_f32, c_ptr, c_ptr, c_size, c_ptr, c_ptr]),
+    'brcnn_rpn_sampled_loss_forward': (c_int, [c_ptr, c_int, c_int, c_int] + [c_ptr] * 5 + [c_int] + [c_ptr] * 4 +
+                                       [c_int, c_ptr, c_ptr, c_size, c_ptr]),
+    'brcnn_rpn_sampled_loss_finalize': (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'brcnn_rpn_sampled_loss_backward': (c_int, [c_ptr, c_int, c_int, c_int] + [c_ptr] * 5 + [c_int] + [c_ptr] * 4 +
+                                        [c_int] + [c_ptr] * 5),
     'brcnn_coco_order_workspace_bytes': (c_size, [c_i64]),
     'brcnn_coco_match': (c_int, [c_ptr] * 6 + [c_int, c_int, c_ptr, c_int, c_ptr, c_int, c_int] + [c_ptr] * 7),
     'brcnn_coco_order': (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_size, c_ptr]),

@@ -1200,6 +1200,33 @@ def rcnn_decode(probs, bbox_pred, dets, num, max_shape, scale_factor, num_classe
     return boxes, scores, labels, valid
 
 
+def rcnn_decode_plain(probs, bbox_pred, dets, num, max_shape, scale_factor, num_classes, score_thr, means, stds,
+                      reg_class_agnostic=False, wh_ratio_clip=16 / 1000):
+    """Second-stage candidates of the standard head (brcnn_rcnn_decode_plain): as `rcnn_decode`, but the score is the
+    softmax probability alone and a class-agnostic head's bbox_pred is (B*K, 4), read by every class.
+    Returns boxes (B,K*C,4), scores (B,K*C), labels (B,K*C) int64, valid (B,K*C) bool."""
+    import ctypes
+    _require_gpu(probs, bbox_pred, dets, num, max_shape, scale_factor)
+    B, K, _ = dets.shape
+    C = int(num_classes)
+    assert probs.shape == (B * K, C + 1) and bbox_pred.shape == (B * K, 4 if reg_class_agnostic else 4 * C)
+    probs, bbox_pred, dets = probs.contiguous().float(), bbox_pred.contiguous().float(), dets.contiguous().float()
+    dev = dets.device
+    boxes = torch.empty((B, K * C, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, K * C), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, K * C), dtype=torch.int64, device=dev)
+    valid = torch.empty((B, K * C), dtype=torch.bool, device=dev)
+    m4 = (ctypes.c_float * 4)(*[float(v) for v in means])
+    s4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    sf = scale_factor.contiguous().float() if scale_factor is not None else None
+    st = _L.load().brcnn_rcnn_decode_plain(_ptr(probs), _ptr(bbox_pred), _ptr(dets), _ptr(num.to(torch.int32).contiguous()),
+                                           _ptr(max_shape.contiguous().float()), _ptr(sf), B, K, C,
+                                           int(bool(reg_class_agnostic)), float(score_thr), m4, s4, float(wh_ratio_clip),
+                                           _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(valid), _stream())
+    _L.check(st, 'brcnn_rcnn_decode_plain')
+    return boxes, scores, labels, valid
+
+
 # --------------------------------------------------------------------------- input front door
 _FLIP_CODE = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}
 

@@ -128,7 +128,8 @@ class ProbConvFCBBoxHead(nn.Module):
                  loss_bbox=dict(type='SmoothL1Loss', beta=1.0, loss_weight=1.0)):
         super().__init__()
         assert with_cls and with_reg and not with_avg_pool
-        assert num_shared_convs + num_shared_fcs + num_cls_convs + num_cls_fcs + num_reg_convs + num_reg_fcs > 0
+        assert self._allow_no_branch or \
+            num_shared_convs + num_shared_fcs + num_cls_convs + num_cls_fcs + num_reg_convs + num_reg_fcs > 0
         if num_cls_convs > 0 or num_reg_convs > 0:
             assert num_shared_fcs == 0
         assert reg_predictor_cfg.get('type') == 'Linear' and cls_predictor_cfg.get('type') == 'Linear'
@@ -177,6 +178,7 @@ class ProbConvFCBBoxHead(nn.Module):
 
     custom_cls_channels = False
     custom_activation = False
+    _allow_no_branch = False    # (BBoxHead: fc_cls / fc_reg straight on the flattened RoI features)
     custom_accuracy = False
 
     def _add_conv_fc_branch(self, num_branch_convs, num_branch_fcs, in_channels, is_shared=False):
@@ -843,6 +845,158 @@ class ProbRoIHead(nn.Module):
                 det_bboxes[:, :4] *= det_bboxes.new_tensor(img_metas[0][b]['scale_factor'])
             results.append(bbox2result(det_bboxes, det_labels, self.bbox_head.num_classes))
         return results
+
+
+# ----------------------------------------------------------------------------- Faster R-CNN baseline heads
+@HEADS.register_module()
+class ConvFCBBoxHead(ProbConvFCBBoxHead):
+    """The standard box heads (bbox_heads/{bbox_head.py:19-379, convfc_bbox_head.py:15-200}) over the implementation
+    behind ProbConvFCBBoxHead: same layers, parameter names, targets and `loss` (bbox_head.py:256-314 is that loss
+    without the IoU-weighted regression term); `get_bboxes` scores with a plain softmax (:317-379)."""
+
+    def __init__(self, *args, **kwargs):
+        for k in ('focal_reg', 'gamma'):
+            if k in kwargs:
+                raise TypeError(f'{type(self).__name__} takes no {k!r} (a ProbConvFCBBoxHead argument)')
+        super().__init__(*args, **kwargs)
+
+    def get_bboxes(self, rois, cls_score, bbox_pred, img_shape, scale_factor, rescale=False, cfg=None):
+        scores = F.softmax(cls_score, dim=-1) if cls_score is not None else None
+        return super().get_bboxes(rois, scores, bbox_pred, img_shape, scale_factor, rescale=rescale, cfg=cfg)
+
+
+@HEADS.register_module()
+class BBoxHead(ConvFCBBoxHead):
+    """bbox_head.py:19-94: fc_cls / fc_reg on the flattened RoI features, no hidden layers"""
+    _allow_no_branch = True
+
+    def __init__(self, **kwargs):
+        for k in ('num_shared_convs', 'num_shared_fcs', 'num_cls_convs', 'num_cls_fcs', 'num_reg_convs', 'num_reg_fcs'):
+            if kwargs.get(k, 0):
+                raise TypeError(f'BBoxHead has no hidden layers ({k}); use ConvFCBBoxHead')
+        super().__init__(**kwargs)
+
+
+@HEADS.register_module()
+class Shared2FCBBoxHead(ConvFCBBoxHead):
+    def __init__(self, fc_out_channels=1024, **kwargs):
+        super().__init__(num_shared_convs=0, num_shared_fcs=2, num_cls_convs=0, num_cls_fcs=0, num_reg_convs=0,
+                         num_reg_fcs=0, fc_out_channels=fc_out_channels, **kwargs)
+
+
+@HEADS.register_module()
+class Shared4Conv1FCBBoxHead(ConvFCBBoxHead):
+    def __init__(self, fc_out_channels=1024, **kwargs):
+        super().__init__(num_shared_convs=4, num_shared_fcs=1, num_cls_convs=0, num_cls_fcs=0, num_reg_convs=0,
+                         num_reg_fcs=0, fc_out_channels=fc_out_channels, **kwargs)
+
+
+@HEADS.register_module()
+class StandardRoIHead(ProbRoIHead):
+    """roi_heads/standard_roi_head.py + test_mixins.py:51-136 without masks: assignment, RandomSampler, the box head's
+    own loss; test-time scores are the head's softmax (no prior).  It shares ProbRoIHead's machinery (extractor, the
+    whole-batch device sampler, the batched NMS) and none of its boosting: the proposals' score column is not read."""
+
+    def __init__(self, bbox_roi_extractor=None, bbox_head=None, mask_roi_extractor=None, mask_head=None, shared_head=None,
+                 train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        if mask_head is not None or mask_roi_extractor is not None or shared_head is not None:
+            raise NotImplementedError('StandardRoIHead: mask and shared heads are not supported')
+        super().__init__(boost=False, prob=False, bbox_roi_extractor=bbox_roi_extractor, bbox_head=bbox_head,
+                         train_cfg=train_cfg, test_cfg=test_cfg, init_cfg=init_cfg)
+        if not isinstance(self.bbox_head, ConvFCBBoxHead):
+            raise TypeError(f'StandardRoIHead needs a softmax box head (BBoxHead / ConvFCBBoxHead family), got '
+                            f'{type(self.bbox_head).__name__}')
+
+    # ---- train -------------------------------------------------------------------------
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        """standard_roi_head.py:52-113"""
+        num_imgs = len(img_metas)
+        if gt_bboxes_ignore is None:
+            gt_bboxes_ignore = [None for _ in range(num_imgs)]
+        sampling_results = []
+        for i in range(num_imgs):
+            assign_result = self.bbox_assigner.assign(proposal_list[i], gt_bboxes[i], gt_bboxes_ignore[i], gt_labels[i])
+            sampling_results.append(self.bbox_sampler.sample(assign_result, proposal_list[i], gt_bboxes[i], gt_labels[i],
+                                                             feats=[lvl[i][None] for lvl in x]))
+        bbox_results = self._bbox_forward_train(x, sampling_results, gt_bboxes, gt_labels, img_metas)
+        return dict(bbox_results['loss_bbox'])
+
+    def device_train_ok(self):
+        from .losses import L1Loss
+        return bool(type(self) is StandardRoIHead and self._device_common_ok() and
+                    type(self.bbox_head.loss_bbox) in (L1Loss, SmoothL1Loss))
+
+    def forward_train_device(self, feats_nhwc, img_metas, dets, num, gt_flat, overlap_work=None, proposal_stream=None):
+        """forward_train on the padded device proposals: the whole-batch sampler, then BBoxHead.loss on the `_ex` loss
+        kernels in plain mode (unit label weights: gamma = alpha = 0)"""
+        from . import train_ops
+        smp, extra = self.sample_device(dets, num, gt_flat, overlap_work, proposal_stream)
+        stage_mark('sampler')
+        if callable(feats_nhwc):
+            feats_nhwc = feats_nhwc()
+        roi_feats = self.bbox_roi_extractor.forward_nhwc(feats_nhwc, smp['rois'])
+        stage_mark('roi_align')
+        cls_score, bbox_pred = self.bbox_head.forward_nhwc(roi_feats)
+        stage_mark('fc_head')
+        from . import autograd as _A
+        _A.release_held_weight_gradients()
+        h = self.bbox_head
+        out3 = train_ops.boost_loss(cls_score, bbox_pred, smp['labels'], torch.zeros_like(smp['priors']),
+                                    smp['bbox_targets'], h.num_classes, 0.0, 0.0, None, 0.0, h.loss_cls.loss_weight,
+                                    h.loss_bbox.loss_weight, 'bbox_num', h.reg_class_agnostic, plain_label_weights=True,
+                                    smooth_l1_beta=getattr(h.loss_bbox, 'beta', 0.0))
+        stage_mark('boost_loss')
+        self.last_samples = smp
+        return dict(loss_cls=out3[0], loss_bbox=out3[1], acc=out3[2].reshape(1)), extra
+
+    # ---- test --------------------------------------------------------------------------
+    def fuse_scores(self, cls_score, prior):
+        return cls_score            # (BBoxHead.get_bboxes applies the softmax)
+
+    def simple_test_padded(self, feats_nhwc, dets, num, img_metas, rescale=False):
+        """test_mixins.py:51-136 for the whole batch on the device, no host sync: extractor, box head, softmax, then
+        ONE launch for per-class decode / clip / rescale / threshold (brcnn_rcnn_decode_plain) and the batched NMS."""
+        cfg = self.test_cfg
+        nms_cfg = dict(cfg.nms)
+        nms_type = nms_cfg.pop('type', 'nms')
+        head = self.bbox_head
+        B, K, _ = dets.shape
+        C = head.num_classes
+        coder = head.bbox_coder
+        if nms_type != 'nms' or nms_cfg.get('class_agnostic', False):
+            raise NotImplementedError('StandardRoIHead: the device test path serves class-aware greedy NMS')
+        if getattr(coder, 'add_ctr_clamp', False) or not getattr(coder, 'clip_border', True):
+            raise NotImplementedError('StandardRoIHead: the device test path needs a clipping DeltaXYWHBBoxCoder '
+                                      'without centre clamp')
+        bidx = torch.arange(B, device=dets.device, dtype=dets.dtype).view(B, 1, 1).expand(B, K, 1)
+        rois = torch.cat([bidx, dets[..., :4]], -1).view(B * K, 5)
+        roi_feats = self.bbox_roi_extractor.forward_nhwc(feats_nhwc, rois)
+        stage_mark('roi_align')
+        cls_score, bbox_pred = head.forward_nhwc(roi_feats)
+        stage_mark('fc_head')
+        max_shape = const_rows([m['img_shape'][:2] for m in img_metas], dets)
+        sf = const_rows([list(m['scale_factor']) for m in img_metas], dets) if rescale else None
+        bb, sc, lb, va = ops.rcnn_decode_plain(cls_score.float().softmax(1), bbox_pred, dets, num, max_shape, sf, C,
+                                               cfg.score_thr, coder.means, coder.stds,
+                                               reg_class_agnostic=head.reg_class_agnostic)
+        if K * C >= nms_cfg.get('split_thr', 10000):
+            # mmcv's per-class branch: class-major slots, one segmented NMS launch over (image, class); same boxes, same order
+            from .postprocess import batched_nms_images_by_level
+            cm = lambda t: t.view(B, K, C, *t.shape[2:]).transpose(1, 2).reshape(B, C * K, *t.shape[2:]).contiguous()   # noqa: E731
+            return batched_nms_images_by_level(cm(bb), cm(sc), cm(lb), cm(va), [K] * C, nms_cfg['iou_threshold'],
+                                               cfg.max_per_img, nms_cfg.get('offset', 0), return_ids=True)
+        return batched_nms_images(bb, sc, lb, va, nms_cfg['iou_threshold'], cfg.max_per_img, nms_cfg.get('offset', 0))
+
+    # ---- test-time augmentation: out of scope for this head ------------------------------
+    supports_tta = False
+
+    def tta_device_ok(self, feats_nhwc=None):
+        return False
+
+    def aug_test(self, x, proposal_list, img_metas, rescale=False):
+        raise NotImplementedError(f'{type(self).__name__} has no test-time augmentation')
+
+    aug_test_padded = aug_test_bboxes = aug_test
 
 
 # ----------------------------------------------------------------------------- variants

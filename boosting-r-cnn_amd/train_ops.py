@@ -269,6 +269,105 @@ def rpn_loss(y, scales, gt_inds, gts, meta):
     return RPNLossFunction.apply(y, scales, gt_inds, gts, meta)
 
 
+# ----------------------------------------------------------------------------- sampled RPN loss (Faster R-CNN baseline)
+class RPNSampledMeta:
+    """host-side description of one sampled RPN loss call (RPNHead: RandomSampler over the assigned anchors)"""
+
+    def __init__(self, batch, sizes, strides, base_anchors, num_anchors, gt_offsets, num, num_expected_pos, neg_pos_ub,
+                 pos_weight, smooth_l1_beta, means, stds, lw_cls, lw_bbox):
+        self.batch, self.sizes, self.A = int(batch), [tuple(s) for s in sizes], int(num_anchors)
+        self.L = len(self.sizes)
+        self.hs, self.ws = _ints([h for h, _ in self.sizes]), _ints([w for _, w in self.sizes])
+        self.sw = _ints([s if isinstance(s, int) else s[0] for s in strides])
+        self.sh = _ints([s if isinstance(s, int) else s[1] for s in strides])
+        self.base = base_anchors                      # list of (A,4) device tensors (kept alive here)
+        self.base_ptrs = (ctypes.c_void_p * self.L)(*[b.data_ptr() for b in base_anchors])
+        self.gt_offsets = _ints(gt_offsets)
+        self.total_gt = int(gt_offsets[-1])
+        self.num, self.num_pos, self.neg_pos_ub = int(num), int(num_expected_pos), float(neg_pos_ub)
+        self.head = [float(pos_weight), float(smooth_l1_beta)] + [float(v) for v in means] + [float(v) for v in stds] + \
+            [float(lw_cls), float(lw_bbox)]
+        self.rows = sum(self.batch * h * w for h, w in self.sizes)
+        self.anchors_per_image = sum(h * w for h, w in self.sizes) * self.A
+
+    def cfg(self, num_total_samples):
+        return _floats(self.head + [float(num_total_samples)])
+
+
+def rpn_num_total_samples(counts, num, num_expected_pos, neg_pos_ub=-1):
+    """AnchorHead.get_targets' normaliser (anchor_head.py:354-355, :469-470): per image max(#drawn positives, 1) +
+    max(#drawn negatives, 1), from the host-side candidate counts"""
+    total = 0
+    for n_pos, n_neg in counts:
+        spos, sneg, _ = sample_counts(n_pos, n_neg, num, num_expected_pos, neg_pos_ub)
+        total += max(spos, 1) + max(sneg, 1)
+    return total
+
+
+def rpn_sampled_draw(gt_inds, perm, meta):
+    """drawn (B, num) int32: per image the drawn positives, then the drawn negatives (flat anchor indices), -1 after;
+    also returns the workspace the loss call goes on with"""
+    _require_gpu(gt_inds, perm)
+    assert gt_inds.dtype == torch.int32 and gt_inds.shape == (meta.batch, meta.anchors_per_image) and gt_inds.is_contiguous()
+    assert perm.dtype == torch.int32 and perm.shape == (meta.batch, meta.num_pos + meta.num) and perm.is_contiguous()
+    lib = _L.load()
+    nb = lib.brcnn_rpn_sampled_workspace_bytes(meta.batch, meta.anchors_per_image, meta.num)
+    ws = torch.empty((nb + 3) // 4, dtype=torch.int32, device=gt_inds.device)
+    drawn = torch.empty((meta.batch, meta.num), dtype=torch.int32, device=gt_inds.device)
+    st = lib.brcnn_rpn_sampled_draw(_ptr(gt_inds), meta.anchors_per_image, meta.batch, meta.num, meta.num_pos,
+                                    meta.neg_pos_ub, _ptr(perm), _ptr(ws), nb, _ptr(drawn), _stream())
+    _L.check(st, 'brcnn_rpn_sampled_draw')
+    return drawn, ws
+
+
+class RPNSampledLossFunction(Function):
+    """losses2 = [loss_rpn_cls, loss_rpn_bbox] over the drawn anchors, from the fused head output y (rows, ystride)"""
+
+    @staticmethod
+    def forward(ctx, y, gt_inds, gts, drawn, ws, meta, num_total_samples):
+        _require_gpu(y, gt_inds, gts, drawn)
+        assert y.dim() == 2 and y.dtype == torch.float32 and y.is_contiguous() and y.shape[0] == meta.rows
+        assert y.shape[1] >= 5 * meta.A
+        assert drawn.dtype == torch.int32 and drawn.shape == (meta.batch, meta.num) and drawn.is_contiguous()
+        lib = _L.load()
+        cfg = meta.cfg(num_total_samples)
+        nb = lib.brcnn_rpn_sampled_workspace_bytes(meta.batch, meta.anchors_per_image, meta.num)
+        if ws is None:
+            ws = torch.empty((nb + 3) // 4, dtype=torch.int32, device=y.device)
+        out = torch.empty((4,), dtype=torch.float32, device=y.device)
+        losses2, coef = out[:2], out[2:]
+        gp = _ptr(gts) if meta.total_gt else None
+        st = lib.brcnn_rpn_sampled_loss_forward(_ptr(y), y.shape[1], meta.batch, meta.L, meta.hs, meta.ws, meta.sw, meta.sh,
+                                                meta.base_ptrs, meta.A, _ptr(gt_inds), gp, meta.gt_offsets, _ptr(drawn),
+                                                meta.num, cfg, _ptr(ws), nb, _stream())
+        _L.check(st, 'brcnn_rpn_sampled_loss_forward')
+        st = lib.brcnn_rpn_sampled_loss_finalize(_ptr(ws), meta.batch, meta.anchors_per_image, meta.num, cfg,
+                                                 _ptr(losses2), _ptr(coef), _stream())
+        _L.check(st, 'brcnn_rpn_sampled_loss_finalize')
+        ctx.save_for_backward(y, gt_inds, gts, drawn, coef)
+        ctx.meta, ctx.cfg = meta, cfg
+        return losses2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g2):
+        y, gt_inds, gts, drawn, coef = ctx.saved_tensors
+        meta = ctx.meta
+        dy = torch.empty_like(y)
+        g2 = g2.float().contiguous()
+        gp = _ptr(gts) if meta.total_gt else None
+        st = _L.load().brcnn_rpn_sampled_loss_backward(
+            _ptr(y), y.shape[1], meta.batch, meta.L, meta.hs, meta.ws, meta.sw, meta.sh, meta.base_ptrs, meta.A,
+            _ptr(gt_inds), gp, meta.gt_offsets, _ptr(drawn), meta.num, ctx.cfg, _ptr(g2), _ptr(coef), _ptr(dy), _stream())
+        _L.check(st, 'brcnn_rpn_sampled_loss_backward')
+        return dy, None, None, None, None, None, None
+
+
+def rpn_sampled_loss(y, gt_inds, gts, drawn, meta, num_total_samples, workspace=None):
+    """(2,) tensor [loss_rpn_cls, loss_rpn_bbox], differentiable w.r.t. y"""
+    return RPNSampledLossFunction.apply(y, gt_inds, gts, drawn, workspace, meta, num_total_samples)
+
+
 # ----------------------------------------------------------------------------- boosting loss
 class BoostLossFunction(Function):
     """out3 = [loss_cls, loss_bbox, acc] of the boosting-reweighted R-CNN loss

@@ -843,6 +843,16 @@ int brcnn_rcnn_decode(const float *probs, const float *bbox_pred, const float *p
                       double wh_ratio_clip, float *boxes, float *scores, int64_t *labels, uint8_t *valid,
                       void *stream);
 
+/* The un-fused form for the standard head (BBoxHead.get_bboxes, bbox_heads/bbox_head.py:317-379): same
+ * layout and outputs as brcnn_rcnn_decode, but scores = prob (the softmax alone; column 4 of the
+ * proposals is not read), and with reg_class_agnostic != 0 bbox_pred is (batch*per_image, 4) and every
+ * class of a proposal reads that one box. */
+int brcnn_rcnn_decode_plain(const float *probs, const float *bbox_pred, const float *proposals, const int32_t *num,
+                            const float *max_shape, const float *scale_factor, int batch, int per_image,
+                            int num_classes, int reg_class_agnostic, float score_thr, const float *means4_host,
+                            const float *stds4_host, double wh_ratio_clip, float *boxes, float *scores,
+                            int64_t *labels, uint8_t *valid, void *stream);
+
 /* ------------------------------------------------------------------------------
  * Test-time augmentation (multi-scale + flip), whole batch, no host round trip: the device form of
  * TwoStageDetector.aug_test (detectors/two_stage.py:184-193).  Per-(aug, image) geometry is one device
@@ -1043,6 +1053,39 @@ int brcnn_rcnn_sample(const float *proposals, const int32_t *num_props, int per_
                       const float *means4_host, const float *stds4_host, int32_t *list_ws,
                       int list_stride, float *rois, int64_t *labels, float *bbox_targets, float *priors,
                       float *ious, int32_t *pos_flags, void *stream);
+/* The sampled RPN loss of the Faster R-CNN baseline (RPNHead: AnchorHead.loss with a RandomSampler,
+ * dense_heads/anchor_head.py:373-497, samplers/random_sampler.py:32-82).  y (rows, ystride) is the fused
+ * head output of all levels, level-major rows, columns [objectness A | deltas 4A | padding]; gt_inds
+ * (batch, n) from brcnn_assign_max_iou on the n anchors of an image.
+ *   brcnn_rpn_sampled_draw: compacts every image's positive / negative candidates in index order and
+ *     gathers the host-drawn picks (perm (batch, num_expected_pos + num) int32, the contract of
+ *     brcnn_rcnn_sample) into drawn (batch, num) int32: positives, then negatives, then -1.
+ *   brcnn_rpn_sampled_loss_forward / _finalize: losses2 = [loss_rpn_cls, loss_rpn_bbox] =
+ *     loss_weight * sum over the drawn anchors of [w * bce_with_logits(x, is_pos), is_pos * sum_4
+ *     l1 | smooth_l1_beta(pred - bbox2delta(anchor, gt))] / num_total_samples; coef2 keeps the two scale
+ *     factors for the backward pass.  Fixed summation order, no float atomics.
+ *   brcnn_rpn_sampled_loss_backward: dy (rows, ystride), zero wherever no drawn anchor reads y.
+ * cfg13_host = [pos_weight (<= 0: 1), smooth_l1_beta (0: L1), means x4, stds x4, loss_weight_cls,
+ * loss_weight_bbox, num_total_samples].  workspace: brcnn_rpn_sampled_workspace_bytes, shared by draw,
+ * forward and finalize of one step. */
+size_t brcnn_rpn_sampled_workspace_bytes(int batch, int anchors_per_image, int num);
+int brcnn_rpn_sampled_draw(const int32_t *gt_inds, int anchors_per_image, int batch, int num,
+                           int num_expected_pos, float neg_pos_ub, const int32_t *perm, void *workspace,
+                           size_t workspace_bytes, int32_t *drawn, void *stream);
+int brcnn_rpn_sampled_loss_forward(const float *y, int ystride, int batch, int num_levels, const int *heights,
+                                   const int *widths, const int *strides_w, const int *strides_h,
+                                   const float *const *base_anchors, int anchors_per_cell,
+                                   const int32_t *gt_inds, const float *gts, const int *gt_offsets_host,
+                                   const int32_t *drawn, int num, const float *cfg13_host, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+int brcnn_rpn_sampled_loss_finalize(const void *workspace, int batch, int anchors_per_image, int num,
+                                    const float *cfg13_host, float *losses2, float *coef2, void *stream);
+int brcnn_rpn_sampled_loss_backward(const float *y, int ystride, int batch, int num_levels, const int *heights,
+                                    const int *widths, const int *strides_w, const int *strides_h,
+                                    const float *const *base_anchors, int anchors_per_cell,
+                                    const int32_t *gt_inds, const float *gts, const int *gt_offsets_host,
+                                    const int32_t *drawn, int num, const float *cfg13_host, const float *g2,
+                                    const float *coef2, float *dy, void *stream);
 size_t brcnn_rpn_loss_workspace_bytes(int batch, int num_levels, const int *heights, const int *widths,
                                       int anchors_per_cell);
 int brcnn_rpn_loss_forward(const float *y, int ystride, int batch, int num_levels, const int *heights,
