@@ -223,6 +223,7 @@ struct SampleParams {
     float* priors;             // (N)
     float* ious;               // (N) or NULL
     int* pos_flags;            // (N) 1 = positive row, or NULL
+    int* gt_flags;             // (N) 1 = a ground truth the sampler added (SamplingResult.pos_is_gt), or NULL
 };
 
 constexpr int SAMPLE_MAX = 2048;       // sampler.num is at most this
@@ -357,6 +358,7 @@ __global__ __launch_bounds__(1024) void rcnn_sample_kernel(const SampleParams p)
         p.priors[r] = prior;
         if (p.ious) p.ious[r] = is_pos ? mo : 1.f - mo;
         if (p.pos_flags) p.pos_flags[r] = is_pos ? 1 : 0;
+        if (p.gt_flags) p.gt_flags[r] = (is_pos && idx < Gadd) ? 1 : 0;
     }
 }
 
@@ -459,14 +461,14 @@ BRCNN_API int brcnn_assign_max_iou(const float* boxes, int64_t box_batch_stride,
     return 0;
 }
 
-BRCNN_API int brcnn_rcnn_sample(const float* proposals, const int32_t* num_props, int per_image, int batch,
-                                const int32_t* gt_inds, const float* max_overlaps, const float* gts,
-                                const int64_t* gt_labels, const int* gt_offsets_host, int add_gt_as_proposals,
-                                int num, int num_expected_pos, float neg_pos_ub, const int32_t* perm,
-                                const int* row_offsets_host, int num_classes, int reg_decoded_bbox,
-                                const float* means4_host, const float* stds4_host, int32_t* list_ws,
-                                int list_stride, float* rois, int64_t* labels, float* bbox_targets, float* priors,
-                                float* ious, int32_t* pos_flags, void* stream) {
+static int rcnn_sample_impl(const float* proposals, const int32_t* num_props, int per_image, int batch,
+                            const int32_t* gt_inds, const float* max_overlaps, const float* gts,
+                            const int64_t* gt_labels, const int* gt_offsets_host, int add_gt_as_proposals,
+                            int num, int num_expected_pos, float neg_pos_ub, const int32_t* perm,
+                            const int* row_offsets_host, int num_classes, int reg_decoded_bbox,
+                            const float* means4_host, const float* stds4_host, int32_t* list_ws,
+                            int list_stride, float* rois, int64_t* labels, float* bbox_targets, float* priors,
+                            float* ious, int32_t* pos_flags, int32_t* gt_flags, void* stream) {
     if (!proposals || !num_props || !gt_inds || !perm || !row_offsets_host || !list_ws || !rois || !labels ||
         !bbox_targets || !priors || per_image <= 0 || num <= 0 || num > SAMPLE_MAX || num_expected_pos < 0 ||
         num_expected_pos > num || !means4_host || !stds4_host)
@@ -485,8 +487,39 @@ BRCNN_API int brcnn_rcnn_sample(const float* proposals, const int32_t* num_props
     for (int k = 0; k < 4; k++) { p.mean[k] = means4_host[k]; p.std[k] = stds4_host[k]; }
     p.lists = list_ws; p.list_stride = list_stride;
     p.rois = rois; p.labels = (long long*)labels; p.bbox_targets = bbox_targets; p.priors = priors; p.ious = ious;
-    p.pos_flags = pos_flags;
+    p.pos_flags = pos_flags; p.gt_flags = gt_flags;
     hipLaunchKernelGGL(rcnn_sample_kernel, dim3(batch), dim3(1024), 0, (hipStream_t)stream, p);
     BRCNN_LAUNCH_CHECK();
     return 0;
+}
+
+BRCNN_API int brcnn_rcnn_sample(const float* proposals, const int32_t* num_props, int per_image, int batch,
+                                const int32_t* gt_inds, const float* max_overlaps, const float* gts,
+                                const int64_t* gt_labels, const int* gt_offsets_host, int add_gt_as_proposals,
+                                int num, int num_expected_pos, float neg_pos_ub, const int32_t* perm,
+                                const int* row_offsets_host, int num_classes, int reg_decoded_bbox,
+                                const float* means4_host, const float* stds4_host, int32_t* list_ws,
+                                int list_stride, float* rois, int64_t* labels, float* bbox_targets, float* priors,
+                                float* ious, int32_t* pos_flags, void* stream) {
+    return rcnn_sample_impl(proposals, num_props, per_image, batch, gt_inds, max_overlaps, gts, gt_labels, gt_offsets_host,
+                            add_gt_as_proposals, num, num_expected_pos, neg_pos_ub, perm, row_offsets_host, num_classes,
+                            reg_decoded_bbox, means4_host, stds4_host, list_ws, list_stride, rois, labels, bbox_targets,
+                            priors, ious, pos_flags, nullptr, stream);
+}
+
+// the same launch, which also writes gt_flags (N): 1 where the row is a ground truth box the sampler added as a
+// proposal (SamplingResult.pos_is_gt, sampling_result.py:32; the rows BBoxHead.refine_bboxes drops)
+BRCNN_API int brcnn_rcnn_sample_gt(const float* proposals, const int32_t* num_props, int per_image, int batch,
+                                   const int32_t* gt_inds, const float* max_overlaps, const float* gts,
+                                   const int64_t* gt_labels, const int* gt_offsets_host, int add_gt_as_proposals,
+                                   int num, int num_expected_pos, float neg_pos_ub, const int32_t* perm,
+                                   const int* row_offsets_host, int num_classes, int reg_decoded_bbox,
+                                   const float* means4_host, const float* stds4_host, int32_t* list_ws,
+                                   int list_stride, float* rois, int64_t* labels, float* bbox_targets, float* priors,
+                                   float* ious, int32_t* pos_flags, int32_t* gt_flags, void* stream) {
+    if (!gt_flags) return BRCNN_EINVAL;
+    return rcnn_sample_impl(proposals, num_props, per_image, batch, gt_inds, max_overlaps, gts, gt_labels, gt_offsets_host,
+                            add_gt_as_proposals, num, num_expected_pos, neg_pos_ub, perm, row_offsets_host, num_classes,
+                            reg_decoded_bbox, means4_host, stds4_host, list_ws, list_stride, rois, labels, bbox_targets,
+                            priors, ious, pos_flags, gt_flags, stream);
 }

@@ -426,7 +426,7 @@ class TwoStageDetector(BaseDetector):
         if proposals is None and self._device_path_ok():
             det, lab, nd = self.simple_test_device(img, img_metas, rescale)
             det, lab, nd = det.cpu(), lab.cpu(), nd.tolist()   # the one host sync
-            nc = self.roi_head.bbox_head.num_classes
+            nc = self.roi_head.num_classes
             return [bbox2result(det[i, :nd[i]], lab[i, :nd[i]], nc) for i in range(len(img_metas))]
         x = self.extract_feat(img)
         proposal_list = self.rpn_head.simple_test_rpn(x, img_metas) if proposals is None else proposals
@@ -476,7 +476,7 @@ class TwoStageDetector(BaseDetector):
             # boxes, labels and counts leave in ONE copy, the one host sync (class ids and counts are exact in fp32)
             host = torch.cat([det.reshape(B, M * 5), lab.to(det.dtype), nd.to(det.dtype).reshape(B, 1)], dim=1).cpu()
             det, lab, nd = host[:, :M * 5].reshape(B, M, 5), host[:, M * 5:M * 6].long(), host[:, M * 6].long().tolist()
-            nc = self.roi_head.bbox_head.num_classes
+            nc = self.roi_head.num_classes
             return [bbox2result(det[i, :nd[i]], lab[i, :nd[i]], nc) for i in range(B)]
         x = [self.extract_feat(img) for img in imgs]
         proposal_list = self.rpn_head.aug_test_rpn(x, img_metas)
@@ -485,7 +485,7 @@ class TwoStageDetector(BaseDetector):
     def _device_path_ok(self):
         rc, rp = self.test_cfg.rcnn, self.test_cfg.rpn
         typ = rc.nms.get('type', 'nms')
-        split = rp.max_per_img * self.roi_head.bbox_head.num_classes >= rc.nms.get('split_thr', 10000)
+        split = rp.max_per_img * self.roi_head.num_classes >= rc.nms.get('split_thr', 10000)
         return (typ == 'nms' or (typ == 'soft_nms' and split)) and rp.nms.get('type', 'nms') == 'nms' and \
             not rc.nms.get('class_agnostic', False) and getattr(self.roi_head, 'device_test_path', True)
 
@@ -496,6 +496,18 @@ class FasterRCNN(TwoStageDetector):
     same file are outside the hot path)."""
 
     def __init__(self, backbone, rpn_head, roi_head, train_cfg, test_cfg, neck=None,
+                 pretrained=None, init_cfg=None):
+        super().__init__(backbone=backbone, neck=neck, rpn_head=rpn_head, roi_head=roi_head,
+                         train_cfg=train_cfg, test_cfg=test_cfg, pretrained=pretrained,
+                         init_cfg=init_cfg)
+
+
+@DETECTORS.register_module()
+class CascadeRCNN(TwoStageDetector):
+    """mmdet/models/detectors/cascade_rcnn.py:6-24: a TwoStageDetector whose RoI head is a CascadeRoIHead (the
+    reference's `show_result` override is a visualisation helper and not part of the model)."""
+
+    def __init__(self, backbone, neck=None, rpn_head=None, roi_head=None, train_cfg=None, test_cfg=None,
                  pretrained=None, init_cfg=None):
         super().__init__(backbone=backbone, neck=neck, rpn_head=rpn_head, roi_head=roi_head,
                          train_cfg=train_cfg, test_cfg=test_cfg, pretrained=pretrained,

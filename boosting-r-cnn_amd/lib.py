@@ -180,6 +180,13 @@ SIGNATURES = {
     'brcnn_rpn_sampled_loss_finalize': (c_int, [c_ptr, c_int, c_int, c_int, c_ptr, c_ptr, c_ptr, c_ptr]),
     'brcnn_rpn_sampled_loss_backward': (c_int, [c_ptr, c_int, c_int, c_int] + [c_ptr] * 5 + [c_int] + [c_ptr] * 4 +
                                         [c_int] + [c_ptr] * 5),
+    'brcnn_rcnn_sample_gt': (c_int, [c_ptr, c_ptr, c_int, c_int] + [c_ptr] * 5 + [c_int, c_int, c_int, c_f32, c_ptr, c_ptr,
+                                     c_int, c_int, c_ptr, c_ptr, c_ptr, c_int] + [c_ptr] * 8),
+    'brcnn_cascade_refine_test': (c_int, [c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr] + [c_int] * 5 +
+                                  [c_ptr, c_ptr, c_f64, c_ptr, c_ptr, c_ptr]),
+    'brcnn_cascade_mean_softmax': (c_int, [c_ptr, c_ptr, c_int, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr]),
+    'brcnn_cascade_refine_train': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_ptr, c_int, c_int,
+                                           c_ptr, c_ptr, c_f64, c_int, c_ptr, c_ptr, c_ptr]),
     'brcnn_coco_order_workspace_bytes': (c_size, [c_i64]),
     'brcnn_coco_match': (c_int, [c_ptr] * 6 + [c_int, c_int, c_ptr, c_int, c_ptr, c_int, c_int] + [c_ptr] * 7),
     'brcnn_coco_order': (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_size, c_ptr]),

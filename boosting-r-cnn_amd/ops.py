@@ -1227,6 +1227,65 @@ def rcnn_decode_plain(probs, bbox_pred, dets, num, max_shape, scale_factor, num_
     return boxes, scores, labels, valid
 
 
+# --------------------------------------------------------------------------- Cascade R-CNN, test time
+def _rows_in_place(t):
+    """a fp32 (rows, cols) device tensor the cascade kernels read with a row stride: the two column blocks of the heads'
+    fused output go in as they are, anything else is made dense first"""
+    assert t.dim() == 2 and t.dtype == torch.float32
+    if t.shape[1] > 1 and t.stride(1) != 1 or t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1]))
+
+
+def cascade_refine_test(dets, num, cls_score, bbox_pred, max_shape, num_classes, means, stds, reg_class_agnostic=False,
+                        logit_sum=None, wh_ratio_clip=16 / 1000):
+    """The between-stage step of CascadeRoIHead.simple_test for a whole batch (brcnn_cascade_refine_test): dets (B,K,5)
+    zero padded / num (B,) int32, cls_score (B*K, C+1) raw logits, bbox_pred (B*K, 4 | 4C), max_shape (B,2).  Every
+    real row is regressed by its arg-max foreground class and clipped.  `logit_sum` None: this is the first stage and
+    a new (B*K, C+1) sum = cls_score is returned; else cls_score is added into it in place.
+    Returns (dets_out (B,K,5) [boxes, 0], logit_sum)."""
+    import ctypes
+    _require_gpu(dets, num, cls_score, bbox_pred, max_shape, logit_sum)
+    B, K, five = dets.shape
+    C = int(num_classes)
+    assert five == 5 and dets.dtype == torch.float32 and dets.is_contiguous()
+    assert cls_score.shape == (B * K, C + 1) and bbox_pred.shape == (B * K, 4 if reg_class_agnostic else 4 * C)
+    assert num.dtype == torch.int32 and num.shape == (B,) and num.is_contiguous()
+    assert max_shape.shape == (B, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
+    cls_score, cs = _rows_in_place(cls_score)
+    bbox_pred, rs = _rows_in_place(bbox_pred)
+    first = logit_sum is None
+    if first:
+        logit_sum = torch.empty((B * K, C + 1), dtype=torch.float32, device=dets.device)
+    assert logit_sum.shape == (B * K, C + 1) and logit_sum.dtype == torch.float32 and logit_sum.is_contiguous()
+    out = torch.empty_like(dets)
+    m4 = (ctypes.c_float * 4)(*[float(v) for v in means])
+    s4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    st = _L.load().brcnn_cascade_refine_test(_ptr(dets), _ptr(num), _ptr(cls_score), cs, _ptr(bbox_pred), rs, _ptr(max_shape),
+                                             B, K, C, int(bool(reg_class_agnostic)), int(first), m4, s4,
+                                             float(wh_ratio_clip), _ptr(out), _ptr(logit_sum), _stream())
+    _L.check(st, 'brcnn_cascade_refine_test')
+    return out, logit_sum
+
+
+def cascade_mean_softmax(logit_sum, cls_score_last, num_stages, want_mean=False):
+    """probs (rows, C+1) = softmax((logit_sum + cls_score_last) / float(num_stages)) (brcnn_cascade_mean_softmax): the
+    stage ensemble of CascadeRoIHead.simple_test and the softmax of the last head's get_bboxes in one launch.
+    `logit_sum` is None for a single stage.  `want_mean`: returns (probs, the averaged logits) instead."""
+    _require_gpu(logit_sum, cls_score_last)
+    rows, cols = cls_score_last.shape
+    assert (logit_sum is None) == (int(num_stages) == 1)
+    if logit_sum is not None:
+        assert logit_sum.shape == (rows, cols) and logit_sum.dtype == torch.float32 and logit_sum.is_contiguous()
+    cls_score_last, cs = _rows_in_place(cls_score_last)
+    probs = torch.empty((rows, cols), dtype=torch.float32, device=cls_score_last.device)
+    mean = torch.empty_like(probs) if want_mean else None
+    st = _L.load().brcnn_cascade_mean_softmax(_ptr(logit_sum), _ptr(cls_score_last), cs, rows, cols - 1, int(num_stages),
+                                              _ptr(probs), _ptr(mean), _stream())
+    _L.check(st, 'brcnn_cascade_mean_softmax')
+    return (probs, mean) if want_mean else probs
+
+
 # --------------------------------------------------------------------------- input front door
 _FLIP_CODE = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}
 

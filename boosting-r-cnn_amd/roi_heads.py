@@ -494,6 +494,12 @@ class ProbRoIHead(nn.Module):
             not h.reg_decoded_bbox and self.train_cfg.pos_weight <= 0 and self.bbox_roi_extractor._fusable())
 
     _needs_overlaps = False     # (DyProbRoIHead: the assignment's max_overlaps also without `quality`)
+    _want_gt_flags = False      # (CascadeRoIHead: which sampled rows are added ground truth, for the refinement)
+
+    @property
+    def num_classes(self):
+        """foreground classes of the detections this head returns (the detector shapes its results by it)"""
+        return self.bbox_head.num_classes
 
     def sample_device(self, dets, num, gt_flat, overlap_work=None, proposal_stream=None):
         """assignment + RandomSampler + targets + priors of the whole batch (prob_roi_head.py:23-69,
@@ -550,7 +556,8 @@ class ProbRoIHead(nn.Module):
         out = train_ops.rcnn_sample(dets, num, gt_inds, mo, gts, gt_labels, offs, perm_dev, rows, sp.num, num_pos,
                                     sp.neg_pos_ub, self.bbox_head.num_classes, coder.means, coder.stds,
                                     add_gt_as_proposals=sp.add_gt_as_proposals,
-                                    reg_decoded_bbox=self.bbox_head.reg_decoded_bbox, want_ious=self.quality)
+                                    reg_decoded_bbox=self.bbox_head.reg_decoded_bbox, want_ious=self.quality,
+                                    want_gt_flags=self._want_gt_flags)
         out['rows'] = rows
         # host-side knowledge of the draw: sampled positives of the batch, the proposals' overlaps (DyProbRoIHead)
         out['num_pos_host'] = sum(train_ops.sample_counts(p_, n_, sp.num, num_pos, sp.neg_pos_ub)[0] for p_, n_ in cnt)
@@ -979,6 +986,293 @@ class StandardRoIHead(ProbRoIHead):
         bb, sc, lb, va = ops.rcnn_decode_plain(cls_score.float().softmax(1), bbox_pred, dets, num, max_shape, sf, C,
                                                cfg.score_thr, coder.means, coder.stds,
                                                reg_class_agnostic=head.reg_class_agnostic)
+        if K * C >= nms_cfg.get('split_thr', 10000):
+            # mmcv's per-class branch: class-major slots, one segmented NMS launch over (image, class); same boxes, same order
+            from .postprocess import batched_nms_images_by_level
+            cm = lambda t: t.view(B, K, C, *t.shape[2:]).transpose(1, 2).reshape(B, C * K, *t.shape[2:]).contiguous()   # noqa: E731
+            return batched_nms_images_by_level(cm(bb), cm(sc), cm(lb), cm(va), [K] * C, nms_cfg['iou_threshold'],
+                                               cfg.max_per_img, nms_cfg.get('offset', 0), return_ids=True)
+        return batched_nms_images(bb, sc, lb, va, nms_cfg['iou_threshold'], cfg.max_per_img, nms_cfg.get('offset', 0))
+
+    # ---- test-time augmentation: out of scope for this head ------------------------------
+    supports_tta = False
+
+    def tta_device_ok(self, feats_nhwc=None):
+        return False
+
+    def aug_test(self, x, proposal_list, img_metas, rescale=False):
+        raise NotImplementedError(f'{type(self).__name__} has no test-time augmentation')
+
+    aug_test_padded = aug_test_bboxes = aug_test
+
+
+# ----------------------------------------------------------------------------- Cascade R-CNN baseline
+class _CascadeStage:
+    """One stage of a CascadeRoIHead as the whole-batch sampler sees a RoI head (`ProbRoIHead.sample_device` reads the
+    assigner, the sampler, the head and its own pinned host buffers off `self`): every stage has its own sampler and so
+    its own `_count_host` buffers, sized for that sampler.  Not a Module: the heads stay registered once, in the
+    CascadeRoIHead's ModuleLists."""
+    quality = False
+    _needs_overlaps = False
+
+    def __init__(self, assigner, sampler, head, extractor, train_cfg, want_gt_flags):
+        self.bbox_assigner, self.bbox_sampler, self.bbox_head, self.bbox_roi_extractor = assigner, sampler, head, extractor
+        self.train_cfg, self._want_gt_flags = train_cfg, want_gt_flags
+
+    sample_device = ProbRoIHead.sample_device
+    _device_common_ok = ProbRoIHead._device_common_ok
+
+
+@HEADS.register_module()
+class CascadeRoIHead(nn.Module):
+    """roi_heads/cascade_roi_head.py:15-400 without masks: `num_stages` x (extractor, box head, assigner, sampler); each
+    stage is trained on the boxes the stage before it regressed (BBoxHead.refine_bboxes), its loss weighted by
+    `stage_loss_weights`; at test time the boxes pass through every stage and the stages' logits are averaged before
+    the last head's get_bboxes.  Module layout and parameter names are the reference's (`bbox_head.{i}.shared_fcs...`,
+    `bbox_roi_extractor.{i}`).  On the device the hand-over between two stages is one launch (csrc/cascade.hip)."""
+
+    def __init__(self, num_stages, stage_loss_weights, bbox_roi_extractor=None, bbox_head=None, mask_roi_extractor=None,
+                 mask_head=None, shared_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__()
+        assert bbox_roi_extractor is not None and bbox_head is not None
+        for name, val in (('mask_head', mask_head), ('mask_roi_extractor', mask_roi_extractor), ('shared_head', shared_head)):
+            if val is not None:
+                raise NotImplementedError(f'CascadeRoIHead: {name} is not supported (box heads only)')
+        self.num_stages, self.stage_loss_weights = int(num_stages), list(stage_loss_weights)
+        assert len(self.stage_loss_weights) == self.num_stages >= 1
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        per_stage = lambda c: list(c) if isinstance(c, (list, tuple)) else [c for _ in range(self.num_stages)]  # noqa: E731
+        extractors, heads = per_stage(bbox_roi_extractor), per_stage(bbox_head)
+        assert len(extractors) == len(heads) == self.num_stages
+        self.bbox_roi_extractor = nn.ModuleList(build_roi_extractor(e) for e in extractors)
+        self.bbox_head = nn.ModuleList(build_head(h) for h in heads)
+        for i, h in enumerate(self.bbox_head):
+            if not isinstance(h, ConvFCBBoxHead):
+                raise TypeError(f'CascadeRoIHead needs softmax box heads (BBoxHead / ConvFCBBoxHead family), got '
+                                f'{type(h).__name__} at stage {i}')
+            if h.custom_activation:
+                raise NotImplementedError(f'CascadeRoIHead: a box head with custom_activation (stage {i}) is not supported')
+            if h.num_classes != self.bbox_head[0].num_classes:
+                raise ValueError('CascadeRoIHead: every stage must have the same num_classes')
+            coder = h.bbox_coder
+            if getattr(coder, 'add_ctr_clamp', False) or not getattr(coder, 'clip_border', True):
+                raise NotImplementedError(f'CascadeRoIHead: stage {i} needs a DeltaXYWHBBoxCoder with clip_border=True and '
+                                          f'without add_ctr_clamp (the refinement between stages clips to the image)')
+        self.bbox_assigner, self.bbox_sampler = [], []
+        if self.train_cfg is not None:
+            assert isinstance(self.train_cfg, (list, tuple)) and len(self.train_cfg) == self.num_stages, \
+                'CascadeRoIHead: train_cfg is a list with one assigner + sampler per stage'
+            for i, cfg in enumerate(self.train_cfg):
+                self.bbox_assigner.append(build_assigner(cfg.assigner))
+                self.current_stage = i
+                self.bbox_sampler.append(build_sampler(cfg.sampler, context=self))
+        if self.test_cfg is not None:
+            self._check_test_cfg()
+
+    with_bbox = True
+    with_mask = False
+    with_shared_head = False
+
+    @property
+    def num_classes(self):
+        return self.bbox_head[-1].num_classes
+
+    def _check_test_cfg(self):
+        nms_cfg = self.test_cfg.nms
+        if nms_cfg.get('type', 'nms') != 'nms':
+            raise NotImplementedError(f"CascadeRoIHead: test_cfg.nms type {nms_cfg.get('type')!r} is not supported "
+                                      f"(greedy 'nms' only)")
+        if nms_cfg.get('class_agnostic', False):
+            raise NotImplementedError('CascadeRoIHead: test_cfg.nms class_agnostic=True is not supported')
+
+    # ---- shared pieces -------------------------------------------------------------------
+    def _bbox_forward(self, stage, x, rois):
+        ex = self.bbox_roi_extractor[stage]
+        bbox_feats = ex(x[:ex.num_inputs], rois)
+        cls_score, bbox_pred = self.bbox_head[stage](bbox_feats)
+        return dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_feats)
+
+    def regress_by_class(self, stage, rois, label, bbox_pred, img_meta):
+        """bbox_head.py:461-498: rois (n, 4 | 5) regressed by the deltas of `label`, clipped to the image"""
+        head = self.bbox_head[stage]
+        bbox_pred = bbox_pred.float()
+        if not head.reg_class_agnostic:
+            label = label * 4
+            bbox_pred = torch.gather(bbox_pred, 1, torch.stack((label, label + 1, label + 2, label + 3), 1))
+        assert bbox_pred.size(1) == 4
+        max_shape = img_meta['img_shape']
+        if rois.size(1) == 4:
+            return head.bbox_coder.decode(rois, bbox_pred, max_shape=max_shape)
+        bboxes = head.bbox_coder.decode(rois[:, 1:], bbox_pred, max_shape=max_shape)
+        return torch.cat((rois[:, [0]], bboxes), dim=1)
+
+    def refine_bboxes(self, stage, rois, labels, bbox_preds, pos_is_gts, img_metas):
+        """bbox_head.py:382-458: per image the sampled rois regressed by their labels, the added ground truths dropped"""
+        bboxes_list = []
+        for i in range(len(img_metas)):
+            inds = torch.nonzero(rois[:, 0] == i, as_tuple=False).squeeze(dim=1)
+            bboxes = self.regress_by_class(stage, rois[inds, 1:], labels[inds], bbox_preds[inds], img_metas[i])
+            keep = pos_is_gts[i].new_ones(inds.numel())
+            keep[:len(pos_is_gts[i])] = 1 - pos_is_gts[i]
+            bboxes_list.append(bboxes[keep.type(torch.bool)])
+        return bboxes_list
+
+    # ---- train: the host mirror (cascade_roi_head.py:191-286) -------------------------------
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+        losses = dict()
+        num_imgs = len(img_metas)
+        if gt_bboxes_ignore is None:
+            gt_bboxes_ignore = [None for _ in range(num_imgs)]
+        for i in range(self.num_stages):
+            self.current_stage = i
+            head, lw = self.bbox_head[i], self.stage_loss_weights[i]
+            sampling_results = []
+            for j in range(num_imgs):
+                assign_result = self.bbox_assigner[i].assign(proposal_list[j], gt_bboxes[j], gt_bboxes_ignore[j], gt_labels[j])
+                sampling_results.append(self.bbox_sampler[i].sample(assign_result, proposal_list[j], gt_bboxes[j], gt_labels[j],
+                                                                    feats=[lvl[j][None] for lvl in x]))
+            rois = bbox2roi([res.bboxes for res in sampling_results])
+            bbox_results = self._bbox_forward(i, x, rois)
+            bbox_targets = head.get_targets(sampling_results, gt_bboxes, gt_labels, self.train_cfg[i])
+            for name, value in head.loss(bbox_results['cls_score'], bbox_results['bbox_pred'], rois, *bbox_targets).items():
+                losses[f's{i}.{name}'] = value * lw if 'loss' in name else value
+            if i < self.num_stages - 1:
+                with torch.no_grad():
+                    cls_score = bbox_results['cls_score']
+                    if cls_score.numel() == 0:      # (no proposal in the whole batch)
+                        break
+                    roi_labels = bbox_targets[0]
+                    roi_labels = torch.where(roi_labels == head.num_classes, cls_score[:, :-1].argmax(1), roi_labels)
+                    proposal_list = self.refine_bboxes(i, rois, roi_labels, bbox_results['bbox_pred'],
+                                                       [res.pos_is_gt for res in sampling_results], img_metas)
+        return losses
+
+    # ---- train: device-resident ----------------------------------------------------------------
+    def _stage(self, i):
+        stages = self.__dict__.get('_stages')
+        if stages is None:
+            stages = self.__dict__['_stages'] = [
+                _CascadeStage(self.bbox_assigner[s], self.bbox_sampler[s], self.bbox_head[s], self.bbox_roi_extractor[s],
+                              self.train_cfg[s], s < self.num_stages - 1) for s in range(self.num_stages)]
+        return stages[i]
+
+    def device_train_ok(self):
+        """every stage within what the whole-batch assignment / sampling / plain loss kernels cover"""
+        from .losses import L1Loss
+        return bool(type(self) is CascadeRoIHead and self.train_cfg is not None and
+                    all(self._stage(i)._device_common_ok() and type(self.bbox_head[i].loss_bbox) in (L1Loss, SmoothL1Loss)
+                        for i in range(self.num_stages)))
+
+    def forward_train_device(self, feats_nhwc, img_metas, dets, num, gt_flat, overlap_work=None, proposal_stream=None):
+        """forward_train on the padded device proposals; returns (losses, overlap_work's result).  Per stage: the
+        whole-batch sampler (ONE blocking host read, the candidate counts the host `randperm` stream needs; stage i's
+        draws precede stage i+1's, as in the reference), extractor, head, the plain loss kernels, then ONE launch that
+        turns the sampled rows into the next stage's padded proposals (brcnn_cascade_refine_train, no host read)."""
+        from . import autograd as _A, train_ops
+        losses, extra, max_shape, samples = dict(), None, None, []
+        for i in range(self.num_stages):
+            head, lw = self.bbox_head[i], self.stage_loss_weights[i]
+            smp, ex = self._stage(i).sample_device(dets, num, gt_flat, overlap_work if i == 0 else None,
+                                                   proposal_stream if i == 0 else None)
+            stage_mark('sampler')
+            if i == 0:
+                extra = ex
+                if callable(feats_nhwc):
+                    feats_nhwc = feats_nhwc()
+            samples.append(smp)
+            if smp['rows'][-1] == 0:        # (no proposal in the whole batch: the reference stops here too)
+                break
+            roi_feats = self.bbox_roi_extractor[i].forward_nhwc(feats_nhwc, smp['rois'])
+            stage_mark('roi_align')
+            cls_score, bbox_pred = head.forward_nhwc(roi_feats)
+            stage_mark('fc_head')
+            if i == 0:
+                _A.release_held_weight_gradients()
+            out3 = train_ops.boost_loss(cls_score, bbox_pred, smp['labels'], torch.zeros_like(smp['priors']),
+                                        smp['bbox_targets'], head.num_classes, 0.0, 0.0, None, 0.0, head.loss_cls.loss_weight,
+                                        head.loss_bbox.loss_weight, 'bbox_num', head.reg_class_agnostic,
+                                        plain_label_weights=True, smooth_l1_beta=getattr(head.loss_bbox, 'beta', 0.0))
+            stage_mark('boost_loss')
+            losses[f's{i}.loss_cls'], losses[f's{i}.loss_bbox'] = out3[0] * lw, out3[1] * lw
+            losses[f's{i}.acc'] = out3[2].reshape(1)
+            if i < self.num_stages - 1:
+                if max_shape is None:
+                    max_shape = const_rows([m['img_shape'][:2] for m in img_metas], dets)
+                coder = head.bbox_coder
+                with torch.no_grad():
+                    dets, num = train_ops.cascade_refine_train(
+                        smp['rois'], smp['labels'], smp['gt_flags'], smp['rows'], cls_score, bbox_pred, max_shape,
+                        head.num_classes, coder.means, coder.stds, reg_class_agnostic=head.reg_class_agnostic)
+                stage_mark('cascade_refine')
+        self.last_samples = samples
+        return losses, extra
+
+    # ---- test: the host mirror (cascade_roi_head.py:288-400) -------------------------------------
+    def simple_test(self, x, proposal_list, img_metas, proposals=None, rescale=False):
+        num_imgs = len(proposal_list)
+        last = self.bbox_head[-1]
+        rois = bbox2roi(proposal_list)
+        if rois.shape[0] == 0:
+            return [[np.zeros((0, 5), dtype=np.float32) for _ in range(last.num_classes)]] * num_imgs
+        per_img = tuple(len(p) for p in proposal_list)
+        ms_scores = []
+        for i in range(self.num_stages):
+            bbox_results = self._bbox_forward(i, x, rois)
+            rois = rois.split(per_img, 0)
+            cls_score = bbox_results['cls_score'].split(per_img, 0)
+            bbox_pred = bbox_results['bbox_pred'].split(per_img, 0)
+            ms_scores.append(cls_score)
+            if i < self.num_stages - 1:
+                refined = []
+                for j in range(num_imgs):
+                    if rois[j].shape[0] > 0:
+                        refined.append(self.regress_by_class(i, rois[j], cls_score[j][:, :-1].argmax(dim=1), bbox_pred[j],
+                                                             img_metas[j]))
+                rois = torch.cat(refined)
+        cls_score = [sum([score[i] for score in ms_scores]) / float(len(ms_scores)) for i in range(num_imgs)]
+        results = []
+        for i in range(num_imgs):
+            if rois[i].shape[0] == 0:
+                results.append([np.zeros((0, 5), dtype=np.float32) for _ in range(last.num_classes)])
+                continue
+            det_bbox, det_label = last.get_bboxes(rois[i], cls_score[i], bbox_pred[i], img_metas[i]['img_shape'],
+                                                  img_metas[i]['scale_factor'], rescale=rescale, cfg=self.test_cfg)
+            results.append(bbox2result(det_bbox, det_label, last.num_classes))
+        return results
+
+    # ---- test: device-resident ---------------------------------------------------------------------
+    def simple_test_padded(self, feats_nhwc, dets, num, img_metas, rescale=False):
+        """simple_test for the whole batch on the device, no host sync: `num_stages` x (extractor, box head) with ONE
+        launch between two stages (arg-max class, regress, clip, logits accumulated: brcnn_cascade_refine_test), then
+        the mean of the stages' logits + softmax (brcnn_cascade_mean_softmax), the per-class decode of the last stage
+        (brcnn_rcnn_decode_plain) and the batched NMS.  Returns what StandardRoIHead.simple_test_padded returns."""
+        self._check_test_cfg()
+        cfg = self.test_cfg
+        nms_cfg = dict(cfg.nms)
+        nms_cfg.pop('type', 'nms')
+        B, K, _ = dets.shape
+        last = self.bbox_head[-1]
+        C = last.num_classes
+        cur, num = dets.contiguous().float(), num.to(torch.int32).contiguous()
+        max_shape = const_rows([m['img_shape'][:2] for m in img_metas], cur)
+        bidx = torch.arange(B, device=cur.device, dtype=cur.dtype).view(B, 1, 1).expand(B, K, 1)
+        logit_sum = None
+        for i, head in enumerate(self.bbox_head):
+            rois = torch.cat([bidx, cur[..., :4]], -1).view(B * K, 5)
+            roi_feats = self.bbox_roi_extractor[i].forward_nhwc(feats_nhwc, rois)
+            stage_mark('roi_align')
+            cls_score, bbox_pred = head.forward_nhwc(roi_feats)
+            stage_mark('fc_head')
+            if i < self.num_stages - 1:
+                coder = head.bbox_coder
+                cur, logit_sum = ops.cascade_refine_test(cur, num, cls_score.float(), bbox_pred.float(), max_shape, C,
+                                                         coder.means, coder.stds, reg_class_agnostic=head.reg_class_agnostic,
+                                                         logit_sum=logit_sum)
+        probs = ops.cascade_mean_softmax(logit_sum, cls_score.float(), self.num_stages)
+        sf = const_rows([list(m['scale_factor']) for m in img_metas], cur) if rescale else None
+        coder = last.bbox_coder
+        bb, sc, lb, va = ops.rcnn_decode_plain(probs, bbox_pred, cur, num, max_shape, sf, C, cfg.score_thr, coder.means,
+                                               coder.stds, reg_class_agnostic=last.reg_class_agnostic)
         if K * C >= nms_cfg.get('split_thr', 10000):
             # mmcv's per-class branch: class-major slots, one segmented NMS launch over (image, class); same boxes, same order
             from .postprocess import batched_nms_images_by_level

@@ -141,9 +141,10 @@ def draw_sampler_perms(counts, num, num_expected_pos, neg_pos_ub=-1):
 
 def rcnn_sample(proposals, num_props, gt_inds, max_overlaps, gts, gt_labels, gt_offsets, perm, row_offsets, num,
                 num_expected_pos, neg_pos_ub, num_classes, means, stds, add_gt_as_proposals=True,
-                reg_decoded_bbox=False, want_ious=False, want_pos_flags=False):
+                reg_decoded_bbox=False, want_ious=False, want_pos_flags=False, want_gt_flags=False):
     """Sampled RoIs + targets of the second stage for the whole batch in one launch.
-    Returns dict(rois (N,5), labels (N) int64, bbox_targets (N,4), priors (N) [, ious (N)] [, pos_flags (N) int32])."""
+    Returns dict(rois (N,5), labels (N) int64, bbox_targets (N,4), priors (N) [, ious (N)] [, pos_flags (N) int32]
+    [, gt_flags (N) int32: the ground truths the sampler added, brcnn_rcnn_sample_gt])."""
     _require_gpu(proposals, num_props, gt_inds, max_overlaps, gts, gt_labels, perm)
     B, K, five = proposals.shape
     assert five == 5 and proposals.is_contiguous() and proposals.dtype == torch.float32
@@ -163,18 +164,53 @@ def rcnn_sample(proposals, num_props, gt_inds, max_overlaps, gts, gt_labels, gt_
         out['ious'] = torch.empty((N,), dtype=torch.float32, device=dev)
     if want_pos_flags:
         out['pos_flags'] = torch.empty((N,), dtype=torch.int32, device=dev)
+    if want_gt_flags:
+        out['gt_flags'] = torch.empty((N,), dtype=torch.int32, device=dev)
     if N == 0:
         return out
     total_gt = gt_offsets[-1]
-    st = _L.load().brcnn_rcnn_sample(
+    entry, more = ('brcnn_rcnn_sample_gt', (_ptr(out['gt_flags']),)) if want_gt_flags else ('brcnn_rcnn_sample', ())
+    st = getattr(_L.load(), entry)(
         _ptr(proposals), _ptr(num_props), K, B, _ptr(gt_inds), _ptr(max_overlaps), _ptr(gts) if total_gt else None,
         _ptr(gt_labels) if total_gt else None, _ints(gt_offsets), int(bool(add_gt_as_proposals)), int(num),
         int(num_expected_pos), float(neg_pos_ub), _ptr(perm), _ints(row_offsets), int(num_classes),
         int(bool(reg_decoded_bbox)), _floats(means), _floats(stds), _ptr(lists), stride, _ptr(out['rois']),
         _ptr(out['labels']), _ptr(out['bbox_targets']), _ptr(out['priors']), _ptr(out.get('ious')),
-        _ptr(out.get('pos_flags')), _stream())
-    _L.check(st, 'brcnn_rcnn_sample')
+        _ptr(out.get('pos_flags')), *more, _stream())
+    _L.check(st, entry)
     return out
+
+
+CASCADE_MAX_ROWS = 2048         # rows of one image brcnn_cascade_refine_train serves (the sampler's limit)
+
+
+def cascade_refine_train(rois, labels, gt_flags, row_offsets, cls_score, bbox_pred, max_shape, num_classes, means, stds,
+                         reg_class_agnostic=False, wh_ratio_clip=16 / 1000):
+    """BBoxHead.refine_bboxes for the whole batch in one launch (brcnn_cascade_refine_train): the sampled rois (N,5) /
+    labels (N) int64 / gt_flags (N) int32 of `rcnn_sample(..., want_gt_flags=True)` with their host row offsets, this
+    stage's cls_score (N, C+1) and bbox_pred (N, 4 | 4C), max_shape (B,2).  Background rows are regressed by their
+    arg-max class, the others by their label; added ground truths are dropped, order kept.
+    Returns (props (B, Kout, 5) zero padded, num (B,) int32): the next stage's proposals, on the device."""
+    _require_gpu(rois, labels, gt_flags, cls_score, bbox_pred, max_shape)
+    from .ops import _rows_in_place
+    B = len(row_offsets) - 1
+    N, C = int(row_offsets[-1]), int(num_classes)
+    assert 1 <= B <= MAX_IMAGES and rois.shape == (N, 5) and rois.dtype == torch.float32 and rois.is_contiguous()
+    assert labels.shape == (N,) and labels.dtype == torch.int64 and labels.is_contiguous()
+    assert gt_flags.shape == (N,) and gt_flags.dtype == torch.int32 and gt_flags.is_contiguous()
+    assert cls_score.shape == (N, C + 1) and bbox_pred.shape == (N, 4 if reg_class_agnostic else 4 * C)
+    assert max_shape.shape == (B, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
+    kout = max(1, max(row_offsets[b + 1] - row_offsets[b] for b in range(B)))
+    cls_score, cs = _rows_in_place(cls_score.detach())
+    bbox_pred, rs = _rows_in_place(bbox_pred.detach())
+    props = torch.empty((B, kout, 5), dtype=torch.float32, device=rois.device)
+    num = torch.empty((B,), dtype=torch.int32, device=rois.device)
+    st = _L.load().brcnn_cascade_refine_train(_ptr(rois), _ptr(labels), _ptr(gt_flags), _ints(row_offsets), B, _ptr(cls_score),
+                                              cs, _ptr(bbox_pred), rs, _ptr(max_shape), C, int(bool(reg_class_agnostic)),
+                                              _floats(means), _floats(stds), float(wh_ratio_clip), kout, _ptr(props),
+                                              _ptr(num), _stream())
+    _L.check(st, 'brcnn_cascade_refine_train')
+    return props, num
 
 
 # ----------------------------------------------------------------------------- RPN loss

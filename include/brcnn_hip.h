@@ -854,6 +854,52 @@ int brcnn_rcnn_decode_plain(const float *probs, const float *bbox_pred, const fl
                             int64_t *labels, uint8_t *valid, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * Cascade R-CNN (CascadeRoIHead, mmdet/models/roi_heads/cascade_roi_head.py): handing boxes from one stage to
+ * the next, one launch each on the padded (batch, per_image, 5) layout, no host read.  fp32 only: the heads'
+ * last GEMM writes fp32 logits and deltas in every compute mode.  cls_score / bbox_pred are read in place:
+ * cls_stride / reg_stride are the floats between two consecutive rows (>= C+1, >= 4 | 4C), so the two column
+ * blocks of the heads' fused output need no copy.  Plain stores, no float atomics: two runs give the same bits.
+ *
+ * brcnn_cascade_refine_test -- the between-stage step of CascadeRoIHead.simple_test (cascade_roi_head.py:342-372)
+ *   over BBoxHead.regress_by_class (roi_heads/bbox_heads/bbox_head.py:461-496).  dets (batch, per_image, 5) zero
+ *   padded with num[b] real rows, cls_score (batch*per_image, C+1) raw logits, bbox_pred (batch*per_image, 4 | 4C),
+ *   max_shape (batch, 2) [h, w]; means / stds / wh_ratio_clip of THIS stage's coder.  Per real row: label =
+ *   argmax over the C foreground columns (:368; the lowest index on ties, torch's rule; the background column
+ *   takes no part), delta2bbox of the row's 4 deltas (reg_class_agnostic) or the label's 4 (:482-485), clipped
+ *   to max_shape (:488-495).  Writes dets_out (batch, per_image, 5): boxes in columns 0-3, column 4 zero,
+ *   padded rows zero.  The same launch accumulates the logits the row has just read (:357 ms_scores):
+ *   first != 0: logit_sum = cls_score, else logit_sum += cls_score (one fp32 add, stage order); logit_sum is
+ *   (batch*per_image, C+1) dense, every row.
+ *
+ * brcnn_cascade_mean_softmax -- the ensemble of cascade_roi_head.py:374-378 and the softmax of
+ *   BBoxHead.get_bboxes (bbox_head.py:354-355): probs (rows, C+1) = softmax((logit_sum + cls_score_last) /
+ *   float(num_stages)); the sum in stage order, ONE fp32 division (no reciprocal).  num_stages == 1 reads
+ *   cls_score_last alone (logit_sum may be NULL).  probs feeds brcnn_rcnn_decode_plain.  mean_logits (rows, C+1) or
+ *   NULL: the averaged logits themselves, for inspection (the tests pin them bit for bit).
+ *
+ * brcnn_cascade_refine_train -- BBoxHead.refine_bboxes (bbox_head.py:382-458) as CascadeRoIHead.forward_train
+ *   calls it (cascade_roi_head.py:264-284): rois (N, 5) / labels (N) int64 / gt_flags (N) int32 as
+ *   brcnn_rcnn_sample_gt wrote them, image b owning rows [row_offsets_host[b], row_offsets_host[b+1]) (HOST,
+ *   batch+1 ints, at most 2048 rows per image).  A background row (label == C) takes the arg-max foreground
+ *   class (:279-281), every other row keeps its label; decode + clip as above; the rows with gt_flags set are
+ *   dropped (:451-456) wherever they sit, the survivors keep their order.  Writes props_out (batch, rows_out, 5)
+ *   zero padded (column 4 zero) and num_out (batch) int32 on the device: the next stage's proposals for
+ *   brcnn_assign_max_iou / brcnn_rcnn_sample.  rows_out >= the largest per-image row count. */
+int brcnn_cascade_refine_test(const float *dets, const int32_t *num, const float *cls_score, int cls_stride,
+                              const float *bbox_pred, int reg_stride, const float *max_shape, int batch,
+                              int per_image, int num_classes, int reg_class_agnostic, int first,
+                              const float *means4_host, const float *stds4_host, double wh_ratio_clip,
+                              float *dets_out, float *logit_sum, void *stream);
+int brcnn_cascade_mean_softmax(const float *logit_sum, const float *cls_score_last, int cls_stride, int64_t rows,
+                               int num_classes, int num_stages, float *probs, float *mean_logits, void *stream);
+int brcnn_cascade_refine_train(const float *rois, const int64_t *labels, const int32_t *gt_flags,
+                               const int *row_offsets_host, int batch, const float *cls_score, int cls_stride,
+                               const float *bbox_pred, int reg_stride, const float *max_shape, int num_classes,
+                               int reg_class_agnostic, const float *means4_host, const float *stds4_host,
+                               double wh_ratio_clip, int rows_out, float *props_out, int32_t *num_out,
+                               void *stream);
+
+/* ------------------------------------------------------------------------------
  * Test-time augmentation (multi-scale + flip), whole batch, no host round trip: the device form of
  * TwoStageDetector.aug_test (detectors/two_stage.py:184-193).  Per-(aug, image) geometry is one device
  * table geom (num_augs, batch, 8) = [img_h, img_w, sf0, sf1, sf2, sf3, flip, 0] built by the host from
@@ -1053,6 +1099,18 @@ int brcnn_rcnn_sample(const float *proposals, const int32_t *num_props, int per_
                       const float *means4_host, const float *stds4_host, int32_t *list_ws,
                       int list_stride, float *rois, int64_t *labels, float *bbox_targets, float *priors,
                       float *ious, int32_t *pos_flags, void *stream);
+/* brcnn_rcnn_sample_gt -- the same launch and the same outputs, bit for bit, plus gt_flags (N) int32: 1 where the
+ * row is a ground truth box the sampler added as a proposal (add_gt_as_proposals; SamplingResult.pos_is_gt,
+ * core/bbox/samplers/sampling_result.py:32), wherever in the image's positives it sits.  These are the rows
+ * BBoxHead.refine_bboxes drops between two cascade stages (brcnn_cascade_refine_train). */
+int brcnn_rcnn_sample_gt(const float *proposals, const int32_t *num_props, int per_image, int batch,
+                         const int32_t *gt_inds, const float *max_overlaps, const float *gts,
+                         const int64_t *gt_labels, const int *gt_offsets_host, int add_gt_as_proposals,
+                         int num, int num_expected_pos, float neg_pos_ub, const int32_t *perm,
+                         const int *row_offsets_host, int num_classes, int reg_decoded_bbox,
+                         const float *means4_host, const float *stds4_host, int32_t *list_ws,
+                         int list_stride, float *rois, int64_t *labels, float *bbox_targets, float *priors,
+                         float *ious, int32_t *pos_flags, int32_t *gt_flags, void *stream);
 /* The sampled RPN loss of the Faster R-CNN baseline (RPNHead: AnchorHead.loss with a RandomSampler,
  * dense_heads/anchor_head.py:373-497, samplers/random_sampler.py:32-82).  y (rows, ystride) is the fused
  * head output of all levels, level-major rows, columns [objectness A | deltas 4A | padding]; gt_inds
