@@ -21,7 +21,7 @@ import torch.nn as nn
 from . import ops
 from .blocks import (ConvModule, PackedCache, Scale, bias_init_with_prob, pack_weight, to_nhwc)
 from .postprocess import batched_nms_images
-from .core import (anchor_inside_flags, bbox_overlaps, images_to_levels, multi_apply, unmap)
+from .core import (anchor_inside_flags, bbox_overlaps, const_rows, images_to_levels, multi_apply, unmap)
 from .registry import (HEADS, build_anchor_generator, build_assigner, build_bbox_coder,
                        build_loss, build_sampler)
 
@@ -1088,3 +1088,373 @@ class RPNHead(AnchorHead):
         losses2 = train_ops.rpn_sampled_loss(y, gt_inds, gts, drawn, meta, total, workspace=ws)
         self.last_rpn_targets = (gt_inds, drawn, total)
         return dict(loss_rpn_cls=[losses2[0]], loss_rpn_bbox=[losses2[1]])
+
+
+# ----------------------------------------------------------------------------- RetinaNet baseline
+@HEADS.register_module()
+class RetinaHead(AnchorHead):
+    """The head of RetinaNet (mmdet/models/dense_heads/retina_head.py:8-114 over anchor_head.py:37-750): two towers of
+    `stacked_convs` 3x3 conv + ReLU (`cls_convs.{i}.conv`, `reg_convs.{i}.conv`), then the 3x3 `retina_cls` (A * C sigmoid
+    class logits per cell) and `retina_reg` (4A deltas).  Parameter names and shapes are the reference's.  Execution:
+    every layer is one launch over all pyramid levels on the NHWC conv kernels (bias + ReLU in the read-out); scoring,
+    top-k, decode + class fan-out and the NMS of the whole batch stay on the device (csrc/dense_head.hip), and so do
+    the whole-batch assignment and the focal / L1 loss -- with no sampler there is nothing to draw on the host, and the
+    train step reads nothing back inside the head.  CPU tensors take the reference's per-image chain on torch ops (the
+    host mirror the CPU tests compare with the fixture)."""
+
+    supports_tta = False
+    # nms_pre / level limits of the device path (include/brcnn_hip.h: brcnn_rpn_topk)
+    MAX_NMS_PRE, MAX_LEVELS = 4096, 8
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None, norm_cfg=None,
+                 anchor_generator=dict(type='AnchorGenerator', octave_base_scale=4, scales_per_octave=3,
+                                       ratios=[0.5, 1.0, 2.0], strides=[8, 16, 32, 64, 128]),
+                 init_cfg=None, **kwargs):
+        if norm_cfg is not None:
+            raise NotImplementedError(f'RetinaHead: norm_cfg={norm_cfg!r}; the towers run conv + bias + ReLU in one launch '
+                                      'per layer, a normalisation layer between them is not supported')
+        loss_cls = kwargs.get('loss_cls', dict(type='CrossEntropyLoss', use_sigmoid=True))
+        loss_bbox = kwargs.get('loss_bbox', dict(type='SmoothL1Loss'))
+        if not loss_cls.get('use_sigmoid', False):
+            raise NotImplementedError('RetinaHead: loss_cls.use_sigmoid=False (softmax scores with a background column) is '
+                                      'not supported; scoring and the focal loss are sigmoid')
+        if loss_cls.get('type') != 'FocalLoss':
+            raise NotImplementedError(f"RetinaHead: loss_cls.type={loss_cls.get('type')!r}; only FocalLoss is supported")
+        if loss_bbox.get('type') not in ('L1Loss', 'SmoothL1Loss'):
+            raise NotImplementedError(f"RetinaHead: loss_bbox.type={loss_bbox.get('type')!r}; only L1Loss and SmoothL1Loss "
+                                      'on the encoded deltas are supported')
+        if kwargs.get('reg_decoded_bbox', False):
+            raise NotImplementedError('RetinaHead: reg_decoded_bbox=True (a loss on decoded boxes) is not supported')
+        tc = kwargs.get('train_cfg')
+        if tc and tc.get('sampler') is not None and tc.get('sampler').get('type') != 'PseudoSampler':
+            raise NotImplementedError(f"RetinaHead: train_cfg.sampler.type={tc.get('sampler').get('type')!r}; the focal loss "
+                                      'runs over every anchor (PseudoSampler)')
+        self.stacked_convs, self.conv_cfg, self.norm_cfg = stacked_convs, conv_cfg, norm_cfg
+        super().__init__(num_classes, in_channels, anchor_generator=anchor_generator, init_cfg=init_cfg, **kwargs)
+        for loss in (self.loss_cls, self.loss_bbox):
+            if loss.reduction != 'mean':
+                raise NotImplementedError(f"RetinaHead: {type(loss).__name__}.reduction={loss.reduction!r}; only 'mean'")
+        if getattr(self.bbox_coder, 'add_ctr_clamp', False) or not getattr(self.bbox_coder, 'clip_border', True):
+            raise NotImplementedError('RetinaHead: bbox_coder needs clip_border=True and add_ctr_clamp=False')
+        if self.test_cfg:
+            self._check_test_cfg(self.test_cfg)
+        self._cls_caches = [PackedCache() for _ in range(stacked_convs)]
+        self._reg_caches = [PackedCache() for _ in range(stacked_convs)]
+        self._head_caches = [PackedCache(), PackedCache()]
+        self._base_anchor_cache = {}
+        self.init_weights()
+
+    def _init_layers(self):
+        self.relu = nn.ReLU(inplace=True)
+        self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
+        for i in range(self.stacked_convs):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            self.cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg))
+            self.reg_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg))
+        self.retina_cls = nn.Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 3, padding=1)
+        self.retina_reg = nn.Conv2d(self.feat_channels, self.num_anchors * 4, 3, padding=1)
+
+    def init_weights(self):
+        """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name='retina_cls', bias_prob=0.01))
+        (retina_head.py:38-46)"""
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.normal_(m.weight, 0, 0.01)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.retina_cls.bias, bias_init_with_prob(0.01))
+
+    def _check_test_cfg(self, cfg):
+        nms = cfg.get('nms', dict(type='nms'))
+        if nms.get('type', 'nms') != 'nms':
+            raise NotImplementedError(f"RetinaHead: test_cfg.nms.type={nms.get('type')!r}; only greedy 'nms' is supported "
+                                      '(no soft-NMS)')
+        if nms.get('class_agnostic', False):
+            raise NotImplementedError('RetinaHead: test_cfg.nms.class_agnostic=True is not supported')
+
+    # ------------------------------------------------------------------ forward
+    def _towers(self):
+        return ([m.conv for m in self.cls_convs], self._cls_caches), ([m.conv for m in self.reg_convs], self._reg_caches)
+
+    def forward_rows(self, feats):
+        """inference: list of (B,h,w,C) NHWC maps -> (cls (rows, A*C), reg (rows, 4A)) fp32 in every compute mode,
+        level-major rows, and the level sizes; each layer of each tower is one launch over all levels (the weights are
+        shared across them)"""
+        B = feats[0].shape[0]
+        sizes = [tuple(f.shape[1:3]) for f in feats]
+        x0 = cat_rows(feats)
+        outs = []
+        for (convs, caches), head, hcache in zip(self._towers(), (self.retina_cls, self.retina_reg), self._head_caches):
+            x = x0
+            for conv, cache in zip(convs, caches):
+                w, b = cache.get([conv.weight, conv.bias], lambda c=conv: (pack_weight(c.weight).to(x0.dtype),
+                                                                          c.bias.detach().float().contiguous()))
+                x, _ = ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, True, 1, 1)      # bias + ReLU in the read-out
+            w, b = hcache.get([head.weight, head.bias], lambda h=head: (pack_weight(h.weight).to(x0.dtype),
+                                                                       h.bias.detach().float().contiguous()))
+            outs.append(ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, False, 1, 1, out_f32=True)[0])
+        return outs[0], outs[1], sizes
+
+    def forward_fused(self, feats):
+        """`forward_rows` as per-level views: (cls (B,h,w,A*C), reg (B,h,w,4A)) lists"""
+        yc, yr, sizes = self.forward_rows(feats)
+        B = feats[0].shape[0]
+        return self._split_rows(yc, B, sizes, yc.shape[1]), self._split_rows(yr, B, sizes, yr.shape[1])
+
+    def forward_head_fused(self, feats):
+        """training forward over all levels: (cls (rows, >= A*C), reg (rows, >= 4A)) fp32 with zero padding columns,
+        level-major rows, differentiable, and the level sizes"""
+        from .autograd import ConvNHWCFunction, conv2d_nhwc_multi_autograd, fused_head_weights
+        B = feats[0].shape[0]
+        sizes = tuple(tuple(int(v) for v in f.shape[1:3]) for f in feats)
+        x0 = cat_rows(feats)
+        mult = 32 if x0.dtype == torch.float32 else 64
+        outs = []
+        for (convs, _), head in zip(self._towers(), (self.retina_cls, self.retina_reg)):
+            x = x0
+            for conv in convs:
+                if conv.out_channels % mult == 0:       # ReLU in the kernel's read-out
+                    x = ConvNHWCFunction.apply(x, conv.weight, conv.bias, B, sizes, 1, 1, False, True, False)
+                else:
+                    x = conv2d_nhwc_multi_autograd(x, conv.weight, conv.bias, B, sizes, 1, 1).relu()
+            w, b = fused_head_weights((head,), mult)
+            outs.append(ConvNHWCFunction.apply(x, w, b, B, sizes, 1, 1, False, False, True))   # fp32 head output
+        return outs[0], outs[1], sizes
+
+    @staticmethod
+    def _split_rows(y, B, sizes, width):
+        lv, r0 = [], 0
+        for (h, w) in sizes:
+            n = B * h * w
+            lv.append(y[r0:r0 + n].view(B, h, w, y.shape[1])[..., :width])
+            r0 += n
+        return lv
+
+    def forward_nhwc(self, feats):
+        """list of (B,h,w,C) -> (cls (B,h,w,A*C), reg (B,h,w,4A)) lists, fp32"""
+        from .autograd import wants_grad
+        if not feats[0].is_cuda:
+            cls, reg = self.forward([f.permute(0, 3, 1, 2) for f in feats])
+            return [c.permute(0, 2, 3, 1) for c in cls], [r.permute(0, 2, 3, 1) for r in reg]
+        if wants_grad(feats[0], self.retina_cls.weight, self.cls_convs[0].conv.weight):
+            yc, yr, sizes = self.forward_head_fused(list(feats))
+            B = feats[0].shape[0]
+            return (self._split_rows(yc, B, sizes, self.num_anchors * self.cls_out_channels),
+                    self._split_rows(yr, B, sizes, self.num_anchors * 4))
+        return self.forward_fused(list(feats))
+
+    def forward(self, feats):
+        """reference signature: list of (N,C,h,w) -> lists of (N,A*C,h,w), (N,4A,h,w)"""
+        if not feats[0].is_cuda:        # host mirror: retina_head.py:94-114 on torch ops
+            import torch.nn.functional as F
+            cls, reg = [], []
+            for x in feats:
+                c = r = x
+                for m in self.cls_convs:
+                    c = F.relu(F.conv2d(c, m.conv.weight, m.conv.bias, padding=1))
+                for m in self.reg_convs:
+                    r = F.relu(F.conv2d(r, m.conv.weight, m.conv.bias, padding=1))
+                cls.append(F.conv2d(c, self.retina_cls.weight, self.retina_cls.bias, padding=1))
+                reg.append(F.conv2d(r, self.retina_reg.weight, self.retina_reg.bias, padding=1))
+            return cls, reg
+        cls, reg = self.forward_nhwc([to_nhwc(f) for f in feats])
+        v = lambda lst: [t.permute(0, 3, 1, 2) for t in lst]  # noqa: E731
+        return v(cls), v(reg)
+
+    # ------------------------------------------------------------------ test
+    _base_anchors = ATSSRPNHead._base_anchors
+
+    def _check_limits(self, cfg, sizes):
+        """the sizes the device path serves (brcnn_rpn_topk: k <= 4096, <= 8 levels); anything beyond is refused"""
+        if not 0 < cfg.get('nms_pre', -1) <= self.MAX_NMS_PRE:
+            raise ValueError(f"RetinaHead: nms_pre={cfg.get('nms_pre', -1)} outside (0, {self.MAX_NMS_PRE}] (brcnn_rpn_topk)")
+        if len(sizes) > self.MAX_LEVELS:
+            raise ValueError(f'RetinaHead: {len(sizes)} pyramid levels, at most {self.MAX_LEVELS} are supported')
+
+    def get_bboxes_padded(self, cls_nhwc, reg_nhwc, img_metas, cfg=None, rescale=False, cls_rows=None):
+        """anchor_head.py:507-750 for the whole batch on the device, no host sync: per-anchor max sigmoid, per-level top-k,
+        decode / clip / rescale with the fan-out to classes, score threshold, class-aware NMS, max_per_img.  Inputs are the
+        NHWC head outputs per level (dense, or channel slices of wider tensors); `cls_rows`: the (rows, A*C) tensor the
+        class maps are level-major views of (`forward_rows`), scored by ONE launch instead of one per level.  Returns
+        (dets (B, K, 5) zero padded, labels (B, K), num (B,) int32); `self.last_n_valid` keeps, on the device, how many
+        candidates of each image passed score_thr -- the count mmcv's split_thr decision looks at, a diagnostic here
+        (SingleStageDetector.simple_test copies it out with the results)."""
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_test_cfg(cfg)
+        sizes = [tuple(c.shape[1:3]) for c in cls_nhwc]
+        self._check_limits(cfg, sizes)
+        B, device = cls_nhwc[0].shape[0], cls_nhwc[0].device
+        A, C = self.num_anchors, self.cls_out_channels
+        L = len(cls_nhwc)
+        if cls_rows is not None:
+            assert cls_rows.dim() == 2 and cls_rows.shape[0] == sum(B * h * w for h, w in sizes)
+            scored, raw, r0 = ops.dense_score(cls_rows, A, C), [], 0
+            for (h, w) in sizes:
+                raw.append(scored[r0:r0 + B * h * w].view(B, h * w * A))
+                r0 += B * h * w
+        else:
+            raw = [ops.dense_score(c, A, C).view(B, -1) for c in cls_nhwc]
+        picked = ops.rpn_topk(raw, cfg.nms_pre)         # descending, ties by ascending index, all levels in one launch
+        max_shape = const_rows([m['img_shape'][:2] for m in img_metas], raw[0])
+        sf = const_rows([list(m['scale_factor']) for m in img_metas], raw[0]) if rescale else None
+        bb, sc, lb, va, nv = ops.dense_decode_levels(
+            [p[1] for p in picked], list(cls_nhwc), list(reg_nhwc), [self._base_anchors(l, device) for l in range(L)], sizes,
+            list(self.anchor_generator.strides), C, max_shape, sf, self.bbox_coder.means, self.bbox_coder.stds, cfg.score_thr)
+        self.last_n_valid = nv
+        nms_cfg = dict(cfg.nms)
+        nms_cfg.pop('type', None)
+        T = sc.shape[1] // C
+        # mmcv's batched_nms changes branch at split_thr by the number of candidates that SURVIVE score_thr (n_valid), which
+        # only the device knows here; the branch is chosen by the slot count T * C instead, so no host read is needed.
+        # Both branches keep the same boxes in the same order (the coordinate offsets already isolate the classes), with
+        # one limit: where the reference takes the offset form and this code the per-class one (or the reverse), the
+        # IoUs are computed on un-offset resp. offset fp32 coordinates and can differ in the last ulp -- a pair whose IoU
+        # sits within an ulp of iou_threshold may then be decided differently.
+        if T * C >= nms_cfg.get('split_thr', 10000):
+            # the per-class branch: class-major slots, one segmented NMS launch over (image, class)
+            from .postprocess import batched_nms_images_by_level
+            cm = lambda t: t.view(B, T, C, *t.shape[2:]).transpose(1, 2).reshape(B, C * T, *t.shape[2:]).contiguous()   # noqa: E731
+            return batched_nms_images_by_level(cm(bb), cm(sc), cm(lb), cm(va), [T] * C, nms_cfg['iou_threshold'],
+                                               cfg.max_per_img, nms_cfg.get('offset', 0), return_ids=True)
+        return batched_nms_images(bb, sc, lb, va, nms_cfg['iou_threshold'], cfg.max_per_img, nms_cfg.get('offset', 0))
+
+    def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
+        yc, yr, sizes = self.forward_rows(list(feats_nhwc))
+        B = feats_nhwc[0].shape[0]
+        return self.get_bboxes_padded(self._split_rows(yc, B, sizes, yc.shape[1]), self._split_rows(yr, B, sizes, yr.shape[1]),
+                                      img_metas, rescale=rescale, cls_rows=yc)
+
+    def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False, with_nms=True, batched_nms=None):
+        """reference signature (anchor_head.py:507-587): per-level (N,A*C,h,w) / (N,4A,h,w) -> per image (dets (k,5),
+        labels (k,)).  Device tensors take `get_bboxes_padded`; CPU tensors the reference's chain on torch ops, with the
+        caller's `batched_nms` (this package's NMS is a device kernel)."""
+        if not with_nms:
+            raise NotImplementedError('RetinaHead: with_nms=False is not supported')
+        assert len(cls_scores) == len(bbox_preds)
+        if cls_scores[0].is_cuda:
+            f = lambda lst: [to_nhwc(t.detach()).float().contiguous() for t in lst]  # noqa: E731
+            det, lab, num = self.get_bboxes_padded(f(cls_scores), f(bbox_preds), img_metas, cfg, rescale)
+            num = num.tolist()   # the one host sync
+            return [(det[i, :num[i]], lab[i, :num[i]]) for i in range(len(img_metas))]
+        return self._get_bboxes_host(cls_scores, bbox_preds, img_metas, cfg, rescale, batched_nms)
+
+    def _get_bboxes_host(self, cls_scores, bbox_preds, img_metas, cfg, rescale, batched_nms):
+        from .core import delta2bbox
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_test_cfg(cfg)
+        if batched_nms is None:
+            batched_nms = ops.batched_nms
+        B, C = cls_scores[0].shape[0], self.cls_out_channels
+        anchors_l = self.anchor_generator.grid_anchors([c.shape[-2:] for c in cls_scores], cls_scores[0].device)
+        nms_pre = cfg.get('nms_pre', -1)
+        out = []
+        for b in range(B):
+            boxes_l, scores_l = [], []
+            for cls, reg, anchors in zip(cls_scores, bbox_preds, anchors_l):
+                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
+                d = reg[b].detach().permute(1, 2, 0).reshape(-1, 4)
+                if 0 < nms_pre < s.shape[0]:
+                    _, idx = s.max(-1)[0].sort(descending=True, stable=True)      # ties by ascending index, the shared rule
+                    idx = idx[:nms_pre]
+                    anchors, d, s = anchors[idx], d[idx], s[idx]
+                boxes_l.append(delta2bbox(anchors, d, self.bbox_coder.means, self.bbox_coder.stds,
+                                          max_shape=tuple(img_metas[b]['img_shape'][:2])))
+                scores_l.append(s)
+            boxes, scores = torch.cat(boxes_l), torch.cat(scores_l)
+            if rescale:
+                boxes = boxes / boxes.new_tensor(img_metas[b]['scale_factor'])
+            keep = (scores > cfg.score_thr).reshape(-1)
+            inds = keep.nonzero(as_tuple=False).reshape(-1)
+            labels = torch.arange(C, dtype=torch.long).repeat(scores.shape[0])[inds]
+            cb, cs = boxes[:, None].expand(-1, C, 4).reshape(-1, 4)[inds], scores.reshape(-1)[inds]
+            if cb.numel() == 0:
+                out.append((torch.cat([cb, cs[:, None]], -1), labels))
+                continue
+            dets, kept = batched_nms(cb.contiguous(), cs.contiguous(), labels, dict(cfg.nms))
+            if cfg.max_per_img > 0:
+                dets, kept = dets[:cfg.max_per_img], kept[:cfg.max_per_img]
+            out.append((dets, labels[kept]))
+        return out
+
+    def simple_test(self, feats, img_metas, rescale=False, batched_nms=None):
+        """dense_test_mixins.py:17-37: list of (N,C,h,w) -> per image (dets (k,5), labels (k,))"""
+        return self.get_bboxes(*self(feats), img_metas, rescale=rescale, batched_nms=batched_nms)
+
+    def aug_test(self, feats, img_metas, rescale=False):
+        raise NotImplementedError('RetinaHead has no test-time augmentation')
+
+    # ------------------------------------------------------------------ train
+    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
+        """base_dense_head.py:48-78"""
+        outs = self(x)
+        losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+        if proposal_cfg is None:
+            return losses
+        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
+
+    def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
+        """the device-resident train step of the head: NHWC pyramid -> towers and heads over all levels -> whole-batch
+        assignment and loss kernels; no host read"""
+        if gt_bboxes_ignore is not None:
+            raise NotImplementedError('RetinaHead: gt_bboxes_ignore is not supported on the device path')
+        yc, yr, sizes = self.forward_head_fused(list(feats_nhwc))
+        return self.loss_fused(yc, yr, sizes, gt_bboxes, gt_labels, img_metas)
+
+    loss_single = RPNHead.loss_single
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        """anchor_head.py:423-497.  Device tensors go to the HIP kernels (`loss_fused`); CPU tensors take the reference's
+        per-image chain in torch (the host mirror)."""
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        device = cls_scores[0].device
+        if device.type == 'cuda':
+            if gt_bboxes_ignore is not None:
+                raise NotImplementedError('RetinaHead: gt_bboxes_ignore is not supported on the device path')
+            sizes = tuple(tuple(int(v) for v in s_) for s_ in featmap_sizes)
+            rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float().contiguous()   # noqa: E731
+            return self.loss_fused(rows(cls_scores), rows(bbox_preds), sizes, gt_bboxes, gt_labels, img_metas)
+        num_imgs = len(img_metas)
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
+        num_level_anchors = [a.size(0) for a in anchor_list[0]]
+        flat_anchors = [torch.cat(a) for a in anchor_list]
+        flat_flags = [torch.cat(v) for v in valid_flag_list]
+        ignore = gt_bboxes_ignore if gt_bboxes_ignore is not None else [None] * num_imgs
+        all_valid = self._all_valid
+        self._all_valid = None
+        (labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds, _) = multi_apply(
+            self._get_targets_single, flat_anchors, flat_flags, gt_bboxes, ignore, gt_labels, img_metas, all_valid)
+        if any(l is None for l in labels):
+            return None
+        num_total_pos = sum(max(p.numel(), 1) for p in pos_inds)            # (no sampling: anchor_head.py:469-470)
+        losses_cls, losses_bbox = multi_apply(
+            self.loss_single, cls_scores, bbox_preds, images_to_levels(flat_anchors, num_level_anchors),
+            images_to_levels(labels, num_level_anchors), images_to_levels(label_weights, num_level_anchors),
+            images_to_levels(bbox_targets, num_level_anchors), images_to_levels(bbox_weights, num_level_anchors),
+            num_total_samples=num_total_pos)
+        return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)
+
+    # ------------------------------------------------------------------ device-resident train step
+    _anchor_table = ATSSRPNHead._anchor_table
+    assign_targets_device = ATSSRPNHead.assign_targets_device
+
+    def loss_fused(self, ycls, yreg, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
+        """AnchorHead.loss on the head outputs of all levels (rows, >= A*C) / (rows, >= 4A): whole-batch assignment, then
+        the loss kernels -- targets, the positive count and its reciprocal are formed on the device, nothing is read back.
+        Returns the reference's per-level lists; `self.last_targets` keeps (gt_inds, [k_cls, k_bbox, num_total_pos])."""
+        from . import train_ops
+        from .core import MaxIoUAssigner
+        if type(self.assigner) is not MaxIoUAssigner or self.assigner.ignore_iof_thr > 0:
+            raise NotImplementedError('RetinaHead: the device path assigns with MaxIoUAssigner without ignore regions')
+        device = ycls.device
+        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
+        gt_inds = self.assign_targets_device(sizes, img_metas, gts, offs, device)
+        L = len(sizes)
+        meta = train_ops.DenseLossMeta(
+            len(img_metas), sizes, self.anchor_generator.strides, [self._base_anchors(l, device) for l in range(L)],
+            self.num_anchors, self.cls_out_channels, offs, self.loss_cls.gamma, self.loss_cls.alpha,
+            self.train_cfg.pos_weight, getattr(self.loss_bbox, 'beta', 0.0), self.bbox_coder.means, self.bbox_coder.stds,
+            self.loss_cls.loss_weight, self.loss_bbox.loss_weight)
+        losses, coef = train_ops.dense_loss(ycls, yreg, gt_inds, gts, labels, meta)
+        self.last_targets = (gt_inds, coef)
+        return dict(loss_cls=list(losses[0].unbind(0)), loss_bbox=list(losses[1].unbind(0)))

@@ -103,6 +103,51 @@ class BaseDetector(nn.Module):
         if bb is not None and hasattr(bb, 'init_weights'):
             bb.init_weights(pretrained=True)
 
+    def set_compute_dtype(self, dtype):
+        """'f32' (default: exact-fp32 MFMA, the parity path), 'bf16' or 'f16' (16-bit MFMA conv stack with
+        fp32 accumulation; head outputs, proposal stage, losses and NMS stay fp32).  Training in 'f16' wants
+        loss scaling (apis.train_detector wires the recipes' `fp16 = dict(loss_scale=512.)`)."""
+        from . import blocks
+        blocks.set_compute_dtype(dtype)
+        return self
+
+    def prepare_winograd_layers(self):
+        """the frozen 3x3 stride-1 conv + BatchNorm / bias layers of the backbone and the neck (a Bottleneck's conv2, the
+        neck's plain ConvModules) may take the Winograd single-layer route (blocks.prepare_winograd_layer; the policy
+        table decides per layer size, ops.winograd_layer_route).  Returns the number of layers prepared."""
+        from .backbones import Bottleneck
+        from .blocks import ConvModule, prepare_winograd_layer
+        n = 0
+        for part in (self.backbone, self.neck if self.with_neck else None):
+            for m in (part.modules() if part is not None else ()):
+                if isinstance(m, Bottleneck) and not m.with_dcn:
+                    n += prepare_winograd_layer(m.conv2, m._c[1])
+                elif isinstance(m, ConvModule) and (m.norm is None or isinstance(m.norm, nn.BatchNorm2d)):
+                    n += prepare_winograd_layer(m.conv, m._cache)
+        return n
+
+    # ---- features ----------------------------------------------------------------------
+    def extract_feat_nhwc(self, img):
+        # training: the neck's lateral convs run inside the backbone's stage loop (FPN.lateral_tap) so that the
+        # gradient fan-in of a stage output (lateral conv + next stage) costs no aten add
+        tap = None
+        if self.with_neck and torch.is_grad_enabled() and hasattr(self.neck, 'lateral_tap') and \
+                getattr(self.backbone, 'supports_tap', False):
+            self.neck.__dict__.pop('_pre_laterals', None)
+            tap = self.neck.lateral_tap
+        if hasattr(self.backbone, 'forward_from_nchw'):
+            x = self.backbone.forward_from_nchw(img, tap) if tap is not None else self.backbone.forward_from_nchw(img)
+        else:
+            x = self.backbone.forward_nhwc(to_nhwc(img), tap) if tap is not None else self.backbone.forward_nhwc(to_nhwc(img))
+        stage_mark('backbone')
+        if self.with_neck:
+            x = self.neck.forward_nhwc(x)
+            stage_mark('neck')
+        return x
+
+    def extract_feat(self, img):
+        return tuple(to_nchw_view(f) for f in self.extract_feat_nhwc(img))
+
     def forward_test(self, imgs, img_metas, **kwargs):
         for var, name in [(imgs, 'imgs'), (img_metas, 'img_metas')]:
             if not isinstance(var, list):
@@ -203,14 +248,6 @@ class TwoStageDetector(BaseDetector):
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
         self._rpn_scale_cache = None    # host copy of rpn_head.scales (freeze_for_inference)
 
-    def set_compute_dtype(self, dtype):
-        """'f32' (default: exact-fp32 MFMA, the parity path), 'bf16' or 'f16' (16-bit MFMA conv stack with
-        fp32 accumulation; head outputs, proposal stage, losses and NMS stay fp32).  Training in 'f16' wants
-        loss scaling (apis.train_detector wires the recipes' `fp16 = dict(loss_scale=512.)`)."""
-        from . import blocks
-        blocks.set_compute_dtype(dtype)
-        return self
-
     def freeze_for_inference(self):
         """read the (tiny) host-side constants once so that `simple_test_device` issues no
         device->host copies: the five learnable rpn_reg scales.  The weights are frozen from here on, so the RPN tower
@@ -221,43 +258,6 @@ class TwoStageDetector(BaseDetector):
             self.rpn_head.prepare_winograd()
         self.prepare_winograd_layers()
         return self
-
-    def prepare_winograd_layers(self):
-        """the frozen 3x3 stride-1 conv + BatchNorm / bias layers of the backbone and the neck (a Bottleneck's conv2, the
-        neck's plain ConvModules) may take the Winograd single-layer route (blocks.prepare_winograd_layer; the policy
-        table decides per layer size, ops.winograd_layer_route).  Returns the number of layers prepared."""
-        from .backbones import Bottleneck
-        from .blocks import ConvModule, prepare_winograd_layer
-        n = 0
-        for part in (self.backbone, self.neck if self.with_neck else None):
-            for m in (part.modules() if part is not None else ()):
-                if isinstance(m, Bottleneck) and not m.with_dcn:
-                    n += prepare_winograd_layer(m.conv2, m._c[1])
-                elif isinstance(m, ConvModule) and (m.norm is None or isinstance(m.norm, nn.BatchNorm2d)):
-                    n += prepare_winograd_layer(m.conv, m._cache)
-        return n
-
-    # ---- features ----------------------------------------------------------------------
-    def extract_feat_nhwc(self, img):
-        # training: the neck's lateral convs run inside the backbone's stage loop (FPN.lateral_tap) so that the
-        # gradient fan-in of a stage output (lateral conv + next stage) costs no aten add
-        tap = None
-        if self.with_neck and torch.is_grad_enabled() and hasattr(self.neck, 'lateral_tap') and \
-                getattr(self.backbone, 'supports_tap', False):
-            self.neck.__dict__.pop('_pre_laterals', None)
-            tap = self.neck.lateral_tap
-        if hasattr(self.backbone, 'forward_from_nchw'):
-            x = self.backbone.forward_from_nchw(img, tap) if tap is not None else self.backbone.forward_from_nchw(img)
-        else:
-            x = self.backbone.forward_nhwc(to_nhwc(img), tap) if tap is not None else self.backbone.forward_nhwc(to_nhwc(img))
-        stage_mark('backbone')
-        if self.with_neck:
-            x = self.neck.forward_nhwc(x)
-            stage_mark('neck')
-        return x
-
-    def extract_feat(self, img):
-        return tuple(to_nchw_view(f) for f in self.extract_feat_nhwc(img))
 
     # ---- train ---------------------------------------------------------------------------
     def _device_train_ok(self, img, gt_bboxes_ignore, proposals):
@@ -512,3 +512,85 @@ class CascadeRCNN(TwoStageDetector):
         super().__init__(backbone=backbone, neck=neck, rpn_head=rpn_head, roi_head=roi_head,
                          train_cfg=train_cfg, test_cfg=test_cfg, pretrained=pretrained,
                          init_cfg=init_cfg)
+
+
+# ----------------------------------------------------------------------------- single-stage detectors
+@DETECTORS.register_module()
+class SingleStageDetector(BaseDetector):
+    """mmdet/models/detectors/single_stage.py:11-154: backbone -> neck -> one dense `bbox_head` that is trained on the
+    pyramid directly and whose `get_bboxes` yields the detections.  `simple_test` keeps the whole batch on the device
+    (NHWC feature maps, padded detections with counts) and synchronises with the host once, when results are copied out;
+    `forward_train` hands the NHWC pyramid to the head's device-resident loss."""
+
+    def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__(init_cfg)
+        self.backbone = build_backbone(backbone)
+        if neck is not None:
+            self.neck = build_neck(neck)
+        bbox_head = bbox_head.copy()
+        bbox_head.update(train_cfg=train_cfg)
+        bbox_head.update(test_cfg=test_cfg)
+        self.bbox_head = build_head(bbox_head)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    def freeze_for_inference(self):
+        """the weights are frozen from here on: the backbone's and the neck's 3x3 layers may keep Winograd-transformed
+        filters (fp32 compute only).  The head reads nothing back from the device, so there is nothing else to cache."""
+        self.prepare_winograd_layers()
+        return self
+
+    def forward_dummy(self, img):
+        return self.bbox_head(self.extract_feat(img))
+
+    # ---- train ---------------------------------------------------------------------------
+    def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None, **kwargs):
+        if img.is_cuda and hasattr(self.bbox_head, 'forward_train_nhwc'):
+            from .graphs import trunk_features
+            feats = trunk_features(self, img)       # backbone + neck: eager, or replayed from HIP graphs (graph_trunk)
+            return self.bbox_head.forward_train_nhwc(feats, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore)
+        x = self.extract_feat(img)
+        return self.bbox_head.forward_train(x, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore)
+
+    graph_trunk = False         # (see TwoStageDetector.graph_trunk)
+
+    def _device_path_ok(self):
+        """device tensors always take the device-resident path: what it does not serve is refused by the head"""
+        return True
+
+    # ---- test ----------------------------------------------------------------------------
+    def simple_test_device(self, img, img_metas, rescale=False):
+        """Whole inference pass with no host synchronisation: returns device tensors
+        (det_bboxes (B,M,5), det_labels (B,M), num_dets (B,))."""
+        feats = self.extract_feat_nhwc(img)
+        out = self.bbox_head.simple_test_padded(feats, img_metas, rescale=rescale)
+        stage_mark('dense_head')
+        return out
+
+    def simple_test(self, img, img_metas, rescale=False):
+        nc = self.bbox_head.num_classes
+        if img.is_cuda:
+            det, lab, nd = self.simple_test_device(img, img_metas, rescale)
+            B, M = lab.shape
+            # boxes, labels and counts leave in ONE copy, the one host sync (class ids and counts are exact in fp32)
+            # the head's n_valid (candidates above score_thr per image, what mmcv's split_thr decision looks at) rides along:
+            # `self.last_n_valid`, a diagnostic
+            nv = getattr(self.bbox_head, 'last_n_valid', None)
+            nv = nd if nv is None else nv
+            host = torch.cat([det.reshape(B, M * 5), lab.to(det.dtype), nd.to(det.dtype).reshape(B, 1),
+                              nv.to(det.dtype).reshape(B, 1)], dim=1).cpu()
+            det, lab, nd = host[:, :M * 5].reshape(B, M, 5), host[:, M * 5:M * 6].long(), host[:, M * 6].long().tolist()
+            self.last_n_valid = host[:, M * 6 + 1].long().tolist()
+            return [bbox2result(det[i, :nd[i]], lab[i, :nd[i]], nc) for i in range(B)]
+        results = self.bbox_head.simple_test(self.extract_feat(img), img_metas, rescale=rescale)
+        return [bbox2result(d, l, nc) for d, l in results]
+
+    def aug_test(self, imgs, img_metas, rescale=False):
+        raise NotImplementedError(f'{type(self).__name__} has no test-time augmentation')
+
+
+@DETECTORS.register_module()
+class RetinaNet(SingleStageDetector):
+    """mmdet/models/detectors/retinanet.py:6-17"""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)

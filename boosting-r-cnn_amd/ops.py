@@ -1227,6 +1227,80 @@ def rcnn_decode_plain(probs, bbox_pred, dets, num, max_shape, scale_factor, num_
     return boxes, scores, labels, valid
 
 
+# --------------------------------------------------------------------------- dense (single-stage) head, test time
+def _nhwc_rows(t):
+    """`_last_dim_strided` for the maps of a pyramid's coarsest levels too: dims of size 1 (a 1 x 1 or 1 x 2 map) carry
+    whatever stride the producer left and do not take part in the collapse.  Returns (rows, channels, row_stride)"""
+    ch = t.shape[-1]
+    assert t.stride(-1) == 1 or ch == 1
+    dims = [(n, s) for n, s in zip(t.shape[:-1], t.stride()[:-1]) if n != 1]
+    for (_, s0), (n1, s1) in zip(dims[:-1], dims[1:]):
+        assert s0 == s1 * n1, 'dense head ops need row-collapsible views'
+    return t.numel() // ch, ch, (dims[-1][1] if dims else ch)
+
+
+def dense_score(cls, num_anchors, num_classes):
+    """max_c sigmoid(cls[..., a * C + c]) per anchor (anchor_head.py:646-669; brcnn_dense_score).  cls (B,h,w,>= A*C) NHWC,
+    possibly a channel slice of a wider tensor (read in place); returns (B,h,w,A) dense fp32, the input of `rpn_topk`."""
+    _require_gpu(cls)
+    assert cls.dtype == torch.float32
+    rows, ac, cs = _nhwc_rows(cls)
+    a, c = int(num_anchors), int(num_classes)
+    assert ac == a * c
+    out = torch.empty(tuple(cls.shape[:-1]) + (a,), dtype=torch.float32, device=cls.device)
+    st = _L.load().brcnn_dense_score(_ptr(cls), _ptr(out), rows, a, c, int(cs), _stream())
+    _L.check(st, 'brcnn_dense_score')
+    return out
+
+
+def dense_decode_levels(topk_inds, cls_scores, bbox_preds, base_anchors, feat_hws, strides, num_classes, max_shape,
+                        scale_factor, means, stds, score_thr, wh_ratio_clip=16 / 1000):
+    """The candidates of multiclass_nms for all levels and images in one launch (brcnn_dense_decode_levels).  Per-level
+    lists: topk_inds (B,k_l) int64, cls_scores (B,H_l,W_l,A*C) and bbox_preds (B,H_l,W_l,4A) NHWC (possibly channel slices),
+    base_anchors (A,4), feat_hws, strides; max_shape (B,2) [h, w], scale_factor (B,4) or None.
+    Returns boxes (B,T*C,4), scores (B,T*C), labels (B,T*C) int64, valid (B,T*C) bool, n_valid (B,) int32; T = sum k_l,
+    (level, pick, class) order."""
+    import ctypes
+    L = len(topk_inds)
+    _require_gpu(*topk_inds, *cls_scores, *bbox_preds, *base_anchors, max_shape, scale_factor)
+    b = topk_inds[0].shape[0]
+    a, c = base_anchors[0].size(0), int(num_classes)
+    inds = [t.contiguous() for t in topk_inds]
+    bases = [t.contiguous().float() for t in base_anchors]
+    cstr, pstr = [], []
+    for c_, p_ in zip(cls_scores, bbox_preds):
+        assert c_.dtype == torch.float32 and p_.dtype == torch.float32 and c_.shape[:3] == p_.shape[:3] and c_.shape[0] == b
+        _, ac, cs = _nhwc_rows(c_)
+        _, a4, ps = _nhwc_rows(p_)
+        assert ac == a * c and a4 == 4 * a
+        cstr.append(int(cs))
+        pstr.append(int(ps))
+    counts = [int(t.shape[1]) for t in inds]
+    n = sum(counts) * c
+    dev = bbox_preds[0].device
+    assert max_shape.shape == (b, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
+    if scale_factor is not None:
+        assert scale_factor.shape == (b, 4) and scale_factor.dtype == torch.float32 and scale_factor.is_contiguous()
+    boxes = torch.empty((b, n, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, n), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, n), dtype=torch.int64, device=dev)
+    valid = torch.empty((b, n), dtype=torch.bool, device=dev)
+    n_valid = torch.empty((b,), dtype=torch.int32, device=dev)
+    ptrs = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])     # noqa: E731
+    ints = lambda vs: (ctypes.c_int * L)(*[int(v) for v in vs])               # noqa: E731
+    sw = [s_ if isinstance(s_, int) else s_[0] for s_ in strides]
+    sh = [s_ if isinstance(s_, int) else s_[1] for s_ in strides]
+    m4 = (ctypes.c_float * 4)(*[float(v) for v in means])
+    s4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    st = _L.load().brcnn_dense_decode_levels(
+        ptrs(inds), ptrs(cls_scores), ints(cstr), ptrs(bbox_preds), ints(pstr), ptrs(bases), b, L, ints(counts),
+        ints([h for h, _ in feat_hws]), ints([w for _, w in feat_hws]), a, c, ints(sw), ints(sh), _ptr(max_shape),
+        _ptr(scale_factor), m4, s4, float(wh_ratio_clip), float(score_thr), _ptr(boxes), _ptr(scores), _ptr(labels),
+        _ptr(valid), _ptr(n_valid), _stream())
+    _L.check(st, 'brcnn_dense_decode_levels')
+    return boxes, scores, labels, valid, n_valid
+
+
 # --------------------------------------------------------------------------- Cascade R-CNN, test time
 def _rows_in_place(t):
     """a fp32 (rows, cols) device tensor the cascade kernels read with a row stride: the two column blocks of the heads'

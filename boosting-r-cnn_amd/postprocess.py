@@ -15,6 +15,20 @@ import torch
 
 from . import ops
 
+_INDEX_CACHE = {}
+
+
+def _column_index(cols, device):
+    """host column numbers as a device index tensor, uploaded once per distinct list (indexing with a python list is an
+    H2D copy, i.e. a stream synchronisation, on every call)"""
+    key = (tuple(int(c) for c in cols), str(device))
+    t = _INDEX_CACHE.get(key)
+    if t is None:
+        if len(_INDEX_CACHE) > 256:
+            _INDEX_CACHE.clear()
+        t = _INDEX_CACHE[key] = torch.tensor(key[0], dtype=torch.long, device=device)
+    return t
+
 
 def batched_nms_images(boxes, scores, ids, valid, iou_threshold, max_keep, offset=0, fused=None):
     """boxes (B,T,4), scores (B,T), ids (B,T) long, valid (B,T) bool.
@@ -118,8 +132,8 @@ def batched_nms_images_by_level(boxes, scores, ids, valid, level_sizes, iou_thre
     for n in level_sizes:
         bounds.append(bounds[-1] + int(n))
     csum = torch.cat([valid.new_zeros((B, 1), dtype=torch.long), torch.cumsum(valid, 1)], 1)   # (B, T+1)
-    ends = csum[:, bounds[1:]]                      # (B, L) within-image end of level l
-    begins = csum[:, bounds[:-1]]
+    ends = csum.index_select(1, _column_index(bounds[1:], device))      # (B, L) within-image end of level l
+    begins = csum.index_select(1, _column_index(bounds[:-1], device))
     base = (torch.arange(B, device=device) * T)[:, None]
     ranges = torch.stack([(begins + base).reshape(-1), (ends + base).reshape(-1)], 1).to(torch.int32)
     if soft is not None:

@@ -404,6 +404,82 @@ def rpn_sampled_loss(y, gt_inds, gts, drawn, meta, num_total_samples, workspace=
     return RPNSampledLossFunction.apply(y, gt_inds, gts, drawn, workspace, meta, num_total_samples)
 
 
+# ----------------------------------------------------------------------------- dense head loss (RetinaNet baseline)
+class DenseLossMeta:
+    """host-side description of one dense-head loss call (RetinaHead: focal loss over every anchor, no sampler)"""
+
+    def __init__(self, batch, sizes, strides, base_anchors, num_anchors, num_classes, gt_offsets, focal_gamma, focal_alpha,
+                 pos_weight, smooth_l1_beta, means, stds, lw_cls, lw_bbox):
+        self.batch, self.sizes, self.A, self.C = int(batch), [tuple(s) for s in sizes], int(num_anchors), int(num_classes)
+        self.L = len(self.sizes)
+        self.hs, self.ws = _ints([h for h, _ in self.sizes]), _ints([w for _, w in self.sizes])
+        self.sw = _ints([s if isinstance(s, int) else s[0] for s in strides])
+        self.sh = _ints([s if isinstance(s, int) else s[1] for s in strides])
+        self.base = base_anchors                      # list of (A,4) device tensors (kept alive here)
+        self.base_ptrs = (ctypes.c_void_p * self.L)(*[b.data_ptr() for b in base_anchors])
+        self.gt_offsets = _ints(gt_offsets)
+        self.total_gt = int(gt_offsets[-1])
+        self.cfg = _floats([focal_gamma, focal_alpha, pos_weight, smooth_l1_beta] + list(means) + list(stds) +
+                           [lw_cls, lw_bbox])
+        self.rows = sum(self.batch * h * w for h, w in self.sizes)
+        self.anchors_per_image = sum(h * w for h, w in self.sizes) * self.A
+
+
+class DenseLossFunction(Function):
+    """losses (2, L) = [loss_cls per level, loss_bbox per level] from the head outputs of all levels: cls (rows, >= A*C),
+    reg (rows, >= 4A), level-major rows"""
+
+    @staticmethod
+    def forward(ctx, cls, reg, gt_inds, gts, gt_labels, meta):
+        _require_gpu(cls, reg, gt_inds, gts, gt_labels)
+        for t, need in ((cls, meta.A * meta.C), (reg, 4 * meta.A)):
+            assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == meta.rows
+            assert t.shape[1] >= need
+        assert gt_inds.dtype == torch.int32 and gt_inds.shape == (meta.batch, meta.anchors_per_image) and gt_inds.is_contiguous()
+        if meta.total_gt:
+            assert gts.dtype == torch.float32 and gts.shape == (meta.total_gt, 4) and gts.is_contiguous()
+            assert gt_labels.dtype == torch.int64 and gt_labels.shape == (meta.total_gt,) and gt_labels.is_contiguous()
+        lib = _L.load()
+        dev = cls.device
+        nb = lib.brcnn_dense_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.A, meta.C)
+        ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=dev)
+        out = torch.empty((2 * meta.L + 3,), dtype=torch.float32, device=dev)
+        losses, coef = out[:2 * meta.L], out[2 * meta.L:]
+        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
+        st = lib.brcnn_dense_loss_forward(_ptr(cls), cls.shape[1], _ptr(reg), reg.shape[1], meta.batch, meta.L, meta.hs,
+                                          meta.ws, meta.sw, meta.sh, meta.base_ptrs, meta.A, meta.C, _ptr(gt_inds), gp, lp,
+                                          meta.gt_offsets, meta.cfg, _ptr(ws), nb, _stream())
+        _L.check(st, 'brcnn_dense_loss_forward')
+        st = lib.brcnn_dense_loss_finalize(_ptr(ws), nb, meta.batch, meta.L, meta.hs, meta.ws, meta.A, meta.C, meta.cfg,
+                                           _ptr(losses), _ptr(coef), _stream())
+        _L.check(st, 'brcnn_dense_loss_finalize')
+        ctx.save_for_backward(cls, reg, gt_inds, gts, gt_labels, coef)
+        ctx.meta = meta
+        ctx.mark_non_differentiable(coef)
+        return losses.view(2, meta.L), coef
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g2, _gc):
+        cls, reg, gt_inds, gts, gt_labels, coef = ctx.saved_tensors
+        meta = ctx.meta
+        dcls, dreg = torch.empty_like(cls), torch.empty_like(reg)
+        g2 = g2.float().contiguous()
+        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
+        st = _L.load().brcnn_dense_loss_backward(
+            _ptr(cls), cls.shape[1], _ptr(reg), reg.shape[1], meta.batch, meta.L, meta.hs, meta.ws, meta.sw, meta.sh,
+            meta.base_ptrs, meta.A, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg, _ptr(g2), _ptr(coef),
+            _ptr(dcls), _ptr(dreg), _stream())
+        _L.check(st, 'brcnn_dense_loss_backward')
+        return dcls, dreg, None, None, None, None
+
+
+def dense_loss(cls, reg, gt_inds, gts, gt_labels, meta):
+    """(losses (2, L), coef3 = [loss_weight_cls / num_total_pos, loss_weight_bbox / num_total_pos, num_total_pos]);
+    the losses are differentiable w.r.t. cls and reg"""
+    return DenseLossFunction.apply(cls, reg, gt_inds, gts, gt_labels, meta)
+
+
 # ----------------------------------------------------------------------------- boosting loss
 class BoostLossFunction(Function):
     """out3 = [loss_cls, loss_bbox, acc] of the boosting-reweighted R-CNN loss

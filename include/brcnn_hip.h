@@ -1190,6 +1190,60 @@ int brcnn_boost_loss_backward_ex(const float *cls_score, const float *bbox_pred,
                                  void *stream);
 
 /* ------------------------------------------------------------------------------
+ * The dense (single-stage) detection head: RetinaHead over AnchorHead (models/dense_heads/anchor_head.py), csrc/dense_head.hip.
+ * Head outputs are NHWC and read in place: `rows` pixels with A * C class logits (anchor-major) resp. 4A deltas each,
+ * consecutive pixels `*_stride` floats apart.
+ *   brcnn_dense_score: score[r * A + a] = max_c sigmoid(cls[r, a * C + c]) (anchor_head.py:646-669), the maximum over the
+ *     fp32 sigmoid VALUES; the dense (rows, A) result feeds brcnn_rpn_topk.
+ *   brcnn_dense_decode_levels: everything between the top-k and multiclass_nms (anchor_head.py:672-710,
+ *     core/post_processing/bbox_nms.py) for all levels and images in one launch.  Per level l: topk_inds[l] (batch,
+ *     counts[l]) int64 flat anchor indices as brcnn_rpn_decode_levels takes them, cls[l] / bbox_pred[l] the level's head
+ *     outputs (batch, h, w, stride).  max_shape (batch, 2) [h, w] the clip border, scale_factor (batch, 4) or NULL (a true
+ *     fp32 division).  With T = sum(counts), in (level, pick, class) order -- the order of the reference's `nonzero`:
+ *     boxes (batch, T*C, 4), scores (batch, T*C) the class sigmoid, labels (batch, T*C), valid (batch, T*C) = score >
+ *     score_thr, and n_valid (batch) the number of valid candidates per image.
+ *   brcnn_dense_loss_forward / _finalize / _backward: AnchorHead.loss without a sampler (anchor_head.py:373-491 with
+ *     PseudoSampler).  cls (rows, cls_stride) / reg (rows, reg_stride): the head outputs of all levels, level-major rows
+ *     (level l: batch * h_l * w_l rows).  gt_inds (batch, anchors per image) from brcnn_assign_max_iou: k > 0 positive
+ *     (label gt_labels[gt_offsets[b] + k - 1]), 0 negative (background), < 0 label weight 0.  losses (2, L) =
+ *     [loss_cls per level, loss_bbox per level]: loss_weight * sum / num_total_pos with the sigmoid focal term of
+ *     brcnn_sigmoid_focal_loss_forward over every weighted (anchor, class) pair and L1 | SmoothL1 on pred -
+ *     bbox2delta(anchor, gt) over the positives; num_total_pos = sum over images of max(n_pos, 1) is counted by forward
+ *     and inverted by finalize on the device.  coef3 = [loss_weight_cls / num_total_pos, loss_weight_bbox /
+ *     num_total_pos, num_total_pos] goes to backward, which writes every element of dcls / dreg (padding columns: 0).
+ *     Fixed summation order, no float atomics.
+ * cfg14_host = [focal gamma, focal alpha, pos_weight (<= 0: 1), smooth_l1_beta (0: L1), means x4, stds x4,
+ * loss_weight_cls, loss_weight_bbox].  workspace: brcnn_dense_loss_workspace_bytes, shared by forward and finalize.
+ * -------------------------------------------------------------------------- */
+int brcnn_dense_score(const float *cls, float *score, int64_t rows, int num_anchors, int num_classes, int cls_stride,
+                      void *stream);
+int brcnn_dense_decode_levels(const int64_t *const *topk_inds, const float *const *cls, const int *cls_strides,
+                              const float *const *bbox_pred, const int *pred_strides,
+                              const float *const *base_anchors, int batch, int num_levels, const int *counts,
+                              const int *heights, const int *widths, int num_anchors, int num_classes,
+                              const int *strides_w, const int *strides_h, const float *max_shape,
+                              const float *scale_factor, const float *means4_host, const float *stds4_host,
+                              double wh_ratio_clip, float score_thr, float *boxes, float *scores, int64_t *labels,
+                              uint8_t *valid, int32_t *n_valid, void *stream);
+size_t brcnn_dense_loss_workspace_bytes(int batch, int num_levels, const int *heights, const int *widths,
+                                        int anchors_per_cell, int num_classes);
+int brcnn_dense_loss_forward(const float *cls, int cls_stride, const float *reg, int reg_stride, int batch,
+                             int num_levels, const int *heights, const int *widths, const int *strides_w,
+                             const int *strides_h, const float *const *base_anchors, int anchors_per_cell,
+                             int num_classes, const int32_t *gt_inds, const float *gts, const int64_t *gt_labels,
+                             const int *gt_offsets_host, const float *cfg14_host, void *workspace,
+                             size_t workspace_bytes, void *stream);
+int brcnn_dense_loss_finalize(const void *workspace, size_t workspace_bytes, int batch, int num_levels,
+                              const int *heights, const int *widths, int anchors_per_cell, int num_classes,
+                              const float *cfg14_host, float *losses, float *coef3, void *stream);
+int brcnn_dense_loss_backward(const float *cls, int cls_stride, const float *reg, int reg_stride, int batch,
+                              int num_levels, const int *heights, const int *widths, const int *strides_w,
+                              const int *strides_h, const float *const *base_anchors, int anchors_per_cell,
+                              int num_classes, const int32_t *gt_inds, const float *gts, const int64_t *gt_labels,
+                              const int *gt_offsets_host, const float *cfg14_host, const float *grad_losses,
+                              const float *coef3, float *dcls, float *dreg, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Optimizer step of the train loop: SGD with momentum and weight decay after clipping the global gradient
  * norm (torch.optim.SGD + mmcv OptimizerHook grad_clip; configs/_base_/schedules/schedule_1x.py:2-3,
  * configs/boosting_rcnn/boosting_rcnn_r50_pafpn_1x_utdac.py:130), as three stages over tables of tensors
