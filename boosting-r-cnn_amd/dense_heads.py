@@ -1301,6 +1301,12 @@ class RetinaHead(AnchorHead):
             [p[1] for p in picked], list(cls_nhwc), list(reg_nhwc), [self._base_anchors(l, device) for l in range(L)], sizes,
             list(self.anchor_generator.strides), C, max_shape, sf, self.bbox_coder.means, self.bbox_coder.stds, cfg.score_thr)
         self.last_n_valid = nv
+        return self._nms_candidates(bb, sc, lb, va, C, cfg)
+
+    @staticmethod
+    def _nms_candidates(bb, sc, lb, va, C, cfg):
+        """class-aware NMS + max_per_img of the (level, pick, class) candidate slots of a dense head (shared with FCOSHead)"""
+        B = bb.shape[0]
         nms_cfg = dict(cfg.nms)
         nms_cfg.pop('type', None)
         T = sc.shape[1] // C
@@ -1458,3 +1464,493 @@ class RetinaHead(AnchorHead):
         losses, coef = train_ops.dense_loss(ycls, yreg, gt_inds, gts, labels, meta)
         self.last_targets = (gt_inds, coef)
         return dict(loss_cls=list(losses[0].unbind(0)), loss_bbox=list(losses[1].unbind(0)))
+
+
+INF = 1e8
+
+
+def distance2bbox(points, distance):
+    """core/bbox/transforms.py:118-141 without the clip: (n, 2) points and (n, 4) [l, t, r, b] distances -> corner boxes"""
+    return torch.stack([points[..., 0] - distance[..., 0], points[..., 1] - distance[..., 1],
+                        points[..., 0] + distance[..., 2], points[..., 1] + distance[..., 3]], -1)
+
+
+@HEADS.register_module()
+class FCOSHead(nn.Module):
+    """The head of FCOS (mmdet/models/dense_heads/fcos_head.py:18-649 over anchor_free_head.py:16-330): two towers of
+    `stacked_convs` 3x3 conv + GroupNorm + ReLU (`cls_convs.{i}.{conv,gn}`, `reg_convs.{i}.{conv,gn}`), then the 3x3
+    `conv_cls` (C sigmoid class logits per cell), `conv_reg` (4 distances) and `conv_centerness`, and one `Scale` per
+    level (`scales.{l}.scale`).  No anchors: the candidates are the cell centres.  Parameter names and shapes are the
+    reference's.  Execution: every tower layer is one conv launch plus one GroupNorm+ReLU launch over all pyramid levels;
+    each tower ends in ONE fused fp32 head conv, the centerness riding with the tower it reads ([cls C | ctr 1 | pad] and
+    [reg 4 | pad], or [cls C | pad] and [reg 4 | ctr 1 | pad] under `centerness_on_reg`).  The kernels of
+    csrc/fcos_head.hip read these two tensors in place and apply the `Scale`, the exp / relu and the test-time `* stride`
+    themselves: scoring, top-k, decode + class fan-out and the NMS of the whole batch, and in training the point
+    assignment and the focal / centerness-weighted IoU / centerness loss, all on the device -- inference reads the host
+    once (when the results leave), the head's train step never.  CPU tensors take the reference's chain on torch ops (the
+    host mirror the CPU tests compare with the fixture)."""
+
+    supports_tta = False
+    MAX_NMS_PRE, MAX_LEVELS = 4096, 8        # brcnn_rpn_topk
+
+    def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=4, strides=(4, 8, 16, 32, 64),
+                 regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, INF)), center_sampling=False,
+                 center_sample_radius=1.5, norm_on_bbox=False, centerness_on_reg=False, dcn_on_last_conv=False,
+                 conv_bias='auto',
+                 loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                 loss_bbox=dict(type='IoULoss', loss_weight=1.0),
+                 loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
+                 conv_cfg=None, norm_cfg=dict(type='GN', num_groups=32, requires_grad=True), train_cfg=None, test_cfg=None,
+                 init_cfg=None):
+        super().__init__()
+        name = 'FCOSHead'
+        if norm_cfg is None or norm_cfg.get('type') != 'GN':
+            raise NotImplementedError(f'{name}: norm_cfg={norm_cfg!r}; the towers run conv + GroupNorm + ReLU, only GN is '
+                                      'supported')
+        if conv_bias != 'auto':
+            raise NotImplementedError(f"{name}: conv_bias={conv_bias!r}; only 'auto' (no tower bias under GN) is supported")
+        if dcn_on_last_conv:
+            raise NotImplementedError(f'{name}: dcn_on_last_conv=True is not supported')
+        if not loss_cls.get('use_sigmoid', False):
+            raise NotImplementedError(f'{name}: loss_cls.use_sigmoid=False (softmax scores with a background column) is not '
+                                      'supported; scoring and the focal loss are sigmoid')
+        if loss_cls.get('type') != 'FocalLoss':
+            raise NotImplementedError(f"{name}: loss_cls.type={loss_cls.get('type')!r}; only FocalLoss is supported")
+        if loss_bbox.get('type') not in ('IoULoss', 'GIoULoss') or \
+                (loss_bbox.get('type') == 'IoULoss' and (loss_bbox.get('linear', False) or loss_bbox.get('mode', 'log') != 'log')):
+            raise NotImplementedError(f'{name}: loss_bbox={loss_bbox!r}; only IoULoss(mode=\'log\') and GIoULoss are supported')
+        if loss_centerness.get('type') != 'CrossEntropyLoss' or not loss_centerness.get('use_sigmoid', False):
+            raise NotImplementedError(f'{name}: loss_centerness={loss_centerness!r}; only the sigmoid CrossEntropyLoss is '
+                                      'supported')
+        if len(strides) != len(regress_ranges):
+            raise ValueError(f'{name}: {len(strides)} strides but {len(regress_ranges)} regress_ranges')
+        if len(strides) > self.MAX_LEVELS:
+            raise ValueError(f'{name}: {len(strides)} pyramid levels, at most {self.MAX_LEVELS} are supported')
+        if feat_channels > 256 or feat_channels % 4:
+            raise NotImplementedError(f'{name}: feat_channels={feat_channels}; the GroupNorm kernels take up to 256 channels in '
+                                      'whole quads')
+        self.num_classes, self.cls_out_channels = num_classes, num_classes
+        self.in_channels, self.feat_channels, self.stacked_convs = in_channels, feat_channels, stacked_convs
+        self.strides = [int(s) if not isinstance(s, (tuple, list)) else int(s[0]) for s in strides]
+        self.regress_ranges = tuple(tuple(r) for r in regress_ranges)
+        self.center_sampling, self.center_sample_radius = center_sampling, center_sample_radius
+        self.norm_on_bbox, self.centerness_on_reg = norm_on_bbox, centerness_on_reg
+        self.conv_cfg, self.norm_cfg = conv_cfg, norm_cfg
+        self.loss_cls, self.loss_bbox = build_loss(loss_cls), build_loss(loss_bbox)
+        self.loss_centerness = build_loss(loss_centerness)
+        for loss in (self.loss_cls, self.loss_bbox, self.loss_centerness):
+            if loss.reduction != 'mean':
+                raise NotImplementedError(f"{name}: {type(loss).__name__}.reduction={loss.reduction!r}; only 'mean'")
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        if self.test_cfg:
+            self._check_test_cfg(self.test_cfg)
+        self._init_layers()
+        self._tower_caches = [[PackedCache() for _ in range(stacked_convs)] for _ in range(2)]
+        self._head_caches = [PackedCache(), PackedCache()]
+        self._scale_cache = PackedCache()
+        self.init_weights()
+
+    def _init_layers(self):
+        self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
+        for i in range(self.stacked_convs):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            for convs in (self.cls_convs, self.reg_convs):
+                convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                        norm_cfg=self.norm_cfg, bias='auto'))
+        self.conv_cls = nn.Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
+        self.conv_reg = nn.Conv2d(self.feat_channels, 4, 3, padding=1)
+        self.conv_centerness = nn.Conv2d(self.feat_channels, 1, 3, padding=1)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
+
+    def init_weights(self):
+        """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name='conv_cls', bias_prob=0.01))
+        (fcos_head.py:80-88)"""
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.normal_(m.weight, 0, 0.01)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.conv_cls.bias, bias_init_with_prob(0.01))
+
+    def _check_test_cfg(self, cfg):
+        nms = cfg.get('nms', dict(type='nms'))
+        if nms.get('type', 'nms') != 'nms':
+            raise NotImplementedError(f"FCOSHead: test_cfg.nms.type={nms.get('type')!r}; only greedy 'nms' is supported "
+                                      '(no soft-NMS)')
+        if nms.get('class_agnostic', False):
+            raise NotImplementedError('FCOSHead: test_cfg.nms.class_agnostic=True is not supported')
+
+    # ------------------------------------------------------------------ forward
+    def _head_groups(self):
+        """the heads each tower ends in, in the column order of its fused output"""
+        if self.centerness_on_reg:
+            return (self.conv_cls,), (self.conv_reg, self.conv_centerness)
+        return (self.conv_cls, self.conv_centerness), (self.conv_reg,)
+
+    def _layout(self, a, r):
+        C = self.cls_out_channels
+        return ops.FcosLayout(a, r, C, 0, 0, self.centerness_on_reg, 4 if self.centerness_on_reg else C,
+                              self.norm_on_bbox, type(self.loss_bbox).__name__ == 'GIoULoss')
+
+    def _scales_tensor(self):
+        """the per-level Scale parameters as one (L,) fp32 device tensor, for the kernels (inference: cached)"""
+        ps = [s.scale for s in self.scales]
+        return self._scale_cache.get(ps, lambda: torch.stack([p.detach().float().reshape(()) for p in ps]).contiguous())
+
+    def forward_rows(self, feats):
+        """inference: list of (B,h,w,C) NHWC maps -> (A (rows, >= C+1 | C), R (rows, >= 4 | 5)) fp32 in every compute mode,
+        level-major rows, zero padding columns, and the level sizes"""
+        B = feats[0].shape[0]
+        sizes = [tuple(int(v) for v in f.shape[1:3]) for f in feats]
+        x0 = cat_rows(feats)
+        outs = []
+        for convs, caches, heads, hcache in zip((self.cls_convs, self.reg_convs), self._tower_caches, self._head_groups(),
+                                                self._head_caches):
+            x = x0
+            for m, cache in zip(convs, caches):
+                w = cache.get([m.conv.weight], lambda c=m: pack_weight(c.conv.weight).to(x0.dtype))
+                x, _ = ops.conv2d_nhwc_multi(x, w, B, sizes, None, None, None, False, 1, 1)
+                x = ops.groupnorm_nhwc_multi(x, m.norm.weight.detach(), m.norm.bias.detach(), m.norm.num_groups, B, sizes,
+                                             m.norm.eps, m.with_activation)
+
+            def builder(hs=heads):
+                w = torch.cat([pack_weight(h.weight) for h in hs], 0)
+                b = torch.cat([h.bias.detach().float() for h in hs], 0)
+                pad = -w.shape[0] % 8
+                if pad:
+                    w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
+                    b = torch.cat([b, b.new_zeros(pad)], 0)
+                return w.to(x0.dtype).contiguous(), b.contiguous()
+            w, b = hcache.get([t for h in heads for t in (h.weight, h.bias)], builder)
+            outs.append(ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, False, 1, 1, out_f32=True)[0])
+        return outs[0], outs[1], sizes
+
+    def forward_head_fused(self, feats):
+        """training forward over all levels: (A, R) fp32 with zero padding columns, level-major rows, differentiable, and the
+        level sizes"""
+        from .autograd import ConvNHWCFunction, GroupNormNHWCFunction, conv2d_nhwc_multi_autograd, fused_head_weights
+        B = feats[0].shape[0]
+        sizes = tuple(tuple(int(v) for v in f.shape[1:3]) for f in feats)
+        x0 = cat_rows(feats)
+        mult = 32 if x0.dtype == torch.float32 else 64
+        outs = []
+        for convs, heads in zip((self.cls_convs, self.reg_convs), self._head_groups()):
+            x = x0
+            for m in convs:
+                x = conv2d_nhwc_multi_autograd(x, m.conv.weight, None, B, sizes, 1, 1)
+                x = GroupNormNHWCFunction.apply(x, m.norm.weight, m.norm.bias, m.norm.num_groups, B, sizes, m.norm.eps,
+                                                m.with_activation)
+            w, b = fused_head_weights(heads, mult)
+            outs.append(ConvNHWCFunction.apply(x, w, b, B, sizes, 1, 1, False, False, True))      # fp32 head output
+        return outs[0], outs[1], sizes
+
+    def _decode_rows(self, a, r, sizes, B, training):
+        """(A, R) rows -> the reference's per-level NHWC (cls, bbox_pred AFTER scale / exp | relu [* stride], centerness)"""
+        C, co = self.cls_out_channels, (4 if self.centerness_on_reg else self.cls_out_channels)
+        cls, reg, ctr, r0 = [], [], [], 0
+        for l, (h, w) in enumerate(sizes):
+            n = B * h * w
+            va, vr = a[r0:r0 + n].view(B, h, w, a.shape[1]), r[r0:r0 + n].view(B, h, w, r.shape[1])
+            d = vr[..., :4] * self.scales[l].scale
+            if self.norm_on_bbox:
+                d = d.relu()
+                d = d if training else d * self.strides[l]
+            else:
+                d = d.exp()
+            cls.append(va[..., :C])
+            reg.append(d)
+            ctr.append((vr if self.centerness_on_reg else va)[..., co:co + 1])
+            r0 += n
+        return cls, reg, ctr
+
+    def forward_nhwc(self, feats):
+        """list of (B,h,w,C) -> (cls (B,h,w,C), bbox_pred (B,h,w,4) decoded distances, centerness (B,h,w,1)) lists, fp32"""
+        from .autograd import wants_grad
+        if not feats[0].is_cuda:
+            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
+            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
+        B = feats[0].shape[0]
+        if wants_grad(feats[0], self.conv_cls.weight, self.cls_convs[0].conv.weight):
+            a, r, sizes = self.forward_head_fused(list(feats))
+        else:
+            a, r, sizes = self.forward_rows(list(feats))
+        return self._decode_rows(a, r, sizes, B, self.training)
+
+    def forward(self, feats):
+        """reference signature (fcos_head.py:111-161): list of (N,C,h,w) -> lists of (N,C,h,w) class logits, (N,4,h,w)
+        distances after Scale and exp / relu, (N,1,h,w) centerness logits"""
+        if not feats[0].is_cuda:        # host mirror on torch ops
+            import torch.nn.functional as F
+            cls, reg, ctr = [], [], []
+            for x, scale, stride in zip(feats, self.scales, self.strides):
+                c = r = x
+                for m in self.cls_convs:
+                    c = F.relu(F.group_norm(F.conv2d(c, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
+                                            m.norm.bias, m.norm.eps))
+                for m in self.reg_convs:
+                    r = F.relu(F.group_norm(F.conv2d(r, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
+                                            m.norm.bias, m.norm.eps))
+                cls.append(F.conv2d(c, self.conv_cls.weight, self.conv_cls.bias, padding=1))
+                ctr.append(F.conv2d(r if self.centerness_on_reg else c, self.conv_centerness.weight,
+                                    self.conv_centerness.bias, padding=1))
+                d = (F.conv2d(r, self.conv_reg.weight, self.conv_reg.bias, padding=1) * scale.scale).float()
+                if self.norm_on_bbox:
+                    d = F.relu(d)
+                    d = d if self.training else d * stride
+                else:
+                    d = d.exp()
+                reg.append(d)
+            return cls, reg, ctr
+        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
+        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
+
+    # ------------------------------------------------------------------ test
+    def get_points(self, featmap_sizes, dtype, device):
+        """per level (h*w, 2) [x, y] cell centres: (x*s + s//2, y*s + s//2) (fcos_head.py:473-483)"""
+        pts = []
+        for (h, w), s in zip(featmap_sizes, self.strides):
+            ys, xs = torch.meshgrid(torch.arange(h, dtype=dtype, device=device), torch.arange(w, dtype=dtype, device=device),
+                                    indexing='ij')
+            pts.append(torch.stack((xs.reshape(-1) * s, ys.reshape(-1) * s), dim=-1) + s // 2)
+        return pts
+
+    def _check_limits(self, cfg, sizes):
+        if not 0 < cfg.get('nms_pre', -1) <= self.MAX_NMS_PRE:
+            raise ValueError(f"FCOSHead: nms_pre={cfg.get('nms_pre', -1)} outside (0, {self.MAX_NMS_PRE}] (brcnn_rpn_topk)")
+        if len(sizes) != len(self.strides):
+            raise ValueError(f'FCOSHead: {len(sizes)} pyramid levels for {len(self.strides)} strides')
+
+    def get_bboxes_rows(self, a, r, layout, scales, sizes, img_metas, cfg=None, rescale=False):
+        """fcos_head.py:329-471 for the whole batch on the device, no host sync: per-point max of class sigmoid x centerness
+        sigmoid, per-level top-k, decode / clip / rescale with the fan-out to classes, score threshold on the class score,
+        class-aware NMS, max_per_img.  Returns (dets (B, K, 5) zero padded, labels (B, K), num (B,) int32);
+        `self.last_n_valid` as RetinaHead keeps it."""
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_test_cfg(cfg)
+        self._check_limits(cfg, sizes)
+        B = len(img_metas)
+        scored, raw, r0 = ops.fcos_score(a, r, layout), [], 0
+        for (h, w) in sizes:
+            raw.append(scored[r0:r0 + B * h * w].view(B, h * w))
+            r0 += B * h * w
+        picked = ops.rpn_topk(raw, cfg.nms_pre)         # descending, ties by ascending index, all levels in one launch
+        max_shape = const_rows([m['img_shape'][:2] for m in img_metas], scored)
+        sf = const_rows([list(m['scale_factor']) for m in img_metas], scored) if rescale else None
+        bb, sc, lb, va, nv = ops.fcos_decode_levels([p[1] for p in picked], a, r, layout, scales, sizes, self.strides,
+                                                    max_shape, sf, cfg.score_thr)
+        self.last_n_valid = nv
+        return RetinaHead._nms_candidates(bb, sc, lb, va, self.cls_out_channels, cfg)
+
+    def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
+        a, r, sizes = self.forward_rows(list(feats_nhwc))
+        return self.get_bboxes_rows(a, r, self._layout(a, r), self._scales_tensor(), sizes, img_metas, rescale=rescale)
+
+    def _rows_from_reference(self, cls_scores, bbox_preds, centernesses, training):
+        """the reference-signature tensors (decoded distances) as the kernels' (A, R) rows with unit scales: the raw value
+        is log(d), or under norm_on_bbox d itself (test time: d / stride, exact for power-of-two strides; a distance
+        the relu left at exactly 0 takes no gradient, as through the relu)"""
+        rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float()   # noqa: E731
+        if self.norm_on_bbox:
+            raw = bbox_preds if training else [d / s for d, s in zip(bbox_preds, self.strides)]
+        else:
+            raw = [d.log() for d in bbox_preds]
+        cls, reg, ctr = rows(cls_scores), rows(raw), rows(centernesses)
+        if self.centerness_on_reg:
+            return cls.contiguous(), torch.cat([reg, ctr], 1).contiguous()
+        return torch.cat([cls, ctr], 1).contiguous(), reg.contiguous()
+
+    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg=None, rescale=False, with_nms=True,
+                   batched_nms=None):
+        """reference signature (fcos_head.py:263-327): per-level (N,C,h,w) / (N,4,h,w) / (N,1,h,w) -> per image (dets (k,5),
+        labels (k,)).  Device tensors take `get_bboxes_rows`; CPU tensors the reference's chain on torch ops, with the
+        caller's `batched_nms` (this package's NMS is a device kernel)."""
+        if not with_nms:
+            raise NotImplementedError('FCOSHead: with_nms=False is not supported')
+        assert len(cls_scores) == len(bbox_preds) == len(centernesses)
+        if cls_scores[0].is_cuda:
+            sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
+            a, r = self._rows_from_reference([t.detach() for t in cls_scores], [t.detach() for t in bbox_preds],
+                                             [t.detach() for t in centernesses], False)
+            det, lab, num = self.get_bboxes_rows(a, r, self._layout(a, r), a.new_ones(len(sizes)), sizes, img_metas, cfg,
+                                                 rescale)
+            num = num.tolist()   # the one host sync
+            return [(det[i, :num[i]], lab[i, :num[i]]) for i in range(len(img_metas))]
+        return self._get_bboxes_host(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms)
+
+    def _get_bboxes_host(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms):
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_test_cfg(cfg)
+        if batched_nms is None:
+            batched_nms = ops.batched_nms
+        B, C = cls_scores[0].shape[0], self.cls_out_channels
+        points_l = self.get_points([c.shape[-2:] for c in cls_scores], bbox_preds[0].dtype, bbox_preds[0].device)
+        nms_pre = cfg.get('nms_pre', -1)
+        out = []
+        for b in range(B):
+            boxes_l, scores_l, ctr_l = [], [], []
+            h_img, w_img = img_metas[b]['img_shape'][:2]
+            for cls, reg, ctr, pts in zip(cls_scores, bbox_preds, centernesses, points_l):
+                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
+                ct = ctr[b].detach().permute(1, 2, 0).reshape(-1).sigmoid()
+                d = reg[b].detach().permute(1, 2, 0).reshape(-1, 4)
+                if 0 < nms_pre < s.shape[0]:
+                    _, idx = (s * ct[:, None]).max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
+                    idx = idx[:nms_pre]
+                    pts, d, s, ct = pts[idx], d[idx], s[idx], ct[idx]
+                bx = torch.stack([pts[:, 0] - d[:, 0], pts[:, 1] - d[:, 1], pts[:, 0] + d[:, 2], pts[:, 1] + d[:, 3]], -1)
+                hi = bx.new_tensor([w_img, h_img, w_img, h_img])
+                bx = torch.where(bx < 0, bx.new_zeros(()), bx)
+                bx = torch.where(bx > hi, hi, bx)
+                boxes_l.append(bx)
+                scores_l.append(s)
+                ctr_l.append(ct)
+            boxes, scores, ctrs = torch.cat(boxes_l), torch.cat(scores_l), torch.cat(ctr_l)
+            if rescale:
+                boxes = boxes / boxes.new_tensor(img_metas[b]['scale_factor'])
+            keep = (scores > cfg.score_thr).reshape(-1)          # before the centerness factor (bbox_nms.py:48-58)
+            inds = keep.nonzero(as_tuple=False).reshape(-1)
+            labels = torch.arange(C, dtype=torch.long).repeat(scores.shape[0])[inds]
+            cb = boxes[:, None].expand(-1, C, 4).reshape(-1, 4)[inds]
+            cs = (scores * ctrs[:, None]).reshape(-1)[inds]
+            if cb.numel() == 0:
+                out.append((torch.cat([cb, cs[:, None]], -1), labels))
+                continue
+            dets, kept = batched_nms(cb.contiguous(), cs.contiguous(), labels, dict(cfg.nms))
+            if cfg.max_per_img > 0:
+                dets, kept = dets[:cfg.max_per_img], kept[:cfg.max_per_img]
+            out.append((dets, labels[kept]))
+        return out
+
+    def simple_test(self, feats, img_metas, rescale=False, batched_nms=None):
+        """dense_test_mixins.py:17-37: list of (N,C,h,w) -> per image (dets (k,5), labels (k,))"""
+        return self.get_bboxes(*self(feats), img_metas, rescale=rescale, batched_nms=batched_nms)
+
+    def aug_test(self, feats, img_metas, rescale=False):
+        raise NotImplementedError('FCOSHead has no test-time augmentation')
+
+    # ------------------------------------------------------------------ train
+    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
+        """base_dense_head.py:48-78"""
+        outs = self(x)
+        losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+        if proposal_cfg is None:
+            return losses
+        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
+
+    def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
+        """the device-resident train step of the head: NHWC pyramid -> towers and fused heads over all levels -> point
+        assignment and loss kernels; no host read"""
+        if gt_bboxes_ignore is not None:
+            raise NotImplementedError('FCOSHead: gt_bboxes_ignore is not supported on the device path')
+        a, r, sizes = self.forward_head_fused(list(feats_nhwc))
+        scales = torch.stack([s.scale.float().reshape(()) for s in self.scales])
+        return self.loss_fused(a, r, scales, sizes, gt_bboxes, gt_labels, img_metas)
+
+    def loss_fused(self, a, r, scales, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
+        """FCOSHead.loss on the fused head outputs of all levels: whole-batch point assignment, then the loss kernels --
+        targets and both normalisers are formed on the device (averaged over ranks there when distributed), nothing is
+        read back.  `self.last_targets` keeps (gt_inds, coef3, norm2)."""
+        from . import train_ops
+        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
+        gts, labels = gts.to(a.device), labels.to(a.device)
+        B = len(img_metas)
+        gt_inds = train_ops.fcos_assign(gts, offs, B, sizes, self.strides, self.regress_ranges, self.center_sampling,
+                                        self.center_sample_radius)
+        giou = type(self.loss_bbox).__name__ == 'GIoULoss'
+        meta = train_ops.FcosLossMeta(B, sizes, self.strides, self.cls_out_channels, offs, self.loss_cls.gamma,
+                                      self.loss_cls.alpha, self.loss_bbox.eps if giou else 1e-6, self.loss_bbox.eps,
+                                      self.loss_cls.loss_weight, self.loss_bbox.loss_weight, self.loss_centerness.loss_weight)
+        hook = None
+        if dist.is_available() and dist.is_initialized():
+            hook = lambda n2: n2.copy_(reduce_mean(n2))     # noqa: E731  (the reference's two reduce_mean calls as one)
+        losses, coef, norm2 = train_ops.fcos_loss(a, r, scales, gt_inds, gts, labels, self._layout(a, r), meta, hook)
+        self.last_targets = (gt_inds, coef, norm2)
+        return dict(loss_cls=losses[0], loss_bbox=losses[1], loss_centerness=losses[2])
+
+    def get_targets(self, points, gt_bboxes_list, gt_labels_list):
+        """fcos_head.py:485-628 on torch ops (the host mirror): per level, images concatenated, (labels, bbox_targets)"""
+        num_points = [p.size(0) for p in points]
+        ranges = torch.cat([p.new_tensor(rr)[None].expand_as(p) for p, rr in zip(points, self.regress_ranges)], 0)
+        pts = torch.cat(points, 0)
+        radius = torch.cat([p.new_full((p.size(0),), s * self.center_sample_radius) for p, s in zip(points, self.strides)])
+        labels_list, targets_list = [], []
+        for gt, gl in zip(gt_bboxes_list, gt_labels_list):
+            n, G = pts.size(0), gl.size(0)
+            if G == 0:
+                labels_list.append(gl.new_full((n,), self.num_classes))
+                targets_list.append(gt.new_zeros((n, 4)))
+                continue
+            areas = ((gt[:, 2] - gt[:, 0]) * (gt[:, 3] - gt[:, 1]))[None].repeat(n, 1)
+            g = gt[None].expand(n, G, 4)
+            xs, ys = pts[:, 0:1].expand(n, G), pts[:, 1:2].expand(n, G)
+            t = torch.stack((xs - g[..., 0], ys - g[..., 1], g[..., 2] - xs, g[..., 3] - ys), -1)
+            if self.center_sampling:
+                cx, cy = (g[..., 0] + g[..., 2]) / 2, (g[..., 1] + g[..., 3]) / 2
+                rad = radius[:, None].expand(n, G)
+                x0, y0, x1, y1 = cx - rad, cy - rad, cx + rad, cy + rad
+                c0 = torch.where(x0 > g[..., 0], x0, g[..., 0])
+                c1 = torch.where(y0 > g[..., 1], y0, g[..., 1])
+                c2 = torch.where(x1 > g[..., 2], g[..., 2], x1)
+                c3 = torch.where(y1 > g[..., 3], g[..., 3], y1)
+                inside = torch.stack((xs - c0, ys - c1, c2 - xs, c3 - ys), -1).min(-1)[0] > 0
+            else:
+                inside = t.min(-1)[0] > 0
+            far = t.max(-1)[0]
+            in_range = (far >= ranges[:, None, 0]) & (far <= ranges[:, None, 1])
+            areas[inside == 0] = INF
+            areas[in_range == 0] = INF
+            min_area, idx = areas.min(dim=1)
+            lab = gl[idx]
+            lab[min_area == INF] = self.num_classes
+            labels_list.append(lab)
+            targets_list.append(t[range(n), idx])
+        labels_list = [l.split(num_points, 0) for l in labels_list]
+        targets_list = [t.split(num_points, 0) for t in targets_list]
+        out_l, out_t = [], []
+        for i in range(len(points)):
+            out_l.append(torch.cat([l[i] for l in labels_list]))
+            t = torch.cat([t[i] for t in targets_list])
+            out_t.append(t / self.strides[i] if self.norm_on_bbox else t)
+        return out_l, out_t
+
+    @staticmethod
+    def centerness_target(pos_bbox_targets):
+        """fcos_head.py:630-649"""
+        lr, tb = pos_bbox_targets[:, [0, 2]], pos_bbox_targets[:, [1, 3]]
+        if len(lr) == 0:
+            return torch.sqrt(lr[..., 0])
+        return torch.sqrt((lr.min(dim=-1)[0] / lr.max(dim=-1)[0]) * (tb.min(dim=-1)[0] / tb.max(dim=-1)[0]))
+
+    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        """fcos_head.py:164-261.  Device tensors go to the HIP kernels (`loss_fused`, with unit scales on log(d) resp. d);
+        CPU tensors take the reference's chain in torch (the host mirror)."""
+        assert len(cls_scores) == len(bbox_preds) == len(centernesses)
+        featmap_sizes = [tuple(int(v) for v in f.size()[-2:]) for f in cls_scores]
+        device = cls_scores[0].device
+        if device.type == 'cuda':
+            if gt_bboxes_ignore is not None:
+                raise NotImplementedError('FCOSHead: gt_bboxes_ignore is not supported on the device path')
+            a, r = self._rows_from_reference(cls_scores, bbox_preds, centernesses, True)
+            return self.loss_fused(a, r, a.new_ones(len(featmap_sizes)), featmap_sizes, gt_bboxes, gt_labels, img_metas)
+        points = self.get_points(featmap_sizes, bbox_preds[0].dtype, device)
+        labels, bbox_targets = self.get_targets(points, gt_bboxes, gt_labels)
+        num_imgs = cls_scores[0].size(0)
+        flat = lambda lst, c: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, c) for t in lst])    # noqa: E731
+        f_cls, f_box = flat(cls_scores, self.cls_out_channels), flat(bbox_preds, 4)
+        f_ctr = flat(centernesses, 1).reshape(-1)
+        f_labels, f_targets = torch.cat(labels), torch.cat(bbox_targets)
+        f_points = torch.cat([p.repeat(num_imgs, 1) for p in points])
+        pos_inds = ((f_labels >= 0) & (f_labels < self.num_classes)).nonzero().reshape(-1)
+        num_pos = max(reduce_mean(torch.tensor(len(pos_inds), dtype=torch.float, device=device)), 1.0)
+        loss_cls = self.loss_cls(f_cls, f_labels, avg_factor=num_pos)
+        pos_box, pos_ctr, pos_t = f_box[pos_inds], f_ctr[pos_inds], f_targets[pos_inds]
+        ctr_t = self.centerness_target(pos_t)
+        denorm = max(reduce_mean(ctr_t.sum().detach()), 1e-6)
+        if len(pos_inds) > 0:
+            pos_pts = f_points[pos_inds]
+            loss_bbox = self.loss_bbox(distance2bbox(pos_pts, pos_box), distance2bbox(pos_pts, pos_t), weight=ctr_t,
+                                       avg_factor=denorm)
+            loss_centerness = self.loss_centerness(pos_ctr, ctr_t, avg_factor=num_pos)
+        else:
+            loss_bbox, loss_centerness = pos_box.sum(), pos_ctr.sum()
+        return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)

@@ -594,3 +594,11 @@ class RetinaNet(SingleStageDetector):
 
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)
+
+
+@DETECTORS.register_module()
+class FCOS(SingleStageDetector):
+    """mmdet/models/detectors/fcos.py:6-17"""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)

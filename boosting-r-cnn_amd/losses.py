@@ -1,7 +1,7 @@
 """Loss leaf functions of the hot path, registered under the reference's names.
 
 Reference: mmdet/models/losses/{utils.py:28-101, focal_loss.py:12-182, varifocal_loss.py:10-134,
-cross_entropy_loss.py:10-251, iou_loss.py:14-50,175-236,456-534, mse_loss.py:9-57, smooth_l1_loss.py:10-146,
+cross_entropy_loss.py:10-251, iou_loss.py:14-50,102-117,175-236,456-534,573-614, mse_loss.py:9-57, smooth_l1_loss.py:10-146,
 accuracy.py:6-79}.  The device-resident train step does not come through here (its loss arithmetic lives in the fused
 HIP kernels `brcnn_rpn_loss_*` / `brcnn_boost_loss_*`); these modules serve the reference-signature entry points --
 host tensors, the per-image chain the tests compare against, off-path callers -- with the reference's fp32 operation
@@ -209,6 +209,24 @@ class IoULoss(_BoxLoss):
 
     def term(self, pred, target, **kwargs):
         return iou_loss(pred, target, None, mode=self.mode, eps=self.eps, reduction='none', **kwargs)
+
+
+def giou_loss(pred, target, weight=None, eps=1e-7, reduction='mean', avg_factor=None):
+    """iou_loss.py:102-117: 1 - GIoU of aligned boxes, union and enclosing area floored at eps"""
+    return weight_reduce_loss(1 - bbox_overlaps(pred, target, mode='giou', is_aligned=True, eps=eps), weight, reduction,
+                              avg_factor)
+
+
+@LOSSES.register_module()
+class GIoULoss(_BoxLoss):
+    keep_none_on_zero_weight = False     # iou_loss.py:589: the shortcut applies whatever the reduction
+
+    def __init__(self, eps=1e-6, reduction='mean', loss_weight=1.0):
+        super().__init__(reduction, loss_weight)
+        self.eps = eps
+
+    def term(self, pred, target, **kwargs):
+        return giou_loss(pred, target, None, eps=self.eps, reduction='none', **kwargs)
 
 
 def ciou_loss(pred, target, weight=None, eps=1e-7, reduction='mean', avg_factor=None):

@@ -1301,6 +1301,72 @@ def dense_decode_levels(topk_inds, cls_scores, bbox_preds, base_anchors, feat_hw
     return boxes, scores, labels, valid, n_valid
 
 
+# --------------------------------------------------------------------------- FCOS head, test time
+class FcosLayout:
+    """where the FCOS kernels find the head outputs: A (rows, stride_a) with the C class logits at `cls_off`, R (rows,
+    stride_r) with the 4 raw distances at `reg_off`, the centerness logit in column `ctr_off` of A, or of R when
+    `ctr_in_r` (centerness_on_reg); plus the two switches the kernels branch on (include/brcnn_hip.h: layout8_host)"""
+
+    def __init__(self, a, r, num_classes, cls_off, reg_off, ctr_in_r, ctr_off, norm_on_bbox=False, giou=False):
+        import ctypes
+        _require_gpu(a, r)
+        for t in (a, r):
+            assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous()
+        assert a.shape[0] == r.shape[0]
+        c = int(num_classes)
+        assert 0 <= cls_off and cls_off + c <= a.shape[1] and 0 <= reg_off and reg_off + 4 <= r.shape[1]
+        host = a if not ctr_in_r else r
+        assert 0 <= ctr_off < host.shape[1]
+        self.C, self.rows = c, int(a.shape[0])
+        self.values = (int(a.shape[1]), int(cls_off), int(r.shape[1]), int(reg_off), int(bool(ctr_in_r)), int(ctr_off),
+                       int(bool(norm_on_bbox)), int(bool(giou)))
+        self.arr = (ctypes.c_int * 8)(*self.values)
+
+
+def fcos_score(a, r, layout):
+    """max_c(sigmoid(cls_c) * sigmoid(ctr)) per row of the head outputs of all levels (fcos_head.py:396; brcnn_fcos_score):
+    (rows,) dense fp32, the input of `rpn_topk` once split by level"""
+    out = torch.empty((layout.rows,), dtype=torch.float32, device=a.device)
+    st = _L.load().brcnn_fcos_score(_ptr(a), _ptr(r), layout.arr, layout.C, layout.rows, _ptr(out), _stream())
+    _L.check(st, 'brcnn_fcos_score')
+    return out
+
+
+def fcos_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, max_shape, scale_factor, score_thr):
+    """The candidates of multiclass_nms(score_factors=centerness) for all levels and images in one launch
+    (brcnn_fcos_decode_levels).  topk_inds: per level (B, k_l) int64 cell indices; scales (L,) fp32 on the device; max_shape
+    (B, 2) [h, w]; scale_factor (B, 4) or None.  Returns boxes (B,T*C,4), scores (B,T*C) = class sigmoid * centerness
+    sigmoid, labels (B,T*C) int64, valid (B,T*C) bool = class sigmoid > score_thr, n_valid (B,) int32; T = sum k_l, (level,
+    pick, class) order."""
+    import ctypes
+    L = len(topk_inds)
+    _require_gpu(*topk_inds, scales, max_shape, scale_factor)
+    b, c = topk_inds[0].shape[0], layout.C
+    inds = [t.contiguous() for t in topk_inds]
+    assert all(t.dtype == torch.int64 and t.shape[0] == b for t in inds)
+    assert scales.dtype == torch.float32 and scales.numel() == L and scales.is_contiguous()
+    assert layout.rows == sum(b * h * w for h, w in feat_hws) and len(feat_hws) == L and len(strides) == L
+    counts = [int(t.shape[1]) for t in inds]
+    n = sum(counts) * c
+    dev = a.device
+    assert max_shape.shape == (b, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
+    if scale_factor is not None:
+        assert scale_factor.shape == (b, 4) and scale_factor.dtype == torch.float32 and scale_factor.is_contiguous()
+    boxes = torch.empty((b, n, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, n), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, n), dtype=torch.int64, device=dev)
+    valid = torch.empty((b, n), dtype=torch.bool, device=dev)
+    n_valid = torch.empty((b,), dtype=torch.int32, device=dev)
+    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in inds])
+    ints = lambda vs: (ctypes.c_int * L)(*[int(v) for v in vs])               # noqa: E731
+    st = _L.load().brcnn_fcos_decode_levels(
+        ptrs, ints(counts), _ptr(a), _ptr(r), layout.arr, _ptr(scales), b, L, ints([h for h, _ in feat_hws]),
+        ints([w for _, w in feat_hws]), ints(strides), c, _ptr(max_shape), _ptr(scale_factor), float(score_thr), _ptr(boxes),
+        _ptr(scores), _ptr(labels), _ptr(valid), _ptr(n_valid), _stream())
+    _L.check(st, 'brcnn_fcos_decode_levels')
+    return boxes, scores, labels, valid, n_valid
+
+
 # --------------------------------------------------------------------------- Cascade R-CNN, test time
 def _rows_in_place(t):
     """a fp32 (rows, cols) device tensor the cascade kernels read with a row stride: the two column blocks of the heads'

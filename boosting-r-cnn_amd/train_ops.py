@@ -480,6 +480,121 @@ def dense_loss(cls, reg, gt_inds, gts, gt_labels, meta):
     return DenseLossFunction.apply(cls, reg, gt_inds, gts, gt_labels, meta)
 
 
+# ----------------------------------------------------------------------------- FCOS head: targets and loss
+class FcosLossMeta:
+    """host-side description of one FCOS loss call: the pyramid, the ground-truth offsets and the loss settings
+    (include/brcnn_hip.h: cfg7_host)"""
+
+    def __init__(self, batch, sizes, strides, num_classes, gt_offsets, focal_gamma, focal_alpha, eps_overlap, eps_loss,
+                 lw_cls, lw_bbox, lw_ctr):
+        self.batch, self.sizes, self.C = int(batch), [tuple(int(v) for v in s) for s in sizes], int(num_classes)
+        self.L = len(self.sizes)
+        if self.batch > MAX_IMAGES:
+            raise ValueError(f'fcos loss: batch {self.batch} exceeds {MAX_IMAGES} images per call')
+        self.hs, self.ws = _ints([h for h, _ in self.sizes]), _ints([w for _, w in self.sizes])
+        self.strides = _ints([s if isinstance(s, int) else s[0] for s in strides])
+        self.gt_offsets = _ints(gt_offsets)
+        self.total_gt = int(gt_offsets[-1])
+        self.cfg = _floats([focal_gamma, focal_alpha, eps_overlap, eps_loss, lw_cls, lw_bbox, lw_ctr])
+        self.rows = sum(self.batch * h * w for h, w in self.sizes)
+        self.points_per_image = sum(h * w for h, w in self.sizes)
+
+
+def fcos_assign(gts, gt_offsets, batch, sizes, strides, regress_ranges, center_sampling=False, center_sample_radius=1.5):
+    """FCOSHead._get_target_single for the whole batch (brcnn_fcos_assign): gts (sum G, 4) fp32 packed, host offsets ->
+    gt_inds (batch, points per image) int32, the image-local index of the ground truth each point takes, -1 background"""
+    _require_gpu(gts)
+    L = len(sizes)
+    assert len(strides) == L and len(regress_ranges) == L and len(gt_offsets) == batch + 1
+    total = int(gt_offsets[-1])
+    if total:
+        assert gts.dtype == torch.float32 and gts.shape == (total, 4) and gts.is_contiguous()
+    n = sum(int(h) * int(w) for h, w in sizes)
+    out = torch.empty((batch, n), dtype=torch.int32, device=gts.device)
+    ranges = _floats([v for lo_hi in regress_ranges for v in lo_hi])
+    st = _L.load().brcnn_fcos_assign(_ptr(gts) if total else None, _ints(gt_offsets), int(batch), L,
+                                     _ints([h for h, _ in sizes]), _ints([w for _, w in sizes]), _ints(strides), ranges,
+                                     int(bool(center_sampling)), float(center_sample_radius), _ptr(out), _stream())
+    _L.check(st, 'brcnn_fcos_assign')
+    return out
+
+
+def _fcos_check(a, r, layout, scales, gt_inds, gts, gt_labels, meta):
+    _require_gpu(a, r, scales, gt_inds, gts, gt_labels)
+    assert layout.rows == meta.rows and layout.C == meta.C
+    assert scales.dtype == torch.float32 and scales.shape == (meta.L,) and scales.is_contiguous()
+    assert gt_inds.dtype == torch.int32 and gt_inds.shape == (meta.batch, meta.points_per_image) and gt_inds.is_contiguous()
+    if meta.total_gt:
+        assert gts.dtype == torch.float32 and gts.shape == (meta.total_gt, 4) and gts.is_contiguous()
+        assert gt_labels.dtype == torch.int64 and gt_labels.shape == (meta.total_gt,) and gt_labels.is_contiguous()
+
+
+def fcos_loss_partials(a, r, layout, scales, gt_inds, gts, gt_labels, meta):
+    """brcnn_fcos_loss_forward: (workspace holding the block partials, norm2 = [n_pos, sum of centerness targets]) on the
+    device; the caller may average norm2 over ranks before `fcos_loss_finalize`"""
+    _fcos_check(a, r, layout, scales, gt_inds, gts, gt_labels, meta)
+    lib = _L.load()
+    nb = lib.brcnn_fcos_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.C)
+    ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=a.device)
+    norm2 = torch.empty((2,), dtype=torch.float32, device=a.device)
+    gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
+    st = lib.brcnn_fcos_loss_forward(_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws,
+                                     meta.strides, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg, _ptr(ws), nb,
+                                     _ptr(norm2), _stream())
+    _L.check(st, 'brcnn_fcos_loss_forward')
+    return ws, norm2
+
+
+def fcos_loss_finalize(ws, norm2, meta):
+    """brcnn_fcos_loss_finalize: out6 = [loss_cls, loss_bbox, loss_centerness | lw_cls / N, lw_bbox / S, lw_ctr / N]"""
+    out = torch.empty((6,), dtype=torch.float32, device=ws.device)
+    st = _L.load().brcnn_fcos_loss_finalize(_ptr(ws), ws.numel() * 4, _ptr(norm2), meta.batch, meta.L, meta.hs, meta.ws,
+                                            meta.C, meta.cfg, _ptr(out[:3]), _ptr(out[3:]), _stream())
+    _L.check(st, 'brcnn_fcos_loss_finalize')
+    return out[:3], out[3:]
+
+
+class FcosLossFunction(Function):
+    """losses (3,) = [loss_cls, loss_bbox, loss_centerness] from the head outputs of all levels, differentiable w.r.t. A, R
+    (the raw outputs) and the per-level scales"""
+
+    @staticmethod
+    def forward(ctx, a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook):
+        scales = scales.detach().float().contiguous()
+        ws, norm2 = fcos_loss_partials(a, r, layout, scales, gt_inds, gts, gt_labels, meta)
+        if norm_hook is not None:
+            norm_hook(norm2)
+        losses, coef = fcos_loss_finalize(ws, norm2, meta)
+        ctx.save_for_backward(a, r, scales, gt_inds, gts, gt_labels, coef)
+        ctx.layout, ctx.meta = layout, meta
+        ctx.mark_non_differentiable(coef, norm2)
+        return losses, coef, norm2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g3, _gc, _gn):
+        a, r, scales, gt_inds, gts, gt_labels, coef = ctx.saved_tensors
+        meta, layout = ctx.meta, ctx.layout
+        da, dr = torch.empty_like(a), torch.empty_like(r)
+        dscale = torch.empty_like(scales)
+        g3 = g3.float().contiguous()
+        lib = _L.load()
+        nb = lib.brcnn_fcos_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.C)
+        ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=a.device)
+        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
+        st = lib.brcnn_fcos_loss_backward(_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws,
+                                          meta.strides, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg, _ptr(g3),
+                                          _ptr(coef), _ptr(ws), nb, _ptr(da), _ptr(dr), _ptr(dscale), _stream())
+        _L.check(st, 'brcnn_fcos_loss_backward')
+        return da, dr, dscale, None, None, None, None, None, None
+
+
+def fcos_loss(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook=None):
+    """(losses (3,), coef3, norm2); `norm_hook(norm2)` may change norm2 in place between the sums and the division (the
+    mean over ranks)"""
+    return FcosLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
+
+
 # ----------------------------------------------------------------------------- boosting loss
 class BoostLossFunction(Function):
     """out3 = [loss_cls, loss_bbox, acc] of the boosting-reweighted R-CNN loss

@@ -1244,6 +1244,59 @@ int brcnn_dense_loss_backward(const float *cls, int cls_stride, const float *reg
                               const float *coef3, float *dcls, float *dreg, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * The anchor-free dense head: FCOSHead (models/dense_heads/fcos_head.py), csrc/fcos_head.hip.  The candidates are the cell
+ * centres: level l with stride s, cell (y, x) is the point (x*s + s/2, y*s + s/2), s/2 an integer division.  The head
+ * outputs are two fp32 row tensors over all levels (level-major rows, level l: batch * h_l * w_l rows), read in place:
+ * A (rows, stride_a) holds the C class logits at column cls_off, R (rows, stride_r) the 4 RAW distances at column reg_off,
+ * and the centerness logit is column ctr_off of A, or of R when ctr_in_r.  layout8_host = [stride_a, cls_off, stride_r,
+ * reg_off, ctr_in_r, ctr_off, norm_on_bbox, giou].  scales: (L) floats ON THE DEVICE, the per-level Scale; the distance
+ * is expf(scale_l * raw), or under norm_on_bbox max(scale_l * raw, 0) (times stride_l at test time only).
+ *   brcnn_fcos_score: score[row] = max_c(sigmoid(cls_c) * sigmoid(ctr)) (fcos_head.py:396), the maximum over the fp32
+ *     products; equal products tie and brcnn_rpn_topk's ascending-index rule decides.  Feeds brcnn_rpn_topk.
+ *   brcnn_fcos_decode_levels: everything between the top-k and multiclass_nms(score_factors=centerness) for all levels and
+ *     images in one launch.  topk_inds[l] (batch, counts[l]) int64 cell indices of level l.  Box (px - d0, py - d1,
+ *     px + d2, py + d3) clipped to max_shape (batch, 2) [h, w], divided by scale_factor (batch, 4) unless NULL.  With T =
+ *     sum(counts), in (level, pick, class) order: boxes (batch, T*C, 4), scores = sigmoid(cls_c) * sigmoid(ctr), labels,
+ *     valid = sigmoid(cls_c) > score_thr (the class score BEFORE the centerness factor), n_valid (batch).
+ *   brcnn_fcos_assign: _get_target_single (fcos_head.py:546-628) for every (image, point): gt_inds (batch, points per
+ *     image) int32, the index of the smallest-area ground truth of the image whose box (or centre box of radius
+ *     stride_l * center_sample_radius, clipped to the box, under center_sampling) strictly contains the point and whose
+ *     largest side distance lies in [ranges[2l], ranges[2l+1]]; ties go to the lowest index; -1 background.
+ *   brcnn_fcos_loss_forward / _finalize / _backward: FCOSHead.loss (fcos_head.py:164-261).  forward leaves block partials
+ *     in the workspace and norm2 = [n_pos, sum of the centerness targets] on the device (the caller may average norm2 over
+ *     ranks); finalize forms N = max(norm2[0], 1), S = max(norm2[1], 1e-6), losses3 = [lw_cls * sum_focal / N, lw_bbox *
+ *     sum(ctr_target * box_loss) / S, lw_ctr * sum_bce / N] and coef3 = [lw_cls / N, lw_bbox / S, lw_ctr / N]; backward
+ *     writes every element of dA (rows, stride_a) and dR (rows, stride_r) (w.r.t. the RAW outputs; other columns 0) and
+ *     dscale (L).  box_loss is -log(max(iou, eps_loss)) or, with giou, 1 - giou of the aligned bbox_overlaps with eps_overlap.
+ *     Fixed summation order, no float atomics.  At most BRCNN_MAX_LEVELS levels and BRCNN_MAX_IMAGES images.
+ * cfg7_host = [focal gamma, focal alpha, eps_overlap, eps_loss, loss_weight_cls, loss_weight_bbox, loss_weight_centerness].
+ * workspace: brcnn_fcos_loss_workspace_bytes, shared by forward and finalize; backward takes one of the same size.
+ * -------------------------------------------------------------------------- */
+int brcnn_fcos_score(const float *a, const float *r, const int *layout8_host, int num_classes, int64_t rows, float *score,
+                     void *stream);
+int brcnn_fcos_decode_levels(const int64_t *const *topk_inds, const int *counts, const float *a, const float *r,
+                             const int *layout8_host, const float *scales, int batch, int num_levels, const int *heights,
+                             const int *widths, const int *strides, int num_classes, const float *max_shape,
+                             const float *scale_factor, float score_thr, float *boxes, float *scores, int64_t *labels,
+                             uint8_t *valid, int32_t *n_valid, void *stream);
+int brcnn_fcos_assign(const float *gts, const int *gt_offsets_host, int batch, int num_levels, const int *heights,
+                      const int *widths, const int *strides, const float *ranges_host, int center_sampling,
+                      double center_sample_radius, int32_t *gt_inds, void *stream);
+size_t brcnn_fcos_loss_workspace_bytes(int batch, int num_levels, const int *heights, const int *widths, int num_classes);
+int brcnn_fcos_loss_forward(const float *a, const float *r, const int *layout8_host, const float *scales, int batch,
+                            int num_levels, const int *heights, const int *widths, const int *strides, int num_classes,
+                            const int32_t *gt_inds, const float *gts, const int64_t *gt_labels, const int *gt_offsets_host,
+                            const float *cfg7_host, void *workspace, size_t workspace_bytes, float *norm2, void *stream);
+int brcnn_fcos_loss_finalize(const void *workspace, size_t workspace_bytes, const float *norm2, int batch, int num_levels,
+                             const int *heights, const int *widths, int num_classes, const float *cfg7_host,
+                             float *losses3, float *coef3, void *stream);
+int brcnn_fcos_loss_backward(const float *a, const float *r, const int *layout8_host, const float *scales, int batch,
+                             int num_levels, const int *heights, const int *widths, const int *strides, int num_classes,
+                             const int32_t *gt_inds, const float *gts, const int64_t *gt_labels, const int *gt_offsets_host,
+                             const float *cfg7_host, const float *grad_losses3, const float *coef3, void *workspace,
+                             size_t workspace_bytes, float *da, float *dr, float *dscale, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Optimizer step of the train loop: SGD with momentum and weight decay after clipping the global gradient
  * norm (torch.optim.SGD + mmcv OptimizerHook grad_clip; configs/_base_/schedules/schedule_1x.py:2-3,
  * configs/boosting_rcnn/boosting_rcnn_r50_pafpn_1x_utdac.py:130), as three stages over tables of tensors
