@@ -436,6 +436,56 @@ class MaxIoUAssigner:
         return AssignResult(num_gts, gt_inds, best_iou, labels=labels)
 
 
+@BBOX_ASSIGNERS.register_module()
+class ATSSAssigner:
+    """atss_assigner.py:10-179 on torch ops, any boxes on any device: per ground truth and level the `topk` boxes whose
+    centres lie nearest to the box centre are candidates; a candidate is positive when its IoU reaches the mean + standard
+    deviation of the candidates' IoUs and its centre lies more than 0.01 inside the box; a box positive for several ground
+    truths goes to the one of highest IoU (equal IoUs: the lowest index).  Equal distances rank by ascending box index (a
+    stable sort) -- the reference leaves that tie to `torch.topk`, whose choice is unspecified; `brcnn_atss_assign`, the
+    whole-batch kernel ATSSHead trains with, applies the same rule."""
+
+    def __init__(self, topk, iou_calculator=dict(type='BboxOverlaps2D'), ignore_iof_thr=-1):
+        self.topk, self.ignore_iof_thr = topk, ignore_iof_thr
+        self.iou_calculator = build_iou_calculator(iou_calculator)
+
+    def assign(self, bboxes, num_level_bboxes, gt_bboxes, gt_bboxes_ignore=None, gt_labels=None):
+        INF = 100000000
+        bboxes = bboxes[:, :4]
+        num_gt, n = gt_bboxes.size(0), bboxes.size(0)
+        overlaps = self.iou_calculator(bboxes, gt_bboxes)                                      # (n, num_gt)
+        gt_inds = overlaps.new_zeros((n,), dtype=torch.long)
+        if num_gt == 0 or n == 0:
+            labels = None if gt_labels is None else overlaps.new_full((n,), -1, dtype=torch.long)
+            return AssignResult(num_gt, gt_inds, overlaps.new_zeros((n,)), labels=labels)
+        gt_ctr, ctr = (gt_bboxes[:, :2] + gt_bboxes[:, 2:4]) / 2.0, (bboxes[:, :2] + bboxes[:, 2:4]) / 2.0
+        distances = (ctr[:, None, :] - gt_ctr[None, :, :]).pow(2).sum(-1).sqrt()
+        if self.ignore_iof_thr > 0 and gt_bboxes_ignore is not None and gt_bboxes_ignore.numel() > 0:
+            ignored = self.iou_calculator(bboxes, gt_bboxes_ignore, mode='iof').max(dim=1)[0] > self.ignore_iof_thr
+            distances[ignored, :] = INF
+            gt_inds[ignored] = -1
+        picks, start = [], 0
+        for count in num_level_bboxes:
+            _, order = distances[start:start + count].sort(dim=0, stable=True)                  # ties: ascending index
+            picks.append(order[:min(self.topk, count)] + start)
+            start += count
+        picks = torch.cat(picks, dim=0)                                                        # (candidates, num_gt)
+        cand_iou = overlaps.gather(0, picks)
+        thr = cand_iou.mean(0) + cand_iou.std(0)
+        side = torch.stack([ctr[picks, 0] - gt_bboxes[:, 0], ctr[picks, 1] - gt_bboxes[:, 1],
+                            gt_bboxes[:, 2] - ctr[picks, 0], gt_bboxes[:, 3] - ctr[picks, 1]], dim=1).min(dim=1)[0]
+        is_pos = (cand_iou >= thr[None, :]) & (side > 0.01)
+        claimed = torch.full_like(overlaps, -INF)
+        cols = torch.arange(num_gt, device=picks.device)[None, :].expand_as(picks)
+        claimed[picks[is_pos], cols[is_pos]] = overlaps[picks[is_pos], cols[is_pos]]
+        max_overlaps, best = claimed.max(dim=1)                                                 # equal IoUs: the first index
+        gt_inds = torch.where(max_overlaps != -INF, best + 1, gt_inds)
+        labels = None
+        if gt_labels is not None:
+            labels = torch.where(gt_inds > 0, gt_labels[(gt_inds - 1).clamp(min=0)], gt_inds.new_full((), -1))
+        return AssignResult(num_gt, gt_inds, max_overlaps, labels=labels)
+
+
 class SamplingResult:
     """sampling_result.py:26-55: the sampled rows split into positives / negatives with their targets"""
 

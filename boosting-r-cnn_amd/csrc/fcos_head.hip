@@ -21,9 +21,7 @@
 //                        centerness-weighted IoU-log | GIoU loss and the centerness BCE over the positives, the targets
 //                        formed in the kernel.  Block partials (fixed order within a thread, LDS tree) -> one workgroup
 //                        (strided sums, LDS tree): no float atomics, the same bits from run to run.
-#include "common.h"
-#include <float.h>
-#include <math.h>
+#include "head_loss.h"
 
 namespace {
 
@@ -48,8 +46,6 @@ struct FcosGeom {
     FcosLayout lay;
     float gamma, alpha, eps_overlap, eps_loss, lw_cls, lw_bbox, lw_ctr;
 };
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 __device__ __forceinline__ const float* ctr_ptr(const FcosLayout& y, const float* a, const float* r, size_t row) {
     return y.ctr_in_r ? r + row * y.sr + y.ctr_off : a + row * y.sa + y.ctr_off;
@@ -193,21 +189,6 @@ __global__ __launch_bounds__(256) void fcos_assign_kernel(const FcosGeom g, cons
 }
 
 // ----------------------------------------------------------------------------------------------------------------- loss
-// brcnn_sigmoid_focal_loss_forward / _backward's element (csrc/focal_loss.hip), the same arithmetic
-template <bool BWD>
-__device__ __forceinline__ float focal_elem(float x, bool is_pos, float gamma, float alpha) {
-    const float p = 1.f / (1.f + expf(-x));
-    if (!BWD) {
-        const float term_p = powf(1.f - p, gamma) * logf(fmaxf(p, FLT_MIN));
-        const float term_n = powf(p, gamma) * logf(fmaxf(1.f - p, FLT_MIN));
-        return is_pos ? -alpha * term_p : -(1.f - alpha) * term_n;
-    } else {
-        const float term_p = powf(1.f - p, gamma) * (1.f - p - gamma * p * logf(fmaxf(p, FLT_MIN)));
-        const float term_n = powf(p, gamma) * (gamma * (1.f - p) * logf(fmaxf(1.f - p, FLT_MIN)) - p);
-        return is_pos ? -alpha * term_p : -(1.f - alpha) * term_n;
-    }
-}
-
 // what one row of the head outputs is: its level, image, point and, for a positive, its targets
 struct Point {
     int l, b, gi;       // gi: index into the packed gts, -1 background
@@ -242,8 +223,7 @@ __device__ __forceinline__ Point locate(const FcosGeom& g, const int* __restrict
 }
 
 // The box term of one positive: loss, and with BWD its derivative w.r.t. the four SCALED raw values (scale * raw).
-// aligned bbox_overlaps (iou2d_calculator.py:192-261) of the two boxes decoded around the point, then -log(max(iou, eps))
-// (iou_loss.py:14-50) or 1 - giou (:102-117)
+// corner_box_loss (head_loss.h) of the two boxes decoded around the point
 template <bool BWD>
 __device__ __forceinline__ float box_term(const FcosGeom& g, const Point& o, const float* __restrict__ raw, float scale,
                                           float* __restrict__ dscaled) {
@@ -255,67 +235,15 @@ __device__ __forceinline__ float box_term(const FcosGeom& g, const Point& o, con
     }
     const float p1x = o.px - d[0], p1y = o.py - d[1], p2x = o.px + d[2], p2y = o.py + d[3];
     const float t1x = o.px - o.t[0], t1y = o.py - o.t[1], t2x = o.px + o.t[2], t2y = o.py + o.t[3];
-    const float pw = p2x - p1x, ph = p2y - p1y;
-    const float area1 = pw * ph, area2 = (t2x - t1x) * (t2y - t1y);
-    const float i1x = fmaxf(p1x, t1x), i1y = fmaxf(p1y, t1y), i2x = fminf(p2x, t2x), i2y = fminf(p2y, t2y);
-    const float iw_raw = i2x - i1x, ih_raw = i2y - i1y;
-    const float iw = fmaxf(iw_raw, 0.f), ih = fmaxf(ih_raw, 0.f);
-    const float overlap = iw * ih;
-    const float union_raw = area1 + area2 - overlap;
-    const float uni = fmaxf(union_raw, g.eps_overlap);
-    const float iou = overlap / uni;
-    float loss, e1x = 0.f, e1y = 0.f, e2x = 0.f, e2y = 0.f, ew_raw = 0.f, eh_raw = 0.f, ew = 0.f, eh = 0.f, hull_raw = 0.f,
-                hull = 1.f;
-    if (g.lay.giou) {
-        e1x = fminf(p1x, t1x); e1y = fminf(p1y, t1y); e2x = fmaxf(p2x, t2x); e2y = fmaxf(p2y, t2y);
-        ew_raw = e2x - e1x; eh_raw = e2y - e1y;
-        ew = fmaxf(ew_raw, 0.f); eh = fmaxf(eh_raw, 0.f);
-        hull_raw = ew * eh;
-        hull = fmaxf(hull_raw, g.eps_overlap);
-        loss = 1.f - (iou - (hull - uni) / hull);
-    } else {
-        loss = -logf(fmaxf(iou, g.eps_loss));
-    }
+    float gp[4];
+    const float loss = corner_box_loss<BWD>(g.lay.giou, g.eps_overlap, g.eps_loss, p1x, p1y, p2x, p2y, t1x, t1y, t2x, t2y, gp);
     if (BWD) {
-        // reverse of the chain above; a max / min / clamp passes the gradient to the operand it selected
-        float g_iou, g_uni = 0.f, g_hull = 0.f;
-        if (g.lay.giou) {
-            g_iou = -1.f;
-            g_uni = -1.f / hull;                             // d(loss)/d(uni) through (hull - uni) / hull
-            g_hull = uni / (hull * hull);                     // d(loss)/d(hull): loss = 1 - iou + 1 - uni / hull
-        } else {
-            g_iou = iou > g.eps_loss ? -1.f / iou : 0.f;
-        }
-        float g_overlap = g_iou / uni;
-        g_uni += -g_iou * overlap / (uni * uni);
-        const float g_union_raw = union_raw > g.eps_overlap ? g_uni : 0.f;
-        const float g_area1 = g_union_raw;
-        g_overlap -= g_union_raw;
-        const float g_iw = iw_raw >= 0.f ? g_overlap * ih : 0.f, g_ih = ih_raw >= 0.f ? g_overlap * iw : 0.f;
-        float g1x = -(g_area1 * ph), g2x = g_area1 * ph, g1y = -(g_area1 * pw), g2y = g_area1 * pw;
-        if (p2x < t2x) g2x += g_iw; else if (p2x == t2x) g2x += 0.5f * g_iw;
-        if (p1x > t1x) g1x -= g_iw; else if (p1x == t1x) g1x -= 0.5f * g_iw;
-        if (p2y < t2y) g2y += g_ih; else if (p2y == t2y) g2y += 0.5f * g_ih;
-        if (p1y > t1y) g1y -= g_ih; else if (p1y == t1y) g1y -= 0.5f * g_ih;
-        if (g.lay.giou) {
-            const float g_hull_raw = hull_raw > g.eps_overlap ? g_hull : 0.f;
-            const float g_ew = ew_raw >= 0.f ? g_hull_raw * eh : 0.f, g_eh = eh_raw >= 0.f ? g_hull_raw * ew : 0.f;
-            if (p2x > t2x) g2x += g_ew; else if (p2x == t2x) g2x += 0.5f * g_ew;
-            if (p1x < t1x) g1x -= g_ew; else if (p1x == t1x) g1x -= 0.5f * g_ew;
-            if (p2y > t2y) g2y += g_eh; else if (p2y == t2y) g2y += 0.5f * g_eh;
-            if (p1y < t1y) g1y -= g_eh; else if (p1y == t1y) g1y -= 0.5f * g_eh;
-        }
-        const float gd[4] = {-g1x, -g1y, g2x, g2y};
+        const float gd[4] = {-gp[0], -gp[1], gp[2], gp[3]};
 #pragma unroll
         for (int k = 0; k < 4; k++)
             dscaled[k] = g.lay.norm_on_bbox ? (v[k] > 0.f ? gd[k] : 0.f) : gd[k] * d[k];
     }
     return loss;
-}
-
-// binary_cross_entropy_with_logits, one element: (1 - t) * x - log_sigmoid(x)
-__device__ __forceinline__ float bce_logits(float x, float t) {
-    return (1.f - t) * x - (fminf(x, 0.f) - log1pf(expf(-fabsf(x))));
 }
 
 __device__ __forceinline__ float block_sum(float v, float* red, int tid) {

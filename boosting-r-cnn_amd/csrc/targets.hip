@@ -23,7 +23,7 @@
 //
 // Index / integer outputs are exact; floating point follows the reference's operation order
 // (-ffp-contract=off, correctly rounded division), so IoUs and thresholds compare bit for bit.
-#include "common.h"
+#include "box_iou.h"
 #include <float.h>
 
 namespace {
@@ -59,21 +59,7 @@ struct AssignParams {
     int* counts;                       // (B, 2) [#positive, #negative] or NULL (zeroed by the caller)
 };
 
-// bbox_overlaps(gt, box) for one pair, the reference's operation order (iou2d_calculator.py:232-261):
-// area1 = gt, area2 = box, union = area1 + area2 - overlap, max(union, eps), overlap / union
-__device__ __forceinline__ float pair_iou(const float4 g, const float ga, const float4 b, const float ba) {
-    const float ltx = fmaxf(g.x, b.x), lty = fmaxf(g.y, b.y);
-    const float rbx = fminf(g.z, b.z), rby = fminf(g.w, b.w);
-    float w = rbx - ltx, h = rby - lty;
-    w = w < 0.f ? 0.f : w;
-    h = h < 0.f ? 0.f : h;
-    const float ov = w * h;
-    float un = ga + ba - ov;
-    un = fmaxf(un, 1e-6f);
-    return ov / un;
-}
-
-// the same in two steps: overlap first (most pairs are disjoint and 0 / union == 0 exactly, so the
+// pair_iou (box_iou.h) in two steps: overlap first (most pairs are disjoint and 0 / union == 0 exactly, so the
 // correctly rounded division is only paid where boxes intersect)
 __device__ __forceinline__ float pair_overlap(const float4 g, const float4 b) {
     const float ltx = fmaxf(g.x, b.x), lty = fmaxf(g.y, b.y);

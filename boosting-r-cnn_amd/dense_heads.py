@@ -43,6 +43,22 @@ def reduce_mean(tensor):
     return tensor
 
 
+def valid_cells(anchor_generator, sizes, img_metas, like):
+    """AnchorGenerator.valid_flags of a batch as the (B, L, 2) int32 table [valid_h, valid_w] in cells that the assignment
+    kernels take, on `like`'s device; None when every cell of every image is valid"""
+    import numpy as np
+    if all(anchor_generator.all_valid(list(sizes), m['pad_shape']) for m in img_metas):
+        return None
+    rows = []
+    for m in img_metas:
+        h, w = m['pad_shape'][:2]
+        r = []
+        for (fh, fw), st in zip(sizes, anchor_generator.strides):
+            r += [min(int(np.ceil(h / st[1])), fh), min(int(np.ceil(w / st[0])), fw)]
+        rows.append(r)
+    return const_rows(rows, like).to(torch.int32).view(len(img_metas), len(sizes), 2).contiguous()
+
+
 class AnchorHead(nn.Module):
     """Target assignment shared by anchor-based heads (anchor_head.py:37-268)."""
 
@@ -594,21 +610,10 @@ class ATSSRPNHead(AnchorHead):
     def assign_targets_device(self, sizes, img_metas, gts, gt_offsets, device, want_counts=False):
         """AnchorHead._get_targets_single's assignment for the whole batch on the device: gt_inds
         (B, anchors per image) int32 (-1 ignore / outside, 0 negative, k matched to gt k-1)"""
-        import numpy as np
         from . import train_ops
-        from .core import const_rows
         anchors, geom = self._anchor_table(sizes, device)
         B = len(img_metas)
-        valid_hw = None
-        if not all(self.anchor_generator.all_valid(list(sizes), m['pad_shape']) for m in img_metas):
-            rows = []
-            for m in img_metas:
-                h, w = m['pad_shape'][:2]
-                r = []
-                for (fh, fw), st in zip(sizes, self.anchor_generator.strides):
-                    r += [min(int(np.ceil(h / st[1])), fh), min(int(np.ceil(w / st[0])), fw)]
-                rows.append(r)
-            valid_hw = const_rows(rows, anchors).to(torch.int32).view(B, len(sizes), 2).contiguous()
+        valid_hw = valid_cells(self.anchor_generator, sizes, img_metas, anchors)
         border = self.train_cfg.allowed_border
         img_hw = const_rows([m['img_shape'][:2] for m in img_metas], anchors) if border >= 0 else None
         a = self.assigner
@@ -1954,3 +1959,435 @@ class FCOSHead(nn.Module):
         else:
             loss_bbox, loss_centerness = pos_box.sum(), pos_ctr.sum()
         return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
+
+
+@HEADS.register_module()
+class ATSSHead(AnchorHead):
+    """The head of ATSS (mmdet/models/dense_heads/atss_head.py:14-686 over anchor_head.py): FCOSHead's two GN towers
+    (`cls_convs.{i}.{conv,gn}`, `reg_convs.{i}.{conv,gn}`), then the 3x3 `atss_cls` (C sigmoid class logits), `atss_reg` (4
+    deltas of the cell's ONE anchor, through the level's `scales.{l}.scale`) and `atss_centerness` on the box tower.
+    Parameter names and shapes are the reference's.  Execution is FCOSHead's with its `centerness_on_reg` grouping -- the
+    tower and fused-head code is shared, not copied: A = [cls C | pad], R = [reg 4 | ctr 1 | pad], fp32, raw -- and the
+    kernels of csrc/atss_head.hip apply the Scale themselves: scoring (`brcnn_fcos_score`), top-k, anchor decode + class
+    fan-out and the NMS of the whole batch; in training the adaptive assignment (`brcnn_atss_assign`: k nearest anchors
+    per level, mean + std IoU threshold, centre-inside test, best-IoU resolution) and the focal / centerness-weighted GIoU
+    / centerness loss with the targets formed in the kernel.  Inference reads the host once, the head's train step never.
+    CPU tensors take the reference's chain on torch ops (the host mirror the CPU tests compare with the fixture)."""
+
+    supports_tta = False
+    MAX_NMS_PRE, MAX_LEVELS, MAX_TOPK = 4096, 8, 16        # brcnn_rpn_topk; brcnn_atss_assign
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
+                 loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0), init_cfg=None, **kwargs):
+        name = 'ATSSHead'
+        if norm_cfg is None or norm_cfg.get('type') != 'GN':
+            raise NotImplementedError(f'{name}: norm_cfg={norm_cfg!r}; the towers run conv + GroupNorm + ReLU, only GN is '
+                                      'supported')
+        loss_cls = kwargs.get('loss_cls', dict(type='CrossEntropyLoss', use_sigmoid=True))
+        loss_bbox = kwargs.get('loss_bbox', dict(type='SmoothL1Loss'))
+        if not loss_cls.get('use_sigmoid', False):
+            raise NotImplementedError(f'{name}: loss_cls.use_sigmoid=False (softmax scores with a background column) is not '
+                                      'supported; scoring and the focal loss are sigmoid')
+        if loss_cls.get('type') != 'FocalLoss':
+            raise NotImplementedError(f"{name}: loss_cls.type={loss_cls.get('type')!r}; only FocalLoss is supported")
+        if loss_bbox.get('type') != 'GIoULoss':
+            raise NotImplementedError(f'{name}: loss_bbox={loss_bbox!r}; only GIoULoss on the decoded boxes is supported')
+        if loss_centerness.get('type') != 'CrossEntropyLoss' or not loss_centerness.get('use_sigmoid', False):
+            raise NotImplementedError(f'{name}: loss_centerness={loss_centerness!r}; only the sigmoid CrossEntropyLoss is '
+                                      'supported')
+        if kwargs.get('reg_decoded_bbox', False):
+            raise NotImplementedError(f'{name}: reg_decoded_bbox=True is not supported (the head decodes its deltas itself)')
+        tc = kwargs.get('train_cfg')
+        if tc:
+            asg = tc.get('assigner', {})
+            if asg.get('type') != 'ATSSAssigner':
+                raise NotImplementedError(f"{name}: train_cfg.assigner.type={asg.get('type')!r}; only ATSSAssigner")
+            if not 0 < asg.get('topk', 0) <= self.MAX_TOPK:
+                raise ValueError(f"{name}: train_cfg.assigner.topk={asg.get('topk')} outside (0, {self.MAX_TOPK}]")
+            if asg.get('ignore_iof_thr', -1) > 0:
+                raise NotImplementedError(f"{name}: train_cfg.assigner.ignore_iof_thr={asg.get('ignore_iof_thr')} > 0 (ignore "
+                                          'regions) is not supported')
+            if tc.get('pos_weight', -1) > 0:
+                raise NotImplementedError(f"{name}: train_cfg.pos_weight={tc.get('pos_weight')} > 0 is not supported")
+            if tc.get('allowed_border', -1) >= 0:
+                raise NotImplementedError(f"{name}: train_cfg.allowed_border={tc.get('allowed_border')} >= 0 is not supported "
+                                          '(inside flags = valid flags)')
+        feat_channels = kwargs.get('feat_channels', 256)
+        if feat_channels > 256 or feat_channels % 4:
+            raise NotImplementedError(f'{name}: feat_channels={feat_channels}; the GroupNorm kernels take up to 256 channels in '
+                                      'whole quads')
+        self.stacked_convs, self.conv_cfg, self.norm_cfg = stacked_convs, conv_cfg, norm_cfg
+        super().__init__(num_classes, in_channels, init_cfg=init_cfg, **kwargs)
+        if self.num_anchors != 1:
+            raise NotImplementedError(
+                f'{name}: the anchor_generator gives {self.num_anchors} anchors per cell (several ratios, or scales_per_octave '
+                '> 1); only one is supported -- the anchors of a cell share a centre, their distances to a ground truth '
+                "tie exactly, and the reference's choice among them is torch.topk's unspecified order")
+        if any(s[0] != s[1] for s in self.anchor_generator.strides):
+            raise NotImplementedError(f'{name}: anchor_generator.strides={self.anchor_generator.strides}; only square strides')
+        if len(self.anchor_generator.strides) > self.MAX_LEVELS:
+            raise ValueError(f'{name}: {len(self.anchor_generator.strides)} pyramid levels, at most {self.MAX_LEVELS} are '
+                             'supported')
+        self.sampling = False
+        self.loss_centerness = build_loss(loss_centerness)
+        for loss in (self.loss_cls, self.loss_bbox, self.loss_centerness):
+            if loss.reduction != 'mean':
+                raise NotImplementedError(f"{name}: {type(loss).__name__}.reduction={loss.reduction!r}; only 'mean'")
+        if getattr(self.bbox_coder, 'add_ctr_clamp', False) or not getattr(self.bbox_coder, 'clip_border', True):
+            raise NotImplementedError(f'{name}: bbox_coder needs clip_border=True and add_ctr_clamp=False')
+        if self.test_cfg:
+            self._check_test_cfg(self.test_cfg)
+        self.strides = [int(s[0]) for s in self.anchor_generator.strides]
+        self._tower_caches = [[PackedCache() for _ in range(stacked_convs)] for _ in range(2)]
+        self._head_caches = [PackedCache(), PackedCache()]
+        self._scale_cache = PackedCache()
+        self.init_weights()
+
+    def _init_layers(self):
+        self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
+        for i in range(self.stacked_convs):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            for convs in (self.cls_convs, self.reg_convs):
+                convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                        norm_cfg=self.norm_cfg))
+        self.atss_cls = nn.Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 3, padding=1)
+        self.atss_reg = nn.Conv2d(self.feat_channels, self.num_anchors * 4, 3, padding=1)
+        self.atss_centerness = nn.Conv2d(self.feat_channels, self.num_anchors * 1, 3, padding=1)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.anchor_generator.strides])
+
+    def init_weights(self):
+        """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name='atss_cls', bias_prob=0.01))
+        (atss_head.py:35-43)"""
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.normal_(m.weight, 0, 0.01)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        nn.init.constant_(self.atss_cls.bias, bias_init_with_prob(0.01))
+
+    def _check_test_cfg(self, cfg):
+        nms = cfg.get('nms', dict(type='nms'))
+        if nms.get('type', 'nms') != 'nms':
+            raise NotImplementedError(f"ATSSHead: test_cfg.nms.type={nms.get('type')!r}; only greedy 'nms' is supported "
+                                      '(no soft-NMS)')
+        if nms.get('class_agnostic', False):
+            raise NotImplementedError('ATSSHead: test_cfg.nms.class_agnostic=True is not supported')
+
+    # ------------------------------------------------------------------ forward
+    def _head_groups(self):
+        """FCOSHead's `centerness_on_reg` grouping: the centerness rides on the box tower's fused head conv"""
+        return (self.atss_cls,), (self.atss_reg, self.atss_centerness)
+
+    forward_rows = FCOSHead.forward_rows
+    forward_head_fused = FCOSHead.forward_head_fused
+    _scales_tensor = FCOSHead._scales_tensor
+
+    def _layout(self, a, r):
+        return ops.FcosLayout(a, r, self.cls_out_channels, 0, 0, True, 4, False, True)
+
+    def _base_table(self):
+        """the generator's base anchors as the host array the kernels take (the anchors themselves are never materialised)"""
+        if '_base_host' not in self.__dict__:
+            self.__dict__['_base_host'] = ops.atss_base_anchors(self.anchor_generator.base_anchors)
+        return self.__dict__['_base_host']
+
+    def _split_rows(self, a, r, sizes, B):
+        """(A, R) rows -> the reference's per-level NHWC (cls, bbox_pred AFTER the Scale, centerness)"""
+        C = self.cls_out_channels
+        cls, reg, ctr, r0 = [], [], [], 0
+        for l, (h, w) in enumerate(sizes):
+            n = B * h * w
+            va, vr = a[r0:r0 + n].view(B, h, w, a.shape[1]), r[r0:r0 + n].view(B, h, w, r.shape[1])
+            cls.append(va[..., :C])
+            reg.append(vr[..., :4] * self.scales[l].scale)
+            ctr.append(vr[..., 4:5])
+            r0 += n
+        return cls, reg, ctr
+
+    def forward_nhwc(self, feats):
+        """list of (B,h,w,C) -> (cls (B,h,w,C), bbox_pred (B,h,w,4) scaled deltas, centerness (B,h,w,1)) lists, fp32"""
+        from .autograd import wants_grad
+        if not feats[0].is_cuda:
+            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
+            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
+        B = feats[0].shape[0]
+        if wants_grad(feats[0], self.atss_cls.weight, self.cls_convs[0].conv.weight):
+            a, r, sizes = self.forward_head_fused(list(feats))
+        else:
+            a, r, sizes = self.forward_rows(list(feats))
+        return self._split_rows(a, r, sizes, B)
+
+    def forward(self, feats):
+        """reference signature (atss_head.py:96-141): list of (N,C,h,w) -> lists of (N,C,h,w) class logits, (N,4,h,w) deltas
+        after the Scale, (N,1,h,w) centerness logits"""
+        if not feats[0].is_cuda:        # host mirror on torch ops
+            import torch.nn.functional as F
+            cls, reg, ctr = [], [], []
+            for x, scale in zip(feats, self.scales):
+                c = r = x
+                for m in self.cls_convs:
+                    c = F.relu(F.group_norm(F.conv2d(c, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
+                                            m.norm.bias, m.norm.eps))
+                for m in self.reg_convs:
+                    r = F.relu(F.group_norm(F.conv2d(r, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
+                                            m.norm.bias, m.norm.eps))
+                cls.append(F.conv2d(c, self.atss_cls.weight, self.atss_cls.bias, padding=1))
+                reg.append((F.conv2d(r, self.atss_reg.weight, self.atss_reg.bias, padding=1) * scale.scale).float())
+                ctr.append(F.conv2d(r, self.atss_centerness.weight, self.atss_centerness.bias, padding=1))
+            return cls, reg, ctr
+        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
+        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
+
+    # ------------------------------------------------------------------ test
+    def _check_limits(self, cfg, sizes):
+        if not 0 < cfg.get('nms_pre', -1) <= self.MAX_NMS_PRE:
+            raise ValueError(f"ATSSHead: nms_pre={cfg.get('nms_pre', -1)} outside (0, {self.MAX_NMS_PRE}] (brcnn_rpn_topk)")
+        if len(sizes) != len(self.strides):
+            raise ValueError(f'ATSSHead: {len(sizes)} pyramid levels for {len(self.strides)} strides')
+
+    def get_bboxes_rows(self, a, r, layout, scales, sizes, img_metas, cfg=None, rescale=False):
+        """atss_head.py:372-504 for the whole batch on the device, no host sync: per-anchor max of class sigmoid x centerness
+        sigmoid, per-level top-k, anchor decode / clip / rescale with the fan-out to classes, score threshold on the class
+        score, class-aware NMS, max_per_img.  Returns (dets (B, K, 5) zero padded, labels (B, K), num (B,) int32);
+        `self.last_n_valid` as RetinaHead keeps it."""
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_test_cfg(cfg)
+        self._check_limits(cfg, sizes)
+        B = len(img_metas)
+        scored, raw, r0 = ops.fcos_score(a, r, layout), [], 0
+        for (h, w) in sizes:
+            raw.append(scored[r0:r0 + B * h * w].view(B, h * w))
+            r0 += B * h * w
+        picked = ops.rpn_topk(raw, cfg.nms_pre)         # descending, ties by ascending index, all levels in one launch
+        max_shape = const_rows([m['img_shape'][:2] for m in img_metas], scored)
+        sf = const_rows([list(m['scale_factor']) for m in img_metas], scored) if rescale else None
+        bb, sc, lb, va, nv = ops.atss_decode_levels([p[1] for p in picked], a, r, layout, scales, sizes, self.strides,
+                                                    self._base_table(), max_shape, sf, self.bbox_coder.means,
+                                                    self.bbox_coder.stds, cfg.score_thr)
+        self.last_n_valid = nv
+        return RetinaHead._nms_candidates(bb, sc, lb, va, self.cls_out_channels, cfg)
+
+    def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
+        a, r, sizes = self.forward_rows(list(feats_nhwc))
+        return self.get_bboxes_rows(a, r, self._layout(a, r), self._scales_tensor(), sizes, img_metas, rescale=rescale)
+
+    @staticmethod
+    def _rows_from_reference(cls_scores, bbox_preds, centernesses):
+        """the reference-signature tensors (deltas after the Scale) as the kernels' (A, R) rows, to be read with unit scales"""
+        rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float()   # noqa: E731
+        return rows(cls_scores).contiguous(), torch.cat([rows(bbox_preds), rows(centernesses)], 1).contiguous()
+
+    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg=None, rescale=False, with_nms=True,
+                   batched_nms=None):
+        """reference signature (atss_head.py:312-370): per-level (N,C,h,w) / (N,4,h,w) / (N,1,h,w) -> per image (dets (k,5),
+        labels (k,)).  Device tensors take `get_bboxes_rows`; CPU tensors the reference's chain on torch ops, with the
+        caller's `batched_nms` (this package's NMS is a device kernel)."""
+        if not with_nms:
+            raise NotImplementedError('ATSSHead: with_nms=False is not supported')
+        assert len(cls_scores) == len(bbox_preds) == len(centernesses)
+        if cls_scores[0].is_cuda:
+            sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
+            a, r = self._rows_from_reference([t.detach() for t in cls_scores], [t.detach() for t in bbox_preds],
+                                             [t.detach() for t in centernesses])
+            det, lab, num = self.get_bboxes_rows(a, r, self._layout(a, r), a.new_ones(len(sizes)), sizes, img_metas, cfg,
+                                                 rescale)
+            num = num.tolist()   # the one host sync
+            return [(det[i, :num[i]], lab[i, :num[i]]) for i in range(len(img_metas))]
+        return self._get_bboxes_host(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms)
+
+    def _get_bboxes_host(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms):
+        from .core import delta2bbox
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_test_cfg(cfg)
+        if batched_nms is None:
+            batched_nms = ops.batched_nms
+        B, C = cls_scores[0].shape[0], self.cls_out_channels
+        anchors_l = self.anchor_generator.grid_anchors([c.shape[-2:] for c in cls_scores], cls_scores[0].device)
+        nms_pre = cfg.get('nms_pre', -1)
+        out = []
+        for b in range(B):
+            boxes_l, scores_l, ctr_l = [], [], []
+            for cls, reg, ctr, anchors in zip(cls_scores, bbox_preds, centernesses, anchors_l):
+                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
+                ct = ctr[b].detach().permute(1, 2, 0).reshape(-1).sigmoid()
+                d = reg[b].detach().permute(1, 2, 0).reshape(-1, 4)
+                if 0 < nms_pre < s.shape[0]:
+                    _, idx = (s * ct[:, None]).max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
+                    idx = idx[:nms_pre]
+                    anchors, d, s, ct = anchors[idx], d[idx], s[idx], ct[idx]
+                boxes_l.append(delta2bbox(anchors, d, self.bbox_coder.means, self.bbox_coder.stds,
+                                          max_shape=tuple(img_metas[b]['img_shape'][:2])))
+                scores_l.append(s)
+                ctr_l.append(ct)
+            boxes, scores, ctrs = torch.cat(boxes_l), torch.cat(scores_l), torch.cat(ctr_l)
+            if rescale:
+                boxes = boxes / boxes.new_tensor(img_metas[b]['scale_factor'])
+            keep = (scores > cfg.score_thr).reshape(-1)          # before the centerness factor (bbox_nms.py:48-58)
+            inds = keep.nonzero(as_tuple=False).reshape(-1)
+            labels = torch.arange(C, dtype=torch.long).repeat(scores.shape[0])[inds]
+            cb = boxes[:, None].expand(-1, C, 4).reshape(-1, 4)[inds]
+            cs = (scores * ctrs[:, None]).reshape(-1)[inds]
+            if cb.numel() == 0:
+                out.append((torch.cat([cb, cs[:, None]], -1), labels))
+                continue
+            dets, kept = batched_nms(cb.contiguous(), cs.contiguous(), labels, dict(cfg.nms))
+            if cfg.max_per_img > 0:
+                dets, kept = dets[:cfg.max_per_img], kept[:cfg.max_per_img]
+            out.append((dets, labels[kept]))
+        return out
+
+    def simple_test(self, feats, img_metas, rescale=False, batched_nms=None):
+        """dense_test_mixins.py:17-37: list of (N,C,h,w) -> per image (dets (k,5), labels (k,))"""
+        return self.get_bboxes(*self(feats), img_metas, rescale=rescale, batched_nms=batched_nms)
+
+    def aug_test(self, feats, img_metas, rescale=False):
+        raise NotImplementedError('ATSSHead has no test-time augmentation')
+
+    # ------------------------------------------------------------------ train
+    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
+        """base_dense_head.py:48-78"""
+        outs = self(x)
+        losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+        if proposal_cfg is None:
+            return losses
+        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
+
+    def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
+        """the device-resident train step of the head: NHWC pyramid -> towers and fused heads over all levels -> adaptive
+        assignment and loss kernels; no host read"""
+        if gt_bboxes_ignore is not None:
+            raise NotImplementedError('ATSSHead: gt_bboxes_ignore is not supported on the device path')
+        a, r, sizes = self.forward_head_fused(list(feats_nhwc))
+        scales = torch.stack([s.scale.float().reshape(()) for s in self.scales])
+        return self.loss_fused(a, r, scales, sizes, gt_bboxes, gt_labels, img_metas)
+
+    def loss_fused(self, a, r, scales, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
+        """ATSSHead.loss on the fused head outputs of all levels: whole-batch adaptive assignment, then the loss kernels --
+        targets and both normalisers are formed on the device (averaged over ranks there when distributed), nothing is
+        read back.  Returns the reference's per-level lists; `self.last_targets` keeps (gt_inds, coef3, norm2)."""
+        from . import train_ops
+        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
+        gts, labels = gts.to(a.device), labels.to(a.device)
+        B = len(img_metas)
+        sizes = [tuple(int(v) for v in s) for s in sizes]
+        base = self._base_table()
+        gt_inds = train_ops.atss_assign(gts, offs, B, sizes, self.strides, base, self.assigner.topk,
+                                        valid_cells(self.anchor_generator, sizes, img_metas, a))
+        meta = train_ops.AtssLossMeta(B, sizes, self.strides, base, self.cls_out_channels, offs, self.loss_cls.gamma,
+                                      self.loss_cls.alpha, self.loss_bbox.eps, self.loss_cls.loss_weight,
+                                      self.loss_bbox.loss_weight, self.loss_centerness.loss_weight, self.bbox_coder.means,
+                                      self.bbox_coder.stds)
+        hook = None
+        if dist.is_available() and dist.is_initialized():
+            hook = lambda n2: n2.copy_(reduce_mean(n2))     # noqa: E731  (the reference's two reduce_mean calls as one)
+        losses, coef, norm2 = train_ops.atss_loss(a, r, scales, gt_inds, gts, labels, self._layout(a, r), meta, hook)
+        self.last_targets = (gt_inds, coef, norm2)
+        return dict(loss_cls=list(losses[0].unbind(0)), loss_bbox=list(losses[1].unbind(0)),
+                    loss_centerness=list(losses[2].unbind(0)))
+
+    def get_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
+                    gt_labels_list=None, label_channels=1, unmap_outputs=True):
+        """atss_head.py:506-568 on torch ops (the host mirror): (anchors, labels, label weights, box targets, box weights) per
+        level with the images stacked, and the two sample counts"""
+        num_imgs = len(img_metas)
+        assert len(anchor_list) == len(valid_flag_list) == num_imgs
+        num_level_anchors = [a.size(0) for a in anchor_list[0]]
+        flat_anchors = [torch.cat(list(a)) for a in anchor_list]
+        flat_flags = [torch.cat(list(v)) for v in valid_flag_list]
+        ignore = gt_bboxes_ignore_list if gt_bboxes_ignore_list is not None else [None] * num_imgs
+        gt_labels_list = gt_labels_list if gt_labels_list is not None else [None] * num_imgs
+        res = multi_apply(self._get_target_single, flat_anchors, flat_flags, [num_level_anchors] * num_imgs, gt_bboxes_list,
+                          ignore, gt_labels_list, img_metas, label_channels=label_channels, unmap_outputs=unmap_outputs)
+        all_anchors, all_labels, all_lw, all_bt, all_bw, pos_list, neg_list = res
+        if any(l is None for l in all_labels):
+            return None
+        num_total_pos = sum(max(p.numel(), 1) for p in pos_list)
+        num_total_neg = sum(max(p.numel(), 1) for p in neg_list)
+        return tuple(images_to_levels(t, num_level_anchors) for t in (all_anchors, all_labels, all_lw, all_bt, all_bw)) + \
+            (num_total_pos, num_total_neg)
+
+    def _get_target_single(self, flat_anchors, valid_flags, num_level_anchors, gt_bboxes, gt_bboxes_ignore, gt_labels,
+                           img_meta, label_channels=1, unmap_outputs=True):
+        """atss_head.py:570-678"""
+        inside_flags = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
+        if not inside_flags.any():
+            return (None,) * 7
+        anchors = flat_anchors[inside_flags, :]
+        inside_per_level = [int(f.sum()) for f in torch.split(inside_flags, num_level_anchors)]
+        assign_result = self.assigner.assign(anchors, inside_per_level, gt_bboxes, gt_bboxes_ignore, gt_labels)
+        sampling_result = self.sampler.sample(assign_result, anchors, gt_bboxes)
+        n = anchors.shape[0]
+        bbox_targets, bbox_weights = torch.zeros_like(anchors), torch.zeros_like(anchors)
+        labels = anchors.new_full((n,), self.num_classes, dtype=torch.long)
+        label_weights = anchors.new_zeros(n, dtype=torch.float)
+        pos_inds, neg_inds = sampling_result.pos_inds, sampling_result.neg_inds
+        if len(pos_inds) > 0:
+            bbox_targets[pos_inds, :] = self.bbox_coder.encode(sampling_result.pos_bboxes, sampling_result.pos_gt_bboxes)
+            bbox_weights[pos_inds, :] = 1.0
+            labels[pos_inds] = 0 if gt_labels is None else gt_labels[sampling_result.pos_assigned_gt_inds]
+            label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
+        if len(neg_inds) > 0:
+            label_weights[neg_inds] = 1.0
+        if unmap_outputs:
+            total = flat_anchors.size(0)
+            anchors = unmap(anchors, total, inside_flags)
+            labels = unmap(labels, total, inside_flags, fill=self.num_classes)
+            label_weights = unmap(label_weights, total, inside_flags)
+            bbox_targets = unmap(bbox_targets, total, inside_flags)
+            bbox_weights = unmap(bbox_weights, total, inside_flags)
+        return anchors, labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds
+
+    def centerness_target(self, anchors, bbox_targets):
+        """atss_head.py:294-310: from the anchor centre to the box the encoded target decodes to"""
+        gts = self.bbox_coder.decode(anchors, bbox_targets)
+        cx, cy = (anchors[:, 2] + anchors[:, 0]) / 2, (anchors[:, 3] + anchors[:, 1]) / 2
+        lr = torch.stack([cx - gts[:, 0], gts[:, 2] - cx], dim=1)
+        tb = torch.stack([cy - gts[:, 1], gts[:, 3] - cy], dim=1)
+        return torch.sqrt((lr.min(dim=-1)[0] / lr.max(dim=-1)[0]) * (tb.min(dim=-1)[0] / tb.max(dim=-1)[0]))
+
+    def loss_single(self, anchors, cls_score, bbox_pred, centerness, labels, label_weights, bbox_targets, num_total_samples):
+        """atss_head.py:143-216"""
+        anchors = anchors.reshape(-1, 4)
+        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels).contiguous()
+        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4)
+        centerness = centerness.permute(0, 2, 3, 1).reshape(-1)
+        bbox_targets, labels, label_weights = bbox_targets.reshape(-1, 4), labels.reshape(-1), label_weights.reshape(-1)
+        loss_cls = self.loss_cls(cls_score, labels, label_weights, avg_factor=num_total_samples)
+        pos_inds = ((labels >= 0) & (labels < self.num_classes)).nonzero().squeeze(1)
+        if len(pos_inds) > 0:
+            pos_anchors, pos_targets = anchors[pos_inds], bbox_targets[pos_inds]
+            ctr_t = self.centerness_target(pos_anchors, pos_targets)
+            loss_bbox = self.loss_bbox(self.bbox_coder.decode(pos_anchors, bbox_pred[pos_inds]),
+                                       self.bbox_coder.decode(pos_anchors, pos_targets), weight=ctr_t, avg_factor=1.0)
+            loss_centerness = self.loss_centerness(centerness[pos_inds], ctr_t, avg_factor=num_total_samples)
+        else:
+            loss_bbox, loss_centerness = bbox_pred.sum() * 0, centerness.sum() * 0
+            ctr_t = bbox_targets.new_tensor(0.)
+        return loss_cls, loss_bbox, loss_centerness, ctr_t.sum()
+
+    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        """atss_head.py:218-292.  Device tensors go to the HIP kernels (`loss_fused`, with unit scales on the scaled deltas);
+        CPU tensors take the reference's chain in torch (the host mirror)."""
+        assert len(cls_scores) == len(bbox_preds) == len(centernesses)
+        featmap_sizes = [tuple(int(v) for v in f.size()[-2:]) for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        device = cls_scores[0].device
+        if device.type == 'cuda':
+            if gt_bboxes_ignore is not None:
+                raise NotImplementedError('ATSSHead: gt_bboxes_ignore is not supported on the device path')
+            a, r = self._rows_from_reference(cls_scores, bbox_preds, centernesses)
+            return self.loss_fused(a, r, a.new_ones(len(featmap_sizes)), featmap_sizes, gt_bboxes, gt_labels, img_metas)
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
+        self._all_valid = None
+        targets = self.get_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore, gt_labels,
+                                   label_channels=self.cls_out_channels)
+        if targets is None:
+            return None
+        anchors, labels, label_weights, bbox_targets, _, num_total_pos, _ = targets
+        num_total_samples = max(reduce_mean(torch.tensor(num_total_pos, dtype=torch.float, device=device)).item(), 1.0)
+        losses_cls, losses_bbox, losses_ctr, factors = multi_apply(
+            self.loss_single, anchors, cls_scores, bbox_preds, centernesses, labels, label_weights, bbox_targets,
+            num_total_samples=num_total_samples)
+        avg = reduce_mean(sum(factors)).clamp_(min=1).item()
+        return dict(loss_cls=losses_cls, loss_bbox=[x / avg for x in losses_bbox], loss_centerness=losses_ctr)

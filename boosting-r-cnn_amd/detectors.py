@@ -602,3 +602,11 @@ class FCOS(SingleStageDetector):
 
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)
+
+
+@DETECTORS.register_module()
+class ATSS(SingleStageDetector):
+    """mmdet/models/detectors/atss.py:6-17"""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)

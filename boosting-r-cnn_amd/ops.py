@@ -1367,6 +1367,56 @@ def fcos_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, max_s
     return boxes, scores, labels, valid, n_valid
 
 
+# --------------------------------------------------------------------------- ATSS head, test time
+def atss_base_anchors(base_anchors):
+    """the (L, 4) base anchors of a one-anchor-per-cell generator as the host float array the ATSS entries take"""
+    import ctypes
+    vals = []
+    for b in base_anchors:
+        if tuple(b.shape) != (1, 4):
+            raise ValueError(f'atss: {b.shape[0]} base anchors on a level; the ATSS kernels take one anchor per cell')
+        vals += [float(v) for v in b.reshape(-1).tolist()]
+    return (ctypes.c_float * len(vals))(*vals)
+
+
+def atss_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, base_anchors, max_shape, scale_factor, means, stds,
+                       score_thr, wh_ratio_clip=16 / 1000):
+    """`fcos_decode_levels` with the anchor decode of ATSSHead (brcnn_atss_decode_levels): the box is delta2bbox(anchor of the
+    picked cell, scale_l * raw) clipped to max_shape and divided by scale_factor.  base_anchors: `atss_base_anchors`.  Returns
+    boxes (B,T*C,4), scores (B,T*C) = class sigmoid * centerness sigmoid, labels (B,T*C) int64, valid (B,T*C) bool = class
+    sigmoid > score_thr, n_valid (B,) int32; (level, pick, class) order."""
+    import ctypes
+    L = len(topk_inds)
+    _require_gpu(*topk_inds, scales, max_shape, scale_factor)
+    b, c = topk_inds[0].shape[0], layout.C
+    inds = [t.contiguous() for t in topk_inds]
+    assert all(t.dtype == torch.int64 and t.shape[0] == b for t in inds)
+    assert scales.dtype == torch.float32 and scales.numel() == L and scales.is_contiguous()
+    assert layout.rows == sum(b * h * w for h, w in feat_hws) and len(feat_hws) == L and len(strides) == L
+    assert len(base_anchors) == 4 * L
+    counts = [int(t.shape[1]) for t in inds]
+    n = sum(counts) * c
+    dev = a.device
+    assert max_shape.shape == (b, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
+    if scale_factor is not None:
+        assert scale_factor.shape == (b, 4) and scale_factor.dtype == torch.float32 and scale_factor.is_contiguous()
+    boxes = torch.empty((b, n, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, n), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, n), dtype=torch.int64, device=dev)
+    valid = torch.empty((b, n), dtype=torch.bool, device=dev)
+    n_valid = torch.empty((b,), dtype=torch.int32, device=dev)
+    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in inds])
+    ints = lambda vs: (ctypes.c_int * L)(*[int(v) for v in vs])               # noqa: E731
+    m4 = (ctypes.c_float * 4)(*[float(v) for v in means])
+    s4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    st = _L.load().brcnn_atss_decode_levels(
+        ptrs, ints(counts), _ptr(a), _ptr(r), layout.arr, _ptr(scales), b, L, ints([h for h, _ in feat_hws]),
+        ints([w for _, w in feat_hws]), ints(strides), base_anchors, c, _ptr(max_shape), _ptr(scale_factor), m4, s4,
+        float(wh_ratio_clip), float(score_thr), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(valid), _ptr(n_valid), _stream())
+    _L.check(st, 'brcnn_atss_decode_levels')
+    return boxes, scores, labels, valid, n_valid
+
+
 # --------------------------------------------------------------------------- Cascade R-CNN, test time
 def _rows_in_place(t):
     """a fp32 (rows, cols) device tensor the cascade kernels read with a row stride: the two column blocks of the heads'

@@ -595,6 +595,122 @@ def fcos_loss(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook=Non
     return FcosLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
 
 
+# ----------------------------------------------------------------------------- ATSS head: assignment and loss
+ATSS_MAX_TOPK = 16
+
+
+def atss_assign(gts, gt_offsets, batch, sizes, strides, base_anchors, topk, valid_hw=None, want_overlaps=False):
+    """ATSSAssigner.assign for the whole batch (brcnn_atss_assign): gts (sum G, 4) fp32 packed, host offsets, base_anchors
+    from `ops.atss_base_anchors`, valid_hw (batch, L, 2) int32 or None -> gt_inds (batch, anchors per image) int32: k > 0
+    positive for ground truth k - 1 of the image, 0 negative, -1 invalid cell [, max_overlaps]"""
+    _require_gpu(gts, valid_hw)
+    L = len(sizes)
+    if not 0 < int(topk) <= ATSS_MAX_TOPK:
+        raise ValueError(f'atss_assign: topk={topk} outside (0, {ATSS_MAX_TOPK}]')
+    if L > 8:
+        raise ValueError(f'atss_assign: {L} pyramid levels, at most 8 are supported')
+    if batch > MAX_IMAGES:
+        raise ValueError(f'atss_assign: batch {batch} exceeds {MAX_IMAGES} images per call')
+    assert len(strides) == L and len(base_anchors) == 4 * L and len(gt_offsets) == batch + 1
+    total = int(gt_offsets[-1])
+    if total:
+        assert gts.dtype == torch.float32 and gts.shape == (total, 4) and gts.is_contiguous()
+    if valid_hw is not None:
+        assert valid_hw.dtype == torch.int32 and valid_hw.shape == (batch, L, 2) and valid_hw.is_contiguous()
+    n = sum(int(h) * int(w) for h, w in sizes)
+    dev = gts.device
+    out = torch.empty((batch, n), dtype=torch.int32, device=dev)
+    ov = torch.empty((batch, n), dtype=torch.float32, device=dev) if want_overlaps else None
+    ws = torch.empty((batch, n), dtype=torch.int64, device=dev)
+    st = _L.load().brcnn_atss_assign(_ptr(gts) if total else None, _ints(gt_offsets), int(batch), L,
+                                     _ints([h for h, _ in sizes]), _ints([w for _, w in sizes]), _ints(strides), base_anchors,
+                                     _ptr(valid_hw), int(topk), _ptr(ws), ws.numel() * 8, _ptr(out), _ptr(ov), _stream())
+    _L.check(st, 'brcnn_atss_assign')
+    return (out, ov) if want_overlaps else out
+
+
+class AtssLossMeta:
+    """host-side description of one ATSS loss call: the pyramid and its base anchors, the ground-truth offsets and the loss
+    settings (include/brcnn_hip.h: cfg15_host)"""
+
+    def __init__(self, batch, sizes, strides, base_anchors, num_classes, gt_offsets, focal_gamma, focal_alpha, eps, lw_cls,
+                 lw_bbox, lw_ctr, means, stds, wh_ratio_clip=16 / 1000):
+        self.batch, self.sizes, self.C = int(batch), [tuple(int(v) for v in s) for s in sizes], int(num_classes)
+        self.L = len(self.sizes)
+        if self.batch > MAX_IMAGES:
+            raise ValueError(f'atss loss: batch {self.batch} exceeds {MAX_IMAGES} images per call')
+        self.hs, self.ws = _ints([h for h, _ in self.sizes]), _ints([w for _, w in self.sizes])
+        self.strides = _ints(strides)
+        self.base = base_anchors
+        assert len(base_anchors) == 4 * self.L
+        self.gt_offsets = _ints(gt_offsets)
+        self.total_gt = int(gt_offsets[-1])
+        self.cfg = _floats([focal_gamma, focal_alpha, eps, lw_cls, lw_bbox, lw_ctr] + list(means) + list(stds) +
+                           [abs(math.log(wh_ratio_clip))])
+        self.rows = sum(self.batch * h * w for h, w in self.sizes)
+        self.anchors_per_image = sum(h * w for h, w in self.sizes)
+
+
+class AtssLossFunction(Function):
+    """losses (3, L) = [loss_cls | loss_bbox | loss_centerness] per level from the head outputs of all levels, differentiable
+    w.r.t. A, R (the raw outputs) and the per-level scales"""
+
+    @staticmethod
+    def forward(ctx, a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook):
+        scales = scales.detach().float().contiguous()
+        _require_gpu(a, r, scales, gt_inds, gts, gt_labels)
+        assert layout.rows == meta.rows and layout.C == meta.C
+        assert scales.shape == (meta.L,)
+        assert gt_inds.dtype == torch.int32 and gt_inds.shape == (meta.batch, meta.anchors_per_image) and gt_inds.is_contiguous()
+        if meta.total_gt:
+            assert gts.dtype == torch.float32 and gts.shape == (meta.total_gt, 4) and gts.is_contiguous()
+            assert gt_labels.dtype == torch.int64 and gt_labels.shape == (meta.total_gt,) and gt_labels.is_contiguous()
+        lib = _L.load()
+        nb = lib.brcnn_atss_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.C)
+        ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=a.device)
+        norm2 = torch.empty((2,), dtype=torch.float32, device=a.device)
+        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
+        st = lib.brcnn_atss_loss_forward(_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws,
+                                         meta.strides, meta.base, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg,
+                                         _ptr(ws), nb, _ptr(norm2), _stream())
+        _L.check(st, 'brcnn_atss_loss_forward')
+        if norm_hook is not None:
+            norm_hook(norm2)
+        out = torch.empty((3 * meta.L + 3,), dtype=torch.float32, device=a.device)
+        losses, coef = out[:3 * meta.L], out[3 * meta.L:]
+        st = lib.brcnn_atss_loss_finalize(_ptr(ws), nb, _ptr(norm2), meta.batch, meta.L, meta.hs, meta.ws, meta.C, meta.cfg,
+                                          _ptr(losses), _ptr(coef), _stream())
+        _L.check(st, 'brcnn_atss_loss_finalize')
+        ctx.save_for_backward(a, r, scales, gt_inds, gts, gt_labels, coef)
+        ctx.layout, ctx.meta = layout, meta
+        ctx.mark_non_differentiable(coef, norm2)
+        return losses.view(3, meta.L), coef, norm2
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g3, _gc, _gn):
+        a, r, scales, gt_inds, gts, gt_labels, coef = ctx.saved_tensors
+        meta, layout = ctx.meta, ctx.layout
+        da, dr = torch.empty_like(a), torch.empty_like(r)
+        dscale = torch.empty_like(scales)
+        g3 = g3.float().contiguous()
+        lib = _L.load()
+        nb = lib.brcnn_atss_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.C)
+        ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=a.device)
+        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
+        st = lib.brcnn_atss_loss_backward(_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws,
+                                          meta.strides, meta.base, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg,
+                                          _ptr(g3), _ptr(coef), _ptr(ws), nb, _ptr(da), _ptr(dr), _ptr(dscale), _stream())
+        _L.check(st, 'brcnn_atss_loss_backward')
+        return da, dr, dscale, None, None, None, None, None, None
+
+
+def atss_loss(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook=None):
+    """(losses (3, L), coef3, norm2); `norm_hook(norm2)` may change norm2 in place between the sums and the division (the
+    mean over ranks)"""
+    return AtssLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
+
+
 # ----------------------------------------------------------------------------- boosting loss
 class BoostLossFunction(Function):
     """out3 = [loss_cls, loss_bbox, acc] of the boosting-reweighted R-CNN loss

@@ -1297,6 +1297,69 @@ int brcnn_fcos_loss_backward(const float *a, const float *r, const int *layout8_
                              size_t workspace_bytes, float *da, float *dr, float *dscale, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * The ATSS head: ATSSHead + ATSSAssigner (models/dense_heads/atss_head.py, core/bbox/assigners/atss_assigner.py),
+ * csrc/atss_head.hip.  ONE anchor per cell, never materialised: level l, cell (y, x) has the anchor base_l + (x * stride_l,
+ * y * stride_l, x * stride_l, y * stride_l), base_anchors_host (L, 4) the generator's base anchors -- exact in fp32.  The head
+ * outputs are FCOSHead's two row tensors A / R with their layout8_host (norm_on_bbox and giou are not read): RAW values,
+ * level-major rows, the centerness wherever the layout puts it.  scales: (L) floats ON THE DEVICE; delta = scale_l * raw.
+ * The per-anchor ranking score max_c(sigmoid(cls_c) * sigmoid(ctr)) is brcnn_fcos_score.
+ *   brcnn_atss_assign: ATSSAssigner.assign (atss_assigner.py:34-179) for a whole batch.  gts (sum G, 4) packed with host
+ *     offsets; valid_hw (batch, L, 2) int32 [valid_h, valid_w] in cells as brcnn_assign_max_iou takes it, or NULL = every
+ *     cell valid (allowed_border < 0: inside flags = valid flags).  Per (ground truth, level) the candidates are the
+ *     min(topk, VALID cells of the level) anchors nearest to the box centre by sqrt(dx*dx + dy*dy) of the fp32 centres
+ *     (x1 + x2) / 2; EQUAL DISTANCES RANK BY ASCENDING ANCHOR INDEX (the reference leaves that tie to torch.topk, whose
+ *     choice is unspecified; this rule is the library's own).  thr = mean + unbiased std of the candidates' IoUs
+ *     (BboxOverlaps2D, eps 1e-6), summed sequentially in (level, rank) order; a candidate is positive when iou >= thr and
+ *     min(cx - x1, cy - y1, x2 - cx, y2 - cy) > 0.01 (a NaN thr -- a single candidate -- makes none).  An anchor positive
+ *     for several ground truths goes to the highest IoU, equal IoUs to the lowest index (an integer atomic max on
+ *     (IoU bits << 32 | ~index): order-independent).  gt_inds (batch, anchors per image) int32: k > 0 positive for ground
+ *     truth k - 1 of the image, 0 negative, -1 invalid cell; max_overlaps (same shape) or NULL: the winner's IoU, -1e8
+ *     elsewhere.  workspace: batch * anchors per image * 8 bytes.  0 < topk <= 16.
+ *   brcnn_atss_decode_levels: everything between the top-k and multiclass_nms(score_factors=centerness)
+ *     (atss_head.py:372-504) as brcnn_fcos_decode_levels does it, the box being delta2bbox(anchor, scale_l * raw, means,
+ *     stds, wh_ratio_clip) in brcnn_dense_decode_levels' operation order, clipped to max_shape, divided by scale_factor.
+ *     valid = sigmoid(cls_c) > score_thr (BEFORE the centerness factor), score = sigmoid(cls_c) * sigmoid(ctr).
+ *   brcnn_atss_loss_forward / _finalize / _backward: ATSSHead.loss (atss_head.py:143-310), the targets formed in the kernel
+ *     from gt_inds (brcnn_atss_assign's convention; < 0: weight 0).  Per positive: target = bbox2delta(anchor, gt), gt' =
+ *     delta2bbox(anchor, target) (the reference's round trip), centerness target sqrt(min(l,r)/max(l,r) * min(t,b)/max(t,b))
+ *     from the anchor centre to gt', box loss (1 - giou(delta2bbox(anchor, scale_l * raw), gt')) * centerness target,
+ *     centerness BCE.  forward leaves block partials and norm2 = [sum over images of max(n_pos, 1), sum of the centerness
+ *     targets] on the device (the caller may average norm2 over ranks); finalize forms N = max(norm2[0], 1), S =
+ *     max(norm2[1], 1), losses (3, L) = [lw_cls * focal_l / N | lw_bbox * box_l / S | lw_ctr * bce_l / N] per level and
+ *     coef3 = [lw_cls / N, lw_bbox / S, lw_ctr / N]; backward takes grad_losses (3, L) and writes every element of dA and
+ *     dR (w.r.t. the RAW outputs, through the scale, the decode, its exp and its clamp -- zero where the clamp is active;
+ *     other columns 0) and dscale (L).  Fixed summation order, no float atomics.
+ * cfg15_host = [focal gamma, focal alpha, giou eps, loss_weight_cls, loss_weight_bbox, loss_weight_centerness, means x4,
+ * stds x4, |log(wh_ratio_clip)|].  workspace: brcnn_atss_loss_workspace_bytes, shared by forward and finalize; backward takes one
+ * of the same size.  At most BRCNN_MAX_LEVELS levels and BRCNN_MAX_IMAGES images.
+ * -------------------------------------------------------------------------- */
+int brcnn_atss_assign(const float *gts, const int *gt_offsets_host, int batch, int num_levels, const int *heights,
+                      const int *widths, const int *strides, const float *base_anchors_host, const int32_t *valid_hw,
+                      int topk, void *workspace, size_t workspace_bytes, int32_t *gt_inds, float *max_overlaps,
+                      void *stream);
+int brcnn_atss_decode_levels(const int64_t *const *topk_inds, const int *counts, const float *a, const float *r,
+                             const int *layout8_host, const float *scales, int batch, int num_levels, const int *heights,
+                             const int *widths, const int *strides, const float *base_anchors_host, int num_classes,
+                             const float *max_shape, const float *scale_factor, const float *means4_host,
+                             const float *stds4_host, double wh_ratio_clip, float score_thr, float *boxes, float *scores,
+                             int64_t *labels, uint8_t *valid, int32_t *n_valid, void *stream);
+size_t brcnn_atss_loss_workspace_bytes(int batch, int num_levels, const int *heights, const int *widths, int num_classes);
+int brcnn_atss_loss_forward(const float *a, const float *r, const int *layout8_host, const float *scales, int batch,
+                            int num_levels, const int *heights, const int *widths, const int *strides,
+                            const float *base_anchors_host, int num_classes, const int32_t *gt_inds, const float *gts,
+                            const int64_t *gt_labels, const int *gt_offsets_host, const float *cfg15_host, void *workspace,
+                            size_t workspace_bytes, float *norm2, void *stream);
+int brcnn_atss_loss_finalize(const void *workspace, size_t workspace_bytes, const float *norm2, int batch, int num_levels,
+                             const int *heights, const int *widths, int num_classes, const float *cfg15_host, float *losses,
+                             float *coef3, void *stream);
+int brcnn_atss_loss_backward(const float *a, const float *r, const int *layout8_host, const float *scales, int batch,
+                             int num_levels, const int *heights, const int *widths, const int *strides,
+                             const float *base_anchors_host, int num_classes, const int32_t *gt_inds, const float *gts,
+                             const int64_t *gt_labels, const int *gt_offsets_host, const float *cfg15_host,
+                             const float *grad_losses, const float *coef3, void *workspace, size_t workspace_bytes,
+                             float *da, float *dr, float *dscale, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Optimizer step of the train loop: SGD with momentum and weight decay after clipping the global gradient
  * norm (torch.optim.SGD + mmcv OptimizerHook grad_clip; configs/_base_/schedules/schedule_1x.py:2-3,
  * configs/boosting_rcnn/boosting_rcnn_r50_pafpn_1x_utdac.py:130), as three stages over tables of tensors
