@@ -13,37 +13,24 @@
 //   atss_decode_levels : fcos_decode_levels_kernel with the anchor decode of dense_decode_levels_kernel.
 //   atss_loss_*        : ATSSHead.loss, the block-partial scheme of fcos_loss_* (fixed order within a thread, LDS tree, one
 //                        finalize workgroup): no float atomics, the same bits from run to run.
+//
+// The layout, the geometry, the decode kernel and the loss kernels are centerness_head.h's, instantiated with AtssTraits.
 #include "box_iou.h"
-#include "head_loss.h"
+#include "centerness_head.h"
 
 namespace {
 
-constexpr int AT_THREADS = 256;
-constexpr int AT_PER_THREAD = 8;
-constexpr int AT_CHUNK = AT_THREADS * AT_PER_THREAD;        // elements (class term) or anchors (anchor terms) per workgroup
-constexpr int AT_SEGS = 2 * BRCNN_MAX_LEVELS;               // (level, term): 2 * l = class term, 2 * l + 1 = anchor terms
 constexpr int AT_MAX_TOPK = 16;
 
-struct AtssLayout {
-    int sa, cls_off, sr, reg_off, ctr_in_r, ctr_off;
-};
-
-struct AtssGeom {
-    int L, C, B, n;                         // n: anchors per image
-    int h[BRCNN_MAX_LEVELS], w[BRCNN_MAX_LEVELS], stride[BRCNN_MAX_LEVELS];
+struct AtssGeom : CenternessGeom {
     float base[BRCNN_MAX_LEVELS][4];
-    int start[BRCNN_MAX_LEVELS + 1];        // first anchor of each level within an image
-    long long row0[BRCNN_MAX_LEVELS + 1];   // first row of each level in A / R
-    int blk0[AT_SEGS + 1];                  // first workgroup of each (level, term) pair
-    int pblk0[BRCNN_MAX_LEVELS + 1];        // first workgroup of each level in the backward pass over the anchors
-    int gt_off[BRCNN_MAX_IMAGES + 1];
-    AtssLayout lay;
-    float gamma, alpha, eps, lw_cls, lw_bbox, lw_ctr, mean[4], std[4], max_ratio;
+    float eps, mean[4], std[4], max_ratio;
 };
 
-__device__ __forceinline__ const float* ctr_ptr(const AtssLayout& y, const float* a, const float* r, size_t row) {
-    return y.ctr_in_r ? r + row * y.sr + y.ctr_off : a + row * y.sa + y.ctr_off;
-}
+struct AtssDecode : CenternessDecode {
+    float base[BRCNN_MAX_LEVELS][4];
+    float mean[4], std[4], max_ratio;
+};
 
 __device__ __forceinline__ float4 anchor_of(const float* base, int width, int stride, int cell) {
     const float sx = (float)((cell % width) * stride), sy = (float)((cell / width) * stride);
@@ -86,7 +73,7 @@ __device__ __forceinline__ unsigned long long block_min(unsigned long long v, un
     __syncthreads();
     red[tid] = v;
     __syncthreads();
-    for (int d = AT_THREADS / 2; d > 0; d >>= 1) {
+    for (int d = CH_THREADS / 2; d > 0; d >>= 1) {
         if (tid < d && red[tid + d] < red[tid]) red[tid] = red[tid + d];
         __syncthreads();
     }
@@ -95,7 +82,7 @@ __device__ __forceinline__ unsigned long long block_min(unsigned long long v, un
 
 __global__ __launch_bounds__(256) void atss_assign_kernel(const AtssGeom g, const AtssAssign as, const float* __restrict__ gts,
                                                          unsigned long long* __restrict__ keys) {
-    __shared__ unsigned long long red[AT_THREADS];
+    __shared__ unsigned long long red[CH_THREADS];
     __shared__ int cand[BRCNN_MAX_LEVELS * AT_MAX_TOPK];          // anchor index within the image
     __shared__ float cand_iou[BRCNN_MAX_LEVELS * AT_MAX_TOPK];
     __shared__ float cand_side[BRCNN_MAX_LEVELS * AT_MAX_TOPK];   // min(cx - x1, cy - y1, x2 - cx, y2 - cy)
@@ -121,7 +108,7 @@ __global__ __launch_bounds__(256) void atss_assign_kernel(const AtssGeom g, cons
         unsigned long long prev = 0ull;
         for (int rank = 0; rank < k; rank++) {
             unsigned long long best = ~0ull;
-            for (int cell = tid; cell < hw; cell += AT_THREADS) {
+            for (int cell = tid; cell < hw; cell += CH_THREADS) {
                 if (cell / g.w[l] >= vh || cell % g.w[l] >= vw) continue;
                 const float4 an = anchor_of(g.base[l], g.w[l], g.stride[l], cell);
                 const float dx = (an.x + an.z) / 2.f - gcx, dy = (an.y + an.w) / 2.f - gcy;
@@ -135,7 +122,7 @@ __global__ __launch_bounds__(256) void atss_assign_kernel(const AtssGeom g, cons
         m += k;
     }
     __syncthreads();
-    for (int c = tid; c < m; c += AT_THREADS) {
+    for (int c = tid; c < m; c += CH_THREADS) {
         const int idx = cand[c];
         int l = 0;
 #pragma unroll
@@ -161,7 +148,7 @@ __global__ __launch_bounds__(256) void atss_assign_kernel(const AtssGeom g, cons
     }
     __syncthreads();
     const float thr = s_thr;
-    for (int c = tid; c < m; c += AT_THREADS) {
+    for (int c = tid; c < m; c += CH_THREADS) {
         if (cand_iou[c] >= thr && cand_side[c] > 0.01f) {
             const unsigned long long key = ((unsigned long long)__float_as_uint(cand_iou[c]) << 32) | (0xffffffffu - (unsigned)j);
             atomicMax(keys + (size_t)b * g.n + cand[c], key);
@@ -192,214 +179,91 @@ __global__ __launch_bounds__(256) void atss_assign_write_kernel(const AtssGeom g
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------ test time
-struct AtssDecode {
-    int num, C, T;
-    const int64_t* inds[BRCNN_MAX_LEVELS];
-    int hw[BRCNN_MAX_LEVELS], width[BRCNN_MAX_LEVELS], stride[BRCNN_MAX_LEVELS], col0[BRCNN_MAX_LEVELS + 1];
-    long long row0[BRCNN_MAX_LEVELS];
-    float base[BRCNN_MAX_LEVELS][4];
-    AtssLayout lay;
-    float mean[4], std[4], max_ratio, score_thr;
-};
-
-__global__ __launch_bounds__(256) void atss_decode_levels_kernel(const AtssDecode lv, int batch, const float* __restrict__ a,
-                                                                const float* __restrict__ r,
-                                                                const float* __restrict__ scales,
-                                                                const float* __restrict__ max_shape,
-                                                                const float* __restrict__ scale_factor,
-                                                                float* __restrict__ boxes, float* __restrict__ scores,
-                                                                int64_t* __restrict__ labels, uint8_t* __restrict__ valid,
-                                                                int* __restrict__ n_valid) {
-    const long long per_image = (long long)lv.T * lv.C;
-    const long long total = (long long)batch * per_image;
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(t / per_image);
-        const long long q = t - (long long)b * per_image;
-        const int col = (int)(q / lv.C), c = (int)(q - (long long)col * lv.C);
-        int l = 0;
-#pragma unroll
-        for (int i = 1; i < BRCNN_MAX_LEVELS; i++)
-            if (i < lv.num && col >= lv.col0[i]) l = i;
-        const int count = lv.col0[l + 1] - lv.col0[l];
-        long long cell = lv.inds[l][(size_t)b * count + (col - lv.col0[l])];
-        cell = cell < 0 ? 0 : (cell >= lv.hw[l] ? lv.hw[l] - 1 : cell);     // (a picked index is an anchor of the level)
-        const size_t row = (size_t)(lv.row0[l] + (long long)b * lv.hw[l] + cell);
-        const float s = sigmoidf_(a[row * lv.lay.sa + lv.lay.cls_off + c]);
-        const float ct = sigmoidf_(*ctr_ptr(lv.lay, a, r, row));
-        const float4 an = anchor_of(lv.base[l], lv.width[l], lv.stride[l], (int)cell);
-        const float* raw = r + row * lv.lay.sr + lv.lay.reg_off;
-        const float sc = scales[l];
-        const float d[4] = {sc * raw[0], sc * raw[1], sc * raw[2], sc * raw[3]};
-        const float4 o = decode_anchor<false>(an, d, lv.mean, lv.std, lv.max_ratio, nullptr);
-        float ox1 = o.x, oy1 = o.y, ox2 = o.z, oy2 = o.w;
-        const float mh = max_shape[2 * b], mw = max_shape[2 * b + 1];
-        ox1 = ox1 < 0.f ? 0.f : ox1; ox1 = ox1 > mw ? mw : ox1;
-        oy1 = oy1 < 0.f ? 0.f : oy1; oy1 = oy1 > mh ? mh : oy1;
-        ox2 = ox2 < 0.f ? 0.f : ox2; ox2 = ox2 > mw ? mw : ox2;
-        oy2 = oy2 < 0.f ? 0.f : oy2; oy2 = oy2 > mh ? mh : oy2;
-        if (scale_factor) {
-            const float* sf = scale_factor + 4 * b;
-            ox1 = ox1 / sf[0]; oy1 = oy1 / sf[1]; ox2 = ox2 / sf[2]; oy2 = oy2 / sf[3];
-        }
-        *reinterpret_cast<float4*>(boxes + (size_t)t * 4) = make_float4(ox1, oy1, ox2, oy2);
-        scores[t] = s * ct;
-        labels[t] = c;
-        const bool ok = s > lv.score_thr;       // the class score alone: multiclass_nms masks before it applies the factor
-        valid[t] = ok ? 1 : 0;
-        // an integer count, one atomic per wave and image (see dense_decode_levels_kernel)
-        const unsigned long long active = __ballot(1);
-        const int first = __ffsll((long long)active) - 1;
-        const int b_first = __shfl(b, first, WAVE);
-        const unsigned long long same = __ballot(ok && b == b_first);
-        if ((int)(threadIdx.x & (WAVE - 1)) == first && same) atomicAdd(n_valid + b_first, __popcll(same));
-        if (ok && b != b_first) atomicAdd(n_valid + b, 1);
-    }
-}
-
-// ----------------------------------------------------------------------------------------------------------------- loss
-__device__ __forceinline__ int level_of_row(const AtssGeom& g, long long row) {
-    int l = 0;
-#pragma unroll
-    for (int i = 1; i < BRCNN_MAX_LEVELS; i++)
-        if (i < g.L && row >= g.row0[i]) l = i;
-    return l;
-}
-
+// ------------------------------------------------------------------------------------------------- test time and loss
 // what one row of the head outputs is: its image, its state and, for a positive, its anchor and targets
-struct Cell {
+struct AnchorCell {
     int b, gi;          // gi: index into the packed gts (positive), -1 negative, -2 invalid (weight 0)
     float4 an, gt;      // the anchor; gt' = delta2bbox(anchor, bbox2delta(anchor, gt))
     float ctr_t;
 };
 
-__device__ __forceinline__ Cell locate(const AtssGeom& g, const int* __restrict__ gt_inds, const float* __restrict__ gts,
-                                       int l, long long r, bool want_targets) {
-    Cell o;
-    const int hw = g.h[l] * g.w[l];
-    o.b = (int)(r / hw);
-    const int cell = (int)(r - (long long)o.b * hw);
-    const int gi = gt_inds[(size_t)o.b * g.n + g.start[l] + cell];
-    o.gi = gi < 0 ? -2 : ((gi > 0 && gi <= g.gt_off[o.b + 1] - g.gt_off[o.b]) ? g.gt_off[o.b] + gi - 1 : -1);
-    if (want_targets && o.gi >= 0) {
-        o.an = anchor_of(g.base[l], g.w[l], g.stride[l], cell);
-        const float4 gt = *reinterpret_cast<const float4*>(gts + (size_t)o.gi * 4);
-        // bbox2delta (delta_xywh_bbox_coder.py:99-141)
-        const float pw = o.an.z - o.an.x, ph = o.an.w - o.an.y;
-        float t[4];
-        t[0] = ((gt.x + gt.z) * 0.5f - (o.an.x + o.an.z) * 0.5f) / pw;
-        t[1] = ((gt.y + gt.w) * 0.5f - (o.an.y + o.an.w) * 0.5f) / ph;
-        t[2] = logf((gt.z - gt.x) / pw);
-        t[3] = logf((gt.w - gt.y) / ph);
+struct AtssTraits {
+    using Geom = AtssGeom;
+    using Decode = AtssDecode;
+    using Cell = AnchorCell;
+    static constexpr int PARTIALS = 3;              // the positives are counted from gt_inds, per image
+    static constexpr bool HAS_INVALID = true;
+
+    static __device__ __forceinline__ int grad(const AtssGeom& g, int term, int l) { return term * g.L + l; }     // gl (3, L)
+
+    // delta2bbox of the cell's anchor, after the Scale
+    static __device__ __forceinline__ float4 decode_box(const AtssDecode& lv, int l, int cell, const float* __restrict__ raw,
+                                                        float sc) {
+        const float4 an = anchor_of(lv.base[l], lv.width[l], lv.stride[l], cell);
+        const float d[4] = {sc * raw[0], sc * raw[1], sc * raw[2], sc * raw[3]};
+        return decode_anchor<false>(an, d, lv.mean, lv.std, lv.max_ratio, nullptr);
+    }
+
+    static __device__ __forceinline__ AnchorCell locate(const AtssGeom& g, const int* __restrict__ gt_inds,
+                                                        const float* __restrict__ gts, int l, long long r, bool want_targets) {
+        AnchorCell o;
+        const int hw = g.h[l] * g.w[l];
+        o.b = (int)(r / hw);
+        const int cell = (int)(r - (long long)o.b * hw);
+        const int gi = gt_inds[(size_t)o.b * g.n + g.start[l] + cell];
+        o.gi = gi < 0 ? -2 : ((gi > 0 && gi <= g.gt_off[o.b + 1] - g.gt_off[o.b]) ? g.gt_off[o.b] + gi - 1 : -1);
+        if (want_targets && o.gi >= 0) {
+            o.an = anchor_of(g.base[l], g.w[l], g.stride[l], cell);
+            const float4 gt = *reinterpret_cast<const float4*>(gts + (size_t)o.gi * 4);
+            // bbox2delta (delta_xywh_bbox_coder.py:99-141)
+            const float pw = o.an.z - o.an.x, ph = o.an.w - o.an.y;
+            float t[4];
+            t[0] = ((gt.x + gt.z) * 0.5f - (o.an.x + o.an.z) * 0.5f) / pw;
+            t[1] = ((gt.y + gt.w) * 0.5f - (o.an.y + o.an.w) * 0.5f) / ph;
+            t[2] = logf((gt.z - gt.x) / pw);
+            t[3] = logf((gt.w - gt.y) / ph);
 #pragma unroll
-        for (int k = 0; k < 4; k++) t[k] = (t[k] - g.mean[k]) / g.std[k];
-        o.gt = decode_anchor<false>(o.an, t, g.mean, g.std, g.max_ratio, nullptr);
-        // centerness_target (atss_head.py:294-310)
-        const float cx = (o.an.z + o.an.x) / 2.f, cy = (o.an.w + o.an.y) / 2.f;
-        const float l_ = cx - o.gt.x, t_ = cy - o.gt.y, r_ = o.gt.z - cx, b_ = o.gt.w - cy;
-        o.ctr_t = sqrtf((fminf(l_, r_) / fmaxf(l_, r_)) * (fminf(t_, b_) / fmaxf(t_, b_)));
-    }
-    return o;
-}
-
-// The box term of one positive: 1 - giou(delta2bbox(anchor, scale * raw), gt'), and with BWD its derivative w.r.t. the four
-// SCALED raw values
-template <bool BWD>
-__device__ __forceinline__ float box_term(const AtssGeom& g, const Cell& o, const float* __restrict__ raw, float scale,
-                                          float* __restrict__ dscaled) {
-    const float d[4] = {scale * raw[0], scale * raw[1], scale * raw[2], scale * raw[3]};
-    float jac[4], gp[4];
-    const float4 p = decode_anchor<BWD>(o.an, d, g.mean, g.std, g.max_ratio, jac);
-    const float loss = corner_box_loss<BWD>(true, g.eps, g.eps, p.x, p.y, p.z, p.w, o.gt.x, o.gt.y, o.gt.z, o.gt.w, gp);
-    if (BWD) {
-        // x1 = gx - gw / 2, x2 = gx + gw / 2
-        dscaled[0] = (gp[0] + gp[2]) * jac[0];
-        dscaled[1] = (gp[1] + gp[3]) * jac[1];
-        dscaled[2] = (gp[2] - gp[0]) * 0.5f * jac[2];
-        dscaled[3] = (gp[3] - gp[1]) * 0.5f * jac[3];
-    }
-    return loss;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red, int tid) {
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-    for (int d = AT_THREADS / 2; d > 0; d >>= 1) {
-        if (tid < d) red[tid] += red[tid + d];
-        __syncthreads();
-    }
-    return red[0];
-}
-
-// partials: 3 arrays of `nblk` floats.  A class workgroup writes [sum, 0, 0]; an anchor workgroup [box sum, centerness BCE
-// sum, sum of the centerness targets]
-__global__ __launch_bounds__(256) void atss_loss_forward_kernel(const AtssGeom g, const float* __restrict__ a,
-                                                               const float* __restrict__ r,
-                                                               const float* __restrict__ scales,
-                                                               const int* __restrict__ gt_inds,
-                                                               const float* __restrict__ gts,
-                                                               const int64_t* __restrict__ gt_labels,
-                                                               float* __restrict__ partials) {
-    __shared__ float red[AT_THREADS];
-    const int blk = blockIdx.x, tid = threadIdx.x, nblk = g.blk0[AT_SEGS];
-    int seg = 0;
-#pragma unroll
-    for (int i = 1; i < AT_SEGS; i++)
-        if (i < 2 * g.L && blk >= g.blk0[i]) seg = i;
-    const int l = seg >> 1;
-    const bool anchors = seg & 1;
-    const long long rows = (long long)g.B * g.h[l] * g.w[l];
-    const long long total = anchors ? rows : rows * g.C;
-    const long long e0 = (long long)(blk - g.blk0[seg]) * AT_CHUNK;
-    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
-    for (int j = 0; j < AT_PER_THREAD; j++) {
-        const long long e = e0 + (long long)j * AT_THREADS + tid;
-        if (e >= total) break;
-        if (!anchors) {
-            const long long rr = e / g.C;
-            const int c = (int)(e - rr * g.C);
-            const Cell o = locate(g, gt_inds, gts, l, rr, false);
-            if (o.gi == -2) continue;
-            const bool hit = o.gi >= 0 && gt_labels[o.gi] == c;
-            acc0 += focal_elem<false>(a[(size_t)(g.row0[l] + rr) * g.lay.sa + g.lay.cls_off + c], hit, g.gamma, g.alpha);
-        } else {
-            const Cell o = locate(g, gt_inds, gts, l, e, true);
-            if (o.gi < 0) continue;
-            const size_t row = (size_t)(g.row0[l] + e);
-            acc0 += box_term<false>(g, o, r + row * g.lay.sr + g.lay.reg_off, scales[l], nullptr) * o.ctr_t;
-            acc1 += bce_logits(*ctr_ptr(g.lay, a, r, row), o.ctr_t);
-            acc2 += o.ctr_t;
+            for (int k = 0; k < 4; k++) t[k] = (t[k] - g.mean[k]) / g.std[k];
+            o.gt = decode_anchor<false>(o.an, t, g.mean, g.std, g.max_ratio, nullptr);
+            // centerness_target (atss_head.py:294-310)
+            const float cx = (o.an.z + o.an.x) / 2.f, cy = (o.an.w + o.an.y) / 2.f;
+            const float l_ = cx - o.gt.x, t_ = cy - o.gt.y, r_ = o.gt.z - cx, b_ = o.gt.w - cy;
+            o.ctr_t = sqrtf((fminf(l_, r_) / fmaxf(l_, r_)) * (fminf(t_, b_) / fmaxf(t_, b_)));
         }
+        return o;
     }
-    const float s0 = block_sum(acc0, red, tid), s1 = block_sum(acc1, red, tid), s2 = block_sum(acc2, red, tid);
-    if (tid == 0) {
-        partials[blk] = s0;
-        partials[nblk + blk] = s1;
-        partials[2 * nblk + blk] = s2;
-    }
-}
 
-// the sum of partials[which] over the workgroups of (level l, term)
-__device__ __forceinline__ float level_sum(const AtssGeom& g, const float* __restrict__ partials, int which, int l, int term,
-                                           float* red, int tid) {
-    const int nblk = g.blk0[AT_SEGS], seg = 2 * l + term;
-    float s = 0.f;
-    for (int i = g.blk0[seg] + tid; i < g.blk0[seg + 1]; i += AT_THREADS) s += partials[which * nblk + i];
-    return block_sum(s, red, tid);
-}
+    // The box term of one positive: 1 - giou(delta2bbox(anchor, scale * raw), gt'), and with BWD its derivative w.r.t. the four
+    // SCALED raw values
+    template <bool BWD>
+    static __device__ __forceinline__ float box_term(const AtssGeom& g, const AnchorCell& o, const float* __restrict__ raw,
+                                                     float scale, float* __restrict__ dscaled) {
+        const float d[4] = {scale * raw[0], scale * raw[1], scale * raw[2], scale * raw[3]};
+        float jac[4], gp[4];
+        const float4 p = decode_anchor<BWD>(o.an, d, g.mean, g.std, g.max_ratio, jac);
+        const float loss = corner_box_loss<BWD>(true, g.eps, g.eps, p.x, p.y, p.z, p.w, o.gt.x, o.gt.y, o.gt.z, o.gt.w, gp);
+        if (BWD) {
+            // x1 = gx - gw / 2, x2 = gx + gw / 2
+            dscaled[0] = (gp[0] + gp[2]) * jac[0];
+            dscaled[1] = (gp[1] + gp[3]) * jac[1];
+            dscaled[2] = (gp[2] - gp[0]) * 0.5f * jac[2];
+            dscaled[3] = (gp[3] - gp[1]) * 0.5f * jac[3];
+        }
+        return loss;
+    }
+};  // AtssTraits
 
 // norm2 = [sum over images of max(number of positives, 1), sum of the centerness targets]; a count is an integer below
 // 2^24, exact in fp32
 __global__ __launch_bounds__(256) void atss_loss_norm_kernel(const AtssGeom g, const int* __restrict__ gt_inds,
                                                             const float* __restrict__ partials, float* __restrict__ norm2) {
-    __shared__ float red[AT_THREADS];
+    __shared__ float red[CH_THREADS];
     const int tid = threadIdx.x;
     float cnt = 0.f;
     for (int b = 0; b < g.B; b++) {
         const int G = g.gt_off[b + 1] - g.gt_off[b];
         float c = 0.f;
-        for (int i = tid; i < g.n; i += AT_THREADS) {
+        for (int i = tid; i < g.n; i += CH_THREADS) {
             const int gi = gt_inds[(size_t)b * g.n + i];
             c += (gi > 0 && gi <= G) ? 1.f : 0.f;
         }
@@ -414,7 +278,7 @@ __global__ __launch_bounds__(256) void atss_loss_norm_kernel(const AtssGeom g, c
 __global__ __launch_bounds__(256) void atss_loss_finalize_kernel(const AtssGeom g, const float* __restrict__ partials,
                                                                 const float* __restrict__ norm2,
                                                                 float* __restrict__ losses, float* __restrict__ coef3) {
-    __shared__ float red[AT_THREADS];
+    __shared__ float red[CH_THREADS];
     const int tid = threadIdx.x;
     const float N = fmaxf(norm2[0], 1.f), S = fmaxf(norm2[1], 1.f);
     for (int l = 0; l < g.L; l++) {
@@ -433,164 +297,16 @@ __global__ __launch_bounds__(256) void atss_loss_finalize_kernel(const AtssGeom 
     }
 }
 
-// one thread per element of dA (rows, stride_a), padding columns included: every element is written
-__global__ __launch_bounds__(256) void atss_loss_backward_a_kernel(const AtssGeom g, const float* __restrict__ a,
-                                                                  const float* __restrict__ r,
-                                                                  const int* __restrict__ gt_inds,
-                                                                  const float* __restrict__ gts,
-                                                                  const int64_t* __restrict__ gt_labels,
-                                                                  const float* __restrict__ gl,
-                                                                  const float* __restrict__ coef3, float* __restrict__ da) {
-    const long long total = g.row0[g.L] * g.lay.sa;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-        const long long row = e / g.lay.sa;
-        const int ch = (int)(e - row * g.lay.sa);
-        const bool is_cls = ch >= g.lay.cls_off && ch < g.lay.cls_off + g.C;
-        const bool is_ctr = !g.lay.ctr_in_r && ch == g.lay.ctr_off;
-        float v = 0.f;
-        if (is_cls || is_ctr) {
-            const int l = level_of_row(g, row);
-            const Cell o = locate(g, gt_inds, gts, l, row - g.row0[l], is_ctr);
-            if (is_cls) {
-                if (o.gi != -2) {
-                    const bool hit = o.gi >= 0 && gt_labels[o.gi] == ch - g.lay.cls_off;
-                    v = gl[l] * coef3[0] * focal_elem<true>(a[e], hit, g.gamma, g.alpha);
-                }
-            } else if (o.gi >= 0) {
-                v = gl[2 * g.L + l] * coef3[2] * (sigmoidf_(a[e]) - o.ctr_t);
-            }
-        }
-        da[e] = v;
-    }
-}
-
-// one thread per row of dR (rows, stride_r): the 4 delta columns, the centerness column when it rides on R, zeros elsewhere;
-// and per workgroup the partial of dscale_l = sum over the level's rows of d(scaled) * raw
-__global__ __launch_bounds__(256) void atss_loss_backward_r_kernel(const AtssGeom g, const float* __restrict__ a,
-                                                                  const float* __restrict__ r,
-                                                                  const float* __restrict__ scales,
-                                                                  const int* __restrict__ gt_inds,
-                                                                  const float* __restrict__ gts,
-                                                                  const float* __restrict__ gl,
-                                                                  const float* __restrict__ coef3, float* __restrict__ dr,
-                                                                  float* __restrict__ dscale_partials) {
-    __shared__ float red[AT_THREADS];
-    const int blk = blockIdx.x, tid = threadIdx.x;
-    int l = 0;
-#pragma unroll
-    for (int i = 1; i < BRCNN_MAX_LEVELS; i++)
-        if (i < g.L && blk >= g.pblk0[i]) l = i;
-    const long long rows = (long long)g.B * g.h[l] * g.w[l];
-    const long long e0 = (long long)(blk - g.pblk0[l]) * AT_CHUNK;
-    float acc = 0.f;
-    for (int j = 0; j < AT_PER_THREAD; j++) {
-        const long long e = e0 + (long long)j * AT_THREADS + tid;
-        if (e >= rows) break;
-        const size_t row = (size_t)(g.row0[l] + e);
-        float* out = dr + row * g.lay.sr;
-        const Cell o = locate(g, gt_inds, gts, l, e, true);
-        float ds[4] = {0.f, 0.f, 0.f, 0.f}, dc = 0.f;
-        if (o.gi >= 0) {
-            const float* raw = r + row * g.lay.sr + g.lay.reg_off;
-            const float sc = scales[l];
-            box_term<true>(g, o, raw, sc, ds);
-            const float k = gl[g.L + l] * coef3[1] * o.ctr_t;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                ds[q] = k * ds[q];
-                acc += ds[q] * raw[q];
-                ds[q] = ds[q] * sc;
-            }
-            if (g.lay.ctr_in_r) dc = gl[2 * g.L + l] * coef3[2] * (sigmoidf_(r[row * g.lay.sr + g.lay.ctr_off]) - o.ctr_t);
-        }
-        for (int ch = 0; ch < g.lay.sr; ch++) {
-            const int q = ch - g.lay.reg_off;
-            out[ch] = (q >= 0 && q < 4) ? ds[q] : ((g.lay.ctr_in_r && ch == g.lay.ctr_off) ? dc : 0.f);
-        }
-    }
-    const float s = block_sum(acc, red, tid);
-    if (tid == 0) dscale_partials[blk] = s;
-}
-
-__global__ __launch_bounds__(256) void atss_dscale_kernel(const AtssGeom g, const float* __restrict__ dscale_partials,
-                                                         float* __restrict__ dscale) {
-    __shared__ float red[AT_THREADS];
-    const int tid = threadIdx.x;
-    for (int l = 0; l < g.L; l++) {
-        float s = 0.f;
-        for (int i = g.pblk0[l] + tid; i < g.pblk0[l + 1]; i += AT_THREADS) s += dscale_partials[i];
-        const float t = block_sum(s, red, tid);
-        if (tid == 0) dscale[l] = t;
-    }
-}
-
 // --------------------------------------------------------------------------------------------------------------- host
-bool layout_ok(const int* v, int C) {
-    if (!v) return false;
-    const int sa = v[0], cls_off = v[1], sr = v[2], reg_off = v[3], ctr_in_r = v[4], ctr_off = v[5];
-    if (sa <= 0 || sr <= 0 || cls_off < 0 || reg_off < 0 || ctr_off < 0 || cls_off + C > sa || reg_off + 4 > sr) return false;
-    if (ctr_in_r ? (ctr_off >= sr || (ctr_off >= reg_off && ctr_off < reg_off + 4))
-                 : (ctr_off >= sa || (ctr_off >= cls_off && ctr_off < cls_off + C)))
-        return false;
-    return true;
-}
-
-AtssLayout make_layout(const int* v) {
-    AtssLayout y;
-    y.sa = v[0]; y.cls_off = v[1]; y.sr = v[2]; y.reg_off = v[3]; y.ctr_in_r = v[4] != 0; y.ctr_off = v[5];
-    return y;
-}
-
-bool level_ok(int h, int w, int stride) {
-    return h > 0 && w > 0 && stride > 0 && stride <= 0x7fff && (long long)h * w <= 0x7fffffffLL &&
-           (long long)h * stride <= 0x7fffffLL && (long long)w * stride <= 0x7fffffLL;
-}
-
+// cfg15_host: [focal gamma, focal alpha, eps of the GIoU, loss_weight_cls, loss_weight_bbox, loss_weight_centerness,
+// means (4), stds (4), |log(wh_ratio_clip)|]
 int fill_geom(AtssGeom& g, int batch, int num_levels, const int* heights, const int* widths, const int* strides,
               const float* base, int C, const int* gt_offsets_host, const int* layout8, const float* cfg15) {
-    if (batch <= 0 || batch > BRCNN_MAX_IMAGES || num_levels <= 0 || num_levels > BRCNN_MAX_LEVELS || C <= 0 ||
-        C > 0x7fffff || !heights || !widths || !strides)
-        return BRCNN_EINVAL;
-    g.L = num_levels; g.C = C; g.B = batch;
-    long long anchors = 0, rows = 0, blocks = 0, pblocks = 0;
-    for (int l = 0; l < num_levels; l++) {
-        if (!level_ok(heights[l], widths[l], strides[l])) return BRCNN_EINVAL;
-        g.h[l] = heights[l]; g.w[l] = widths[l]; g.stride[l] = strides[l];
-        for (int k = 0; k < 4; k++) g.base[l][k] = base ? base[4 * l + k] : 0.f;
-        g.start[l] = (int)anchors;
-        g.row0[l] = rows;
-        const long long cells = (long long)batch * heights[l] * widths[l];
-        anchors += (long long)heights[l] * widths[l];
-        rows += cells;
-        g.blk0[2 * l] = (int)blocks;
-        blocks += (cells * C + AT_CHUNK - 1) / AT_CHUNK;
-        g.blk0[2 * l + 1] = (int)blocks;
-        blocks += (cells + AT_CHUNK - 1) / AT_CHUNK;
-        g.pblk0[l] = (int)pblocks;
-        pblocks += (cells + AT_CHUNK - 1) / AT_CHUNK;
-        if (anchors > 0x7fffffffLL / batch || blocks > 0x3fffffffLL) return BRCNN_EINVAL;
-    }
-    for (int l = num_levels; l < BRCNN_MAX_LEVELS; l++) {
-        g.h[l] = g.w[l] = g.stride[l] = 1;
-        for (int k = 0; k < 4; k++) g.base[l][k] = 0.f;
-    }
-    for (int l = num_levels; l <= BRCNN_MAX_LEVELS; l++) { g.start[l] = (int)anchors; g.row0[l] = rows; g.pblk0[l] = (int)pblocks; }
-    for (int s = 2 * num_levels; s <= AT_SEGS; s++) g.blk0[s] = (int)blocks;
-    g.n = (int)anchors;
-    for (int b = 0; b <= BRCNN_MAX_IMAGES; b++) g.gt_off[b] = 0;
-    if (gt_offsets_host) {
-        for (int b = 0; b <= batch; b++) {
-            if (gt_offsets_host[b] < 0 || (b > 0 && gt_offsets_host[b] < gt_offsets_host[b - 1])) return BRCNN_EINVAL;
-            g.gt_off[b] = gt_offsets_host[b];
-        }
-        for (int b = batch + 1; b <= BRCNN_MAX_IMAGES; b++) g.gt_off[b] = gt_offsets_host[batch];
-    }
-    g.lay = AtssLayout{};
-    if (layout8) {
-        if (!layout_ok(layout8, C)) return BRCNN_EINVAL;
-        g.lay = make_layout(layout8);
-    }
-    g.gamma = g.alpha = 0.f; g.eps = 1e-6f; g.lw_cls = g.lw_bbox = g.lw_ctr = 1.f; g.max_ratio = 0.f;
+    const int st = fill_geom_common(g, batch, num_levels, heights, widths, strides, C, gt_offsets_host, layout8);
+    if (st) return st;
+    for (int l = 0; l < BRCNN_MAX_LEVELS; l++)
+        for (int k = 0; k < 4; k++) g.base[l][k] = (base && l < num_levels) ? base[4 * l + k] : 0.f;
+    g.eps = 1e-6f; g.max_ratio = 0.f;
     for (int k = 0; k < 4; k++) { g.mean[k] = 0.f; g.std[k] = 1.f; }
     if (cfg15) {
         g.gamma = cfg15[0]; g.alpha = cfg15[1]; g.eps = cfg15[2];
@@ -602,11 +318,6 @@ int fill_geom(AtssGeom& g, int batch, int num_levels, const int* heights, const 
         g.max_ratio = cfg15[14];
     }
     return 0;
-}
-
-inline size_t loss_workspace_bytes(const AtssGeom& g) {
-    // forward / finalize: 3 partial arrays; backward: one dscale partial per anchor workgroup (fewer)
-    return (size_t)3 * (size_t)g.blk0[AT_SEGS] * sizeof(float);
 }
 
 }  // namespace
@@ -629,7 +340,7 @@ BRCNN_API int brcnn_atss_assign(const float* gts, const int* gt_offsets_host, in
     unsigned long long* keys = (unsigned long long*)workspace;
     BRCNN_HIP_CHECK(hipMemsetAsync(keys, 0, need, (hipStream_t)stream));
     if (total_gt > 0) {
-        hipLaunchKernelGGL(atss_assign_kernel, dim3(total_gt), dim3(AT_THREADS), 0, (hipStream_t)stream, g, as, gts, keys);
+        hipLaunchKernelGGL(atss_assign_kernel, dim3(total_gt), dim3(CH_THREADS), 0, (hipStream_t)stream, g, as, gts, keys);
         BRCNN_LAUNCH_CHECK();
     }
     const long long total = (long long)batch * g.n;
@@ -648,43 +359,17 @@ BRCNN_API int brcnn_atss_decode_levels(const int64_t* const* topk_inds, const in
                                        const float* scale_factor, const float* means4_host, const float* stds4_host,
                                        double wh_ratio_clip, float score_thr, float* boxes, float* scores, int64_t* labels,
                                        uint8_t* valid, int32_t* n_valid, void* stream) {
-    if (batch < 0 || num_levels <= 0 || num_levels > BRCNN_MAX_LEVELS || num_classes <= 0 ||
-        num_classes > 0x7fffff || !topk_inds || !counts || !a || !r || !layout_ok(layout8_host, num_classes) || !scales ||
-        !heights || !widths || !strides || !base_anchors_host || !max_shape || !means4_host || !stds4_host ||
-        !(wh_ratio_clip > 0.0) || !boxes || !scores || !labels || !valid || !n_valid)
-        return BRCNN_EINVAL;
+    if (!base_anchors_host || !means4_host || !stds4_host || !(wh_ratio_clip > 0.0)) return BRCNN_EINVAL;
     AtssDecode lv = {};
-    lv.num = num_levels; lv.C = num_classes;
-    lv.lay = make_layout(layout8_host);
-    long long T = 0, rows = 0;
-    for (int l = 0; l < num_levels; l++) {
-        if (counts[l] <= 0 || !level_ok(heights[l], widths[l], strides[l]) || !topk_inds[l] ||
-            counts[l] > (long long)heights[l] * widths[l])
-            return BRCNN_EINVAL;
-        lv.inds[l] = topk_inds[l];
-        lv.hw[l] = heights[l] * widths[l]; lv.width[l] = widths[l]; lv.stride[l] = strides[l];
+    const int st = fill_decode_common(lv, topk_inds, counts, a, r, layout8_host, scales, batch, num_levels, heights, widths,
+                                      strides, num_classes, max_shape, score_thr, boxes, scores, labels, valid, n_valid);
+    if (st) return st;
+    for (int l = 0; l < num_levels; l++)
         for (int k = 0; k < 4; k++) lv.base[l][k] = base_anchors_host[4 * l + k];
-        lv.row0[l] = rows;
-        rows += (long long)batch * lv.hw[l];
-        lv.col0[l] = (int)T;
-        T += counts[l];
-        if (T * num_classes > 0x7fffffffLL) return BRCNN_EINVAL;
-    }
-    for (int l = num_levels; l < BRCNN_MAX_LEVELS; l++) { lv.hw[l] = lv.width[l] = lv.stride[l] = 1; }
-    for (int l = num_levels; l <= BRCNN_MAX_LEVELS; l++) lv.col0[l] = (int)T;
-    lv.T = (int)T;
     for (int k = 0; k < 4; k++) { lv.mean[k] = means4_host[k]; lv.std[k] = stds4_host[k]; }
     lv.max_ratio = (float)fabs(log(wh_ratio_clip));
-    lv.score_thr = score_thr;
-    if (batch == 0) return 0;
-    BRCNN_HIP_CHECK(hipMemsetAsync(n_valid, 0, sizeof(int32_t) * batch, (hipStream_t)stream));
-    const long long total = (long long)batch * T * num_classes;
-    long long g = (total + 255) / 256;
-    if (g > 4096) g = 4096;
-    hipLaunchKernelGGL(atss_decode_levels_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, lv, batch, a, r, scales,
-                       max_shape, scale_factor, boxes, scores, labels, valid, n_valid);
-    BRCNN_LAUNCH_CHECK();
-    return 0;
+    return launch_decode_levels<AtssTraits>(lv, batch, a, r, scales, max_shape, scale_factor, boxes, scores, labels, valid,
+                                            n_valid, stream);
 }
 
 BRCNN_API size_t brcnn_atss_loss_workspace_bytes(int batch, int num_levels, const int* heights, const int* widths,
@@ -693,7 +378,7 @@ BRCNN_API size_t brcnn_atss_loss_workspace_bytes(int batch, int num_levels, cons
     int ones[BRCNN_MAX_LEVELS];
     for (int l = 0; l < BRCNN_MAX_LEVELS; l++) ones[l] = 1;
     if (fill_geom(g, batch, num_levels, heights, widths, ones, nullptr, num_classes, nullptr, nullptr, nullptr)) return 0;
-    return loss_workspace_bytes(g);
+    return loss_workspace_bytes<AtssTraits>(g);
 }
 
 BRCNN_API int brcnn_atss_loss_forward(const float* a, const float* r, const int* layout8_host, const float* scales,
@@ -708,13 +393,13 @@ BRCNN_API int brcnn_atss_loss_forward(const float* a, const float* r, const int*
                              layout8_host, cfg15_host);
     if (st) return st;
     if (!a || !r || !scales || !gt_inds || !workspace || !norm2 || ((!gts || !gt_labels) && g.gt_off[batch] > 0) ||
-        workspace_bytes < loss_workspace_bytes(g))
+        workspace_bytes < loss_workspace_bytes<AtssTraits>(g))
         return BRCNN_EINVAL;
     float* partials = (float*)workspace;
-    hipLaunchKernelGGL(atss_loss_forward_kernel, dim3(g.blk0[AT_SEGS]), dim3(AT_THREADS), 0, (hipStream_t)stream, g, a, r,
-                       scales, gt_inds, gts, gt_labels, partials);
+    hipLaunchKernelGGL(centerness_loss_forward_kernel<AtssTraits>, dim3(g.blk0[CH_SEGS]), dim3(CH_THREADS), 0,
+                       (hipStream_t)stream, g, a, r, scales, gt_inds, gts, gt_labels, partials);
     BRCNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(atss_loss_norm_kernel, dim3(1), dim3(AT_THREADS), 0, (hipStream_t)stream, g, gt_inds, partials, norm2);
+    hipLaunchKernelGGL(atss_loss_norm_kernel, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, gt_inds, partials, norm2);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }
@@ -728,8 +413,8 @@ BRCNN_API int brcnn_atss_loss_finalize(const void* workspace, size_t workspace_b
     if (!cfg15_host) return BRCNN_EINVAL;
     const int st = fill_geom(g, batch, num_levels, heights, widths, ones, nullptr, num_classes, nullptr, nullptr, cfg15_host);
     if (st) return st;
-    if (!workspace || !norm2 || !losses || !coef3 || workspace_bytes < loss_workspace_bytes(g)) return BRCNN_EINVAL;
-    hipLaunchKernelGGL(atss_loss_finalize_kernel, dim3(1), dim3(AT_THREADS), 0, (hipStream_t)stream, g,
+    if (!workspace || !norm2 || !losses || !coef3 || workspace_bytes < loss_workspace_bytes<AtssTraits>(g)) return BRCNN_EINVAL;
+    hipLaunchKernelGGL(atss_loss_finalize_kernel, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g,
                        (const float*)workspace, norm2, losses, coef3);
     BRCNN_LAUNCH_CHECK();
     return 0;
@@ -747,19 +432,6 @@ BRCNN_API int brcnn_atss_loss_backward(const float* a, const float* r, const int
     const int st = fill_geom(g, batch, num_levels, heights, widths, strides, base_anchors_host, num_classes, gt_offsets_host,
                              layout8_host, cfg15_host);
     if (st) return st;
-    if (!a || !r || !scales || !gt_inds || !grad_losses || !coef3 || !workspace || !da || !dr || !dscale ||
-        ((!gts || !gt_labels) && g.gt_off[batch] > 0) || workspace_bytes < loss_workspace_bytes(g))
-        return BRCNN_EINVAL;
-    long long ga = (g.row0[g.L] * g.lay.sa + 255) / 256;
-    if (ga > 8192) ga = 8192;
-    hipLaunchKernelGGL(atss_loss_backward_a_kernel, dim3((int)ga), dim3(256), 0, (hipStream_t)stream, g, a, r, gt_inds, gts,
-                       gt_labels, grad_losses, coef3, da);
-    BRCNN_LAUNCH_CHECK();
-    float* dsp = (float*)workspace;
-    hipLaunchKernelGGL(atss_loss_backward_r_kernel, dim3(g.pblk0[g.L]), dim3(AT_THREADS), 0, (hipStream_t)stream, g, a, r,
-                       scales, gt_inds, gts, grad_losses, coef3, dr, dsp);
-    BRCNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(atss_dscale_kernel, dim3(1), dim3(AT_THREADS), 0, (hipStream_t)stream, g, dsp, dscale);
-    BRCNN_LAUNCH_CHECK();
-    return 0;
+    return launch_loss_backward<AtssTraits>(g, a, r, scales, gt_inds, gts, gt_labels, grad_losses, coef3, workspace,
+                                            workspace_bytes, da, dr, dscale, stream);
 }

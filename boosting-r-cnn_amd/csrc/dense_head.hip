@@ -19,7 +19,7 @@
 // Work is laid out along the NHWC rows: consecutive lanes read consecutive channels.  The loss sums go block partial
 // (fixed order within a thread, LDS tree) -> one finalize workgroup (strided sums, LDS tree): no float atomics, the
 // same bits from run to run.
-#include "common.h"
+#include "decode_tail.h"
 #include <float.h>
 #include <math.h>
 
@@ -94,30 +94,8 @@ __global__ __launch_bounds__(256) void dense_decode_levels_kernel(const DenseDec
         dh = fminf(fmaxf(dh, -lv.max_ratio), lv.max_ratio);
         const float gw = pw * expf(dw), gh = ph * expf(dh);
         const float gx = px + dxw, gy = py + dyh;
-        float ox1 = gx - gw * 0.5f, oy1 = gy - gh * 0.5f;
-        float ox2 = gx + gw * 0.5f, oy2 = gy + gh * 0.5f;
-        const float mh = max_shape[2 * b], mw = max_shape[2 * b + 1];
-        ox1 = ox1 < 0.f ? 0.f : ox1; ox1 = ox1 > mw ? mw : ox1;
-        oy1 = oy1 < 0.f ? 0.f : oy1; oy1 = oy1 > mh ? mh : oy1;
-        ox2 = ox2 < 0.f ? 0.f : ox2; ox2 = ox2 > mw ? mw : ox2;
-        oy2 = oy2 < 0.f ? 0.f : oy2; oy2 = oy2 > mh ? mh : oy2;
-        if (scale) {
-            const float* sf = scale + 4 * b;
-            ox1 = ox1 / sf[0]; oy1 = oy1 / sf[1]; ox2 = ox2 / sf[2]; oy2 = oy2 / sf[3];
-        }
-        *reinterpret_cast<float4*>(boxes + (size_t)t * 4) = make_float4(ox1, oy1, ox2, oy2);
-        scores[t] = s;
-        labels[t] = c;
-        const bool ok = s > lv.score_thr;
-        valid[t] = ok ? 1 : 0;
-        // an integer count (the order of the additions does not matter), one atomic per wave and image instead of one
-        // per candidate: the lanes that share the first active lane's image are counted with a ballot
-        const unsigned long long active = __ballot(1);
-        const int first = __ffsll((long long)active) - 1;
-        const int b_first = __shfl(b, first, WAVE);
-        const unsigned long long same = __ballot(ok && b == b_first);
-        if ((int)(threadIdx.x & (WAVE - 1)) == first && same) atomicAdd(n_valid + b_first, __popcll(same));
-        if (ok && b != b_first) atomicAdd(n_valid + b, 1);
+        store_candidate(t, b, c, gx - gw * 0.5f, gy - gh * 0.5f, gx + gw * 0.5f, gy + gh * 0.5f, s, s > lv.score_thr, max_shape,
+                        scale, boxes, scores, labels, valid, n_valid);
     }
 }
 

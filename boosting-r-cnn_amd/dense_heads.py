@@ -60,7 +60,8 @@ def valid_cells(anchor_generator, sizes, img_metas, like):
 
 
 class AnchorHead(nn.Module):
-    """Target assignment shared by anchor-based heads (anchor_head.py:37-268)."""
+    """Target assignment shared by anchor-based heads (anchor_head.py:37-268), and what their device paths share: the
+    cached anchor tables, the whole-batch MaxIoU assignment and the proposal stage of the two RPN heads."""
 
     def __init__(self, num_classes, in_channels, feat_channels=256,
                  anchor_generator=dict(type='AnchorGenerator', scales=[8, 16, 32],
@@ -151,6 +152,151 @@ class AnchorHead(nn.Module):
             bbox_weights = unmap(bbox_weights, n, inside_flags)
         return (labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds,
                 sampling_result)
+
+    def loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights,
+                    num_total_samples):
+        """anchor_head.py:373-421"""
+        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
+        loss_cls = self.loss_cls(cls_score, labels.reshape(-1), label_weights.reshape(-1), avg_factor=num_total_samples)
+        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4)
+        if self.reg_decoded_bbox:
+            bbox_pred = self.bbox_coder.decode(anchors.reshape(-1, 4), bbox_pred)
+        loss_bbox = self.loss_bbox(bbox_pred, bbox_targets.reshape(-1, 4), bbox_weights.reshape(-1, 4),
+                                   avg_factor=num_total_samples)
+        return loss_cls, loss_bbox
+
+    # ------------------------------------------------------------------ device path: anchor tables + assignment
+    def _base_anchors(self, level, device):
+        key = (level, str(device))
+        if key not in self._base_anchor_cache:
+            self._base_anchor_cache[key] = self.anchor_generator.base_anchors[level].to(device)
+        return self._base_anchor_cache[key]
+
+    def _anchor_table(self, sizes, device):
+        """all levels' grid anchors of ONE image as a cached (n, 4) tensor + the level geometry"""
+        key = (tuple(sizes), str(device))
+        cache = self.__dict__.setdefault('_anchor_tables', {})
+        if key not in cache:
+            if len(cache) > 64:
+                cache.clear()
+            anchors = torch.cat(self.anchor_generator.grid_anchors(list(sizes), device), 0).contiguous()
+            starts = [0]
+            for (h, w) in sizes:
+                starts.append(starts[-1] + h * w * self.num_anchors)
+            cache[key] = (anchors, (starts, [w for _, w in sizes], self.num_anchors))
+        return cache[key]
+
+    def assign_targets_device(self, sizes, img_metas, gts, gt_offsets, device, want_counts=False):
+        """AnchorHead._get_targets_single's assignment for the whole batch on the device: gt_inds
+        (B, anchors per image) int32 (-1 ignore / outside, 0 negative, k matched to gt k-1)"""
+        from . import train_ops
+        anchors, geom = self._anchor_table(sizes, device)
+        B = len(img_metas)
+        valid_hw = valid_cells(self.anchor_generator, sizes, img_metas, anchors)
+        border = self.train_cfg.allowed_border
+        img_hw = const_rows([m['img_shape'][:2] for m in img_metas], anchors) if border >= 0 else None
+        a = self.assigner
+        return train_ops.assign_max_iou(anchors, gts, gt_offsets, a.pos_iou_thr, a.neg_iou_thr, a.min_pos_iou,
+                                        a.match_low_quality, batch=B, geom=geom, valid_hw=valid_hw, img_hw=img_hw,
+                                        allowed_border=border, want_counts=want_counts)
+
+    # ------------------------------------------------------------------ device path: the RPN proposal stage
+    def _proposals_padded(self, cls_nhwc, reg_nhwc, iou_nhwc, img_metas, cfg=None, reg_scales=None):
+        """Device-resident proposal stage for the whole batch (no host sync).
+
+        Inputs are the NHWC head outputs per level: (B,h,w,A), (B,h,w,4A), (B,h,w,A) (dense or
+        channel-slice views of the fused head output; then `reg_scales` carries the per-level
+        Scale still to be applied to the raw deltas).
+        Returns (dets (B, max_per_img, 5) zero-padded, num (B,) int32)."""
+        cfg = copy.deepcopy(self.test_cfg if cfg is None else cfg)
+        assert self.use_sigmoid_cls and self.cls_out_channels == 1
+        nms_cfg = dict(cfg.nms)
+        assert nms_cfg.pop('type', 'nms') == 'nms', 'RPN proposals use greedy NMS'
+        B = cls_nhwc[0].shape[0]
+        device = cls_nhwc[0].device
+        shapes = {tuple(m['img_shape'][:2]) for m in img_metas}
+        A = self.num_anchors
+        sc_l, pr_l, va_l, id_l = [], [], [], []
+        raw = [self._proposal_scores(cls_nhwc[lvl], None if iou_nhwc is None else iou_nhwc[lvl]).view(B, -1)
+               for lvl in range(len(cls_nhwc))]
+        if 0 < cfg.nms_pre <= 4096:
+            # descending, ties by ascending index (the shared tie rule), all levels in one launch
+            picked = ops.rpn_topk(raw, cfg.nms_pre)
+        else:
+            picked = []
+            for score in raw:
+                n = score.shape[1]
+                if cfg.nms_pre > 0 and n > cfg.nms_pre:
+                    ranked, rank_inds = score.sort(dim=1, descending=True, stable=True)
+                    picked.append((ranked[:, :cfg.nms_pre], rank_inds[:, :cfg.nms_pre].contiguous()))
+                else:
+                    picked.append((score, torch.arange(n, device=device).expand(B, n).contiguous()))
+        dev_scales = isinstance(reg_scales, torch.Tensor)
+        if (len(shapes) == 1 or dev_scales) and cfg.min_bbox_size >= 0 and device.type == 'cuda':
+            # every level decoded by one launch that also writes the validity and level-id columns of
+            # the (B, T) candidate slots; device-resident scales (training) also take the per-image
+            # clip border from a device table, so a batch of differently sized images stays one launch
+            L = len(cls_nhwc)
+            from .core import const_rows
+            per_image = const_rows([m['img_shape'][:2] for m in img_metas], raw[0]) if dev_scales and len(shapes) > 1 \
+                else None
+            props, valid, ids = ops.rpn_decode_levels(
+                [picked[l][1] for l in range(L)], [reg_nhwc[l] for l in range(L)],
+                [self._base_anchors(l, device) for l in range(L)], [tuple(cls_nhwc[l].shape[1:3]) for l in range(L)],
+                list(self.anchor_generator.strides), self.bbox_coder.means, self.bbox_coder.stds, next(iter(shapes)),
+                cfg.min_bbox_size, pred_scales=None if reg_scales is None else (reg_scales if dev_scales else list(reg_scales)),
+                max_shapes=per_image)
+            sc_l = [picked[l][0] for l in range(L)]
+            scores = torch.cat(sc_l, 1)
+            return self._proposals_from_candidates(props, scores, ids, valid, sc_l, nms_cfg, cfg)
+        for lvl in range(len(cls_nhwc)):
+            h, w = cls_nhwc[lvl].shape[1:3]
+            score, topk_inds = picked[lvl]
+            stride = self.anchor_generator.strides[lvl]
+            rs = 1.0 if reg_scales is None else reg_scales[lvl]
+            if len(shapes) == 1:
+                max_shape = next(iter(shapes))
+                props, valid = ops.rpn_decode(topk_inds, reg_nhwc[lvl], self._base_anchors(lvl, device),
+                                              (h, w), stride, self.bbox_coder.means,
+                                              self.bbox_coder.stds, max_shape, cfg.min_bbox_size,
+                                              pred_scale=rs)
+            else:   # per-image clip border
+                pl, vl = [], []
+                for b in range(B):
+                    p1, v1 = ops.rpn_decode(topk_inds[b:b + 1], reg_nhwc[lvl][b:b + 1],
+                                            self._base_anchors(lvl, device), (h, w), stride,
+                                            self.bbox_coder.means, self.bbox_coder.stds,
+                                            img_metas[b]['img_shape'][:2], cfg.min_bbox_size,
+                                            pred_scale=rs)
+                    pl.append(p1)
+                    vl.append(v1)
+                props, valid = torch.cat(pl), torch.cat(vl)
+            if cfg.min_bbox_size < 0:
+                valid = torch.ones_like(valid)
+            sc_l.append(score)
+            pr_l.append(props)
+            va_l.append(valid.bool())
+            id_l.append(torch.full((B, score.shape[1]), lvl, dtype=torch.long, device=device))
+        scores = torch.cat(sc_l, 1)            # (B, T)
+        props = torch.cat(pr_l, 1)             # (B, T, 4)
+        valid = torch.cat(va_l, 1)             # (B, T)  `proposals[valid_mask]` (:750-754)
+        ids = torch.cat(id_l, 1)
+        return self._proposals_from_candidates(props, scores, ids, valid, sc_l, nms_cfg, cfg)
+
+    @staticmethod
+    def _proposals_from_candidates(props, scores, ids, valid, sc_l, nms_cfg, cfg):
+        if scores.shape[1] >= nms_cfg.get('split_thr', 10000):
+            # mmcv batched_nms switches to its per-id (per-level) loop at >= split_thr candidates
+            # (the training proposal cfg: 15 150 per image).  Both of its branches keep the same
+            # boxes in the same order (the coordinate offsets already isolate the levels), so the
+            # whole batch runs as one segmented launch over (image, level) segments.
+            from .postprocess import batched_nms_images_by_level
+            return batched_nms_images_by_level(props, scores, ids, valid, [s_.shape[1] for s_ in sc_l],
+                                               nms_cfg['iou_threshold'], cfg.max_per_img,
+                                               nms_cfg.get('offset', 0))
+        dets, _, num = batched_nms_images(props, scores, ids, valid, nms_cfg['iou_threshold'],
+                                          cfg.max_per_img, nms_cfg.get('offset', 0))
+        return dets, num
 
 
 @HEADS.register_module()
@@ -593,34 +739,6 @@ class ATSSRPNHead(AnchorHead):
         y = ConvNHWCFunction.apply(x, w, b, B, sizes, 1, self.rpn_cls.padding[0], False, False, True)   # fp32 head output
         return y, sizes
 
-    def _anchor_table(self, sizes, device):
-        """all levels' grid anchors of ONE image as a cached (n, 4) tensor + the level geometry"""
-        key = (tuple(sizes), str(device))
-        cache = self.__dict__.setdefault('_anchor_tables', {})
-        if key not in cache:
-            if len(cache) > 64:
-                cache.clear()
-            anchors = torch.cat(self.anchor_generator.grid_anchors(list(sizes), device), 0).contiguous()
-            starts = [0]
-            for (h, w) in sizes:
-                starts.append(starts[-1] + h * w * self.num_anchors)
-            cache[key] = (anchors, (starts, [w for _, w in sizes], self.num_anchors))
-        return cache[key]
-
-    def assign_targets_device(self, sizes, img_metas, gts, gt_offsets, device, want_counts=False):
-        """AnchorHead._get_targets_single's assignment for the whole batch on the device: gt_inds
-        (B, anchors per image) int32 (-1 ignore / outside, 0 negative, k matched to gt k-1)"""
-        from . import train_ops
-        anchors, geom = self._anchor_table(sizes, device)
-        B = len(img_metas)
-        valid_hw = valid_cells(self.anchor_generator, sizes, img_metas, anchors)
-        border = self.train_cfg.allowed_border
-        img_hw = const_rows([m['img_shape'][:2] for m in img_metas], anchors) if border >= 0 else None
-        a = self.assigner
-        return train_ops.assign_max_iou(anchors, gts, gt_offsets, a.pos_iou_thr, a.neg_iou_thr, a.min_pos_iou,
-                                        a.match_low_quality, batch=B, geom=geom, valid_hw=valid_hw, img_hw=img_hw,
-                                        allowed_border=border, want_counts=want_counts)
-
     def loss_fused(self, y, sizes, gt_bboxes, img_metas, gt_flat=None, scales=None):
         """ATSSRPNHead.loss on the fused head output: assignment + every loss term in HIP kernels, no
         host synchronisation.  Each loss comes back as a one-element list holding the sum over the
@@ -665,108 +783,9 @@ class ATSSRPNHead(AnchorHead):
     def _proposal_scores(self, cls, iou):
         return ops.rpn_score(cls, iou)
 
-    def _base_anchors(self, level, device):
-        key = (level, str(device))
-        if key not in self._base_anchor_cache:
-            self._base_anchor_cache[key] = self.anchor_generator.base_anchors[level].to(device)
-        return self._base_anchor_cache[key]
-
     def get_bboxes_padded(self, cls_nhwc, reg_nhwc, iou_nhwc, img_metas, cfg=None, reg_scales=None):
-        """Device-resident proposal stage for the whole batch (no host sync).
-
-        Inputs are the NHWC head outputs per level: (B,h,w,A), (B,h,w,4A), (B,h,w,A) (dense or
-        channel-slice views of the fused head output; then `reg_scales` carries the per-level
-        Scale still to be applied to the raw deltas).
-        Returns (dets (B, max_per_img, 5) zero-padded, num (B,) int32)."""
-        cfg = copy.deepcopy(self.test_cfg if cfg is None else cfg)
-        assert self.use_sigmoid_cls and self.cls_out_channels == 1
-        nms_cfg = dict(cfg.nms)
-        assert nms_cfg.pop('type', 'nms') == 'nms', 'RPN proposals use greedy NMS'
-        B = cls_nhwc[0].shape[0]
-        device = cls_nhwc[0].device
-        shapes = {tuple(m['img_shape'][:2]) for m in img_metas}
-        A = self.num_anchors
-        sc_l, pr_l, va_l, id_l = [], [], [], []
-        raw = [self._proposal_scores(cls_nhwc[lvl], None if iou_nhwc is None else iou_nhwc[lvl]).view(B, -1)
-               for lvl in range(len(cls_nhwc))]
-        if 0 < cfg.nms_pre <= 4096:
-            # descending, ties by ascending index (the shared tie rule), all levels in one launch
-            picked = ops.rpn_topk(raw, cfg.nms_pre)
-        else:
-            picked = []
-            for score in raw:
-                n = score.shape[1]
-                if cfg.nms_pre > 0 and n > cfg.nms_pre:
-                    ranked, rank_inds = score.sort(dim=1, descending=True, stable=True)
-                    picked.append((ranked[:, :cfg.nms_pre], rank_inds[:, :cfg.nms_pre].contiguous()))
-                else:
-                    picked.append((score, torch.arange(n, device=device).expand(B, n).contiguous()))
-        dev_scales = isinstance(reg_scales, torch.Tensor)
-        if (len(shapes) == 1 or dev_scales) and cfg.min_bbox_size >= 0 and device.type == 'cuda':
-            # every level decoded by one launch that also writes the validity and level-id columns of
-            # the (B, T) candidate slots; device-resident scales (training) also take the per-image
-            # clip border from a device table, so a batch of differently sized images stays one launch
-            L = len(cls_nhwc)
-            from .core import const_rows
-            per_image = const_rows([m['img_shape'][:2] for m in img_metas], raw[0]) if dev_scales and len(shapes) > 1 \
-                else None
-            props, valid, ids = ops.rpn_decode_levels(
-                [picked[l][1] for l in range(L)], [reg_nhwc[l] for l in range(L)],
-                [self._base_anchors(l, device) for l in range(L)], [tuple(cls_nhwc[l].shape[1:3]) for l in range(L)],
-                list(self.anchor_generator.strides), self.bbox_coder.means, self.bbox_coder.stds, next(iter(shapes)),
-                cfg.min_bbox_size, pred_scales=None if reg_scales is None else (reg_scales if dev_scales else list(reg_scales)),
-                max_shapes=per_image)
-            sc_l = [picked[l][0] for l in range(L)]
-            scores = torch.cat(sc_l, 1)
-            return self._proposals_from_candidates(props, scores, ids, valid, sc_l, nms_cfg, cfg)
-        for lvl in range(len(cls_nhwc)):
-            h, w = cls_nhwc[lvl].shape[1:3]
-            score, topk_inds = picked[lvl]
-            stride = self.anchor_generator.strides[lvl]
-            rs = 1.0 if reg_scales is None else reg_scales[lvl]
-            if len(shapes) == 1:
-                max_shape = next(iter(shapes))
-                props, valid = ops.rpn_decode(topk_inds, reg_nhwc[lvl], self._base_anchors(lvl, device),
-                                              (h, w), stride, self.bbox_coder.means,
-                                              self.bbox_coder.stds, max_shape, cfg.min_bbox_size,
-                                              pred_scale=rs)
-            else:   # per-image clip border
-                pl, vl = [], []
-                for b in range(B):
-                    p1, v1 = ops.rpn_decode(topk_inds[b:b + 1], reg_nhwc[lvl][b:b + 1],
-                                            self._base_anchors(lvl, device), (h, w), stride,
-                                            self.bbox_coder.means, self.bbox_coder.stds,
-                                            img_metas[b]['img_shape'][:2], cfg.min_bbox_size,
-                                            pred_scale=rs)
-                    pl.append(p1)
-                    vl.append(v1)
-                props, valid = torch.cat(pl), torch.cat(vl)
-            if cfg.min_bbox_size < 0:
-                valid = torch.ones_like(valid)
-            sc_l.append(score)
-            pr_l.append(props)
-            va_l.append(valid.bool())
-            id_l.append(torch.full((B, score.shape[1]), lvl, dtype=torch.long, device=device))
-        scores = torch.cat(sc_l, 1)            # (B, T)
-        props = torch.cat(pr_l, 1)             # (B, T, 4)
-        valid = torch.cat(va_l, 1)             # (B, T)  `proposals[valid_mask]` (:750-754)
-        ids = torch.cat(id_l, 1)
-        return self._proposals_from_candidates(props, scores, ids, valid, sc_l, nms_cfg, cfg)
-
-    @staticmethod
-    def _proposals_from_candidates(props, scores, ids, valid, sc_l, nms_cfg, cfg):
-        if scores.shape[1] >= nms_cfg.get('split_thr', 10000):
-            # mmcv batched_nms switches to its per-id (per-level) loop at >= split_thr candidates
-            # (the training proposal cfg: 15 150 per image).  Both of its branches keep the same
-            # boxes in the same order (the coordinate offsets already isolate the levels), so the
-            # whole batch runs as one segmented launch over (image, level) segments.
-            from .postprocess import batched_nms_images_by_level
-            return batched_nms_images_by_level(props, scores, ids, valid, [s_.shape[1] for s_ in sc_l],
-                                               nms_cfg['iou_threshold'], cfg.max_per_img,
-                                               nms_cfg.get('offset', 0))
-        dets, _, num = batched_nms_images(props, scores, ids, valid, nms_cfg['iou_threshold'],
-                                          cfg.max_per_img, nms_cfg.get('offset', 0))
-        return dets, num
+        """the device-resident proposal stage (`AnchorHead._proposals_padded`), ranked by sqrt(sigmoid(cls) * sigmoid(iou))"""
+        return self._proposals_padded(cls_nhwc, reg_nhwc, iou_nhwc, img_metas, cfg, reg_scales)
 
     def get_bboxes(self, cls_scores, bbox_preds, iou_preds, img_metas, cfg=None, rescale=False,
                    with_nms=True):
@@ -825,7 +844,7 @@ class RPNHead(AnchorHead):
     `rpn_cls` / `rpn_reg`; sigmoid objectness, 256 anchors drawn per image for the loss.  Parameter names and shapes
     are the reference's.  Execution: the 3x3 conv and the two 1x1 heads (as ONE launch, [cls A | reg 4A]) run over
     all pyramid levels at once on the NHWC conv kernels; the proposal stage and the whole-batch assignment are the
-    head-agnostic ones ATSSRPNHead uses; the sampled loss has its own kernels (csrc/rpn_sampled.hip)."""
+    head-agnostic ones of AnchorHead that ATSSRPNHead uses too; the sampled loss has its own kernels (csrc/rpn_sampled.hip)."""
 
     plain_rpn = True        # (detectors.py: no IoU branch, no per-level Scale, no early RPN backward pass)
     supports_tta = False
@@ -932,10 +951,6 @@ class RPNHead(AnchorHead):
         return v(cls), v(reg)
 
     # ------------------------------------------------------------------ proposals
-    _base_anchors = ATSSRPNHead._base_anchors
-    _proposals_from_candidates = staticmethod(ATSSRPNHead._proposals_from_candidates)
-    _atss_get_bboxes_padded = ATSSRPNHead.get_bboxes_padded
-
     def _check_proposal_limits(self, cfg, sizes):
         """the sizes the device proposal stage serves (brcnn_rpn_topk: k <= 4096; brcnn_nms_prepare_levels: <= 8 levels,
         <= 16384 candidates per image); anything beyond is refused, not served some slower way"""
@@ -963,7 +978,7 @@ class RPNHead(AnchorHead):
         scales = None
         if per_image_shapes and len({tuple(m['img_shape'][:2]) for m in img_metas}) > 1:
             scales = torch.ones(len(cls_nhwc), dtype=torch.float32, device=cls_nhwc[0].device)
-        return self._atss_get_bboxes_padded(cls_nhwc, reg_nhwc, None, img_metas, cfg=cfg, reg_scales=scales)
+        return self._proposals_padded(cls_nhwc, reg_nhwc, None, img_metas, cfg=cfg, reg_scales=scales)
 
     def proposals_fused(self, y, sizes, img_metas, cfg):
         """proposal stage straight from the fused training head output (channel-slice views, no copies)"""
@@ -1003,18 +1018,6 @@ class RPNHead(AnchorHead):
             return losses
         return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
 
-    def loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights,
-                    num_total_samples):
-        """anchor_head.py:373-421"""
-        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
-        loss_cls = self.loss_cls(cls_score, labels.reshape(-1), label_weights.reshape(-1), avg_factor=num_total_samples)
-        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4)
-        if self.reg_decoded_bbox:
-            bbox_pred = self.bbox_coder.decode(anchors.reshape(-1, 4), bbox_pred)
-        loss_bbox = self.loss_bbox(bbox_pred, bbox_targets.reshape(-1, 4), bbox_weights.reshape(-1, 4),
-                                   avg_factor=num_total_samples)
-        return loss_cls, loss_bbox
-
     def loss(self, cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=None):
         """rpn_head.py:70-101 / anchor_head.py:423-497.  Device tensors of a covered configuration go to the HIP
         kernels (`loss_fused`); otherwise the reference's per-image chain in torch (the host path: `self.last_drawn`
@@ -1049,9 +1052,6 @@ class RPNHead(AnchorHead):
         return dict(loss_rpn_cls=losses_cls, loss_rpn_bbox=losses_bbox)
 
     # ------------------------------------------------------------------ device-resident train step
-    _anchor_table = ATSSRPNHead._anchor_table
-    assign_targets_device = ATSSRPNHead.assign_targets_device
-
     def _tower_fusable(self):
         return True
 
@@ -1095,9 +1095,264 @@ class RPNHead(AnchorHead):
         return dict(loss_rpn_cls=[losses2[0]], loss_rpn_bbox=[losses2[1]])
 
 
+# ----------------------------------------------------------------------------- single-stage detection heads
+class DenseDetHead:
+    """What RetinaHead, FCOSHead and ATSSHead share beyond their layers (a mixin in front of the nn.Module base): the
+    test-cfg and limit checks, the Normal(0.01) / bias_prob initialisation, the class-aware NMS of the device path's
+    candidate slots, the `get_bboxes` skeleton (device or host dispatch, the one host sync) with the tail of the host
+    mirror, and the reference's simple_test / forward_train drivers.  A head supplies `_get_bboxes_device(outs, img_metas,
+    cfg, rescale)` -> padded (dets, labels, num) and `_get_bboxes_host(*outs, img_metas, cfg, rescale, batched_nms)`."""
+
+    supports_tta = False
+    # nms_pre / level limits of the device path (include/brcnn_hip.h: brcnn_rpn_topk)
+    MAX_NMS_PRE, MAX_LEVELS = 4096, 8
+
+    def _init_normal(self, cls_conv):
+        """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name=<the class conv>, bias_prob=0.01))"""
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.normal_(m.weight, 0, 0.01)
+                if m.bias is not None:
+                    nn.init.constant_(m.bias, 0)
+        nn.init.constant_(cls_conv.bias, bias_init_with_prob(0.01))
+
+    def _check_test_cfg(self, cfg):
+        name = type(self).__name__
+        nms = cfg.get('nms', dict(type='nms'))
+        if nms.get('type', 'nms') != 'nms':
+            raise NotImplementedError(f"{name}: test_cfg.nms.type={nms.get('type')!r}; only greedy 'nms' is supported "
+                                      '(no soft-NMS)')
+        if nms.get('class_agnostic', False):
+            raise NotImplementedError(f'{name}: test_cfg.nms.class_agnostic=True is not supported')
+
+    def _check_limits(self, cfg, sizes):
+        """the sizes the device path serves (brcnn_rpn_topk: k <= 4096, <= 8 levels); anything beyond is refused"""
+        name = type(self).__name__
+        if not 0 < cfg.get('nms_pre', -1) <= self.MAX_NMS_PRE:
+            raise ValueError(f"{name}: nms_pre={cfg.get('nms_pre', -1)} outside (0, {self.MAX_NMS_PRE}] (brcnn_rpn_topk)")
+        self._check_levels(sizes)
+
+    def _check_levels(self, sizes):
+        if len(sizes) > self.MAX_LEVELS:
+            raise ValueError(f'{type(self).__name__}: {len(sizes)} pyramid levels, at most {self.MAX_LEVELS} are supported')
+
+    def _refuse_ignore(self, gt_bboxes_ignore):
+        if gt_bboxes_ignore is not None:
+            raise NotImplementedError(f'{type(self).__name__}: gt_bboxes_ignore is not supported on the device path')
+
+    @staticmethod
+    def _nms_candidates(bb, sc, lb, va, C, cfg):
+        """class-aware NMS + max_per_img of the (level, pick, class) candidate slots of a dense head"""
+        B = bb.shape[0]
+        nms_cfg = dict(cfg.nms)
+        nms_cfg.pop('type', None)
+        T = sc.shape[1] // C
+        # mmcv's batched_nms changes branch at split_thr by the number of candidates that SURVIVE score_thr (n_valid), which
+        # only the device knows here; the branch is chosen by the slot count T * C instead, so no host read is needed.
+        # Both branches keep the same boxes in the same order (the coordinate offsets already isolate the classes), with
+        # one limit: where the reference takes the offset form and this code the per-class one (or the reverse), the
+        # IoUs are computed on un-offset resp. offset fp32 coordinates and can differ in the last ulp -- a pair whose IoU
+        # sits within an ulp of iou_threshold may then be decided differently.
+        if T * C >= nms_cfg.get('split_thr', 10000):
+            # the per-class branch: class-major slots, one segmented NMS launch over (image, class)
+            from .postprocess import batched_nms_images_by_level
+            cm = lambda t: t.view(B, T, C, *t.shape[2:]).transpose(1, 2).reshape(B, C * T, *t.shape[2:]).contiguous()   # noqa: E731
+            return batched_nms_images_by_level(cm(bb), cm(sc), cm(lb), cm(va), [T] * C, nms_cfg['iou_threshold'],
+                                               cfg.max_per_img, nms_cfg.get('offset', 0), return_ids=True)
+        return batched_nms_images(bb, sc, lb, va, nms_cfg['iou_threshold'], cfg.max_per_img, nms_cfg.get('offset', 0))
+
+    def _get_bboxes(self, outs, img_metas, cfg, rescale, with_nms, batched_nms):
+        """`get_bboxes` behind each head's reference signature; `outs`: the per-level lists of the head's outputs.  Device
+        tensors take the head's padded device path and are cut to size after its one host sync; CPU tensors take the
+        reference's chain on torch ops with the caller's `batched_nms` (this package's NMS is a device kernel)."""
+        if not with_nms:
+            raise NotImplementedError(f'{type(self).__name__}: with_nms=False is not supported')
+        assert all(len(o) == len(outs[0]) for o in outs)
+        if outs[0][0].is_cuda:
+            det, lab, num = self._get_bboxes_device([[t.detach() for t in o] for o in outs], img_metas, cfg, rescale)
+            num = num.tolist()   # the one host sync
+            return [(det[i, :num[i]], lab[i, :num[i]]) for i in range(len(img_metas))]
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_test_cfg(cfg)
+        return self._get_bboxes_host(*outs, img_metas, cfg, rescale, ops.batched_nms if batched_nms is None else batched_nms)
+
+    def _host_nms(self, boxes, scores, factor, img_meta, cfg, rescale, batched_nms):
+        """the tail of the host mirror for one image: rescale, score threshold on the class score (before the optional
+        per-box `factor`, bbox_nms.py:48-58), fan-out to classes, class-aware NMS, max_per_img -> (dets (k,5), labels (k,))"""
+        C = self.cls_out_channels
+        if rescale:
+            boxes = boxes / boxes.new_tensor(img_meta['scale_factor'])
+        keep = (scores > cfg.score_thr).reshape(-1)
+        inds = keep.nonzero(as_tuple=False).reshape(-1)
+        labels = torch.arange(C, dtype=torch.long).repeat(scores.shape[0])[inds]
+        cb = boxes[:, None].expand(-1, C, 4).reshape(-1, 4)[inds]
+        cs = (scores if factor is None else scores * factor[:, None]).reshape(-1)[inds]
+        if cb.numel() == 0:
+            return torch.cat([cb, cs[:, None]], -1), labels
+        dets, kept = batched_nms(cb.contiguous(), cs.contiguous(), labels, dict(cfg.nms))
+        if cfg.max_per_img > 0:
+            dets, kept = dets[:cfg.max_per_img], kept[:cfg.max_per_img]
+        return dets, labels[kept]
+
+    def simple_test(self, feats, img_metas, rescale=False, batched_nms=None):
+        """dense_test_mixins.py:17-37: list of (N,C,h,w) -> per image (dets (k,5), labels (k,))"""
+        return self.get_bboxes(*self(feats), img_metas, rescale=rescale, batched_nms=batched_nms)
+
+    def aug_test(self, feats, img_metas, rescale=False):
+        raise NotImplementedError(f'{type(self).__name__} has no test-time augmentation')
+
+    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
+        """base_dense_head.py:48-78"""
+        outs = self(x)
+        losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+        if proposal_cfg is None:
+            return losses
+        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
+
+
+class GNTowerHead(DenseDetHead):
+    """What FCOSHead and ATSSHead share on top of DenseDetHead: two towers of `stacked_convs` 3x3 conv + GroupNorm + ReLU
+    (`cls_convs`, `reg_convs`), each ending in ONE fused fp32 head conv whose columns `_head_groups()` names, one `Scale`
+    per level, and the (A, R) row tensors the kernels of csrc/fcos_head.hip and csrc/atss_head.hip read in place.  A head
+    supplies `_head_groups`, `_layout`, `_rows_from_reference`, `_decode_candidates` and `loss_fused`."""
+
+    def _init_towers(self):
+        self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
+        for i in range(self.stacked_convs):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            for convs in (self.cls_convs, self.reg_convs):
+                convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                        norm_cfg=self.norm_cfg, bias='auto'))
+        self._tower_caches = [[PackedCache() for _ in range(self.stacked_convs)] for _ in range(2)]
+        self._head_caches = [PackedCache(), PackedCache()]
+        self._scale_cache = PackedCache()
+
+    def _check_levels(self, sizes):
+        if len(sizes) != len(self.strides):
+            raise ValueError(f'{type(self).__name__}: {len(sizes)} pyramid levels for {len(self.strides)} strides')
+
+    def _scales_tensor(self):
+        """the per-level Scale parameters as one (L,) fp32 device tensor, for the kernels (inference: cached)"""
+        ps = [s.scale for s in self.scales]
+        return self._scale_cache.get(ps, lambda: torch.stack([p.detach().float().reshape(()) for p in ps]).contiguous())
+
+    def forward_rows(self, feats):
+        """inference: list of (B,h,w,C) NHWC maps -> (A (rows, >= C+1 | C), R (rows, >= 4 | 5)) fp32 in every compute mode,
+        level-major rows, zero padding columns, and the level sizes"""
+        B = feats[0].shape[0]
+        sizes = [tuple(int(v) for v in f.shape[1:3]) for f in feats]
+        x0 = cat_rows(feats)
+        outs = []
+        for convs, caches, heads, hcache in zip((self.cls_convs, self.reg_convs), self._tower_caches, self._head_groups(),
+                                                self._head_caches):
+            x = x0
+            for m, cache in zip(convs, caches):
+                w = cache.get([m.conv.weight], lambda c=m: pack_weight(c.conv.weight).to(x0.dtype))
+                x, _ = ops.conv2d_nhwc_multi(x, w, B, sizes, None, None, None, False, 1, 1)
+                x = ops.groupnorm_nhwc_multi(x, m.norm.weight.detach(), m.norm.bias.detach(), m.norm.num_groups, B, sizes,
+                                             m.norm.eps, m.with_activation)
+
+            def builder(hs=heads):
+                w = torch.cat([pack_weight(h.weight) for h in hs], 0)
+                b = torch.cat([h.bias.detach().float() for h in hs], 0)
+                pad = -w.shape[0] % 8
+                if pad:
+                    w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
+                    b = torch.cat([b, b.new_zeros(pad)], 0)
+                return w.to(x0.dtype).contiguous(), b.contiguous()
+            w, b = hcache.get([t for h in heads for t in (h.weight, h.bias)], builder)
+            outs.append(ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, False, 1, 1, out_f32=True)[0])
+        return outs[0], outs[1], sizes
+
+    def forward_head_fused(self, feats):
+        """training forward over all levels: (A, R) fp32 with zero padding columns, level-major rows, differentiable, and the
+        level sizes"""
+        from .autograd import ConvNHWCFunction, GroupNormNHWCFunction, conv2d_nhwc_multi_autograd, fused_head_weights
+        B = feats[0].shape[0]
+        sizes = tuple(tuple(int(v) for v in f.shape[1:3]) for f in feats)
+        x0 = cat_rows(feats)
+        mult = 32 if x0.dtype == torch.float32 else 64
+        outs = []
+        for convs, heads in zip((self.cls_convs, self.reg_convs), self._head_groups()):
+            x = x0
+            for m in convs:
+                x = conv2d_nhwc_multi_autograd(x, m.conv.weight, None, B, sizes, 1, 1)
+                x = GroupNormNHWCFunction.apply(x, m.norm.weight, m.norm.bias, m.norm.num_groups, B, sizes, m.norm.eps,
+                                                m.with_activation)
+            w, b = fused_head_weights(heads, mult)
+            outs.append(ConvNHWCFunction.apply(x, w, b, B, sizes, 1, 1, False, False, True))      # fp32 head output
+        return outs[0], outs[1], sizes
+
+    def _towers_host(self, x):
+        """the host mirror of the two towers on torch ops: one (N,C,h,w) map -> (class tower, box tower) outputs"""
+        import torch.nn.functional as F
+        outs = []
+        for convs in (self.cls_convs, self.reg_convs):
+            y = x
+            for m in convs:
+                y = F.relu(F.group_norm(F.conv2d(y, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
+                                        m.norm.bias, m.norm.eps))
+            outs.append(y)
+        return outs
+
+    @staticmethod
+    def _level_views(a, r, sizes, B):
+        """the (A, R) rows of each level as (B, h, w, columns) views"""
+        r0 = 0
+        for (h, w) in sizes:
+            n = B * h * w
+            yield a[r0:r0 + n].view(B, h, w, a.shape[1]), r[r0:r0 + n].view(B, h, w, r.shape[1])
+            r0 += n
+
+    def get_bboxes_rows(self, a, r, layout, scales, sizes, img_metas, cfg=None, rescale=False):
+        """fcos_head.py:329-471 / atss_head.py:372-504 for the whole batch on the device, no host sync: per-candidate max of
+        class sigmoid x centerness sigmoid, per-level top-k, the head's decode (`_decode_candidates`) / clip / rescale with
+        the fan-out to classes, score threshold on the class score, class-aware NMS, max_per_img.  Returns (dets (B, K, 5)
+        zero padded, labels (B, K), num (B,) int32); `self.last_n_valid` as RetinaHead keeps it."""
+        cfg = self.test_cfg if cfg is None else cfg
+        self._check_test_cfg(cfg)
+        self._check_limits(cfg, sizes)
+        B = len(img_metas)
+        scored, raw, r0 = ops.fcos_score(a, r, layout), [], 0
+        for (h, w) in sizes:
+            raw.append(scored[r0:r0 + B * h * w].view(B, h * w))
+            r0 += B * h * w
+        picked = ops.rpn_topk(raw, cfg.nms_pre)         # descending, ties by ascending index, all levels in one launch
+        max_shape = const_rows([m['img_shape'][:2] for m in img_metas], scored)
+        sf = const_rows([list(m['scale_factor']) for m in img_metas], scored) if rescale else None
+        bb, sc, lb, va, nv = self._decode_candidates([p[1] for p in picked], a, r, layout, scales, sizes, max_shape, sf, cfg)
+        self.last_n_valid = nv
+        return self._nms_candidates(bb, sc, lb, va, self.cls_out_channels, cfg)
+
+    def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
+        a, r, sizes = self.forward_rows(list(feats_nhwc))
+        return self.get_bboxes_rows(a, r, self._layout(a, r), self._scales_tensor(), sizes, img_metas, rescale=rescale)
+
+    def _get_bboxes_device(self, outs, img_metas, cfg, rescale):
+        sizes = [tuple(int(v) for v in c.shape[-2:]) for c in outs[0]]
+        a, r = self._rows_from_reference(*outs)
+        return self.get_bboxes_rows(a, r, self._layout(a, r), a.new_ones(len(sizes)), sizes, img_metas, cfg, rescale)
+
+    def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
+        """the device-resident train step of the head: NHWC pyramid -> towers and fused heads over all levels -> the head's
+        assignment and loss kernels; no host read"""
+        self._refuse_ignore(gt_bboxes_ignore)
+        a, r, sizes = self.forward_head_fused(list(feats_nhwc))
+        scales = torch.stack([s.scale.float().reshape(()) for s in self.scales])
+        return self.loss_fused(a, r, scales, sizes, gt_bboxes, gt_labels, img_metas)
+
+    @staticmethod
+    def _norm_hook():
+        """`norm_hook` of the loss kernels' two normalisers: their mean over the ranks (the reference's two reduce_mean
+        calls as one), None when not distributed"""
+        if dist.is_available() and dist.is_initialized():
+            return lambda n2: n2.copy_(reduce_mean(n2))
+        return None
+
+
 # ----------------------------------------------------------------------------- RetinaNet baseline
 @HEADS.register_module()
-class RetinaHead(AnchorHead):
+class RetinaHead(DenseDetHead, AnchorHead):
     """The head of RetinaNet (mmdet/models/dense_heads/retina_head.py:8-114 over anchor_head.py:37-750): two towers of
     `stacked_convs` 3x3 conv + ReLU (`cls_convs.{i}.conv`, `reg_convs.{i}.conv`), then the 3x3 `retina_cls` (A * C sigmoid
     class logits per cell) and `retina_reg` (4A deltas).  Parameter names and shapes are the reference's.  Execution:
@@ -1106,10 +1361,6 @@ class RetinaHead(AnchorHead):
     the whole-batch assignment and the focal / L1 loss -- with no sampler there is nothing to draw on the host, and the
     train step reads nothing back inside the head.  CPU tensors take the reference's per-image chain on torch ops (the
     host mirror the CPU tests compare with the fixture)."""
-
-    supports_tta = False
-    # nms_pre / level limits of the device path (include/brcnn_hip.h: brcnn_rpn_topk)
-    MAX_NMS_PRE, MAX_LEVELS = 4096, 8
 
     def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None, norm_cfg=None,
                  anchor_generator=dict(type='AnchorGenerator', octave_base_scale=4, scales_per_octave=3,
@@ -1162,20 +1413,7 @@ class RetinaHead(AnchorHead):
     def init_weights(self):
         """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name='retina_cls', bias_prob=0.01))
         (retina_head.py:38-46)"""
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.normal_(m.weight, 0, 0.01)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-        nn.init.constant_(self.retina_cls.bias, bias_init_with_prob(0.01))
-
-    def _check_test_cfg(self, cfg):
-        nms = cfg.get('nms', dict(type='nms'))
-        if nms.get('type', 'nms') != 'nms':
-            raise NotImplementedError(f"RetinaHead: test_cfg.nms.type={nms.get('type')!r}; only greedy 'nms' is supported "
-                                      '(no soft-NMS)')
-        if nms.get('class_agnostic', False):
-            raise NotImplementedError('RetinaHead: test_cfg.nms.class_agnostic=True is not supported')
+        self._init_normal(self.retina_cls)
 
     # ------------------------------------------------------------------ forward
     def _towers(self):
@@ -1267,15 +1505,6 @@ class RetinaHead(AnchorHead):
         return v(cls), v(reg)
 
     # ------------------------------------------------------------------ test
-    _base_anchors = ATSSRPNHead._base_anchors
-
-    def _check_limits(self, cfg, sizes):
-        """the sizes the device path serves (brcnn_rpn_topk: k <= 4096, <= 8 levels); anything beyond is refused"""
-        if not 0 < cfg.get('nms_pre', -1) <= self.MAX_NMS_PRE:
-            raise ValueError(f"RetinaHead: nms_pre={cfg.get('nms_pre', -1)} outside (0, {self.MAX_NMS_PRE}] (brcnn_rpn_topk)")
-        if len(sizes) > self.MAX_LEVELS:
-            raise ValueError(f'RetinaHead: {len(sizes)} pyramid levels, at most {self.MAX_LEVELS} are supported')
-
     def get_bboxes_padded(self, cls_nhwc, reg_nhwc, img_metas, cfg=None, rescale=False, cls_rows=None):
         """anchor_head.py:507-750 for the whole batch on the device, no host sync: per-anchor max sigmoid, per-level top-k,
         decode / clip / rescale with the fan-out to classes, score threshold, class-aware NMS, max_per_img.  Inputs are the
@@ -1308,27 +1537,6 @@ class RetinaHead(AnchorHead):
         self.last_n_valid = nv
         return self._nms_candidates(bb, sc, lb, va, C, cfg)
 
-    @staticmethod
-    def _nms_candidates(bb, sc, lb, va, C, cfg):
-        """class-aware NMS + max_per_img of the (level, pick, class) candidate slots of a dense head (shared with FCOSHead)"""
-        B = bb.shape[0]
-        nms_cfg = dict(cfg.nms)
-        nms_cfg.pop('type', None)
-        T = sc.shape[1] // C
-        # mmcv's batched_nms changes branch at split_thr by the number of candidates that SURVIVE score_thr (n_valid), which
-        # only the device knows here; the branch is chosen by the slot count T * C instead, so no host read is needed.
-        # Both branches keep the same boxes in the same order (the coordinate offsets already isolate the classes), with
-        # one limit: where the reference takes the offset form and this code the per-class one (or the reverse), the
-        # IoUs are computed on un-offset resp. offset fp32 coordinates and can differ in the last ulp -- a pair whose IoU
-        # sits within an ulp of iou_threshold may then be decided differently.
-        if T * C >= nms_cfg.get('split_thr', 10000):
-            # the per-class branch: class-major slots, one segmented NMS launch over (image, class)
-            from .postprocess import batched_nms_images_by_level
-            cm = lambda t: t.view(B, T, C, *t.shape[2:]).transpose(1, 2).reshape(B, C * T, *t.shape[2:]).contiguous()   # noqa: E731
-            return batched_nms_images_by_level(cm(bb), cm(sc), cm(lb), cm(va), [T] * C, nms_cfg['iou_threshold'],
-                                               cfg.max_per_img, nms_cfg.get('offset', 0), return_ids=True)
-        return batched_nms_images(bb, sc, lb, va, nms_cfg['iou_threshold'], cfg.max_per_img, nms_cfg.get('offset', 0))
-
     def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
         yc, yr, sizes = self.forward_rows(list(feats_nhwc))
         B = feats_nhwc[0].shape[0]
@@ -1339,22 +1547,14 @@ class RetinaHead(AnchorHead):
         """reference signature (anchor_head.py:507-587): per-level (N,A*C,h,w) / (N,4A,h,w) -> per image (dets (k,5),
         labels (k,)).  Device tensors take `get_bboxes_padded`; CPU tensors the reference's chain on torch ops, with the
         caller's `batched_nms` (this package's NMS is a device kernel)."""
-        if not with_nms:
-            raise NotImplementedError('RetinaHead: with_nms=False is not supported')
-        assert len(cls_scores) == len(bbox_preds)
-        if cls_scores[0].is_cuda:
-            f = lambda lst: [to_nhwc(t.detach()).float().contiguous() for t in lst]  # noqa: E731
-            det, lab, num = self.get_bboxes_padded(f(cls_scores), f(bbox_preds), img_metas, cfg, rescale)
-            num = num.tolist()   # the one host sync
-            return [(det[i, :num[i]], lab[i, :num[i]]) for i in range(len(img_metas))]
-        return self._get_bboxes_host(cls_scores, bbox_preds, img_metas, cfg, rescale, batched_nms)
+        return self._get_bboxes((cls_scores, bbox_preds), img_metas, cfg, rescale, with_nms, batched_nms)
+
+    def _get_bboxes_device(self, outs, img_metas, cfg, rescale):
+        cls, reg = ([to_nhwc(t).float().contiguous() for t in o] for o in outs)
+        return self.get_bboxes_padded(cls, reg, img_metas, cfg, rescale)
 
     def _get_bboxes_host(self, cls_scores, bbox_preds, img_metas, cfg, rescale, batched_nms):
         from .core import delta2bbox
-        cfg = self.test_cfg if cfg is None else cfg
-        self._check_test_cfg(cfg)
-        if batched_nms is None:
-            batched_nms = ops.batched_nms
         B, C = cls_scores[0].shape[0], self.cls_out_channels
         anchors_l = self.anchor_generator.grid_anchors([c.shape[-2:] for c in cls_scores], cls_scores[0].device)
         nms_pre = cfg.get('nms_pre', -1)
@@ -1371,47 +1571,16 @@ class RetinaHead(AnchorHead):
                 boxes_l.append(delta2bbox(anchors, d, self.bbox_coder.means, self.bbox_coder.stds,
                                           max_shape=tuple(img_metas[b]['img_shape'][:2])))
                 scores_l.append(s)
-            boxes, scores = torch.cat(boxes_l), torch.cat(scores_l)
-            if rescale:
-                boxes = boxes / boxes.new_tensor(img_metas[b]['scale_factor'])
-            keep = (scores > cfg.score_thr).reshape(-1)
-            inds = keep.nonzero(as_tuple=False).reshape(-1)
-            labels = torch.arange(C, dtype=torch.long).repeat(scores.shape[0])[inds]
-            cb, cs = boxes[:, None].expand(-1, C, 4).reshape(-1, 4)[inds], scores.reshape(-1)[inds]
-            if cb.numel() == 0:
-                out.append((torch.cat([cb, cs[:, None]], -1), labels))
-                continue
-            dets, kept = batched_nms(cb.contiguous(), cs.contiguous(), labels, dict(cfg.nms))
-            if cfg.max_per_img > 0:
-                dets, kept = dets[:cfg.max_per_img], kept[:cfg.max_per_img]
-            out.append((dets, labels[kept]))
+            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), None, img_metas[b], cfg, rescale, batched_nms))
         return out
 
-    def simple_test(self, feats, img_metas, rescale=False, batched_nms=None):
-        """dense_test_mixins.py:17-37: list of (N,C,h,w) -> per image (dets (k,5), labels (k,))"""
-        return self.get_bboxes(*self(feats), img_metas, rescale=rescale, batched_nms=batched_nms)
-
-    def aug_test(self, feats, img_metas, rescale=False):
-        raise NotImplementedError('RetinaHead has no test-time augmentation')
-
     # ------------------------------------------------------------------ train
-    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
-        """base_dense_head.py:48-78"""
-        outs = self(x)
-        losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
-        if proposal_cfg is None:
-            return losses
-        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
-
     def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
         """the device-resident train step of the head: NHWC pyramid -> towers and heads over all levels -> whole-batch
         assignment and loss kernels; no host read"""
-        if gt_bboxes_ignore is not None:
-            raise NotImplementedError('RetinaHead: gt_bboxes_ignore is not supported on the device path')
+        self._refuse_ignore(gt_bboxes_ignore)
         yc, yr, sizes = self.forward_head_fused(list(feats_nhwc))
         return self.loss_fused(yc, yr, sizes, gt_bboxes, gt_labels, img_metas)
-
-    loss_single = RPNHead.loss_single
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
         """anchor_head.py:423-497.  Device tensors go to the HIP kernels (`loss_fused`); CPU tensors take the reference's
@@ -1420,8 +1589,7 @@ class RetinaHead(AnchorHead):
         assert len(featmap_sizes) == self.anchor_generator.num_levels
         device = cls_scores[0].device
         if device.type == 'cuda':
-            if gt_bboxes_ignore is not None:
-                raise NotImplementedError('RetinaHead: gt_bboxes_ignore is not supported on the device path')
+            self._refuse_ignore(gt_bboxes_ignore)
             sizes = tuple(tuple(int(v) for v in s_) for s_ in featmap_sizes)
             rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float().contiguous()   # noqa: E731
             return self.loss_fused(rows(cls_scores), rows(bbox_preds), sizes, gt_bboxes, gt_labels, img_metas)
@@ -1446,9 +1614,6 @@ class RetinaHead(AnchorHead):
         return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)
 
     # ------------------------------------------------------------------ device-resident train step
-    _anchor_table = ATSSRPNHead._anchor_table
-    assign_targets_device = ATSSRPNHead.assign_targets_device
-
     def loss_fused(self, ycls, yreg, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
         """AnchorHead.loss on the head outputs of all levels (rows, >= A*C) / (rows, >= 4A): whole-batch assignment, then
         the loss kernels -- targets, the positive count and its reciprocal are formed on the device, nothing is read back.
@@ -1481,7 +1646,7 @@ def distance2bbox(points, distance):
 
 
 @HEADS.register_module()
-class FCOSHead(nn.Module):
+class FCOSHead(GNTowerHead, nn.Module):
     """The head of FCOS (mmdet/models/dense_heads/fcos_head.py:18-649 over anchor_free_head.py:16-330): two towers of
     `stacked_convs` 3x3 conv + GroupNorm + ReLU (`cls_convs.{i}.{conv,gn}`, `reg_convs.{i}.{conv,gn}`), then the 3x3
     `conv_cls` (C sigmoid class logits per cell), `conv_reg` (4 distances) and `conv_centerness`, and one `Scale` per
@@ -1494,9 +1659,6 @@ class FCOSHead(nn.Module):
     assignment and the focal / centerness-weighted IoU / centerness loss, all on the device -- inference reads the host
     once (when the results leave), the head's train step never.  CPU tensors take the reference's chain on torch ops (the
     host mirror the CPU tests compare with the fixture)."""
-
-    supports_tta = False
-    MAX_NMS_PRE, MAX_LEVELS = 4096, 8        # brcnn_rpn_topk
 
     def __init__(self, num_classes, in_channels, feat_channels=256, stacked_convs=4, strides=(4, 8, 16, 32, 64),
                  regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, INF)), center_sampling=False,
@@ -1550,18 +1712,10 @@ class FCOSHead(nn.Module):
         if self.test_cfg:
             self._check_test_cfg(self.test_cfg)
         self._init_layers()
-        self._tower_caches = [[PackedCache() for _ in range(stacked_convs)] for _ in range(2)]
-        self._head_caches = [PackedCache(), PackedCache()]
-        self._scale_cache = PackedCache()
         self.init_weights()
 
     def _init_layers(self):
-        self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            for convs in (self.cls_convs, self.reg_convs):
-                convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
-                                        norm_cfg=self.norm_cfg, bias='auto'))
+        self._init_towers()
         self.conv_cls = nn.Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
         self.conv_reg = nn.Conv2d(self.feat_channels, 4, 3, padding=1)
         self.conv_centerness = nn.Conv2d(self.feat_channels, 1, 3, padding=1)
@@ -1570,20 +1724,7 @@ class FCOSHead(nn.Module):
     def init_weights(self):
         """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name='conv_cls', bias_prob=0.01))
         (fcos_head.py:80-88)"""
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.normal_(m.weight, 0, 0.01)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-        nn.init.constant_(self.conv_cls.bias, bias_init_with_prob(0.01))
-
-    def _check_test_cfg(self, cfg):
-        nms = cfg.get('nms', dict(type='nms'))
-        if nms.get('type', 'nms') != 'nms':
-            raise NotImplementedError(f"FCOSHead: test_cfg.nms.type={nms.get('type')!r}; only greedy 'nms' is supported "
-                                      '(no soft-NMS)')
-        if nms.get('class_agnostic', False):
-            raise NotImplementedError('FCOSHead: test_cfg.nms.class_agnostic=True is not supported')
+        self._init_normal(self.conv_cls)
 
     # ------------------------------------------------------------------ forward
     def _head_groups(self):
@@ -1597,65 +1738,11 @@ class FCOSHead(nn.Module):
         return ops.FcosLayout(a, r, C, 0, 0, self.centerness_on_reg, 4 if self.centerness_on_reg else C,
                               self.norm_on_bbox, type(self.loss_bbox).__name__ == 'GIoULoss')
 
-    def _scales_tensor(self):
-        """the per-level Scale parameters as one (L,) fp32 device tensor, for the kernels (inference: cached)"""
-        ps = [s.scale for s in self.scales]
-        return self._scale_cache.get(ps, lambda: torch.stack([p.detach().float().reshape(()) for p in ps]).contiguous())
-
-    def forward_rows(self, feats):
-        """inference: list of (B,h,w,C) NHWC maps -> (A (rows, >= C+1 | C), R (rows, >= 4 | 5)) fp32 in every compute mode,
-        level-major rows, zero padding columns, and the level sizes"""
-        B = feats[0].shape[0]
-        sizes = [tuple(int(v) for v in f.shape[1:3]) for f in feats]
-        x0 = cat_rows(feats)
-        outs = []
-        for convs, caches, heads, hcache in zip((self.cls_convs, self.reg_convs), self._tower_caches, self._head_groups(),
-                                                self._head_caches):
-            x = x0
-            for m, cache in zip(convs, caches):
-                w = cache.get([m.conv.weight], lambda c=m: pack_weight(c.conv.weight).to(x0.dtype))
-                x, _ = ops.conv2d_nhwc_multi(x, w, B, sizes, None, None, None, False, 1, 1)
-                x = ops.groupnorm_nhwc_multi(x, m.norm.weight.detach(), m.norm.bias.detach(), m.norm.num_groups, B, sizes,
-                                             m.norm.eps, m.with_activation)
-
-            def builder(hs=heads):
-                w = torch.cat([pack_weight(h.weight) for h in hs], 0)
-                b = torch.cat([h.bias.detach().float() for h in hs], 0)
-                pad = -w.shape[0] % 8
-                if pad:
-                    w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
-                    b = torch.cat([b, b.new_zeros(pad)], 0)
-                return w.to(x0.dtype).contiguous(), b.contiguous()
-            w, b = hcache.get([t for h in heads for t in (h.weight, h.bias)], builder)
-            outs.append(ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, False, 1, 1, out_f32=True)[0])
-        return outs[0], outs[1], sizes
-
-    def forward_head_fused(self, feats):
-        """training forward over all levels: (A, R) fp32 with zero padding columns, level-major rows, differentiable, and the
-        level sizes"""
-        from .autograd import ConvNHWCFunction, GroupNormNHWCFunction, conv2d_nhwc_multi_autograd, fused_head_weights
-        B = feats[0].shape[0]
-        sizes = tuple(tuple(int(v) for v in f.shape[1:3]) for f in feats)
-        x0 = cat_rows(feats)
-        mult = 32 if x0.dtype == torch.float32 else 64
-        outs = []
-        for convs, heads in zip((self.cls_convs, self.reg_convs), self._head_groups()):
-            x = x0
-            for m in convs:
-                x = conv2d_nhwc_multi_autograd(x, m.conv.weight, None, B, sizes, 1, 1)
-                x = GroupNormNHWCFunction.apply(x, m.norm.weight, m.norm.bias, m.norm.num_groups, B, sizes, m.norm.eps,
-                                                m.with_activation)
-            w, b = fused_head_weights(heads, mult)
-            outs.append(ConvNHWCFunction.apply(x, w, b, B, sizes, 1, 1, False, False, True))      # fp32 head output
-        return outs[0], outs[1], sizes
-
     def _decode_rows(self, a, r, sizes, B, training):
         """(A, R) rows -> the reference's per-level NHWC (cls, bbox_pred AFTER scale / exp | relu [* stride], centerness)"""
         C, co = self.cls_out_channels, (4 if self.centerness_on_reg else self.cls_out_channels)
-        cls, reg, ctr, r0 = [], [], [], 0
-        for l, (h, w) in enumerate(sizes):
-            n = B * h * w
-            va, vr = a[r0:r0 + n].view(B, h, w, a.shape[1]), r[r0:r0 + n].view(B, h, w, r.shape[1])
+        cls, reg, ctr = [], [], []
+        for l, (va, vr) in enumerate(self._level_views(a, r, sizes, B)):
             d = vr[..., :4] * self.scales[l].scale
             if self.norm_on_bbox:
                 d = d.relu()
@@ -1665,7 +1752,6 @@ class FCOSHead(nn.Module):
             cls.append(va[..., :C])
             reg.append(d)
             ctr.append((vr if self.centerness_on_reg else va)[..., co:co + 1])
-            r0 += n
         return cls, reg, ctr
 
     def forward_nhwc(self, feats):
@@ -1688,13 +1774,7 @@ class FCOSHead(nn.Module):
             import torch.nn.functional as F
             cls, reg, ctr = [], [], []
             for x, scale, stride in zip(feats, self.scales, self.strides):
-                c = r = x
-                for m in self.cls_convs:
-                    c = F.relu(F.group_norm(F.conv2d(c, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
-                                            m.norm.bias, m.norm.eps))
-                for m in self.reg_convs:
-                    r = F.relu(F.group_norm(F.conv2d(r, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
-                                            m.norm.bias, m.norm.eps))
+                c, r = self._towers_host(x)
                 cls.append(F.conv2d(c, self.conv_cls.weight, self.conv_cls.bias, padding=1))
                 ctr.append(F.conv2d(r if self.centerness_on_reg else c, self.conv_centerness.weight,
                                     self.conv_centerness.bias, padding=1))
@@ -1719,38 +1799,10 @@ class FCOSHead(nn.Module):
             pts.append(torch.stack((xs.reshape(-1) * s, ys.reshape(-1) * s), dim=-1) + s // 2)
         return pts
 
-    def _check_limits(self, cfg, sizes):
-        if not 0 < cfg.get('nms_pre', -1) <= self.MAX_NMS_PRE:
-            raise ValueError(f"FCOSHead: nms_pre={cfg.get('nms_pre', -1)} outside (0, {self.MAX_NMS_PRE}] (brcnn_rpn_topk)")
-        if len(sizes) != len(self.strides):
-            raise ValueError(f'FCOSHead: {len(sizes)} pyramid levels for {len(self.strides)} strides')
+    def _decode_candidates(self, picked, a, r, layout, scales, sizes, max_shape, sf, cfg):
+        return ops.fcos_decode_levels(picked, a, r, layout, scales, sizes, self.strides, max_shape, sf, cfg.score_thr)
 
-    def get_bboxes_rows(self, a, r, layout, scales, sizes, img_metas, cfg=None, rescale=False):
-        """fcos_head.py:329-471 for the whole batch on the device, no host sync: per-point max of class sigmoid x centerness
-        sigmoid, per-level top-k, decode / clip / rescale with the fan-out to classes, score threshold on the class score,
-        class-aware NMS, max_per_img.  Returns (dets (B, K, 5) zero padded, labels (B, K), num (B,) int32);
-        `self.last_n_valid` as RetinaHead keeps it."""
-        cfg = self.test_cfg if cfg is None else cfg
-        self._check_test_cfg(cfg)
-        self._check_limits(cfg, sizes)
-        B = len(img_metas)
-        scored, raw, r0 = ops.fcos_score(a, r, layout), [], 0
-        for (h, w) in sizes:
-            raw.append(scored[r0:r0 + B * h * w].view(B, h * w))
-            r0 += B * h * w
-        picked = ops.rpn_topk(raw, cfg.nms_pre)         # descending, ties by ascending index, all levels in one launch
-        max_shape = const_rows([m['img_shape'][:2] for m in img_metas], scored)
-        sf = const_rows([list(m['scale_factor']) for m in img_metas], scored) if rescale else None
-        bb, sc, lb, va, nv = ops.fcos_decode_levels([p[1] for p in picked], a, r, layout, scales, sizes, self.strides,
-                                                    max_shape, sf, cfg.score_thr)
-        self.last_n_valid = nv
-        return RetinaHead._nms_candidates(bb, sc, lb, va, self.cls_out_channels, cfg)
-
-    def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
-        a, r, sizes = self.forward_rows(list(feats_nhwc))
-        return self.get_bboxes_rows(a, r, self._layout(a, r), self._scales_tensor(), sizes, img_metas, rescale=rescale)
-
-    def _rows_from_reference(self, cls_scores, bbox_preds, centernesses, training):
+    def _rows_from_reference(self, cls_scores, bbox_preds, centernesses, training=False):
         """the reference-signature tensors (decoded distances) as the kernels' (A, R) rows with unit scales: the raw value
         is log(d), or under norm_on_bbox d itself (test time: d / stride, exact for power-of-two strides; a distance
         the relu left at exactly 0 takes no gradient, as through the relu)"""
@@ -1769,24 +1821,9 @@ class FCOSHead(nn.Module):
         """reference signature (fcos_head.py:263-327): per-level (N,C,h,w) / (N,4,h,w) / (N,1,h,w) -> per image (dets (k,5),
         labels (k,)).  Device tensors take `get_bboxes_rows`; CPU tensors the reference's chain on torch ops, with the
         caller's `batched_nms` (this package's NMS is a device kernel)."""
-        if not with_nms:
-            raise NotImplementedError('FCOSHead: with_nms=False is not supported')
-        assert len(cls_scores) == len(bbox_preds) == len(centernesses)
-        if cls_scores[0].is_cuda:
-            sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
-            a, r = self._rows_from_reference([t.detach() for t in cls_scores], [t.detach() for t in bbox_preds],
-                                             [t.detach() for t in centernesses], False)
-            det, lab, num = self.get_bboxes_rows(a, r, self._layout(a, r), a.new_ones(len(sizes)), sizes, img_metas, cfg,
-                                                 rescale)
-            num = num.tolist()   # the one host sync
-            return [(det[i, :num[i]], lab[i, :num[i]]) for i in range(len(img_metas))]
-        return self._get_bboxes_host(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms)
+        return self._get_bboxes((cls_scores, bbox_preds, centernesses), img_metas, cfg, rescale, with_nms, batched_nms)
 
     def _get_bboxes_host(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms):
-        cfg = self.test_cfg if cfg is None else cfg
-        self._check_test_cfg(cfg)
-        if batched_nms is None:
-            batched_nms = ops.batched_nms
         B, C = cls_scores[0].shape[0], self.cls_out_channels
         points_l = self.get_points([c.shape[-2:] for c in cls_scores], bbox_preds[0].dtype, bbox_preds[0].device)
         nms_pre = cfg.get('nms_pre', -1)
@@ -1809,48 +1846,11 @@ class FCOSHead(nn.Module):
                 boxes_l.append(bx)
                 scores_l.append(s)
                 ctr_l.append(ct)
-            boxes, scores, ctrs = torch.cat(boxes_l), torch.cat(scores_l), torch.cat(ctr_l)
-            if rescale:
-                boxes = boxes / boxes.new_tensor(img_metas[b]['scale_factor'])
-            keep = (scores > cfg.score_thr).reshape(-1)          # before the centerness factor (bbox_nms.py:48-58)
-            inds = keep.nonzero(as_tuple=False).reshape(-1)
-            labels = torch.arange(C, dtype=torch.long).repeat(scores.shape[0])[inds]
-            cb = boxes[:, None].expand(-1, C, 4).reshape(-1, 4)[inds]
-            cs = (scores * ctrs[:, None]).reshape(-1)[inds]
-            if cb.numel() == 0:
-                out.append((torch.cat([cb, cs[:, None]], -1), labels))
-                continue
-            dets, kept = batched_nms(cb.contiguous(), cs.contiguous(), labels, dict(cfg.nms))
-            if cfg.max_per_img > 0:
-                dets, kept = dets[:cfg.max_per_img], kept[:cfg.max_per_img]
-            out.append((dets, labels[kept]))
+            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), torch.cat(ctr_l), img_metas[b], cfg, rescale,
+                                      batched_nms))
         return out
 
-    def simple_test(self, feats, img_metas, rescale=False, batched_nms=None):
-        """dense_test_mixins.py:17-37: list of (N,C,h,w) -> per image (dets (k,5), labels (k,))"""
-        return self.get_bboxes(*self(feats), img_metas, rescale=rescale, batched_nms=batched_nms)
-
-    def aug_test(self, feats, img_metas, rescale=False):
-        raise NotImplementedError('FCOSHead has no test-time augmentation')
-
     # ------------------------------------------------------------------ train
-    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
-        """base_dense_head.py:48-78"""
-        outs = self(x)
-        losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
-        if proposal_cfg is None:
-            return losses
-        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
-
-    def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
-        """the device-resident train step of the head: NHWC pyramid -> towers and fused heads over all levels -> point
-        assignment and loss kernels; no host read"""
-        if gt_bboxes_ignore is not None:
-            raise NotImplementedError('FCOSHead: gt_bboxes_ignore is not supported on the device path')
-        a, r, sizes = self.forward_head_fused(list(feats_nhwc))
-        scales = torch.stack([s.scale.float().reshape(()) for s in self.scales])
-        return self.loss_fused(a, r, scales, sizes, gt_bboxes, gt_labels, img_metas)
-
     def loss_fused(self, a, r, scales, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
         """FCOSHead.loss on the fused head outputs of all levels: whole-batch point assignment, then the loss kernels --
         targets and both normalisers are formed on the device (averaged over ranks there when distributed), nothing is
@@ -1865,10 +1865,8 @@ class FCOSHead(nn.Module):
         meta = train_ops.FcosLossMeta(B, sizes, self.strides, self.cls_out_channels, offs, self.loss_cls.gamma,
                                       self.loss_cls.alpha, self.loss_bbox.eps if giou else 1e-6, self.loss_bbox.eps,
                                       self.loss_cls.loss_weight, self.loss_bbox.loss_weight, self.loss_centerness.loss_weight)
-        hook = None
-        if dist.is_available() and dist.is_initialized():
-            hook = lambda n2: n2.copy_(reduce_mean(n2))     # noqa: E731  (the reference's two reduce_mean calls as one)
-        losses, coef, norm2 = train_ops.fcos_loss(a, r, scales, gt_inds, gts, labels, self._layout(a, r), meta, hook)
+        losses, coef, norm2 = train_ops.fcos_loss(a, r, scales, gt_inds, gts, labels, self._layout(a, r), meta,
+                                                  self._norm_hook())
         self.last_targets = (gt_inds, coef, norm2)
         return dict(loss_cls=losses[0], loss_bbox=losses[1], loss_centerness=losses[2])
 
@@ -1933,8 +1931,7 @@ class FCOSHead(nn.Module):
         featmap_sizes = [tuple(int(v) for v in f.size()[-2:]) for f in cls_scores]
         device = cls_scores[0].device
         if device.type == 'cuda':
-            if gt_bboxes_ignore is not None:
-                raise NotImplementedError('FCOSHead: gt_bboxes_ignore is not supported on the device path')
+            self._refuse_ignore(gt_bboxes_ignore)
             a, r = self._rows_from_reference(cls_scores, bbox_preds, centernesses, True)
             return self.loss_fused(a, r, a.new_ones(len(featmap_sizes)), featmap_sizes, gt_bboxes, gt_labels, img_metas)
         points = self.get_points(featmap_sizes, bbox_preds[0].dtype, device)
@@ -1962,20 +1959,19 @@ class FCOSHead(nn.Module):
 
 
 @HEADS.register_module()
-class ATSSHead(AnchorHead):
+class ATSSHead(GNTowerHead, AnchorHead):
     """The head of ATSS (mmdet/models/dense_heads/atss_head.py:14-686 over anchor_head.py): FCOSHead's two GN towers
     (`cls_convs.{i}.{conv,gn}`, `reg_convs.{i}.{conv,gn}`), then the 3x3 `atss_cls` (C sigmoid class logits), `atss_reg` (4
     deltas of the cell's ONE anchor, through the level's `scales.{l}.scale`) and `atss_centerness` on the box tower.
     Parameter names and shapes are the reference's.  Execution is FCOSHead's with its `centerness_on_reg` grouping -- the
-    tower and fused-head code is shared, not copied: A = [cls C | pad], R = [reg 4 | ctr 1 | pad], fp32, raw -- and the
-    kernels of csrc/atss_head.hip apply the Scale themselves: scoring (`brcnn_fcos_score`), top-k, anchor decode + class
+    tower and fused-head code is GNTowerHead's, the base of both heads: A = [cls C | pad], R = [reg 4 | ctr 1 | pad], fp32,
+    raw -- and the kernels of csrc/atss_head.hip apply the Scale themselves: scoring (`brcnn_fcos_score`), top-k, anchor decode + class
     fan-out and the NMS of the whole batch; in training the adaptive assignment (`brcnn_atss_assign`: k nearest anchors
     per level, mean + std IoU threshold, centre-inside test, best-IoU resolution) and the focal / centerness-weighted GIoU
     / centerness loss with the targets formed in the kernel.  Inference reads the host once, the head's train step never.
     CPU tensors take the reference's chain on torch ops (the host mirror the CPU tests compare with the fixture)."""
 
-    supports_tta = False
-    MAX_NMS_PRE, MAX_LEVELS, MAX_TOPK = 4096, 8, 16        # brcnn_rpn_topk; brcnn_atss_assign
+    MAX_TOPK = 16        # brcnn_atss_assign
 
     def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
                  norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
@@ -2039,18 +2035,10 @@ class ATSSHead(AnchorHead):
         if self.test_cfg:
             self._check_test_cfg(self.test_cfg)
         self.strides = [int(s[0]) for s in self.anchor_generator.strides]
-        self._tower_caches = [[PackedCache() for _ in range(stacked_convs)] for _ in range(2)]
-        self._head_caches = [PackedCache(), PackedCache()]
-        self._scale_cache = PackedCache()
         self.init_weights()
 
     def _init_layers(self):
-        self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            for convs in (self.cls_convs, self.reg_convs):
-                convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
-                                        norm_cfg=self.norm_cfg))
+        self._init_towers()
         self.atss_cls = nn.Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 3, padding=1)
         self.atss_reg = nn.Conv2d(self.feat_channels, self.num_anchors * 4, 3, padding=1)
         self.atss_centerness = nn.Conv2d(self.feat_channels, self.num_anchors * 1, 3, padding=1)
@@ -2059,29 +2047,12 @@ class ATSSHead(AnchorHead):
     def init_weights(self):
         """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name='atss_cls', bias_prob=0.01))
         (atss_head.py:35-43)"""
-        for m in self.modules():
-            if isinstance(m, nn.Conv2d):
-                nn.init.normal_(m.weight, 0, 0.01)
-                if m.bias is not None:
-                    nn.init.constant_(m.bias, 0)
-        nn.init.constant_(self.atss_cls.bias, bias_init_with_prob(0.01))
-
-    def _check_test_cfg(self, cfg):
-        nms = cfg.get('nms', dict(type='nms'))
-        if nms.get('type', 'nms') != 'nms':
-            raise NotImplementedError(f"ATSSHead: test_cfg.nms.type={nms.get('type')!r}; only greedy 'nms' is supported "
-                                      '(no soft-NMS)')
-        if nms.get('class_agnostic', False):
-            raise NotImplementedError('ATSSHead: test_cfg.nms.class_agnostic=True is not supported')
+        self._init_normal(self.atss_cls)
 
     # ------------------------------------------------------------------ forward
     def _head_groups(self):
         """FCOSHead's `centerness_on_reg` grouping: the centerness rides on the box tower's fused head conv"""
         return (self.atss_cls,), (self.atss_reg, self.atss_centerness)
-
-    forward_rows = FCOSHead.forward_rows
-    forward_head_fused = FCOSHead.forward_head_fused
-    _scales_tensor = FCOSHead._scales_tensor
 
     def _layout(self, a, r):
         return ops.FcosLayout(a, r, self.cls_out_channels, 0, 0, True, 4, False, True)
@@ -2095,14 +2066,11 @@ class ATSSHead(AnchorHead):
     def _split_rows(self, a, r, sizes, B):
         """(A, R) rows -> the reference's per-level NHWC (cls, bbox_pred AFTER the Scale, centerness)"""
         C = self.cls_out_channels
-        cls, reg, ctr, r0 = [], [], [], 0
-        for l, (h, w) in enumerate(sizes):
-            n = B * h * w
-            va, vr = a[r0:r0 + n].view(B, h, w, a.shape[1]), r[r0:r0 + n].view(B, h, w, r.shape[1])
+        cls, reg, ctr = [], [], []
+        for l, (va, vr) in enumerate(self._level_views(a, r, sizes, B)):
             cls.append(va[..., :C])
             reg.append(vr[..., :4] * self.scales[l].scale)
             ctr.append(vr[..., 4:5])
-            r0 += n
         return cls, reg, ctr
 
     def forward_nhwc(self, feats):
@@ -2125,13 +2093,7 @@ class ATSSHead(AnchorHead):
             import torch.nn.functional as F
             cls, reg, ctr = [], [], []
             for x, scale in zip(feats, self.scales):
-                c = r = x
-                for m in self.cls_convs:
-                    c = F.relu(F.group_norm(F.conv2d(c, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
-                                            m.norm.bias, m.norm.eps))
-                for m in self.reg_convs:
-                    r = F.relu(F.group_norm(F.conv2d(r, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
-                                            m.norm.bias, m.norm.eps))
+                c, r = self._towers_host(x)
                 cls.append(F.conv2d(c, self.atss_cls.weight, self.atss_cls.bias, padding=1))
                 reg.append((F.conv2d(r, self.atss_reg.weight, self.atss_reg.bias, padding=1) * scale.scale).float())
                 ctr.append(F.conv2d(r, self.atss_centerness.weight, self.atss_centerness.bias, padding=1))
@@ -2140,37 +2102,9 @@ class ATSSHead(AnchorHead):
         return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
 
     # ------------------------------------------------------------------ test
-    def _check_limits(self, cfg, sizes):
-        if not 0 < cfg.get('nms_pre', -1) <= self.MAX_NMS_PRE:
-            raise ValueError(f"ATSSHead: nms_pre={cfg.get('nms_pre', -1)} outside (0, {self.MAX_NMS_PRE}] (brcnn_rpn_topk)")
-        if len(sizes) != len(self.strides):
-            raise ValueError(f'ATSSHead: {len(sizes)} pyramid levels for {len(self.strides)} strides')
-
-    def get_bboxes_rows(self, a, r, layout, scales, sizes, img_metas, cfg=None, rescale=False):
-        """atss_head.py:372-504 for the whole batch on the device, no host sync: per-anchor max of class sigmoid x centerness
-        sigmoid, per-level top-k, anchor decode / clip / rescale with the fan-out to classes, score threshold on the class
-        score, class-aware NMS, max_per_img.  Returns (dets (B, K, 5) zero padded, labels (B, K), num (B,) int32);
-        `self.last_n_valid` as RetinaHead keeps it."""
-        cfg = self.test_cfg if cfg is None else cfg
-        self._check_test_cfg(cfg)
-        self._check_limits(cfg, sizes)
-        B = len(img_metas)
-        scored, raw, r0 = ops.fcos_score(a, r, layout), [], 0
-        for (h, w) in sizes:
-            raw.append(scored[r0:r0 + B * h * w].view(B, h * w))
-            r0 += B * h * w
-        picked = ops.rpn_topk(raw, cfg.nms_pre)         # descending, ties by ascending index, all levels in one launch
-        max_shape = const_rows([m['img_shape'][:2] for m in img_metas], scored)
-        sf = const_rows([list(m['scale_factor']) for m in img_metas], scored) if rescale else None
-        bb, sc, lb, va, nv = ops.atss_decode_levels([p[1] for p in picked], a, r, layout, scales, sizes, self.strides,
-                                                    self._base_table(), max_shape, sf, self.bbox_coder.means,
-                                                    self.bbox_coder.stds, cfg.score_thr)
-        self.last_n_valid = nv
-        return RetinaHead._nms_candidates(bb, sc, lb, va, self.cls_out_channels, cfg)
-
-    def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
-        a, r, sizes = self.forward_rows(list(feats_nhwc))
-        return self.get_bboxes_rows(a, r, self._layout(a, r), self._scales_tensor(), sizes, img_metas, rescale=rescale)
+    def _decode_candidates(self, picked, a, r, layout, scales, sizes, max_shape, sf, cfg):
+        return ops.atss_decode_levels(picked, a, r, layout, scales, sizes, self.strides, self._base_table(), max_shape, sf,
+                                      self.bbox_coder.means, self.bbox_coder.stds, cfg.score_thr)
 
     @staticmethod
     def _rows_from_reference(cls_scores, bbox_preds, centernesses):
@@ -2183,25 +2117,10 @@ class ATSSHead(AnchorHead):
         """reference signature (atss_head.py:312-370): per-level (N,C,h,w) / (N,4,h,w) / (N,1,h,w) -> per image (dets (k,5),
         labels (k,)).  Device tensors take `get_bboxes_rows`; CPU tensors the reference's chain on torch ops, with the
         caller's `batched_nms` (this package's NMS is a device kernel)."""
-        if not with_nms:
-            raise NotImplementedError('ATSSHead: with_nms=False is not supported')
-        assert len(cls_scores) == len(bbox_preds) == len(centernesses)
-        if cls_scores[0].is_cuda:
-            sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
-            a, r = self._rows_from_reference([t.detach() for t in cls_scores], [t.detach() for t in bbox_preds],
-                                             [t.detach() for t in centernesses])
-            det, lab, num = self.get_bboxes_rows(a, r, self._layout(a, r), a.new_ones(len(sizes)), sizes, img_metas, cfg,
-                                                 rescale)
-            num = num.tolist()   # the one host sync
-            return [(det[i, :num[i]], lab[i, :num[i]]) for i in range(len(img_metas))]
-        return self._get_bboxes_host(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms)
+        return self._get_bboxes((cls_scores, bbox_preds, centernesses), img_metas, cfg, rescale, with_nms, batched_nms)
 
     def _get_bboxes_host(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms):
         from .core import delta2bbox
-        cfg = self.test_cfg if cfg is None else cfg
-        self._check_test_cfg(cfg)
-        if batched_nms is None:
-            batched_nms = ops.batched_nms
         B, C = cls_scores[0].shape[0], self.cls_out_channels
         anchors_l = self.anchor_generator.grid_anchors([c.shape[-2:] for c in cls_scores], cls_scores[0].device)
         nms_pre = cfg.get('nms_pre', -1)
@@ -2220,48 +2139,11 @@ class ATSSHead(AnchorHead):
                                           max_shape=tuple(img_metas[b]['img_shape'][:2])))
                 scores_l.append(s)
                 ctr_l.append(ct)
-            boxes, scores, ctrs = torch.cat(boxes_l), torch.cat(scores_l), torch.cat(ctr_l)
-            if rescale:
-                boxes = boxes / boxes.new_tensor(img_metas[b]['scale_factor'])
-            keep = (scores > cfg.score_thr).reshape(-1)          # before the centerness factor (bbox_nms.py:48-58)
-            inds = keep.nonzero(as_tuple=False).reshape(-1)
-            labels = torch.arange(C, dtype=torch.long).repeat(scores.shape[0])[inds]
-            cb = boxes[:, None].expand(-1, C, 4).reshape(-1, 4)[inds]
-            cs = (scores * ctrs[:, None]).reshape(-1)[inds]
-            if cb.numel() == 0:
-                out.append((torch.cat([cb, cs[:, None]], -1), labels))
-                continue
-            dets, kept = batched_nms(cb.contiguous(), cs.contiguous(), labels, dict(cfg.nms))
-            if cfg.max_per_img > 0:
-                dets, kept = dets[:cfg.max_per_img], kept[:cfg.max_per_img]
-            out.append((dets, labels[kept]))
+            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), torch.cat(ctr_l), img_metas[b], cfg, rescale,
+                                      batched_nms))
         return out
 
-    def simple_test(self, feats, img_metas, rescale=False, batched_nms=None):
-        """dense_test_mixins.py:17-37: list of (N,C,h,w) -> per image (dets (k,5), labels (k,))"""
-        return self.get_bboxes(*self(feats), img_metas, rescale=rescale, batched_nms=batched_nms)
-
-    def aug_test(self, feats, img_metas, rescale=False):
-        raise NotImplementedError('ATSSHead has no test-time augmentation')
-
     # ------------------------------------------------------------------ train
-    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
-        """base_dense_head.py:48-78"""
-        outs = self(x)
-        losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
-        if proposal_cfg is None:
-            return losses
-        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
-
-    def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
-        """the device-resident train step of the head: NHWC pyramid -> towers and fused heads over all levels -> adaptive
-        assignment and loss kernels; no host read"""
-        if gt_bboxes_ignore is not None:
-            raise NotImplementedError('ATSSHead: gt_bboxes_ignore is not supported on the device path')
-        a, r, sizes = self.forward_head_fused(list(feats_nhwc))
-        scales = torch.stack([s.scale.float().reshape(()) for s in self.scales])
-        return self.loss_fused(a, r, scales, sizes, gt_bboxes, gt_labels, img_metas)
-
     def loss_fused(self, a, r, scales, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
         """ATSSHead.loss on the fused head outputs of all levels: whole-batch adaptive assignment, then the loss kernels --
         targets and both normalisers are formed on the device (averaged over ranks there when distributed), nothing is
@@ -2278,10 +2160,8 @@ class ATSSHead(AnchorHead):
                                       self.loss_cls.alpha, self.loss_bbox.eps, self.loss_cls.loss_weight,
                                       self.loss_bbox.loss_weight, self.loss_centerness.loss_weight, self.bbox_coder.means,
                                       self.bbox_coder.stds)
-        hook = None
-        if dist.is_available() and dist.is_initialized():
-            hook = lambda n2: n2.copy_(reduce_mean(n2))     # noqa: E731  (the reference's two reduce_mean calls as one)
-        losses, coef, norm2 = train_ops.atss_loss(a, r, scales, gt_inds, gts, labels, self._layout(a, r), meta, hook)
+        losses, coef, norm2 = train_ops.atss_loss(a, r, scales, gt_inds, gts, labels, self._layout(a, r), meta,
+                                                  self._norm_hook())
         self.last_targets = (gt_inds, coef, norm2)
         return dict(loss_cls=list(losses[0].unbind(0)), loss_bbox=list(losses[1].unbind(0)),
                     loss_centerness=list(losses[2].unbind(0)))
@@ -2374,8 +2254,7 @@ class ATSSHead(AnchorHead):
         assert len(featmap_sizes) == self.anchor_generator.num_levels
         device = cls_scores[0].device
         if device.type == 'cuda':
-            if gt_bboxes_ignore is not None:
-                raise NotImplementedError('ATSSHead: gt_bboxes_ignore is not supported on the device path')
+            self._refuse_ignore(gt_bboxes_ignore)
             a, r = self._rows_from_reference(cls_scores, bbox_preds, centernesses)
             return self.loss_fused(a, r, a.new_ones(len(featmap_sizes)), featmap_sizes, gt_bboxes, gt_labels, img_metas)
         anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)

@@ -1253,6 +1253,48 @@ def dense_score(cls, num_anchors, num_classes):
     return out
 
 
+class _DecodeLevels:
+    """what the three `*_decode_levels` wrappers share: the checks of the per-level picks (B, k_l) and of max_shape (B, 2) /
+    scale_factor (B, 4) or None, the five outputs over the T * C candidate slots (T = sum k_l) and the ctypes arrays"""
+
+    def __init__(self, topk_inds, num_classes, max_shape, scale_factor, device):
+        import ctypes
+        _require_gpu(*topk_inds, max_shape, scale_factor)
+        self.L, self.b, self.c = len(topk_inds), topk_inds[0].shape[0], int(num_classes)
+        self._ptrs, self._ints, self._f4 = ctypes.c_void_p * self.L, ctypes.c_int * self.L, ctypes.c_float * 4
+        self.inds = [t.contiguous() for t in topk_inds]
+        assert all(t.dtype == torch.int64 and t.shape[0] == self.b for t in self.inds)
+        self.counts = [int(t.shape[1]) for t in self.inds]
+        b, n = self.b, sum(self.counts) * self.c
+        assert max_shape.shape == (b, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
+        if scale_factor is not None:
+            assert scale_factor.shape == (b, 4) and scale_factor.dtype == torch.float32 and scale_factor.is_contiguous()
+        self.outs = (torch.empty((b, n, 4), dtype=torch.float32, device=device),      # boxes
+                     torch.empty((b, n), dtype=torch.float32, device=device),         # scores
+                     torch.empty((b, n), dtype=torch.int64, device=device),           # labels
+                     torch.empty((b, n), dtype=torch.bool, device=device),            # valid
+                     torch.empty((b,), dtype=torch.int32, device=device))             # n_valid
+        self.out_ptrs = tuple(_ptr(t) for t in self.outs)
+
+    def ptrs(self, ts):
+        return self._ptrs(*[t.data_ptr() for t in ts])
+
+    def ints(self, vs):
+        return self._ints(*[int(v) for v in vs])
+
+    def f4(self, vs):
+        return self._f4(*[float(v) for v in vs])
+
+    def rows_head(self, a, r, layout, scales, feat_hws, strides):
+        """the arguments of the (A, R) row layout that the FCOS and ATSS entries start with"""
+        L, b = self.L, self.b
+        _require_gpu(scales)
+        assert scales.dtype == torch.float32 and scales.numel() == L and scales.is_contiguous()
+        assert layout.rows == sum(b * h * w for h, w in feat_hws) and len(feat_hws) == L and len(strides) == L
+        return (self.ptrs(self.inds), self.ints(self.counts), _ptr(a), _ptr(r), layout.arr, _ptr(scales), b, L,
+                self.ints([h for h, _ in feat_hws]), self.ints([w for _, w in feat_hws]), self.ints(strides))
+
+
 def dense_decode_levels(topk_inds, cls_scores, bbox_preds, base_anchors, feat_hws, strides, num_classes, max_shape,
                         scale_factor, means, stds, score_thr, wh_ratio_clip=16 / 1000):
     """The candidates of multiclass_nms for all levels and images in one launch (brcnn_dense_decode_levels).  Per-level
@@ -1260,12 +1302,9 @@ def dense_decode_levels(topk_inds, cls_scores, bbox_preds, base_anchors, feat_hw
     base_anchors (A,4), feat_hws, strides; max_shape (B,2) [h, w], scale_factor (B,4) or None.
     Returns boxes (B,T*C,4), scores (B,T*C), labels (B,T*C) int64, valid (B,T*C) bool, n_valid (B,) int32; T = sum k_l,
     (level, pick, class) order."""
-    import ctypes
-    L = len(topk_inds)
-    _require_gpu(*topk_inds, *cls_scores, *bbox_preds, *base_anchors, max_shape, scale_factor)
-    b = topk_inds[0].shape[0]
-    a, c = base_anchors[0].size(0), int(num_classes)
-    inds = [t.contiguous() for t in topk_inds]
+    _require_gpu(*cls_scores, *bbox_preds, *base_anchors)
+    d = _DecodeLevels(topk_inds, num_classes, max_shape, scale_factor, bbox_preds[0].device)
+    a, c, b = base_anchors[0].size(0), d.c, d.b
     bases = [t.contiguous().float() for t in base_anchors]
     cstr, pstr = [], []
     for c_, p_ in zip(cls_scores, bbox_preds):
@@ -1275,30 +1314,15 @@ def dense_decode_levels(topk_inds, cls_scores, bbox_preds, base_anchors, feat_hw
         assert ac == a * c and a4 == 4 * a
         cstr.append(int(cs))
         pstr.append(int(ps))
-    counts = [int(t.shape[1]) for t in inds]
-    n = sum(counts) * c
-    dev = bbox_preds[0].device
-    assert max_shape.shape == (b, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
-    if scale_factor is not None:
-        assert scale_factor.shape == (b, 4) and scale_factor.dtype == torch.float32 and scale_factor.is_contiguous()
-    boxes = torch.empty((b, n, 4), dtype=torch.float32, device=dev)
-    scores = torch.empty((b, n), dtype=torch.float32, device=dev)
-    labels = torch.empty((b, n), dtype=torch.int64, device=dev)
-    valid = torch.empty((b, n), dtype=torch.bool, device=dev)
-    n_valid = torch.empty((b,), dtype=torch.int32, device=dev)
-    ptrs = lambda ts: (ctypes.c_void_p * L)(*[t.data_ptr() for t in ts])     # noqa: E731
-    ints = lambda vs: (ctypes.c_int * L)(*[int(v) for v in vs])               # noqa: E731
     sw = [s_ if isinstance(s_, int) else s_[0] for s_ in strides]
     sh = [s_ if isinstance(s_, int) else s_[1] for s_ in strides]
-    m4 = (ctypes.c_float * 4)(*[float(v) for v in means])
-    s4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
     st = _L.load().brcnn_dense_decode_levels(
-        ptrs(inds), ptrs(cls_scores), ints(cstr), ptrs(bbox_preds), ints(pstr), ptrs(bases), b, L, ints(counts),
-        ints([h for h, _ in feat_hws]), ints([w for _, w in feat_hws]), a, c, ints(sw), ints(sh), _ptr(max_shape),
-        _ptr(scale_factor), m4, s4, float(wh_ratio_clip), float(score_thr), _ptr(boxes), _ptr(scores), _ptr(labels),
-        _ptr(valid), _ptr(n_valid), _stream())
+        d.ptrs(d.inds), d.ptrs(cls_scores), d.ints(cstr), d.ptrs(bbox_preds), d.ints(pstr), d.ptrs(bases), b, d.L,
+        d.ints(d.counts), d.ints([h for h, _ in feat_hws]), d.ints([w for _, w in feat_hws]), a, c, d.ints(sw), d.ints(sh),
+        _ptr(max_shape), _ptr(scale_factor), d.f4(means), d.f4(stds), float(wh_ratio_clip), float(score_thr), *d.out_ptrs,
+        _stream())
     _L.check(st, 'brcnn_dense_decode_levels')
-    return boxes, scores, labels, valid, n_valid
+    return d.outs
 
 
 # --------------------------------------------------------------------------- FCOS head, test time
@@ -1338,33 +1362,12 @@ def fcos_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, max_s
     (B, 2) [h, w]; scale_factor (B, 4) or None.  Returns boxes (B,T*C,4), scores (B,T*C) = class sigmoid * centerness
     sigmoid, labels (B,T*C) int64, valid (B,T*C) bool = class sigmoid > score_thr, n_valid (B,) int32; T = sum k_l, (level,
     pick, class) order."""
-    import ctypes
-    L = len(topk_inds)
-    _require_gpu(*topk_inds, scales, max_shape, scale_factor)
-    b, c = topk_inds[0].shape[0], layout.C
-    inds = [t.contiguous() for t in topk_inds]
-    assert all(t.dtype == torch.int64 and t.shape[0] == b for t in inds)
-    assert scales.dtype == torch.float32 and scales.numel() == L and scales.is_contiguous()
-    assert layout.rows == sum(b * h * w for h, w in feat_hws) and len(feat_hws) == L and len(strides) == L
-    counts = [int(t.shape[1]) for t in inds]
-    n = sum(counts) * c
-    dev = a.device
-    assert max_shape.shape == (b, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
-    if scale_factor is not None:
-        assert scale_factor.shape == (b, 4) and scale_factor.dtype == torch.float32 and scale_factor.is_contiguous()
-    boxes = torch.empty((b, n, 4), dtype=torch.float32, device=dev)
-    scores = torch.empty((b, n), dtype=torch.float32, device=dev)
-    labels = torch.empty((b, n), dtype=torch.int64, device=dev)
-    valid = torch.empty((b, n), dtype=torch.bool, device=dev)
-    n_valid = torch.empty((b,), dtype=torch.int32, device=dev)
-    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in inds])
-    ints = lambda vs: (ctypes.c_int * L)(*[int(v) for v in vs])               # noqa: E731
+    d = _DecodeLevels(topk_inds, layout.C, max_shape, scale_factor, a.device)
     st = _L.load().brcnn_fcos_decode_levels(
-        ptrs, ints(counts), _ptr(a), _ptr(r), layout.arr, _ptr(scales), b, L, ints([h for h, _ in feat_hws]),
-        ints([w for _, w in feat_hws]), ints(strides), c, _ptr(max_shape), _ptr(scale_factor), float(score_thr), _ptr(boxes),
-        _ptr(scores), _ptr(labels), _ptr(valid), _ptr(n_valid), _stream())
+        *d.rows_head(a, r, layout, scales, feat_hws, strides), d.c, _ptr(max_shape), _ptr(scale_factor), float(score_thr),
+        *d.out_ptrs, _stream())
     _L.check(st, 'brcnn_fcos_decode_levels')
-    return boxes, scores, labels, valid, n_valid
+    return d.outs
 
 
 # --------------------------------------------------------------------------- ATSS head, test time
@@ -1385,36 +1388,13 @@ def atss_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, base_
     picked cell, scale_l * raw) clipped to max_shape and divided by scale_factor.  base_anchors: `atss_base_anchors`.  Returns
     boxes (B,T*C,4), scores (B,T*C) = class sigmoid * centerness sigmoid, labels (B,T*C) int64, valid (B,T*C) bool = class
     sigmoid > score_thr, n_valid (B,) int32; (level, pick, class) order."""
-    import ctypes
-    L = len(topk_inds)
-    _require_gpu(*topk_inds, scales, max_shape, scale_factor)
-    b, c = topk_inds[0].shape[0], layout.C
-    inds = [t.contiguous() for t in topk_inds]
-    assert all(t.dtype == torch.int64 and t.shape[0] == b for t in inds)
-    assert scales.dtype == torch.float32 and scales.numel() == L and scales.is_contiguous()
-    assert layout.rows == sum(b * h * w for h, w in feat_hws) and len(feat_hws) == L and len(strides) == L
-    assert len(base_anchors) == 4 * L
-    counts = [int(t.shape[1]) for t in inds]
-    n = sum(counts) * c
-    dev = a.device
-    assert max_shape.shape == (b, 2) and max_shape.dtype == torch.float32 and max_shape.is_contiguous()
-    if scale_factor is not None:
-        assert scale_factor.shape == (b, 4) and scale_factor.dtype == torch.float32 and scale_factor.is_contiguous()
-    boxes = torch.empty((b, n, 4), dtype=torch.float32, device=dev)
-    scores = torch.empty((b, n), dtype=torch.float32, device=dev)
-    labels = torch.empty((b, n), dtype=torch.int64, device=dev)
-    valid = torch.empty((b, n), dtype=torch.bool, device=dev)
-    n_valid = torch.empty((b,), dtype=torch.int32, device=dev)
-    ptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in inds])
-    ints = lambda vs: (ctypes.c_int * L)(*[int(v) for v in vs])               # noqa: E731
-    m4 = (ctypes.c_float * 4)(*[float(v) for v in means])
-    s4 = (ctypes.c_float * 4)(*[float(v) for v in stds])
+    d = _DecodeLevels(topk_inds, layout.C, max_shape, scale_factor, a.device)
+    assert len(base_anchors) == 4 * d.L
     st = _L.load().brcnn_atss_decode_levels(
-        ptrs, ints(counts), _ptr(a), _ptr(r), layout.arr, _ptr(scales), b, L, ints([h for h, _ in feat_hws]),
-        ints([w for _, w in feat_hws]), ints(strides), base_anchors, c, _ptr(max_shape), _ptr(scale_factor), m4, s4,
-        float(wh_ratio_clip), float(score_thr), _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(valid), _ptr(n_valid), _stream())
+        *d.rows_head(a, r, layout, scales, feat_hws, strides), base_anchors, d.c, _ptr(max_shape), _ptr(scale_factor),
+        d.f4(means), d.f4(stds), float(wh_ratio_clip), float(score_thr), *d.out_ptrs, _stream())
     _L.check(st, 'brcnn_atss_decode_levels')
-    return boxes, scores, labels, valid, n_valid
+    return d.outs
 
 
 # --------------------------------------------------------------------------- Cascade R-CNN, test time

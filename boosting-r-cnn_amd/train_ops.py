@@ -481,23 +481,43 @@ def dense_loss(cls, reg, gt_inds, gts, gt_labels, meta):
 
 
 # ----------------------------------------------------------------------------- FCOS head: targets and loss
-class FcosLossMeta:
-    """host-side description of one FCOS loss call: the pyramid, the ground-truth offsets and the loss settings
-    (include/brcnn_hip.h: cfg7_host)"""
+class CenternessLossMeta:
+    """host-side description of one loss call of a centerness head (FCOS, ATSS): the pyramid, the ground-truth offsets and
+    the loss settings.  A head names its entry points (`brcnn_<kind>_loss_*`), the arguments it adds after the strides
+    (`extra`) and whether the losses come back per level ((3, L)) or summed ((3,))."""
 
-    def __init__(self, batch, sizes, strides, num_classes, gt_offsets, focal_gamma, focal_alpha, eps_overlap, eps_loss,
-                 lw_cls, lw_bbox, lw_ctr):
+    kind, per_level, extra = None, False, ()
+
+    def __init__(self, batch, sizes, strides, num_classes, gt_offsets, cfg):
         self.batch, self.sizes, self.C = int(batch), [tuple(int(v) for v in s) for s in sizes], int(num_classes)
         self.L = len(self.sizes)
         if self.batch > MAX_IMAGES:
-            raise ValueError(f'fcos loss: batch {self.batch} exceeds {MAX_IMAGES} images per call')
+            raise ValueError(f'{self.kind} loss: batch {self.batch} exceeds {MAX_IMAGES} images per call')
         self.hs, self.ws = _ints([h for h, _ in self.sizes]), _ints([w for _, w in self.sizes])
         self.strides = _ints([s if isinstance(s, int) else s[0] for s in strides])
         self.gt_offsets = _ints(gt_offsets)
         self.total_gt = int(gt_offsets[-1])
-        self.cfg = _floats([focal_gamma, focal_alpha, eps_overlap, eps_loss, lw_cls, lw_bbox, lw_ctr])
+        self.cfg = _floats(cfg)
         self.rows = sum(self.batch * h * w for h, w in self.sizes)
-        self.points_per_image = sum(h * w for h, w in self.sizes)
+        self.per_image = sum(h * w for h, w in self.sizes)        # points resp. anchors of one image
+
+    def entry(self, lib, what):
+        return getattr(lib, f'brcnn_{self.kind}_loss_{what}')
+
+    def workspace(self, lib, device):
+        nb = self.entry(lib, 'workspace_bytes')(self.batch, self.L, self.hs, self.ws, self.C)
+        return torch.empty((nb + 3) // 4, dtype=torch.float32, device=device), nb
+
+
+class FcosLossMeta(CenternessLossMeta):
+    """the FCOS loss call (include/brcnn_hip.h: cfg7_host)"""
+
+    kind = 'fcos'
+
+    def __init__(self, batch, sizes, strides, num_classes, gt_offsets, focal_gamma, focal_alpha, eps_overlap, eps_loss,
+                 lw_cls, lw_bbox, lw_ctr):
+        super().__init__(batch, sizes, strides, num_classes, gt_offsets,
+                         [focal_gamma, focal_alpha, eps_overlap, eps_loss, lw_cls, lw_bbox, lw_ctr])
 
 
 def fcos_assign(gts, gt_offsets, batch, sizes, strides, regress_ranges, center_sampling=False, center_sample_radius=1.5):
@@ -519,52 +539,63 @@ def fcos_assign(gts, gt_offsets, batch, sizes, strides, regress_ranges, center_s
     return out
 
 
-def _fcos_check(a, r, layout, scales, gt_inds, gts, gt_labels, meta):
+def _centerness_loss_args(a, r, layout, scales, gt_inds, gts, gt_labels, meta):
+    """the arguments the forward and backward entry points of a centerness head share"""
+    gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
+    return (_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws, meta.strides, *meta.extra,
+            meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg)
+
+
+def _centerness_loss_partials(a, r, layout, scales, gt_inds, gts, gt_labels, meta):
+    """brcnn_<kind>_loss_forward: (workspace holding the block partials, norm2 = [n_pos, sum of centerness targets]) on the
+    device; the caller may average norm2 over ranks before the finalize step"""
     _require_gpu(a, r, scales, gt_inds, gts, gt_labels)
     assert layout.rows == meta.rows and layout.C == meta.C
     assert scales.dtype == torch.float32 and scales.shape == (meta.L,) and scales.is_contiguous()
-    assert gt_inds.dtype == torch.int32 and gt_inds.shape == (meta.batch, meta.points_per_image) and gt_inds.is_contiguous()
+    assert gt_inds.dtype == torch.int32 and gt_inds.shape == (meta.batch, meta.per_image) and gt_inds.is_contiguous()
     if meta.total_gt:
         assert gts.dtype == torch.float32 and gts.shape == (meta.total_gt, 4) and gts.is_contiguous()
         assert gt_labels.dtype == torch.int64 and gt_labels.shape == (meta.total_gt,) and gt_labels.is_contiguous()
+    lib = _L.load()
+    ws, nb = meta.workspace(lib, a.device)
+    norm2 = torch.empty((2,), dtype=torch.float32, device=a.device)
+    st = meta.entry(lib, 'forward')(*_centerness_loss_args(a, r, layout, scales, gt_inds, gts, gt_labels, meta), _ptr(ws), nb,
+                                    _ptr(norm2), _stream())
+    _L.check(st, f'brcnn_{meta.kind}_loss_forward')
+    return ws, norm2
+
+
+def _centerness_loss_finalize(ws, norm2, meta):
+    """brcnn_<kind>_loss_finalize: (losses (3,) or (3, L), coef3 = [lw_cls / N, lw_bbox / S, lw_ctr / N]), one allocation"""
+    n = 3 * meta.L if meta.per_level else 3
+    out = torch.empty((n + 3,), dtype=torch.float32, device=ws.device)
+    st = meta.entry(_L.load(), 'finalize')(_ptr(ws), ws.numel() * 4, _ptr(norm2), meta.batch, meta.L, meta.hs, meta.ws,
+                                           meta.C, meta.cfg, _ptr(out[:n]), _ptr(out[n:]), _stream())
+    _L.check(st, f'brcnn_{meta.kind}_loss_finalize')
+    return (out[:n].view(3, meta.L) if meta.per_level else out[:n]), out[n:]
 
 
 def fcos_loss_partials(a, r, layout, scales, gt_inds, gts, gt_labels, meta):
-    """brcnn_fcos_loss_forward: (workspace holding the block partials, norm2 = [n_pos, sum of centerness targets]) on the
-    device; the caller may average norm2 over ranks before `fcos_loss_finalize`"""
-    _fcos_check(a, r, layout, scales, gt_inds, gts, gt_labels, meta)
-    lib = _L.load()
-    nb = lib.brcnn_fcos_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.C)
-    ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=a.device)
-    norm2 = torch.empty((2,), dtype=torch.float32, device=a.device)
-    gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
-    st = lib.brcnn_fcos_loss_forward(_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws,
-                                     meta.strides, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg, _ptr(ws), nb,
-                                     _ptr(norm2), _stream())
-    _L.check(st, 'brcnn_fcos_loss_forward')
-    return ws, norm2
+    """brcnn_fcos_loss_forward, see `_centerness_loss_partials`"""
+    return _centerness_loss_partials(a, r, layout, scales, gt_inds, gts, gt_labels, meta)
 
 
 def fcos_loss_finalize(ws, norm2, meta):
     """brcnn_fcos_loss_finalize: out6 = [loss_cls, loss_bbox, loss_centerness | lw_cls / N, lw_bbox / S, lw_ctr / N]"""
-    out = torch.empty((6,), dtype=torch.float32, device=ws.device)
-    st = _L.load().brcnn_fcos_loss_finalize(_ptr(ws), ws.numel() * 4, _ptr(norm2), meta.batch, meta.L, meta.hs, meta.ws,
-                                            meta.C, meta.cfg, _ptr(out[:3]), _ptr(out[3:]), _stream())
-    _L.check(st, 'brcnn_fcos_loss_finalize')
-    return out[:3], out[3:]
+    return _centerness_loss_finalize(ws, norm2, meta)
 
 
-class FcosLossFunction(Function):
-    """losses (3,) = [loss_cls, loss_bbox, loss_centerness] from the head outputs of all levels, differentiable w.r.t. A, R
-    (the raw outputs) and the per-level scales"""
+class CenternessLossFunction(Function):
+    """losses = [loss_cls, loss_bbox, loss_centerness] ((3,) for FCOS, (3, L) per level for ATSS) from the head outputs of
+    all levels, differentiable w.r.t. A, R (the raw outputs) and the per-level scales; `meta` selects the head's kernels"""
 
     @staticmethod
     def forward(ctx, a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook):
         scales = scales.detach().float().contiguous()
-        ws, norm2 = fcos_loss_partials(a, r, layout, scales, gt_inds, gts, gt_labels, meta)
+        ws, norm2 = _centerness_loss_partials(a, r, layout, scales, gt_inds, gts, gt_labels, meta)
         if norm_hook is not None:
             norm_hook(norm2)
-        losses, coef = fcos_loss_finalize(ws, norm2, meta)
+        losses, coef = _centerness_loss_finalize(ws, norm2, meta)
         ctx.save_for_backward(a, r, scales, gt_inds, gts, gt_labels, coef)
         ctx.layout, ctx.meta = layout, meta
         ctx.mark_non_differentiable(coef, norm2)
@@ -579,20 +610,19 @@ class FcosLossFunction(Function):
         dscale = torch.empty_like(scales)
         g3 = g3.float().contiguous()
         lib = _L.load()
-        nb = lib.brcnn_fcos_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.C)
-        ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=a.device)
-        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
-        st = lib.brcnn_fcos_loss_backward(_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws,
-                                          meta.strides, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg, _ptr(g3),
-                                          _ptr(coef), _ptr(ws), nb, _ptr(da), _ptr(dr), _ptr(dscale), _stream())
-        _L.check(st, 'brcnn_fcos_loss_backward')
+        ws, nb = meta.workspace(lib, a.device)
+        st = meta.entry(lib, 'backward')(*_centerness_loss_args(a, r, layout, scales, gt_inds, gts, gt_labels, meta), _ptr(g3),
+                                         _ptr(coef), _ptr(ws), nb, _ptr(da), _ptr(dr), _ptr(dscale), _stream())
+        _L.check(st, f'brcnn_{meta.kind}_loss_backward')
         return da, dr, dscale, None, None, None, None, None, None
 
 
 def fcos_loss(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook=None):
     """(losses (3,), coef3, norm2); `norm_hook(norm2)` may change norm2 in place between the sums and the division (the
     mean over ranks)"""
-    return FcosLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
+    return CenternessLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
+
+
 
 
 # ----------------------------------------------------------------------------- ATSS head: assignment and loss
@@ -629,86 +659,27 @@ def atss_assign(gts, gt_offsets, batch, sizes, strides, base_anchors, topk, vali
     return (out, ov) if want_overlaps else out
 
 
-class AtssLossMeta:
-    """host-side description of one ATSS loss call: the pyramid and its base anchors, the ground-truth offsets and the loss
-    settings (include/brcnn_hip.h: cfg15_host)"""
+class AtssLossMeta(CenternessLossMeta):
+    """the ATSS loss call: adds the base anchors of the pyramid; per-level losses (include/brcnn_hip.h: cfg15_host)"""
+
+    kind, per_level = 'atss', True
 
     def __init__(self, batch, sizes, strides, base_anchors, num_classes, gt_offsets, focal_gamma, focal_alpha, eps, lw_cls,
                  lw_bbox, lw_ctr, means, stds, wh_ratio_clip=16 / 1000):
-        self.batch, self.sizes, self.C = int(batch), [tuple(int(v) for v in s) for s in sizes], int(num_classes)
-        self.L = len(self.sizes)
-        if self.batch > MAX_IMAGES:
-            raise ValueError(f'atss loss: batch {self.batch} exceeds {MAX_IMAGES} images per call')
-        self.hs, self.ws = _ints([h for h, _ in self.sizes]), _ints([w for _, w in self.sizes])
-        self.strides = _ints(strides)
-        self.base = base_anchors
+        super().__init__(batch, sizes, strides, num_classes, gt_offsets,
+                         [focal_gamma, focal_alpha, eps, lw_cls, lw_bbox, lw_ctr] + list(means) + list(stds) +
+                         [abs(math.log(wh_ratio_clip))])
         assert len(base_anchors) == 4 * self.L
-        self.gt_offsets = _ints(gt_offsets)
-        self.total_gt = int(gt_offsets[-1])
-        self.cfg = _floats([focal_gamma, focal_alpha, eps, lw_cls, lw_bbox, lw_ctr] + list(means) + list(stds) +
-                           [abs(math.log(wh_ratio_clip))])
-        self.rows = sum(self.batch * h * w for h, w in self.sizes)
-        self.anchors_per_image = sum(h * w for h, w in self.sizes)
-
-
-class AtssLossFunction(Function):
-    """losses (3, L) = [loss_cls | loss_bbox | loss_centerness] per level from the head outputs of all levels, differentiable
-    w.r.t. A, R (the raw outputs) and the per-level scales"""
-
-    @staticmethod
-    def forward(ctx, a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook):
-        scales = scales.detach().float().contiguous()
-        _require_gpu(a, r, scales, gt_inds, gts, gt_labels)
-        assert layout.rows == meta.rows and layout.C == meta.C
-        assert scales.shape == (meta.L,)
-        assert gt_inds.dtype == torch.int32 and gt_inds.shape == (meta.batch, meta.anchors_per_image) and gt_inds.is_contiguous()
-        if meta.total_gt:
-            assert gts.dtype == torch.float32 and gts.shape == (meta.total_gt, 4) and gts.is_contiguous()
-            assert gt_labels.dtype == torch.int64 and gt_labels.shape == (meta.total_gt,) and gt_labels.is_contiguous()
-        lib = _L.load()
-        nb = lib.brcnn_atss_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.C)
-        ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=a.device)
-        norm2 = torch.empty((2,), dtype=torch.float32, device=a.device)
-        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
-        st = lib.brcnn_atss_loss_forward(_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws,
-                                         meta.strides, meta.base, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg,
-                                         _ptr(ws), nb, _ptr(norm2), _stream())
-        _L.check(st, 'brcnn_atss_loss_forward')
-        if norm_hook is not None:
-            norm_hook(norm2)
-        out = torch.empty((3 * meta.L + 3,), dtype=torch.float32, device=a.device)
-        losses, coef = out[:3 * meta.L], out[3 * meta.L:]
-        st = lib.brcnn_atss_loss_finalize(_ptr(ws), nb, _ptr(norm2), meta.batch, meta.L, meta.hs, meta.ws, meta.C, meta.cfg,
-                                          _ptr(losses), _ptr(coef), _stream())
-        _L.check(st, 'brcnn_atss_loss_finalize')
-        ctx.save_for_backward(a, r, scales, gt_inds, gts, gt_labels, coef)
-        ctx.layout, ctx.meta = layout, meta
-        ctx.mark_non_differentiable(coef, norm2)
-        return losses.view(3, meta.L), coef, norm2
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g3, _gc, _gn):
-        a, r, scales, gt_inds, gts, gt_labels, coef = ctx.saved_tensors
-        meta, layout = ctx.meta, ctx.layout
-        da, dr = torch.empty_like(a), torch.empty_like(r)
-        dscale = torch.empty_like(scales)
-        g3 = g3.float().contiguous()
-        lib = _L.load()
-        nb = lib.brcnn_atss_loss_workspace_bytes(meta.batch, meta.L, meta.hs, meta.ws, meta.C)
-        ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=a.device)
-        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
-        st = lib.brcnn_atss_loss_backward(_ptr(a), _ptr(r), layout.arr, _ptr(scales), meta.batch, meta.L, meta.hs, meta.ws,
-                                          meta.strides, meta.base, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg,
-                                          _ptr(g3), _ptr(coef), _ptr(ws), nb, _ptr(da), _ptr(dr), _ptr(dscale), _stream())
-        _L.check(st, 'brcnn_atss_loss_backward')
-        return da, dr, dscale, None, None, None, None, None, None
+        self.base = base_anchors
+        self.extra = (base_anchors,)
 
 
 def atss_loss(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook=None):
     """(losses (3, L), coef3, norm2); `norm_hook(norm2)` may change norm2 in place between the sums and the division (the
     mean over ranks)"""
-    return AtssLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
+    return CenternessLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
+
+
 
 
 # ----------------------------------------------------------------------------- boosting loss
