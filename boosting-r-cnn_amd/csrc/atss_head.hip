@@ -32,11 +32,6 @@ struct AtssDecode : CenternessDecode {
     float mean[4], std[4], max_ratio;
 };
 
-__device__ __forceinline__ float4 anchor_of(const float* base, int width, int stride, int cell) {
-    const float sx = (float)((cell % width) * stride), sy = (float)((cell / width) * stride);
-    return make_float4(base[0] + sx, base[1] + sy, base[2] + sx, base[3] + sy);
-}
-
 // delta2bbox (delta_xywh_bbox_coder.py:144-237) of one anchor, brcnn_dense_decode_levels' operation order, before the clip
 // to the image.  d: the four deltas (scale * raw, or a target).  With GRAD, jac = [d x / d d0, d y / d d1, d w / d d2,
 // d h / d d3] of centre and size (the size's is 0 where the wh_ratio_clip clamp is active)
@@ -253,27 +248,6 @@ struct AtssTraits {
     }
 };  // AtssTraits
 
-// norm2 = [sum over images of max(number of positives, 1), sum of the centerness targets]; a count is an integer below
-// 2^24, exact in fp32
-__global__ __launch_bounds__(256) void atss_loss_norm_kernel(const AtssGeom g, const int* __restrict__ gt_inds,
-                                                            const float* __restrict__ partials, float* __restrict__ norm2) {
-    __shared__ float red[CH_THREADS];
-    const int tid = threadIdx.x;
-    float cnt = 0.f;
-    for (int b = 0; b < g.B; b++) {
-        const int G = g.gt_off[b + 1] - g.gt_off[b];
-        float c = 0.f;
-        for (int i = tid; i < g.n; i += CH_THREADS) {
-            const int gi = gt_inds[(size_t)b * g.n + i];
-            c += (gi > 0 && gi <= G) ? 1.f : 0.f;
-        }
-        cnt += fmaxf(block_sum(c, red, tid), 1.f);
-    }
-    float sum = 0.f;
-    for (int l = 0; l < g.L; l++) sum += level_sum(g, partials, 2, l, 1, red, tid);
-    if (tid == 0) { norm2[0] = cnt; norm2[1] = sum; }
-}
-
 // losses (3, L) = [loss_cls | loss_bbox | loss_centerness] per level; coef3 = [lw_cls / N, lw_bbox / S, lw_ctr / N]
 __global__ __launch_bounds__(256) void atss_loss_finalize_kernel(const AtssGeom g, const float* __restrict__ partials,
                                                                 const float* __restrict__ norm2,
@@ -399,7 +373,7 @@ BRCNN_API int brcnn_atss_loss_forward(const float* a, const float* r, const int*
     hipLaunchKernelGGL(centerness_loss_forward_kernel<AtssTraits>, dim3(g.blk0[CH_SEGS]), dim3(CH_THREADS), 0,
                        (hipStream_t)stream, g, a, r, scales, gt_inds, gts, gt_labels, partials);
     BRCNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(atss_loss_norm_kernel, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, gt_inds, partials, norm2);
+    hipLaunchKernelGGL(anchor_loss_norm_kernel<AtssTraits>, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, gt_inds, partials, norm2);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }

@@ -1,4 +1,5 @@
-// What the centerness heads share (fcos_head.hip, atss_head.hip): the row layout of the head outputs, the pyramid geometry
+// What the dense heads on (A, R) rows share (fcos_head.hip, atss_head.hip; gfl_head.hip takes the geometry, the sums and the
+// norm / dscale kernels): the row layout of the head outputs, the pyramid geometry
 // with its split into workgroups, the test-time decode kernel and the block-partial loss kernels, as templates over a
 // per-head traits type T resolved at compile time:
 //     T::Geom      : CenternessGeom + what the head's targets need (eps values; base anchors, means / stds)
@@ -60,6 +61,13 @@ __device__ __forceinline__ float block_sum(float v, float* red, int tid) {
         __syncthreads();
     }
     return red[0];
+}
+
+// the one anchor of cell `cell` of a level: base + (x * stride, y * stride, x * stride, y * stride), exact in fp32 (atss_head.hip,
+// gfl_head.hip)
+__device__ __forceinline__ float4 anchor_of(const float* base, int width, int stride, int cell) {
+    const float sx = (float)((cell % width) * stride), sy = (float)((cell / width) * stride);
+    return make_float4(base[0] + sx, base[1] + sy, base[2] + sx, base[3] + sy);
 }
 
 // the sum of partials[which] over the workgroups of (level l, term)
@@ -264,6 +272,29 @@ __global__ __launch_bounds__(256) void centerness_dscale_kernel(const typename T
     }
 }
 
+// The normalisers of the anchor heads whose gt_inds follow brcnn_atss_assign (atss_head.hip, gfl_head.hip): norm2 = [sum over
+// images of max(number of positives, 1), sum of partials[2] over the point workgroups (ATSS: the centerness targets; GFL:
+// the positives' weights)]; a count is an integer below 2^24, exact in fp32
+template <class T>
+__global__ __launch_bounds__(256) void anchor_loss_norm_kernel(const typename T::Geom g, const int* __restrict__ gt_inds,
+                                                              const float* __restrict__ partials, float* __restrict__ norm2) {
+    __shared__ float red[CH_THREADS];
+    const int tid = threadIdx.x;
+    float cnt = 0.f;
+    for (int b = 0; b < g.B; b++) {
+        const int G = g.gt_off[b + 1] - g.gt_off[b];
+        float c = 0.f;
+        for (int i = tid; i < g.n; i += CH_THREADS) {
+            const int gi = gt_inds[(size_t)b * g.n + i];
+            c += (gi > 0 && gi <= G) ? 1.f : 0.f;
+        }
+        cnt += fmaxf(block_sum(c, red, tid), 1.f);
+    }
+    float sum = 0.f;
+    for (int l = 0; l < g.L; l++) sum += level_sum(g, partials, 2, l, 1, red, tid);
+    if (tid == 0) { norm2[0] = cnt; norm2[1] = sum; }
+}
+
 // --------------------------------------------------------------------------------------------------------------- host
 bool layout_ok(const int* v, int C) {
     if (!v) return false;
@@ -338,18 +369,13 @@ inline size_t loss_workspace_bytes(const CenternessGeom& g) {
     return (size_t)T::PARTIALS * (size_t)g.blk0[CH_SEGS] * sizeof(float);
 }
 
-// the common part of a *_decode_levels entry: argument checks, the picks and the level geometry of `lv`
-int fill_decode_common(CenternessDecode& lv, const int64_t* const* topk_inds, const int* counts, const float* a, const float* r,
-                       const int* layout8_host, const float* scales, int batch, int num_levels, const int* heights,
-                       const int* widths, const int* strides, int num_classes, const float* max_shape, float score_thr,
-                       const float* boxes, const float* scores, const int64_t* labels, const uint8_t* valid,
-                       const int32_t* n_valid) {
-    if (batch < 0 || num_levels <= 0 || num_levels > BRCNN_MAX_LEVELS || num_classes <= 0 ||
-        num_classes > 0x7fffff || !topk_inds || !counts || !a || !r || !layout_ok(layout8_host, num_classes) || !scales ||
-        !heights || !widths || !strides || !max_shape || !boxes || !scores || !labels || !valid || !n_valid)
+// the picks and the level geometry of `lv`, whatever the layout of the rows (the caller checks and sets lv.lay)
+int fill_decode_picks(CenternessDecode& lv, const int64_t* const* topk_inds, const int* counts, int batch, int num_levels,
+                      const int* heights, const int* widths, const int* strides, int num_classes, float score_thr) {
+    if (batch < 0 || num_levels <= 0 || num_levels > BRCNN_MAX_LEVELS || num_classes <= 0 || num_classes > 0x7fffff ||
+        !topk_inds || !counts || !heights || !widths || !strides)
         return BRCNN_EINVAL;
     lv.num = num_levels; lv.C = num_classes;
-    lv.lay = make_layout(layout8_host);
     long long T = 0, rows = 0;
     for (int l = 0; l < num_levels; l++) {
         if (counts[l] <= 0 || !level_ok(heights[l], widths[l], strides[l]) || !topk_inds[l] ||
@@ -368,6 +394,20 @@ int fill_decode_common(CenternessDecode& lv, const int64_t* const* topk_inds, co
     lv.T = (int)T;
     lv.score_thr = score_thr;
     return 0;
+}
+
+// the common part of a *_decode_levels entry of the centerness heads: argument checks, layout8, the picks and the geometry
+int fill_decode_common(CenternessDecode& lv, const int64_t* const* topk_inds, const int* counts, const float* a, const float* r,
+                       const int* layout8_host, const float* scales, int batch, int num_levels, const int* heights,
+                       const int* widths, const int* strides, int num_classes, const float* max_shape, float score_thr,
+                       const float* boxes, const float* scores, const int64_t* labels, const uint8_t* valid,
+                       const int32_t* n_valid) {
+    if (batch < 0 || num_levels <= 0 || num_levels > BRCNN_MAX_LEVELS || num_classes <= 0 ||
+        num_classes > 0x7fffff || !topk_inds || !counts || !a || !r || !layout_ok(layout8_host, num_classes) || !scales ||
+        !heights || !widths || !strides || !max_shape || !boxes || !scores || !labels || !valid || !n_valid)
+        return BRCNN_EINVAL;
+    lv.lay = make_layout(layout8_host);
+    return fill_decode_picks(lv, topk_inds, counts, batch, num_levels, heights, widths, strides, num_classes, score_thr);
 }
 
 template <class T>

@@ -200,6 +200,101 @@ class AnchorHead(nn.Module):
                                         a.match_low_quality, batch=B, geom=geom, valid_hw=valid_hw, img_hw=img_hw,
                                         allowed_border=border, want_counts=want_counts)
 
+    # ------------------------------------------------------------------ one anchor per cell + ATSSAssigner (ATSSHead, GFLHead)
+    MAX_TOPK = 16        # brcnn_atss_assign
+
+    @classmethod
+    def _check_atss_train_cfg(cls, name, tc, feat_channels):
+        """what the heads on `brcnn_atss_assign` and the GN towers refuse before they build anything"""
+        if tc:
+            asg = tc.get('assigner', {})
+            if asg.get('type') != 'ATSSAssigner':
+                raise NotImplementedError(f"{name}: train_cfg.assigner.type={asg.get('type')!r}; only ATSSAssigner")
+            if not 0 < asg.get('topk', 0) <= cls.MAX_TOPK:
+                raise ValueError(f"{name}: train_cfg.assigner.topk={asg.get('topk')} outside (0, {cls.MAX_TOPK}]")
+            if asg.get('ignore_iof_thr', -1) > 0:
+                raise NotImplementedError(f"{name}: train_cfg.assigner.ignore_iof_thr={asg.get('ignore_iof_thr')} > 0 (ignore "
+                                          'regions) is not supported')
+            if tc.get('pos_weight', -1) > 0:
+                raise NotImplementedError(f"{name}: train_cfg.pos_weight={tc.get('pos_weight')} > 0 is not supported")
+            if tc.get('allowed_border', -1) >= 0:
+                raise NotImplementedError(f"{name}: train_cfg.allowed_border={tc.get('allowed_border')} >= 0 is not supported "
+                                          '(inside flags = valid flags)')
+        if feat_channels > 256 or feat_channels % 4:
+            raise NotImplementedError(f'{name}: feat_channels={feat_channels}; the GroupNorm kernels take up to 256 channels in '
+                                      'whole quads')
+
+    def _check_one_square_anchor(self, name):
+        if self.num_anchors != 1:
+            raise NotImplementedError(
+                f'{name}: the anchor_generator gives {self.num_anchors} anchors per cell (several ratios, or scales_per_octave '
+                '> 1); only one is supported -- the anchors of a cell share a centre, their distances to a ground truth '
+                "tie exactly, and the reference's choice among them is torch.topk's unspecified order")
+        if any(s[0] != s[1] for s in self.anchor_generator.strides):
+            raise NotImplementedError(f'{name}: anchor_generator.strides={self.anchor_generator.strides}; only square strides')
+        if len(self.anchor_generator.strides) > 8:
+            raise ValueError(f'{name}: {len(self.anchor_generator.strides)} pyramid levels, at most 8 are supported')
+
+    def _base_table(self):
+        """the generator's base anchors as the host array the kernels take (the anchors themselves are never materialised)"""
+        if '_base_host' not in self.__dict__:
+            self.__dict__['_base_host'] = ops.atss_base_anchors(self.anchor_generator.base_anchors)
+        return self.__dict__['_base_host']
+
+    def _atss_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
+                      gt_labels_list=None, label_channels=1, unmap_outputs=True, encode=True):
+        """`get_targets` of the heads trained on ATSSAssigner (atss_head.py:506-568, gfl_head.py:474-536) on torch ops, the
+        host mirror: (anchors, labels, label weights, box targets, box weights) per level with the images stacked, and the
+        two sample counts.  `encode`: the box targets are the coder's deltas (ATSSHead) or the ground-truth boxes (GFLHead)"""
+        num_imgs = len(img_metas)
+        assert len(anchor_list) == len(valid_flag_list) == num_imgs
+        num_level_anchors = [a.size(0) for a in anchor_list[0]]
+        flat_anchors = [torch.cat(list(a)) for a in anchor_list]
+        flat_flags = [torch.cat(list(v)) for v in valid_flag_list]
+        ignore = gt_bboxes_ignore_list if gt_bboxes_ignore_list is not None else [None] * num_imgs
+        gt_labels_list = gt_labels_list if gt_labels_list is not None else [None] * num_imgs
+        res = multi_apply(self._get_target_single, flat_anchors, flat_flags, [num_level_anchors] * num_imgs, gt_bboxes_list,
+                          ignore, gt_labels_list, img_metas, label_channels=label_channels, unmap_outputs=unmap_outputs, encode=encode)
+        all_anchors, all_labels, all_lw, all_bt, all_bw, pos_list, neg_list = res
+        if any(l is None for l in all_labels):
+            return None
+        num_total_pos = sum(max(p.numel(), 1) for p in pos_list)
+        num_total_neg = sum(max(p.numel(), 1) for p in neg_list)
+        return tuple(images_to_levels(t, num_level_anchors) for t in (all_anchors, all_labels, all_lw, all_bt, all_bw)) + \
+            (num_total_pos, num_total_neg)
+
+    def _get_target_single(self, flat_anchors, valid_flags, num_level_anchors, gt_bboxes, gt_bboxes_ignore, gt_labels,
+                           img_meta, label_channels=1, unmap_outputs=True, encode=True):
+        """atss_head.py:570-678 / gfl_head.py:538-642"""
+        inside_flags = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
+        if not inside_flags.any():
+            return (None,) * 7
+        anchors = flat_anchors[inside_flags, :]
+        inside_per_level = [int(f.sum()) for f in torch.split(inside_flags, num_level_anchors)]
+        assign_result = self.assigner.assign(anchors, inside_per_level, gt_bboxes, gt_bboxes_ignore, gt_labels)
+        sampling_result = self.sampler.sample(assign_result, anchors, gt_bboxes)
+        n = anchors.shape[0]
+        bbox_targets, bbox_weights = torch.zeros_like(anchors), torch.zeros_like(anchors)
+        labels = anchors.new_full((n,), self.num_classes, dtype=torch.long)
+        label_weights = anchors.new_zeros(n, dtype=torch.float)
+        pos_inds, neg_inds = sampling_result.pos_inds, sampling_result.neg_inds
+        if len(pos_inds) > 0:
+            bbox_targets[pos_inds, :] = self.bbox_coder.encode(sampling_result.pos_bboxes, sampling_result.pos_gt_bboxes) \
+                if encode else sampling_result.pos_gt_bboxes
+            bbox_weights[pos_inds, :] = 1.0
+            labels[pos_inds] = 0 if gt_labels is None else gt_labels[sampling_result.pos_assigned_gt_inds]
+            label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
+        if len(neg_inds) > 0:
+            label_weights[neg_inds] = 1.0
+        if unmap_outputs:
+            total = flat_anchors.size(0)
+            anchors = unmap(anchors, total, inside_flags)
+            labels = unmap(labels, total, inside_flags, fill=self.num_classes)
+            label_weights = unmap(label_weights, total, inside_flags)
+            bbox_targets = unmap(bbox_targets, total, inside_flags)
+            bbox_weights = unmap(bbox_weights, total, inside_flags)
+        return anchors, labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds
+
     # ------------------------------------------------------------------ device path: the RPN proposal stage
     def _proposals_padded(self, cls_nhwc, reg_nhwc, iou_nhwc, img_metas, cfg=None, reg_scales=None):
         """Device-resident proposal stage for the whole batch (no host sync).
@@ -1211,10 +1306,11 @@ class DenseDetHead:
 
 
 class GNTowerHead(DenseDetHead):
-    """What FCOSHead and ATSSHead share on top of DenseDetHead: two towers of `stacked_convs` 3x3 conv + GroupNorm + ReLU
-    (`cls_convs`, `reg_convs`), each ending in ONE fused fp32 head conv whose columns `_head_groups()` names, one `Scale`
-    per level, and the (A, R) row tensors the kernels of csrc/fcos_head.hip and csrc/atss_head.hip read in place.  A head
-    supplies `_head_groups`, `_layout`, `_rows_from_reference`, `_decode_candidates` and `loss_fused`."""
+    """What FCOSHead, ATSSHead and GFLHead share on top of DenseDetHead: two towers of `stacked_convs` 3x3 conv + GroupNorm
+    + ReLU (`cls_convs`, `reg_convs`), each ending in ONE fused fp32 head conv whose columns `_head_groups()` names, one
+    `Scale` per level, and the (A, R) row tensors the kernels of csrc/fcos_head.hip, csrc/atss_head.hip and csrc/gfl_head.hip
+    read in place.  A head supplies `_head_groups`, `_layout`, `_rows_from_reference`, `_decode_candidates` and `loss_fused`,
+    and `_score_rows` when it does not rank by the centerness product."""
 
     def _init_towers(self):
         self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
@@ -1313,7 +1409,7 @@ class GNTowerHead(DenseDetHead):
         self._check_test_cfg(cfg)
         self._check_limits(cfg, sizes)
         B = len(img_metas)
-        scored, raw, r0 = ops.fcos_score(a, r, layout), [], 0
+        scored, raw, r0 = self._score_rows(a, r, layout), [], 0
         for (h, w) in sizes:
             raw.append(scored[r0:r0 + B * h * w].view(B, h * w))
             r0 += B * h * w
@@ -1323,6 +1419,10 @@ class GNTowerHead(DenseDetHead):
         bb, sc, lb, va, nv = self._decode_candidates([p[1] for p in picked], a, r, layout, scales, sizes, max_shape, sf, cfg)
         self.last_n_valid = nv
         return self._nms_candidates(bb, sc, lb, va, self.cls_out_channels, cfg)
+
+    def _score_rows(self, a, r, layout):
+        """the per-row ranking score of the top-k: the centerness heads' max_c(class sigmoid x centerness sigmoid)"""
+        return ops.fcos_score(a, r, layout)
 
     def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
         a, r, sizes = self.forward_rows(list(feats_nhwc))
@@ -1971,8 +2071,6 @@ class ATSSHead(GNTowerHead, AnchorHead):
     / centerness loss with the targets formed in the kernel.  Inference reads the host once, the head's train step never.
     CPU tensors take the reference's chain on torch ops (the host mirror the CPU tests compare with the fixture)."""
 
-    MAX_TOPK = 16        # brcnn_atss_assign
-
     def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
                  norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
                  loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0), init_cfg=None, **kwargs):
@@ -1994,37 +2092,10 @@ class ATSSHead(GNTowerHead, AnchorHead):
                                       'supported')
         if kwargs.get('reg_decoded_bbox', False):
             raise NotImplementedError(f'{name}: reg_decoded_bbox=True is not supported (the head decodes its deltas itself)')
-        tc = kwargs.get('train_cfg')
-        if tc:
-            asg = tc.get('assigner', {})
-            if asg.get('type') != 'ATSSAssigner':
-                raise NotImplementedError(f"{name}: train_cfg.assigner.type={asg.get('type')!r}; only ATSSAssigner")
-            if not 0 < asg.get('topk', 0) <= self.MAX_TOPK:
-                raise ValueError(f"{name}: train_cfg.assigner.topk={asg.get('topk')} outside (0, {self.MAX_TOPK}]")
-            if asg.get('ignore_iof_thr', -1) > 0:
-                raise NotImplementedError(f"{name}: train_cfg.assigner.ignore_iof_thr={asg.get('ignore_iof_thr')} > 0 (ignore "
-                                          'regions) is not supported')
-            if tc.get('pos_weight', -1) > 0:
-                raise NotImplementedError(f"{name}: train_cfg.pos_weight={tc.get('pos_weight')} > 0 is not supported")
-            if tc.get('allowed_border', -1) >= 0:
-                raise NotImplementedError(f"{name}: train_cfg.allowed_border={tc.get('allowed_border')} >= 0 is not supported "
-                                          '(inside flags = valid flags)')
-        feat_channels = kwargs.get('feat_channels', 256)
-        if feat_channels > 256 or feat_channels % 4:
-            raise NotImplementedError(f'{name}: feat_channels={feat_channels}; the GroupNorm kernels take up to 256 channels in '
-                                      'whole quads')
+        self._check_atss_train_cfg(name, kwargs.get('train_cfg'), kwargs.get('feat_channels', 256))
         self.stacked_convs, self.conv_cfg, self.norm_cfg = stacked_convs, conv_cfg, norm_cfg
         super().__init__(num_classes, in_channels, init_cfg=init_cfg, **kwargs)
-        if self.num_anchors != 1:
-            raise NotImplementedError(
-                f'{name}: the anchor_generator gives {self.num_anchors} anchors per cell (several ratios, or scales_per_octave '
-                '> 1); only one is supported -- the anchors of a cell share a centre, their distances to a ground truth '
-                "tie exactly, and the reference's choice among them is torch.topk's unspecified order")
-        if any(s[0] != s[1] for s in self.anchor_generator.strides):
-            raise NotImplementedError(f'{name}: anchor_generator.strides={self.anchor_generator.strides}; only square strides')
-        if len(self.anchor_generator.strides) > self.MAX_LEVELS:
-            raise ValueError(f'{name}: {len(self.anchor_generator.strides)} pyramid levels, at most {self.MAX_LEVELS} are '
-                             'supported')
+        self._check_one_square_anchor(name)
         self.sampling = False
         self.loss_centerness = build_loss(loss_centerness)
         for loss in (self.loss_cls, self.loss_bbox, self.loss_centerness):
@@ -2056,12 +2127,6 @@ class ATSSHead(GNTowerHead, AnchorHead):
 
     def _layout(self, a, r):
         return ops.FcosLayout(a, r, self.cls_out_channels, 0, 0, True, 4, False, True)
-
-    def _base_table(self):
-        """the generator's base anchors as the host array the kernels take (the anchors themselves are never materialised)"""
-        if '_base_host' not in self.__dict__:
-            self.__dict__['_base_host'] = ops.atss_base_anchors(self.anchor_generator.base_anchors)
-        return self.__dict__['_base_host']
 
     def _split_rows(self, a, r, sizes, B):
         """(A, R) rows -> the reference's per-level NHWC (cls, bbox_pred AFTER the Scale, centerness)"""
@@ -2169,54 +2234,9 @@ class ATSSHead(GNTowerHead, AnchorHead):
     def get_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
                     gt_labels_list=None, label_channels=1, unmap_outputs=True):
         """atss_head.py:506-568 on torch ops (the host mirror): (anchors, labels, label weights, box targets, box weights) per
-        level with the images stacked, and the two sample counts"""
-        num_imgs = len(img_metas)
-        assert len(anchor_list) == len(valid_flag_list) == num_imgs
-        num_level_anchors = [a.size(0) for a in anchor_list[0]]
-        flat_anchors = [torch.cat(list(a)) for a in anchor_list]
-        flat_flags = [torch.cat(list(v)) for v in valid_flag_list]
-        ignore = gt_bboxes_ignore_list if gt_bboxes_ignore_list is not None else [None] * num_imgs
-        gt_labels_list = gt_labels_list if gt_labels_list is not None else [None] * num_imgs
-        res = multi_apply(self._get_target_single, flat_anchors, flat_flags, [num_level_anchors] * num_imgs, gt_bboxes_list,
-                          ignore, gt_labels_list, img_metas, label_channels=label_channels, unmap_outputs=unmap_outputs)
-        all_anchors, all_labels, all_lw, all_bt, all_bw, pos_list, neg_list = res
-        if any(l is None for l in all_labels):
-            return None
-        num_total_pos = sum(max(p.numel(), 1) for p in pos_list)
-        num_total_neg = sum(max(p.numel(), 1) for p in neg_list)
-        return tuple(images_to_levels(t, num_level_anchors) for t in (all_anchors, all_labels, all_lw, all_bt, all_bw)) + \
-            (num_total_pos, num_total_neg)
-
-    def _get_target_single(self, flat_anchors, valid_flags, num_level_anchors, gt_bboxes, gt_bboxes_ignore, gt_labels,
-                           img_meta, label_channels=1, unmap_outputs=True):
-        """atss_head.py:570-678"""
-        inside_flags = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
-        if not inside_flags.any():
-            return (None,) * 7
-        anchors = flat_anchors[inside_flags, :]
-        inside_per_level = [int(f.sum()) for f in torch.split(inside_flags, num_level_anchors)]
-        assign_result = self.assigner.assign(anchors, inside_per_level, gt_bboxes, gt_bboxes_ignore, gt_labels)
-        sampling_result = self.sampler.sample(assign_result, anchors, gt_bboxes)
-        n = anchors.shape[0]
-        bbox_targets, bbox_weights = torch.zeros_like(anchors), torch.zeros_like(anchors)
-        labels = anchors.new_full((n,), self.num_classes, dtype=torch.long)
-        label_weights = anchors.new_zeros(n, dtype=torch.float)
-        pos_inds, neg_inds = sampling_result.pos_inds, sampling_result.neg_inds
-        if len(pos_inds) > 0:
-            bbox_targets[pos_inds, :] = self.bbox_coder.encode(sampling_result.pos_bboxes, sampling_result.pos_gt_bboxes)
-            bbox_weights[pos_inds, :] = 1.0
-            labels[pos_inds] = 0 if gt_labels is None else gt_labels[sampling_result.pos_assigned_gt_inds]
-            label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
-        if len(neg_inds) > 0:
-            label_weights[neg_inds] = 1.0
-        if unmap_outputs:
-            total = flat_anchors.size(0)
-            anchors = unmap(anchors, total, inside_flags)
-            labels = unmap(labels, total, inside_flags, fill=self.num_classes)
-            label_weights = unmap(label_weights, total, inside_flags)
-            bbox_targets = unmap(bbox_targets, total, inside_flags)
-            bbox_weights = unmap(bbox_weights, total, inside_flags)
-        return anchors, labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds
+        level with the images stacked, and the two sample counts; the box targets are the encoded deltas"""
+        return self._atss_targets(anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list,
+                                  gt_labels_list, label_channels, unmap_outputs, encode=True)
 
     def centerness_target(self, anchors, bbox_targets):
         """atss_head.py:294-310: from the anchor centre to the box the encoded target decodes to"""
@@ -2270,3 +2290,260 @@ class ATSSHead(GNTowerHead, AnchorHead):
             num_total_samples=num_total_samples)
         avg = reduce_mean(sum(factors)).clamp_(min=1).item()
         return dict(loss_cls=losses_cls, loss_bbox=[x / avg for x in losses_bbox], loss_centerness=losses_ctr)
+
+
+# ----------------------------------------------------------------------------- GFL baseline
+class Integral(nn.Module):
+    """gfl_head.py:16-49: the expectation sum P(y_i) * y_i over the discrete set {0 .. reg_max} of each box side's softmax
+    distribution; `project` is the reference's buffer (checkpoints carry it)"""
+
+    def __init__(self, reg_max=16):
+        super().__init__()
+        self.reg_max = reg_max
+        self.register_buffer('project', torch.linspace(0, self.reg_max, self.reg_max + 1))
+
+    def forward(self, x):
+        """(..., 4 * (reg_max + 1)) logits -> (N, 4) distances"""
+        import torch.nn.functional as F
+        x = F.softmax(x.reshape(-1, self.reg_max + 1), dim=1)
+        return F.linear(x, self.project.type_as(x)).reshape(-1, 4)
+
+
+def bbox2distance(points, bbox, max_dis=None, eps=0.1):
+    """core/bbox/transforms.py: (n, 2) points and (n, 4) corner boxes -> (n, 4) [l, t, r, b] distances, clamped to
+    [0, max_dis - eps]"""
+    d = torch.stack([points[:, 0] - bbox[:, 0], points[:, 1] - bbox[:, 1], bbox[:, 2] - points[:, 0],
+                     bbox[:, 3] - points[:, 1]], -1)
+    return d if max_dis is None else d.clamp(min=0, max=max_dis - eps)
+
+
+@HEADS.register_module()
+class GFLHead(GNTowerHead, AnchorHead):
+    """The head of GFL (mmdet/models/dense_heads/gfl_head.py:52-649 over anchor_head.py): ATSSHead's two GN towers
+    (`cls_convs.{i}.{conv,gn}`, `reg_convs.{i}.{conv,gn}`), then the 3x3 `gfl_cls` (C joint class / quality logits) and
+    `gfl_reg` (4 * (reg_max + 1) logits: per box side a distribution over the distances 0 .. reg_max strides, through the
+    level's `scales.{l}.scale`), and the `integral.project` buffer.  Parameter names and shapes are the reference's.  The
+    towers, the fused head convs and the test-time chain are GNTowerHead's: A = [cls C | pad], R = [4 * (reg_max + 1) logits |
+    pad], fp32, raw -- the kernels of csrc/gfl_head.hip apply the Scale to the logits themselves.  Test time ranks by the
+    class sigmoid alone (`brcnn_dense_score` on A in place), decodes the softmax expectations from the anchor centres with
+    the class fan-out (`brcnn_gfl_decode_levels`) and runs the NMS of the whole batch; training uses ATSS's adaptive
+    assignment (`brcnn_atss_assign`) and `brcnn_gfl_loss_*`: Quality Focal Loss against the IoU of the predicted box, GIoU
+    and Distribution Focal Loss weighted by the anchor's best class score, targets and both normalisers formed in the
+    kernels.  Inference reads the host once, the head's train step never.  CPU tensors take the reference's chain on torch
+    ops (the host mirror the CPU tests compare with the fixture)."""
+
+    MAX_REG = 16         # brcnn_gfl_*
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
+                 loss_dfl=dict(type='DistributionFocalLoss', loss_weight=0.25), reg_max=16, init_cfg=None, **kwargs):
+        name = 'GFLHead'
+        if norm_cfg is None or norm_cfg.get('type') != 'GN':
+            raise NotImplementedError(f'{name}: norm_cfg={norm_cfg!r}; the towers run conv + GroupNorm + ReLU, only GN is '
+                                      'supported')
+        loss_cls = kwargs.get('loss_cls', dict(type='CrossEntropyLoss', use_sigmoid=True))
+        loss_bbox = kwargs.get('loss_bbox', dict(type='SmoothL1Loss'))
+        if loss_cls.get('type') != 'QualityFocalLoss' or not loss_cls.get('use_sigmoid', True):
+            raise NotImplementedError(f'{name}: loss_cls={loss_cls!r}; only the sigmoid QualityFocalLoss is supported')
+        if loss_cls.get('beta', 2.0) < 1:
+            raise NotImplementedError(f"{name}: loss_cls.beta={loss_cls.get('beta')} < 1: the derivative of |quality - "
+                                      'sigmoid|^beta is unbounded where the two meet')
+        if loss_bbox.get('type') != 'GIoULoss':
+            raise NotImplementedError(f'{name}: loss_bbox={loss_bbox!r}; only GIoULoss on the decoded boxes is supported')
+        if loss_dfl.get('type') != 'DistributionFocalLoss':
+            raise NotImplementedError(f'{name}: loss_dfl={loss_dfl!r}; only DistributionFocalLoss is supported')
+        if not (isinstance(reg_max, int) and 1 <= reg_max <= self.MAX_REG):
+            raise ValueError(f'{name}: reg_max={reg_max} outside [1, {self.MAX_REG}]')
+        self._check_atss_train_cfg(name, kwargs.get('train_cfg'), kwargs.get('feat_channels', 256))
+        self.stacked_convs, self.conv_cfg, self.norm_cfg, self.reg_max = stacked_convs, conv_cfg, norm_cfg, reg_max
+        super().__init__(num_classes, in_channels, init_cfg=init_cfg, **kwargs)
+        self._check_one_square_anchor(name)
+        self.sampling = False
+        self.integral = Integral(self.reg_max)
+        self.loss_dfl = build_loss(loss_dfl)
+        for loss in (self.loss_cls, self.loss_bbox, self.loss_dfl):
+            if loss.reduction != 'mean':
+                raise NotImplementedError(f"{name}: {type(loss).__name__}.reduction={loss.reduction!r}; only 'mean'")
+        if self.test_cfg:
+            self._check_test_cfg(self.test_cfg)
+        self.strides = [int(s[0]) for s in self.anchor_generator.strides]
+        self.init_weights()
+
+    def _init_layers(self):
+        self._init_towers()
+        self.gfl_cls = nn.Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
+        self.gfl_reg = nn.Conv2d(self.feat_channels, 4 * (self.reg_max + 1), 3, padding=1)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.anchor_generator.strides])
+
+    def init_weights(self):
+        """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name='gfl_cls', bias_prob=0.01))
+        (gfl_head.py:94-102)"""
+        self._init_normal(self.gfl_cls)
+
+    # ------------------------------------------------------------------ forward
+    def _head_groups(self):
+        return (self.gfl_cls,), (self.gfl_reg,)
+
+    def _layout(self, a, r):
+        return ops.GflLayout(a, r, self.cls_out_channels, self.reg_max)
+
+    def _score_rows(self, a, r, layout):
+        """GFL has no centerness: the top-k ranks by max_c sigmoid(cls_c)"""
+        return ops.gfl_score(a, layout)
+
+    def forward_nhwc(self, feats):
+        """list of (B,h,w,C) -> (cls (B,h,w,C), bbox_pred (B,h,w,4 * (reg_max + 1)) scaled logits) lists, fp32"""
+        from .autograd import wants_grad
+        if not feats[0].is_cuda:
+            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
+            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
+        B = feats[0].shape[0]
+        if wants_grad(feats[0], self.gfl_cls.weight, self.cls_convs[0].conv.weight):
+            a, r, sizes = self.forward_head_fused(list(feats))
+        else:
+            a, r, sizes = self.forward_rows(list(feats))
+        C, W = self.cls_out_channels, 4 * (self.reg_max + 1)
+        cls, reg = [], []
+        for l, (va, vr) in enumerate(self._level_views(a, r, sizes, B)):
+            cls.append(va[..., :C])
+            reg.append(vr[..., :W] * self.scales[l].scale)
+        return cls, reg
+
+    def forward(self, feats):
+        """reference signature (gfl_head.py:154-196): list of (N,C,h,w) -> lists of (N,C,h,w) class logits and
+        (N,4 * (reg_max + 1),h,w) box logits after the Scale"""
+        if not feats[0].is_cuda:        # host mirror on torch ops
+            import torch.nn.functional as F
+            cls, reg = [], []
+            for x, scale in zip(feats, self.scales):
+                c, r = self._towers_host(x)
+                cls.append(F.conv2d(c, self.gfl_cls.weight, self.gfl_cls.bias, padding=1))
+                reg.append((F.conv2d(r, self.gfl_reg.weight, self.gfl_reg.bias, padding=1) * scale.scale).float())
+            return cls, reg
+        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
+        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
+
+    @staticmethod
+    def anchor_center(anchors):
+        """gfl_head.py:198-209"""
+        return torch.stack([(anchors[..., 2] + anchors[..., 0]) / 2, (anchors[..., 3] + anchors[..., 1]) / 2], dim=-1)
+
+    # ------------------------------------------------------------------ test
+    def _decode_candidates(self, picked, a, r, layout, scales, sizes, max_shape, sf, cfg):
+        return ops.gfl_decode_levels(picked, a, r, layout, scales, sizes, self.strides, self._base_table(), max_shape, sf,
+                                     cfg.score_thr)
+
+    @staticmethod
+    def _rows_from_reference(cls_scores, bbox_preds):
+        """the reference-signature tensors (box logits after the Scale) as the kernels' (A, R) rows, to be read with unit
+        scales"""
+        rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float()   # noqa: E731
+        return rows(cls_scores).contiguous(), rows(bbox_preds).contiguous()
+
+    def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False, with_nms=True, batched_nms=None):
+        """reference signature (base_dense_head / gfl_head.py:373-472): per-level (N,C,h,w) / (N,4 * (reg_max + 1),h,w) ->
+        per image (dets (k,5), labels (k,)).  Device tensors take `get_bboxes_rows`; CPU tensors the reference's chain on
+        torch ops, with the caller's `batched_nms` (this package's NMS is a device kernel)."""
+        return self._get_bboxes((cls_scores, bbox_preds), img_metas, cfg, rescale, with_nms, batched_nms)
+
+    def _get_bboxes_host(self, cls_scores, bbox_preds, img_metas, cfg, rescale, batched_nms):
+        B, C = cls_scores[0].shape[0], self.cls_out_channels
+        anchors_l = self.anchor_generator.grid_anchors([c.shape[-2:] for c in cls_scores], cls_scores[0].device)
+        nms_pre = cfg.get('nms_pre', -1)
+        out = []
+        for b in range(B):
+            boxes_l, scores_l = [], []
+            h, w = img_metas[b]['img_shape'][:2]
+            for cls, reg, stride, anchors in zip(cls_scores, bbox_preds, self.strides, anchors_l):
+                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
+                d = self.integral(reg[b].detach().permute(1, 2, 0)) * stride
+                if 0 < nms_pre < s.shape[0]:
+                    _, idx = s.max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
+                    idx = idx[:nms_pre]
+                    anchors, d, s = anchors[idx], d[idx], s[idx]
+                box = distance2bbox(self.anchor_center(anchors), d)
+                boxes_l.append(torch.stack([box[:, 0].clamp(0, w), box[:, 1].clamp(0, h), box[:, 2].clamp(0, w),
+                                            box[:, 3].clamp(0, h)], -1))
+                scores_l.append(s)
+            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), None, img_metas[b], cfg, rescale, batched_nms))
+        return out
+
+    # ------------------------------------------------------------------ train
+    def loss_fused(self, a, r, scales, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
+        """GFLHead.loss on the fused head outputs of all levels: ATSS's whole-batch adaptive assignment, then the loss
+        kernels -- targets, qualities, weights and both normalisers are formed on the device (averaged over ranks there
+        when distributed), nothing is read back.  Returns the reference's per-level lists; `self.last_targets` keeps
+        (gt_inds, coef3, norm2)."""
+        from . import train_ops
+        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
+        gts, labels = gts.to(a.device), labels.to(a.device)
+        B = len(img_metas)
+        sizes = [tuple(int(v) for v in s) for s in sizes]
+        base = self._base_table()
+        gt_inds = train_ops.atss_assign(gts, offs, B, sizes, self.strides, base, self.assigner.topk,
+                                        valid_cells(self.anchor_generator, sizes, img_metas, a))
+        meta = train_ops.GflLossMeta(B, sizes, self.strides, base, self.reg_max, self.cls_out_channels, offs,
+                                     self.loss_cls.beta, self.loss_bbox.eps, self.loss_cls.loss_weight,
+                                     self.loss_bbox.loss_weight, self.loss_dfl.loss_weight)
+        losses, coef, norm2 = train_ops.gfl_loss(a, r, scales, gt_inds, gts, labels, self._layout(a, r), meta,
+                                                 self._norm_hook())
+        self.last_targets = (gt_inds, coef, norm2)
+        return dict(loss_cls=list(losses[0].unbind(0)), loss_bbox=list(losses[1].unbind(0)),
+                    loss_dfl=list(losses[2].unbind(0)))
+
+    def get_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
+                    gt_labels_list=None, label_channels=1, unmap_outputs=True):
+        """gfl_head.py:474-536 on torch ops (the host mirror): ATSSHead's targets with the ground-truth boxes themselves
+        as the box targets"""
+        return self._atss_targets(anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list,
+                                  gt_labels_list, label_channels, unmap_outputs, encode=False)
+
+    def loss_single(self, anchors, cls_score, bbox_pred, labels, label_weights, bbox_targets, stride, num_total_samples):
+        """gfl_head.py:211-297, everything in units of the stride"""
+        anchors = anchors.reshape(-1, 4)
+        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
+        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4 * (self.reg_max + 1))
+        bbox_targets, labels, label_weights = bbox_targets.reshape(-1, 4), labels.reshape(-1), label_weights.reshape(-1)
+        pos_inds = ((labels >= 0) & (labels < self.num_classes)).nonzero().squeeze(1)
+        score = label_weights.new_zeros(labels.shape)
+        if len(pos_inds) > 0:
+            centers = self.anchor_center(anchors[pos_inds]) / stride
+            weight = cls_score.detach().sigmoid().max(dim=1)[0][pos_inds]
+            pos_pred = bbox_pred[pos_inds]
+            decoded = distance2bbox(centers, self.integral(pos_pred))
+            target = bbox_targets[pos_inds] / stride
+            score[pos_inds] = bbox_overlaps(decoded.detach(), target, is_aligned=True)
+            loss_bbox = self.loss_bbox(decoded, target, weight=weight, avg_factor=1.0)
+            loss_dfl = self.loss_dfl(pos_pred.reshape(-1, self.reg_max + 1),
+                                     bbox2distance(centers, target, self.reg_max).reshape(-1),
+                                     weight=weight[:, None].expand(-1, 4).reshape(-1), avg_factor=4.0)
+        else:
+            loss_bbox, loss_dfl = bbox_pred.sum() * 0, bbox_pred.sum() * 0
+            weight = bbox_pred.new_tensor(0)
+        loss_cls = self.loss_cls(cls_score, (labels, score), weight=label_weights, avg_factor=num_total_samples)
+        return loss_cls, loss_bbox, loss_dfl, weight.sum()
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        """gfl_head.py:299-371.  Device tensors go to the HIP kernels (`loss_fused`, with unit scales on the scaled logits);
+        CPU tensors take the reference's chain in torch (the host mirror)."""
+        assert len(cls_scores) == len(bbox_preds)
+        featmap_sizes = [tuple(int(v) for v in f.size()[-2:]) for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        device = cls_scores[0].device
+        if device.type == 'cuda':
+            self._refuse_ignore(gt_bboxes_ignore)
+            a, r = self._rows_from_reference(cls_scores, bbox_preds)
+            return self.loss_fused(a, r, a.new_ones(len(featmap_sizes)), featmap_sizes, gt_bboxes, gt_labels, img_metas)
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
+        self._all_valid = None
+        targets = self.get_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore, gt_labels,
+                                   label_channels=self.cls_out_channels)
+        if targets is None:
+            return None
+        anchors, labels, label_weights, bbox_targets, _, num_total_pos, _ = targets
+        num_total_samples = max(reduce_mean(torch.tensor(num_total_pos, dtype=torch.float, device=device)).item(), 1.0)
+        losses_cls, losses_bbox, losses_dfl, factors = multi_apply(
+            self.loss_single, anchors, cls_scores, bbox_preds, labels, label_weights, bbox_targets, self.strides,
+            num_total_samples=num_total_samples)
+        avg = reduce_mean(sum(factors)).clamp_(min=1).item()
+        return dict(loss_cls=losses_cls, loss_bbox=[x / avg for x in losses_bbox], loss_dfl=[x / avg for x in losses_dfl])

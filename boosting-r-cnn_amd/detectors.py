@@ -610,3 +610,11 @@ class ATSS(SingleStageDetector):
 
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)
+
+
+@DETECTORS.register_module()
+class GFL(SingleStageDetector):
+    """mmdet/models/detectors/gfl.py:6-17"""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)

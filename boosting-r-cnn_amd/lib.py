@@ -215,6 +215,14 @@ SIGNATURES = {
     'brcnn_atss_loss_finalize': (c_int, [c_ptr, c_size, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int] + [c_ptr] * 4),
     'brcnn_atss_loss_backward': (c_int, [c_ptr] * 4 + [c_int, c_int] + [c_ptr] * 4 + [c_int] + [c_ptr] * 8 +
                                  [c_size] + [c_ptr] * 4),
+    'brcnn_gfl_decode_levels': (c_int, [c_ptr] * 6 + [c_int, c_int] + [c_ptr] * 4 + [c_int, c_int, c_ptr, c_ptr, c_f32] +
+                                [c_ptr] * 6),
+    'brcnn_gfl_loss_workspace_bytes': (c_size, [c_int, c_int, c_ptr, c_ptr, c_int]),
+    'brcnn_gfl_loss_forward': (c_int, [c_ptr] * 4 + [c_int, c_int] + [c_ptr] * 4 + [c_int, c_int] + [c_ptr] * 6 +
+                               [c_size, c_ptr, c_ptr]),
+    'brcnn_gfl_loss_finalize': (c_int, [c_ptr, c_size, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int] + [c_ptr] * 4),
+    'brcnn_gfl_loss_backward': (c_int, [c_ptr] * 4 + [c_int, c_int] + [c_ptr] * 4 + [c_int, c_int] + [c_ptr] * 8 +
+                                [c_size] + [c_ptr] * 4),
     'brcnn_coco_order_workspace_bytes': (c_size, [c_i64]),
     'brcnn_coco_match': (c_int, [c_ptr] * 6 + [c_int, c_int, c_ptr, c_int, c_ptr, c_int, c_int] + [c_ptr] * 7),
     'brcnn_coco_order': (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_size, c_ptr]),

@@ -295,6 +295,53 @@ class SmoothL1Loss(_LossModule):
         return torch.where(d < self.beta, 0.5 * d * d / self.beta, d - 0.5 * self.beta)
 
 
+# ----------------------------------------------------------------------------- generalized focal loss
+def quality_focal_loss(pred, target, beta=2.0):
+    """gfocal_loss.py:10-52, unreduced per sample: pred (N, C) logits, target = (label (N,), score (N,)).  Every element
+    is supervised by quality 0, BCE(x, 0) * sigmoid(x)^beta; at the label of a foreground sample (0 <= label < C) by the
+    sample's quality score, BCE(x, score) * |score - sigmoid(x)|^beta"""
+    assert len(target) == 2, 'the target of QFL is the (category label, quality score) pair'
+    label, score = target
+    p = pred.sigmoid()
+    loss = F.binary_cross_entropy_with_logits(pred, torch.zeros_like(pred), reduction='none') * p.pow(beta)
+    pos = ((label >= 0) & (label < pred.size(1))).nonzero().squeeze(1)
+    pos_label = label[pos].long()
+    diff = score[pos] - p[pos, pos_label]
+    loss[pos, pos_label] = F.binary_cross_entropy_with_logits(pred[pos, pos_label], score[pos], reduction='none') * \
+        diff.abs().pow(beta)
+    return loss.sum(dim=1)
+
+
+def distribution_focal_loss(pred, label):
+    """gfocal_loss.py:55-78, unreduced: pred (N, n + 1) logits of the distribution over {0 .. n}, label (N,) the target
+    distance in [0, n): the cross entropies of the two bins around it, each weighted by its closeness to the target"""
+    left = label.long()
+    right = left + 1
+    return F.cross_entropy(pred, left, reduction='none') * (right.float() - label) + \
+        F.cross_entropy(pred, right, reduction='none') * (label - left.float())
+
+
+@LOSSES.register_module()
+class QualityFocalLoss(_LossModule):
+    """the class loss of GFLHead; `target` is the (label, score) pair"""
+
+    def __init__(self, use_sigmoid=True, beta=2.0, reduction='mean', loss_weight=1.0):
+        super().__init__(reduction, loss_weight)
+        assert use_sigmoid is True, 'Only sigmoid in QFL supported now.'
+        self.use_sigmoid, self.beta = use_sigmoid, beta
+
+    def term(self, pred, target):
+        return quality_focal_loss(pred, target, beta=self.beta)
+
+
+@LOSSES.register_module()
+class DistributionFocalLoss(_LossModule):
+    """the loss of GFLHead's box distributions, one row per box side"""
+
+    def term(self, pred, target):
+        return distribution_focal_loss(pred, target)
+
+
 # ----------------------------------------------------------------------------- accuracy
 def accuracy(pred, target, topk=1, thresh=None):
     """accuracy.py:6-51: top-k accuracy in percent (an int `topk` gives one tensor, a tuple a list)"""

@@ -1397,6 +1397,51 @@ def atss_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, base_
     return d.outs
 
 
+# --------------------------------------------------------------------------- GFL head, test time
+GFL_MAX_REG = 16
+
+
+class GflLayout:
+    """where the GFL kernels find the head outputs: A (rows, stride_a) with the C class logits at `cls_off`, R (rows,
+    stride_r) with the 4 * (reg_max + 1) raw box logits at `reg_off` (include/brcnn_hip.h: layout4_host)"""
+
+    def __init__(self, a, r, num_classes, reg_max, cls_off=0, reg_off=0):
+        import ctypes
+        _require_gpu(a, r)
+        for t in (a, r):
+            assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous()
+        assert a.shape[0] == r.shape[0]
+        c, n = int(num_classes), int(reg_max)
+        if not 1 <= n <= GFL_MAX_REG:
+            raise ValueError(f'gfl: reg_max={reg_max} outside [1, {GFL_MAX_REG}]')
+        assert 0 <= cls_off and cls_off + c <= a.shape[1] and 0 <= reg_off and reg_off + 4 * (n + 1) <= r.shape[1]
+        self.C, self.reg_max, self.rows = c, n, int(a.shape[0])
+        self.values = (int(a.shape[1]), int(cls_off), int(r.shape[1]), int(reg_off))
+        self.arr = (ctypes.c_int * 4)(*self.values)
+
+
+def gfl_score(a, layout):
+    """max_c sigmoid(cls_c) per row of A -- GFL ranks by the class score alone --: `dense_score` with one anchor per cell,
+    reading the class columns of A in place.  (rows,) dense fp32, the input of `rpn_topk` once split by level"""
+    off = layout.values[1]
+    return dense_score(a[:, off:off + layout.C], 1, layout.C).view(-1)
+
+
+def gfl_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, base_anchors, max_shape, scale_factor, score_thr):
+    """The candidates of multiclass_nms for all levels and images in one launch (brcnn_gfl_decode_levels): per side the
+    expectation of the softmax over the reg_max + 1 scaled logits, times the stride, laid from the centre of the picked
+    cell's anchor; clipped to max_shape (B, 2), divided by scale_factor (B, 4) unless None.  base_anchors:
+    `atss_base_anchors`.  Returns boxes (B,T*C,4), scores (B,T*C) = class sigmoid, labels (B,T*C) int64, valid (B,T*C) bool =
+    score > score_thr, n_valid (B,) int32; (level, pick, class) order."""
+    d = _DecodeLevels(topk_inds, layout.C, max_shape, scale_factor, a.device)
+    assert len(base_anchors) == 4 * d.L
+    st = _L.load().brcnn_gfl_decode_levels(
+        *d.rows_head(a, r, layout, scales, feat_hws, strides), base_anchors, d.c, layout.reg_max, _ptr(max_shape),
+        _ptr(scale_factor), float(score_thr), *d.out_ptrs, _stream())
+    _L.check(st, 'brcnn_gfl_decode_levels')
+    return d.outs
+
+
 # --------------------------------------------------------------------------- Cascade R-CNN, test time
 def _rows_in_place(t):
     """a fp32 (rows, cols) device tensor the cascade kernels read with a row stride: the two column blocks of the heads'

@@ -682,6 +682,28 @@ def atss_loss(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook=Non
 
 
 
+# ----------------------------------------------------------------------------- GFL head: loss
+class GflLossMeta(CenternessLossMeta):
+    """the GFL loss call: the base anchors of the pyramid and reg_max; per-level losses [loss_cls, loss_bbox, loss_dfl]
+    (include/brcnn_hip.h: cfg5_host).  The assignment is `atss_assign`; `layout` is an `ops.GflLayout`."""
+
+    kind, per_level = 'gfl', True
+
+    def __init__(self, batch, sizes, strides, base_anchors, reg_max, num_classes, gt_offsets, beta, eps, lw_cls, lw_bbox,
+                 lw_dfl):
+        super().__init__(batch, sizes, strides, num_classes, gt_offsets, [beta, eps, lw_cls, lw_bbox, lw_dfl])
+        assert len(base_anchors) == 4 * self.L
+        self.base, self.reg_max = base_anchors, int(reg_max)
+        self.extra = (base_anchors, self.reg_max)
+
+
+def gfl_loss(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook=None):
+    """(losses (3, L), coef3, norm2 = [sum of max(n_pos, 1), sum of the positives' weights]); `norm_hook(norm2)` may change
+    norm2 in place between the sums and the division (the mean over ranks)"""
+    assert layout.reg_max == meta.reg_max
+    return CenternessLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
+
+
 # ----------------------------------------------------------------------------- boosting loss
 class BoostLossFunction(Function):
     """out3 = [loss_cls, loss_bbox, acc] of the boosting-reweighted R-CNN loss

@@ -1360,6 +1360,57 @@ int brcnn_atss_loss_backward(const float *a, const float *r, const int *layout8_
                              float *da, float *dr, float *dscale, void *stream);
 
 /* ------------------------------------------------------------------------------
+ * The GFL head: GFLHead with QualityFocalLoss / DistributionFocalLoss (models/dense_heads/gfl_head.py,
+ * models/losses/gfocal_loss.py), csrc/gfl_head.hip.  ONE anchor per cell as for the ATSS head (base_anchors_host (L, 4)); only
+ * its centre ((x1 + x2) / 2, (y1 + y2) / 2) is used.  The head outputs are two fp32 row tensors over all levels, level-major
+ * rows, read in place: A (rows, stride_a) with the C class logits at column cls_off, R (rows, stride_r) with the 4 *
+ * (reg_max + 1) RAW box logits at column reg_off, side-major [left | top | right | bottom].  layout4_host = [stride_a,
+ * cls_off, stride_r, reg_off].  scales: (L) floats ON THE DEVICE; logit = scale_l * raw.  A side's distance is the
+ * expectation sum p_i * i of the max-subtracted softmax over its reg_max + 1 logits; the exp sum and the expectation are
+ * accumulated in bin order.  1 <= reg_max <= 16.  The per-anchor ranking score max_c sigmoid(cls_c) is brcnn_dense_score
+ * with one anchor per cell, reading A in place; the assignment is brcnn_atss_assign.
+ *   brcnn_gfl_decode_levels: everything between the top-k and multiclass_nms (gfl_head.py:373-472) as
+ *     brcnn_fcos_decode_levels does it: box = (cx - d0 * s, cy - d1 * s, cx + d2 * s, cy + d3 * s) with s = stride_l, clipped
+ *     to max_shape, divided by scale_factor; score = sigmoid(cls_c), valid = score > score_thr; (level, pick, class) order.
+ *   brcnn_gfl_loss_forward / _finalize / _backward: GFLHead.loss (gfl_head.py:211-371), the targets formed in the kernel from
+ *     gt_inds (brcnn_atss_assign's convention; < 0: weight 0), everything in units of the stride.  Per positive: centre /
+ *     stride, target = gt / stride, decoded box from the four integrals, quality = aligned bbox_overlaps(decoded, target)
+ *     (eps 1e-6) and weight = max_c sigmoid(cls_c), both constants; box loss weight * (1 - giou); DFL with t =
+ *     clamp(distance to the target side, 0, reg_max - 0.1), left = floor(t): (CE(left) * (left + 1 - t) + CE(left + 1) *
+ *     (t - left)) summed over the sides, * weight / 4.  Class term over every (anchor, class) of a valid cell: BCE(x, 0) *
+ *     sigmoid(x)^beta, at a positive's label BCE(x, quality) * |quality - sigmoid(x)|^beta; beta >= 1.  forward leaves block
+ *     partials and norm2 = [sum over images of max(n_pos, 1), sum of the positives' weights] on the device (the caller may
+ *     average norm2 over ranks); finalize forms N = max(norm2[0], 1), S = max(norm2[1], 1), losses (3, L) = [lw_cls * qfl_l
+ *     / N | lw_bbox * box_l / S | lw_dfl * dfl_l / S] per level and coef3 = [lw_cls / N, lw_bbox / S, lw_dfl / S]; backward
+ *     takes grad_losses (3, L) and writes every element of dA and dR (w.r.t. the RAW outputs: the GIoU gradient through
+ *     decode, expectation, softmax and scale, the DFL gradient through the log-softmax and the scale; padding columns and
+ *     rows of invalid cells exactly 0) and dscale (L).  Fixed summation order, no float atomics.
+ * cfg5_host = [QFL beta, giou eps, loss_weight_cls, loss_weight_bbox, loss_weight_dfl].  workspace:
+ * brcnn_gfl_loss_workspace_bytes, shared by forward and finalize; backward takes one of the same size.  At most
+ * BRCNN_MAX_LEVELS levels and BRCNN_MAX_IMAGES images.
+ * -------------------------------------------------------------------------- */
+int brcnn_gfl_decode_levels(const int64_t *const *topk_inds, const int *counts, const float *a, const float *r,
+                            const int *layout4_host, const float *scales, int batch, int num_levels, const int *heights,
+                            const int *widths, const int *strides, const float *base_anchors_host, int num_classes,
+                            int reg_max, const float *max_shape, const float *scale_factor, float score_thr, float *boxes,
+                            float *scores, int64_t *labels, uint8_t *valid, int32_t *n_valid, void *stream);
+size_t brcnn_gfl_loss_workspace_bytes(int batch, int num_levels, const int *heights, const int *widths, int num_classes);
+int brcnn_gfl_loss_forward(const float *a, const float *r, const int *layout4_host, const float *scales, int batch,
+                           int num_levels, const int *heights, const int *widths, const int *strides,
+                           const float *base_anchors_host, int reg_max, int num_classes, const int32_t *gt_inds,
+                           const float *gts, const int64_t *gt_labels, const int *gt_offsets_host, const float *cfg5_host,
+                           void *workspace, size_t workspace_bytes, float *norm2, void *stream);
+int brcnn_gfl_loss_finalize(const void *workspace, size_t workspace_bytes, const float *norm2, int batch, int num_levels,
+                            const int *heights, const int *widths, int num_classes, const float *cfg5_host, float *losses,
+                            float *coef3, void *stream);
+int brcnn_gfl_loss_backward(const float *a, const float *r, const int *layout4_host, const float *scales, int batch,
+                            int num_levels, const int *heights, const int *widths, const int *strides,
+                            const float *base_anchors_host, int reg_max, int num_classes, const int32_t *gt_inds,
+                            const float *gts, const int64_t *gt_labels, const int *gt_offsets_host, const float *cfg5_host,
+                            const float *grad_losses, const float *coef3, void *workspace, size_t workspace_bytes, float *da,
+                            float *dr, float *dscale, void *stream);
+
+/* ------------------------------------------------------------------------------
  * Optimizer step of the train loop: SGD with momentum and weight decay after clipping the global gradient
  * norm (torch.optim.SGD + mmcv OptimizerHook grad_clip; configs/_base_/schedules/schedule_1x.py:2-3,
  * configs/boosting_rcnn/boosting_rcnn_r50_pafpn_1x_utdac.py:130), as three stages over tables of tensors
