@@ -1023,13 +1023,15 @@ class DeformIm2colFunction(Function):
     accumulated in fp32 and rounded once)"""
 
     @staticmethod
-    def forward(ctx, x, om, stride, pad, deform_groups=1, modulated=True):
+    def forward(ctx, x, om, stride, pad, deform_groups=1, modulated=True, ordered=False):
+        """`ordered`: dx through brcnn_deform_col2im_nhwc_ordered (integer accumulation: the same bits from run to run)"""
         _require_gpu(x, om)
         x, om = x.contiguous(), om.contiguous()
         assert om.shape[3] == (27 if modulated else 18) * deform_groups and om.dtype == torch.float32
         col, (ho, wo) = ops.deform_im2col_nhwc(x, om, 3, stride, pad, 1, None, deform_groups, modulated)
         ctx.save_for_backward(x, om)
         ctx.cfg = (stride, pad, deform_groups, modulated)
+        ctx.ordered = bool(ordered)
         return col
 
     @staticmethod
@@ -1039,19 +1041,19 @@ class DeformIm2colFunction(Function):
         stride, pad, groups, modulated = ctx.cfg
         n, h, w, c = x.shape
         dcol = dcol.float().contiguous()
-        if groups != 1 or not modulated or x.dtype != torch.float32:
-            dx, dom = ops.deform_col2im_nhwc(x, om, dcol, stride, pad, groups, modulated)
-            return dx.to(x.dtype), dom, None, None, None, None
+        if groups != 1 or not modulated or x.dtype != torch.float32 or ctx.ordered:
+            dx, dom = ops.deform_col2im_nhwc(x, om, dcol, stride, pad, groups, modulated, ctx.ordered)
+            return dx.to(x.dtype), dom, None, None, None, None, None
         dx = torch.zeros_like(x)
         dom = torch.empty_like(om)
         st = _L.load().brcnn_deform_col2im_nhwc(_ptr(x), _ptr(om), _ptr(dcol), _ptr(dx), _ptr(dom), n, h, w, c, 3, 3,
                                                 int(stride), int(pad), 1, 27, c, _stream())
         _L.check(st, 'brcnn_deform_col2im_nhwc')
-        return dx, dom, None, None, None, None
+        return dx, dom, None, None, None, None, None
 
 
-def deform_im2col_autograd(x, om, stride, pad, deform_groups=1, modulated=True):
-    return DeformIm2colFunction.apply(x, om, stride, pad, deform_groups, modulated)
+def deform_im2col_autograd(x, om, stride, pad, deform_groups=1, modulated=True, ordered=False):
+    return DeformIm2colFunction.apply(x, om, stride, pad, deform_groups, modulated, ordered)
 
 
 class DeformConvFunction(Function):
@@ -1064,7 +1066,9 @@ class DeformConvFunction(Function):
     kernel.  (fp32 keeps DeformIm2colFunction + linear_autograd.)"""
 
     @staticmethod
-    def forward(ctx, x, om, weight, stride, pad, deform_groups=1, modulated=True, route=False):
+    def forward(ctx, x, om, weight, stride, pad, deform_groups=1, modulated=True, route=False, relu=False, ordered=False):
+        """`relu`: ReLU in the read-out of the kernel that runs (the backward masks dy with the saved output); `ordered`: dx
+        through brcnn_deform_col2im_nhwc_ordered (integer accumulation: the same bits from run to run)"""
         _require_gpu(x, om, weight)
         if x.dtype not in (torch.bfloat16, torch.float16):
             raise _L.BrcnnHipError(f'DeformConvFunction: bf16 / fp16 activations (got {x.dtype})')
@@ -1073,11 +1077,15 @@ class DeformConvFunction(Function):
         w_p = weight.detach().permute(0, 2, 3, 1).to(x.dtype).contiguous()        # (Cout,3,3,Cp), K order (tap, c)
         cout, cp = w_p.shape[0], w_p.shape[3]
         if not route or ops.deform_conv_route(x, cout, stride, pad, deform_groups):
-            y = ops.deform_conv_nhwc(x, om, w_p, None, None, False, stride, pad, deform_groups, modulated)
+            y = ops.deform_conv_nhwc(x, om, w_p, None, None, bool(relu), stride, pad, deform_groups, modulated)
         else:
             col, (ho, wo) = ops.deform_im2col_nhwc(x, om, 3, stride, pad, 1, None, deform_groups, modulated)
-            y = ops.linear_nhwc(col, w_p.view(cout, 9 * cp)).view(x.shape[0], ho, wo, cout)
-        ctx.save_for_backward(x, om)
+            y = ops.linear_nhwc(col, w_p.view(cout, 9 * cp), None, bool(relu)).view(x.shape[0], ho, wo, cout)
+        if relu:
+            ctx.save_for_backward(x, om, y)
+        else:
+            ctx.save_for_backward(x, om)
+        ctx.relu, ctx.ordered = bool(relu), bool(ordered)
         ctx.w_p = w_p
         ctx.cfg = (stride, pad, deform_groups, modulated)
         return y
@@ -1085,7 +1093,11 @@ class DeformConvFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dy):
-        x, om = ctx.saved_tensors
+        if ctx.relu:
+            x, om, y = ctx.saved_tensors
+            dy = torch.ops.aten.threshold_backward(dy.to(y.dtype), y, 0)
+        else:
+            x, om = ctx.saved_tensors
         stride, pad, groups, modulated = ctx.cfg
         w_p = ctx.w_p
         n, h, w, cp = x.shape
@@ -1096,8 +1108,8 @@ class DeformConvFunction(Function):
         dx = dom = dw = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             dcol = ops.linear_nhwc(dy, w_p.view(cout, 9 * cp).t().contiguous(), out_f32=True)      # (M, 9 Cp) fp32
-            if groups != 1 or not modulated:
-                dx32, dom = ops.deform_col2im_nhwc(x, om, dcol, stride, pad, groups, modulated)
+            if groups != 1 or not modulated or ctx.ordered:
+                dx32, dom = ops.deform_col2im_nhwc(x, om, dcol, stride, pad, groups, modulated, ctx.ordered)
             else:
                 dx32 = torch.zeros((n, h, w, cp), dtype=torch.float32, device=x.device)
                 dom = torch.empty_like(om)
@@ -1113,11 +1125,11 @@ class DeformConvFunction(Function):
                                                    ops._dt(x), _conv_stream())
             _L.check(st, 'brcnn_conv2d_wgrad_nhwc_multi')
             dw = dwp.view(cout, 3, 3, cp).permute(0, 3, 1, 2)
-        return dx, dom, dw, None, None, None, None, None
+        return dx, dom, dw, None, None, None, None, None, None, None
 
 
-def deform_conv_autograd(x, om, weight, stride, pad, deform_groups=1, modulated=True, route=False):
-    return DeformConvFunction.apply(x, om, weight, stride, pad, deform_groups, modulated, route)
+def deform_conv_autograd(x, om, weight, stride, pad, deform_groups=1, modulated=True, route=False, relu=False, ordered=False):
+    return DeformConvFunction.apply(x, om, weight, stride, pad, deform_groups, modulated, route, relu, ordered)
 
 
 class BnActFunction(Function):

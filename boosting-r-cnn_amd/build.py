@@ -32,7 +32,8 @@ EXTRA_FLAGS = {'roi_align.hip': ['-fno-slp-vectorize'], 'focal_loss.hip': ['-fno
                'deform_conv_bf16.hip': ['-fno-slp-vectorize'], 'tta.hip': ['-fno-slp-vectorize'],
                'rpn_sampled.hip': ['-fno-slp-vectorize'], 'cascade.hip': ['-fno-slp-vectorize'],
                'dense_head.hip': ['-fno-slp-vectorize'], 'fcos_head.hip': ['-fno-slp-vectorize'],
-               'atss_head.hip': ['-fno-slp-vectorize'], 'gfl_head.hip': ['-fno-slp-vectorize']}
+               'atss_head.hip': ['-fno-slp-vectorize'], 'gfl_head.hip': ['-fno-slp-vectorize'],
+               'vfnet_head.hip': ['-fno-slp-vectorize']}
 
 
 def hipcc():

@@ -135,7 +135,57 @@ __global__ __launch_bounds__(256) void deform_im2col_nhwc_kernel(const float* __
 //   d off_h = mask * sum_c dcol_c * d val_c / d h,   d off_w likewise,
 //   d mask_logit = mask (1 - mask) * sum_c dcol_c * val_c          (sigmoid applied in the forward)
 // (16-bit x: the same arithmetic on the widened corners; dx stays an fp32 accumulator the caller converts)
-template <int DT>
+// ORDERED: dx is a table of 64-bit integers and a contribution is added as an integer -- integer addition is associative,
+// so the sums (and, after dx_fixed_to_f32_kernel, dx) carry the same bits from run to run, which fp32 atomics in whatever
+// order the waves arrive do not.  The grid is chosen from the data of the call: a pre-pass takes m = max |dcol| (a maximum
+// does not depend on the order either) and its binary exponent ex (m < 2^ex); a contribution dcol * mask * corner weight is
+// at most m in magnitude (mask and weight lie in [0, 1]) and is scaled by 2^(S - ex), S = 62 - ceil(log2(Ho Wo taps 4)): even
+// if every sample of an image fell on one pixel the sum stays below 2^62, so nothing can overflow.  What it costs: each
+// contribution is rounded to a multiple of 2^(ex - S) <= 2 m 2^-S (S = 41 for a 100 x 168 map, 50 for 6 x 7), i.e. an
+// absolute error of at most m 2^-S per contribution whatever its size; a contribution of at least m 2^(24 - S) keeps the
+// full 24 bits of fp32, one below m 2^-S-1 is dropped.  The two words behind the table hold the bits of m and the shift
+// S - ex; a dcol or a contribution that is not finite sets the shift to ORDERED_POISON and the whole of dx reads NaN, so that
+// an overflowed fp16 step is still seen as one.
+constexpr int ORDERED_POISON = -2147483647 - 1;
+
+__global__ __launch_bounds__(256) void dx_ordered_max_kernel(const float* __restrict__ dcol, long long n,
+                                                            unsigned* __restrict__ tail) {
+    unsigned m = 0u;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        m = max(m, __float_as_uint(dcol[i]) & 0x7fffffffu);       // |v| as bits: ordered like the values, NaN above inf
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d));
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(tail, m);
+}
+
+// tail[1] = S - ex, or ORDERED_POISON when max |dcol| is not finite
+__global__ void dx_ordered_shift_kernel(int* __restrict__ tail, int S) {
+    const unsigned bits = (unsigned)tail[0];
+    int ex = 0;
+    frexpf(__uint_as_float(bits), &ex);
+    tail[1] = bits >= 0x7f800000u ? ORDERED_POISON : S - ex;
+}
+
+template <bool ORDERED>
+__device__ __forceinline__ void dx_add(float* dx, size_t i, float v, int* tail) {
+    if (ORDERED) {
+        const int shift = tail[1];
+        if (shift == ORDERED_POISON) return;
+        if (!isfinite(v)) { atomicMin(tail + 1, ORDERED_POISON); return; }
+        atomicAdd(reinterpret_cast<unsigned long long*>(dx) + i, (unsigned long long)__double2ll_rn(ldexp((double)v, shift)));
+    } else {
+        atomicAdd(dx + i, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void dx_fixed_to_f32_kernel(const long long* __restrict__ acc, float* __restrict__ dx,
+                                                             long long n) {
+    const int shift = reinterpret_cast<const int*>(acc + n)[1];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        dx[i] = shift == ORDERED_POISON ? __builtin_nanf("") : (float)ldexp((double)acc[i], -shift);
+}
+
+template <int DT, bool ORDERED = false>
 __global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const void* __restrict__ x,
                                                                 const float* __restrict__ om,
                                                                 const float* __restrict__ dcol,
@@ -162,6 +212,7 @@ __global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const void* __r
     const float h_im = (float)(ho * stride - pad + i * dilation) + off_h;
     const float w_im = (float)(wo * stride - pad + j * dilation) + off_w;
     const bool inside = h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W;
+    int* bad = ORDERED ? reinterpret_cast<int*>(reinterpret_cast<long long*>(dx) + (size_t)N * H * W * C) : nullptr;    // the tail
     float g_h = 0.f, g_w = 0.f, g_m = 0.f;
     if (inside) {
         const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
@@ -187,10 +238,10 @@ __global__ __launch_bounds__(256) void deform_col2im_nhwc_kernel(const void* __r
                 g_h += gg[e] * (-hw * a1[e] - lw * a2[e] + hw * a3[e] + lw * a4[e]);
                 g_w += gg[e] * (-hh * a1[e] + hh * a2[e] - lh * a3[e] + lh * a4[e]);
                 const float gx = gg[e] * mask;
-                if (ok1) atomicAdd(dx + (((size_t)n * H + h_low) * W + w_low) * C + c + e, gx * hh * hw);
-                if (ok2) atomicAdd(dx + (((size_t)n * H + h_low) * W + w_high) * C + c + e, gx * hh * lw);
-                if (ok3) atomicAdd(dx + (((size_t)n * H + h_high) * W + w_low) * C + c + e, gx * lh * hw);
-                if (ok4) atomicAdd(dx + (((size_t)n * H + h_high) * W + w_high) * C + c + e, gx * lh * lw);
+                if (ok1) dx_add<ORDERED>(dx, (((size_t)n * H + h_low) * W + w_low) * C + c + e, gx * hh * hw, bad);
+                if (ok2) dx_add<ORDERED>(dx, (((size_t)n * H + h_low) * W + w_high) * C + c + e, gx * hh * lw, bad);
+                if (ok3) dx_add<ORDERED>(dx, (((size_t)n * H + h_high) * W + w_low) * C + c + e, gx * lh * hw, bad);
+                if (ok4) dx_add<ORDERED>(dx, (((size_t)n * H + h_high) * W + w_high) * C + c + e, gx * lh * lw, bad);
             }
         }
     }
@@ -476,6 +527,66 @@ BRCNN_API int brcnn_deform_col2im_nhwc_g(const void* x, const float* offset_mask
         hipLaunchKernelGGL(deform_col2im_nhwc_kernel<BRCNN_DT_BF16>, grid, dim3(256), 0, s, x, offset_mask, dcol, dx,
                            d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride,
                            channels_padded, deform_groups, modulated);
+    BRCNN_LAUNCH_CHECK();
+    return 0;
+}
+
+// brcnn_deform_col2im_nhwc_g with dx accumulated in integers (ORDERED above): the same bits from run to run.  workspace:
+// 8 bytes per element of dx and the two tail words; every element of dx is written
+BRCNN_API size_t brcnn_deform_col2im_ordered_workspace_bytes(int batch, int height, int width, int channels) {
+    if (batch <= 0 || height <= 0 || width <= 0 || channels <= 0) return 0;
+    return ((size_t)batch * height * width * channels + 1) * sizeof(long long);      // + the tail: bits of max |dcol|, shift
+}
+
+BRCNN_API int brcnn_deform_col2im_nhwc_ordered(const void* x, const float* offset_mask, const float* dcol, float* dx,
+                                               float* d_offset_mask, int batch, int height, int width, int channels, int kh,
+                                               int kw, int stride, int pad, int dilation, int om_stride, int channels_padded,
+                                               int deform_groups, int modulated, int dtype, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    if (!dcol || !dx || !d_offset_mask || !workspace ||
+        !deform_g_args_ok(x, offset_mask, batch, height, width, channels, kh, kw, stride, pad, dilation, channels_padded,
+                          deform_groups, modulated, dtype))
+        return BRCNN_EINVAL;
+    if (om_stride != (modulated ? 3 : 2) * kh * kw * deform_groups) return BRCNN_EINVAL;
+    const size_t need = brcnn_deform_col2im_ordered_workspace_bytes(batch, height, width, channels);
+    if (!need || workspace_bytes < need) return BRCNN_EINVAL;
+    int Ho, Wo;
+    if (!deform_out_size(height, width, kh, kw, stride, pad, dilation, &Ho, &Wo)) return BRCNN_EINVAL;
+    const long long items = (long long)batch * Ho * Wo * kh * kw * deform_groups;
+    if ((items + 3) / 4 >= 0x7fffffffLL) return BRCNN_EINVAL;
+    const dim3 grid((unsigned)((items + 3) / 4));
+    hipStream_t s = (hipStream_t)stream;
+    BRCNN_HIP_CHECK(hipMemsetAsync(workspace, 0, need, s));
+    float* acc = reinterpret_cast<float*>(workspace);
+    const long long n = (long long)batch * height * width * channels;
+    int* tail = reinterpret_cast<int*>(reinterpret_cast<long long*>(workspace) + n);
+    // S: the sum of every sample of one image on one pixel, Ho Wo taps 4 contributions below 2^S each, stays below 2^62
+    const long long pile = (long long)Ho * Wo * kh * kw * 4;
+    int hb = 0;
+    while ((1LL << hb) < pile) hb++;
+    const long long n_dcol = (long long)batch * Ho * Wo * kh * kw * channels_padded;
+    long long gm = (n_dcol + 255) / 256;
+    if (gm > 4096) gm = 4096;
+    hipLaunchKernelGGL(dx_ordered_max_kernel, dim3((unsigned)gm), dim3(256), 0, s, dcol, n_dcol, (unsigned*)tail);
+    BRCNN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(dx_ordered_shift_kernel, dim3(1), dim3(1), 0, s, tail, 62 - hb);
+    BRCNN_LAUNCH_CHECK();
+    if (dtype == BRCNN_DT_F32)
+        hipLaunchKernelGGL((deform_col2im_nhwc_kernel<BRCNN_DT_F32, true>), grid, dim3(256), 0, s, x, offset_mask, dcol, acc,
+                           d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride,
+                           channels_padded, deform_groups, modulated);
+    else if (dtype == BRCNN_DT_F16)
+        hipLaunchKernelGGL((deform_col2im_nhwc_kernel<BRCNN_DT_F16, true>), grid, dim3(256), 0, s, x, offset_mask, dcol, acc,
+                           d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride,
+                           channels_padded, deform_groups, modulated);
+    else
+        hipLaunchKernelGGL((deform_col2im_nhwc_kernel<BRCNN_DT_BF16, true>), grid, dim3(256), 0, s, x, offset_mask, dcol, acc,
+                           d_offset_mask, batch, height, width, channels, Ho, Wo, kh, kw, stride, pad, dilation, om_stride,
+                           channels_padded, deform_groups, modulated);
+    BRCNN_LAUNCH_CHECK();
+    long long g = (n + 255) / 256;
+    if (g > 8192) g = 8192;
+    hipLaunchKernelGGL(dx_fixed_to_f32_kernel, dim3((unsigned)g), dim3(256), 0, s, (const long long*)workspace, dx, n);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }

@@ -1341,43 +1341,63 @@ class GNTowerHead(DenseDetHead):
         outs = []
         for convs, caches, heads, hcache in zip((self.cls_convs, self.reg_convs), self._tower_caches, self._head_groups(),
                                                 self._head_caches):
-            x = x0
-            for m, cache in zip(convs, caches):
-                w = cache.get([m.conv.weight], lambda c=m: pack_weight(c.conv.weight).to(x0.dtype))
-                x, _ = ops.conv2d_nhwc_multi(x, w, B, sizes, None, None, None, False, 1, 1)
-                x = ops.groupnorm_nhwc_multi(x, m.norm.weight.detach(), m.norm.bias.detach(), m.norm.num_groups, B, sizes,
-                                             m.norm.eps, m.with_activation)
-
-            def builder(hs=heads):
-                w = torch.cat([pack_weight(h.weight) for h in hs], 0)
-                b = torch.cat([h.bias.detach().float() for h in hs], 0)
-                pad = -w.shape[0] % 8
-                if pad:
-                    w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
-                    b = torch.cat([b, b.new_zeros(pad)], 0)
-                return w.to(x0.dtype).contiguous(), b.contiguous()
-            w, b = hcache.get([t for h in heads for t in (h.weight, h.bias)], builder)
-            outs.append(ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, False, 1, 1, out_f32=True)[0])
+            outs.append(self._head_rows(self._tower_rows(x0, convs, caches, B, sizes), heads, hcache, B, sizes))
         return outs[0], outs[1], sizes
+
+    @staticmethod
+    def _tower_rows(x, convs, caches, B, sizes):
+        """inference: conv + GroupNorm(+ ReLU) layers over the rows of all levels, one launch each per layer"""
+        dtype = x.dtype
+        for m, cache in zip(convs, caches):
+            w = cache.get([m.conv.weight], lambda c=m: pack_weight(c.conv.weight).to(dtype))
+            x, _ = ops.conv2d_nhwc_multi(x, w, B, sizes, None, None, None, False, 1, 1)
+            x = ops.groupnorm_nhwc_multi(x, m.norm.weight.detach(), m.norm.bias.detach(), m.norm.num_groups, B, sizes,
+                                         m.norm.eps, m.with_activation)
+        return x
+
+    @staticmethod
+    def _head_rows(x, heads, hcache, B, sizes):
+        """inference: the 3x3 convs `heads` as ONE conv with an fp32 result, output columns padded to a multiple of 8"""
+        dtype = x.dtype
+
+        def builder(hs=heads):
+            w = torch.cat([pack_weight(h.weight) for h in hs], 0)
+            b = torch.cat([h.bias.detach().float() for h in hs], 0)
+            pad = -w.shape[0] % 8
+            if pad:
+                w = torch.cat([w, w.new_zeros((pad,) + tuple(w.shape[1:]))], 0)
+                b = torch.cat([b, b.new_zeros(pad)], 0)
+            return w.to(dtype).contiguous(), b.contiguous()
+        w, b = hcache.get([t for h in heads for t in (h.weight, h.bias)], builder)
+        return ops.conv2d_nhwc_multi(x, w, B, sizes, None, b, None, False, 1, 1, out_f32=True)[0]
 
     def forward_head_fused(self, feats):
         """training forward over all levels: (A, R) fp32 with zero padding columns, level-major rows, differentiable, and the
         level sizes"""
-        from .autograd import ConvNHWCFunction, GroupNormNHWCFunction, conv2d_nhwc_multi_autograd, fused_head_weights
         B = feats[0].shape[0]
         sizes = tuple(tuple(int(v) for v in f.shape[1:3]) for f in feats)
         x0 = cat_rows(feats)
-        mult = 32 if x0.dtype == torch.float32 else 64
         outs = []
         for convs, heads in zip((self.cls_convs, self.reg_convs), self._head_groups()):
-            x = x0
-            for m in convs:
-                x = conv2d_nhwc_multi_autograd(x, m.conv.weight, None, B, sizes, 1, 1)
-                x = GroupNormNHWCFunction.apply(x, m.norm.weight, m.norm.bias, m.norm.num_groups, B, sizes, m.norm.eps,
-                                                m.with_activation)
-            w, b = fused_head_weights(heads, mult)
-            outs.append(ConvNHWCFunction.apply(x, w, b, B, sizes, 1, 1, False, False, True))      # fp32 head output
+            outs.append(self._head_fused(self._tower_fused(x0, convs, B, sizes), heads, B, sizes))
         return outs[0], outs[1], sizes
+
+    @staticmethod
+    def _tower_fused(x, convs, B, sizes):
+        """training: `_tower_rows` on the autograd forms of the same kernels"""
+        from .autograd import GroupNormNHWCFunction, conv2d_nhwc_multi_autograd
+        for m in convs:
+            x = conv2d_nhwc_multi_autograd(x, m.conv.weight, None, B, sizes, 1, 1)
+            x = GroupNormNHWCFunction.apply(x, m.norm.weight, m.norm.bias, m.norm.num_groups, B, sizes, m.norm.eps,
+                                            m.with_activation)
+        return x
+
+    @staticmethod
+    def _head_fused(x, heads, B, sizes):
+        """training: `_head_rows`, differentiable (fp32 head output)"""
+        from .autograd import ConvNHWCFunction, fused_head_weights
+        w, b = fused_head_weights(heads, 32 if x.dtype == torch.float32 else 64)
+        return ConvNHWCFunction.apply(x, w, b, B, sizes, 1, 1, False, False, True)
 
     def _towers_host(self, x):
         """the host mirror of the two towers on torch ops: one (N,C,h,w) map -> (class tower, box tower) outputs"""
@@ -2547,3 +2567,428 @@ class GFLHead(GNTowerHead, AnchorHead):
             num_total_samples=num_total_samples)
         avg = reduce_mean(sum(factors)).clamp_(min=1).item()
         return dict(loss_cls=losses_cls, loss_bbox=[x / avg for x in losses_bbox], loss_dfl=[x / avg for x in losses_dfl])
+
+
+# ----------------------------------------------------------------------------- VFNet baseline
+class DeformConv2d(nn.Module):
+    """mmcv.ops.DeformConv2d as VFNetHead uses it: 3x3, stride 1, padding 1, one deform group, no bias -- the only parameter
+    is `weight`; the offsets are an input"""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, 3, 3))
+        nn.init.kaiming_uniform_(self.weight, nonlinearity='relu')
+
+
+def deform_conv2d_host(x, offset, weight):
+    """the host mirror of the DCN v1 deformable 3x3 conv (stride 1, padding 1, one group) on torch ops, differentiable
+    w.r.t. x, offset and weight: x (N, C, H, W), offset (N, 18, H, W) with [2t] = dy, [2t + 1] = dx of tap t, weight (O, C,
+    3, 3).  A sample point outside (-1, H) x (-1, W) is zero, a corner outside the map contributes zero (mmcv's rule)"""
+    N, C, H, W = x.shape
+    ys = torch.arange(H, dtype=x.dtype, device=x.device).view(1, H, 1)
+    xs = torch.arange(W, dtype=x.dtype, device=x.device).view(1, 1, W)
+    flat = x.reshape(N, C, H * W)
+    cols = []
+    for t in range(9):
+        hy = ys + (t // 3 - 1) + offset[:, 2 * t]
+        wx = xs + (t % 3 - 1) + offset[:, 2 * t + 1]
+        inside = (hy > -1) & (wx > -1) & (hy < H) & (wx < W)
+        h0, w0 = hy.detach().floor(), wx.detach().floor()
+        lh, lw = hy - h0, wx - w0
+        val = 0
+        for hh, ww, wt in ((h0, w0, (1 - lh) * (1 - lw)), (h0, w0 + 1, (1 - lh) * lw), (h0 + 1, w0, lh * (1 - lw)),
+                           (h0 + 1, w0 + 1, lh * lw)):
+            ok = inside & (hh >= 0) & (hh <= H - 1) & (ww >= 0) & (ww <= W - 1)
+            idx = (hh.clamp(0, H - 1) * W + ww.clamp(0, W - 1)).long().view(N, 1, H * W).expand(N, C, H * W)
+            val = val + torch.gather(flat, 2, idx).view(N, C, H, W) * torch.where(ok, wt, torch.zeros_like(wt)).unsqueeze(1)
+        cols.append(val)
+    col = torch.stack(cols, 2)                                                      # (N, C, 9, H, W)
+    return torch.einsum('nckhw,ock->nohw', col, weight.reshape(weight.shape[0], C, 9))
+
+
+@HEADS.register_module()
+class VFNetHead(GNTowerHead, AnchorHead):
+    """The head of VarifocalNet (mmdet/models/dense_heads/vfnet_head.py:19-792): two GN towers (`cls_convs.{i}.{conv,gn}`,
+    `reg_convs.{i}.{conv,gn}`); `vfnet_reg_conv` + `vfnet_reg` give a first box per point, D0 = exp(scales.{l}.scale * raw) *
+    reg_denom_l (l, t, r, b) in pixels; the star-shaped deformable convs `vfnet_reg_refine_dconv` (on the box tower's output)
+    and `vfnet_cls_dconv` (on the class tower's) sample nine points of that box; `vfnet_reg_refine` gives the refinement
+    factor, D1 = exp(scales_refine.{l}.scale * raw1) * D0 with D0 a constant, and `vfnet_cls` the IoU-aware class logits.
+    Parameter names and shapes are the reference's.  The towers and the fused fp32 head convs are GNTowerHead's, one launch
+    per layer over all levels; `brcnn_vfnet_star_offsets` forms D0 and the 18 offsets of every cell in one launch; the two
+    deformable convs run per level on the DCN v1 kernels (fp32: im2col + GEMM, 16-bit: the fused kernel where it takes the
+    shape), ReLU in the read-out.  Test time ranks by the class sigmoid (`brcnn_dense_score` on A in place), decodes D1 of the
+    picked rows from their points with the class fan-out (`brcnn_vfnet_decode_levels`) and runs the NMS of the whole batch;
+    training uses ATSS's adaptive assignment (`brcnn_atss_assign`) and `brcnn_vfnet_loss_*`: Varifocal Loss over every (cell,
+    class) -- cells beyond an image's pad_shape count as background, the reference passes no weight --, GIoU on both boxes
+    weighted by their own IoU, targets, weights and the three normalisers formed in the kernels.  Inference reads the host
+    once, the head's train step never (the reference: three `.item()` calls).  CPU tensors take the reference's chain on
+    torch ops (the host mirror the CPU tests compare with the fixture)."""
+
+    INF = 1e8
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, strides=(4, 8, 16, 32, 64), conv_cfg=None,
+                 regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, INF)), center_sampling=False,
+                 center_sample_radius=1.5, sync_num_pos=True, gradient_mul=0.1, bbox_norm_type='reg_denom',
+                 loss_cls_fl=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0), use_vfl=True,
+                 loss_cls=dict(type='VarifocalLoss', use_sigmoid=True, alpha=0.75, gamma=2.0, iou_weighted=True,
+                               loss_weight=1.0),
+                 loss_bbox=dict(type='GIoULoss', loss_weight=1.5), loss_bbox_refine=dict(type='GIoULoss', loss_weight=2.0),
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True), use_atss=True, dcn_on_last_conv=False,
+                 anchor_generator=dict(type='AnchorGenerator', ratios=[1.0], octave_base_scale=8, scales_per_octave=1,
+                                       center_offset=0.0, strides=[8, 16, 32, 64, 128]),
+                 init_cfg=None, **kwargs):
+        name = 'VFNetHead'
+        if not use_atss:
+            raise NotImplementedError(f'{name}: use_atss=False (FCOS targets) is not supported')
+        if not use_vfl:
+            raise NotImplementedError(f'{name}: use_vfl=False (focal loss) is not supported')
+        if dcn_on_last_conv:
+            raise NotImplementedError(f'{name}: dcn_on_last_conv=True is not supported')
+        if not sync_num_pos:
+            raise NotImplementedError(f'{name}: sync_num_pos=False is not supported: the number of positives is averaged over '
+                                      'the ranks and clamped to 1 with the two other normalisers, on the device')
+        if norm_cfg is None or norm_cfg.get('type') != 'GN':
+            raise NotImplementedError(f'{name}: norm_cfg={norm_cfg!r}; the towers run conv + GroupNorm + ReLU, only GN is '
+                                      'supported')
+        if loss_cls.get('type') != 'VarifocalLoss' or not loss_cls.get('use_sigmoid', True):
+            raise NotImplementedError(f'{name}: loss_cls={loss_cls!r}; only the sigmoid VarifocalLoss is supported')
+        if loss_cls.get('gamma', 2.0) < 1:
+            raise NotImplementedError(f"{name}: loss_cls.gamma={loss_cls.get('gamma')} < 1: the derivative of sigmoid^gamma "
+                                      'is unbounded at 0')
+        for key, lb in (('loss_bbox', loss_bbox), ('loss_bbox_refine', loss_bbox_refine)):
+            if lb.get('type') != 'GIoULoss':
+                raise NotImplementedError(f'{name}: {key}={lb!r}; only GIoULoss on the decoded boxes is supported')
+        if bbox_norm_type not in ('reg_denom', 'stride'):
+            raise NotImplementedError(f"{name}: bbox_norm_type={bbox_norm_type!r}; 'reg_denom' or 'stride'")
+        self._check_atss_train_cfg(name, kwargs.get('train_cfg'), kwargs.get('feat_channels', 256))
+        self.stacked_convs, self.conv_cfg, self.norm_cfg = stacked_convs, conv_cfg, norm_cfg
+        self.strides = [int(s) for s in strides]
+        self.regress_ranges = regress_ranges
+        self.reg_denoms = [r[-1] for r in regress_ranges]
+        self.reg_denoms[-1] = self.reg_denoms[-2] * 2
+        self.center_sampling, self.center_sample_radius, self.sync_num_pos = center_sampling, center_sample_radius, sync_num_pos
+        self.gradient_mul, self.bbox_norm_type, self.use_vfl, self.use_atss = gradient_mul, bbox_norm_type, use_vfl, use_atss
+        self.dcn_on_last_conv = dcn_on_last_conv
+        self.anchor_center_offset = anchor_generator.get('center_offset', 0.5)
+        super().__init__(num_classes, in_channels, anchor_generator=anchor_generator, loss_cls=loss_cls, loss_bbox=loss_bbox,
+                         init_cfg=init_cfg, **kwargs)
+        self._check_one_square_anchor(name)
+        if [int(s[0]) for s in self.anchor_generator.strides] != self.strides or len(self.reg_denoms) != len(self.strides):
+            raise ValueError(f'{name}: strides={self.strides}, anchor_generator.strides={self.anchor_generator.strides} and '
+                             f'{len(self.reg_denoms)} regress_ranges must describe the same levels')
+        self.sampling = False
+        self.loss_bbox_refine = build_loss(loss_bbox_refine)
+        for loss in (self.loss_cls, self.loss_bbox, self.loss_bbox_refine):
+            if loss.reduction != 'mean':
+                raise NotImplementedError(f"{name}: {type(loss).__name__}.reduction={loss.reduction!r}; only 'mean'")
+        if self.test_cfg:
+            self._check_test_cfg(self.test_cfg)
+        self.init_weights()
+
+    def _init_layers(self):
+        self._init_towers()
+        C = self.feat_channels
+        self.relu = nn.ReLU(inplace=True)
+        self.vfnet_reg_conv = ConvModule(C, C, 3, stride=1, padding=1, conv_cfg=self.conv_cfg, norm_cfg=self.norm_cfg,
+                                         bias='auto')
+        self.vfnet_reg = nn.Conv2d(C, 4, 3, padding=1)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.strides])
+        self.vfnet_reg_refine_dconv = DeformConv2d(C, C)
+        self.vfnet_reg_refine = nn.Conv2d(C, 4, 3, padding=1)
+        self.scales_refine = nn.ModuleList([Scale(1.0) for _ in self.strides])
+        self.vfnet_cls_dconv = DeformConv2d(C, C)
+        self.vfnet_cls = nn.Conv2d(C, self.cls_out_channels, 3, padding=1)
+        self._vf_caches = {k: PackedCache() for k in ('reg_conv', 'reg', 'refine', 'cls', 'refine_dconv', 'cls_dconv',
+                                                      'scales_refine')}
+
+    def init_weights(self):
+        """init_cfg=dict(type='Normal', layer='Conv2d', std=0.01, override=dict(name='vfnet_cls', bias_prob=0.01))
+        (vfnet_head.py:101-109); the two DeformConv2d are no Conv2d and keep their own initialisation"""
+        self._init_normal(self.vfnet_cls)
+
+    # ------------------------------------------------------------------ forward
+    def _denoms(self):
+        return [float(d) for d in (self.reg_denoms if self.bbox_norm_type == 'reg_denom' else self.strides)]
+
+    def _scales_refine_tensor(self):
+        ps = [s.scale for s in self.scales_refine]
+        return self._vf_caches['scales_refine'].get(
+            ps, lambda: torch.stack([p.detach().float().reshape(()) for p in ps]).contiguous())
+
+    def _check_dcn_channels(self, x):
+        mult = 4 if x.dtype == torch.float32 else 8
+        if self.feat_channels % mult:
+            raise NotImplementedError(f'VFNetHead: feat_channels={self.feat_channels}; the deformable conv kernels take '
+                                      f'channels in multiples of {mult} in {x.dtype}')
+
+    def _star_dconv_rows(self, x, off, m, cache, B, sizes):
+        """inference: relu(star deformable conv) of the rows of all levels, level by level (DCN v1 kernels)"""
+        C = self.feat_channels
+        w = cache.get([m.weight], lambda: pack_weight(m.weight).to(x.dtype).contiguous())
+        sixteen = x.dtype != torch.float32
+        out, r = torch.empty_like(x), 0
+        for h, wd in sizes:
+            n = B * h * wd
+            xl, ol = x[r:r + n].view(B, h, wd, C), off[r:r + n].view(B, h, wd, 18)
+            if sixteen and ops.deform_conv_route(xl, C, 1, 1, 1):
+                out[r:r + n] = ops.deform_conv_nhwc(xl, ol, w, None, None, True, 1, 1, 1, False).view(n, C)
+            else:
+                col, _ = ops.deform_im2col_nhwc(xl, ol, 3, 1, 1, 1, None, 1, False)
+                out[r:r + n] = ops.linear_nhwc(col, w.view(C, 9 * C), None, True)
+            r += n
+        return out
+
+    def _star_dconv_fused(self, x, offs, m, B, sizes):
+        """training: `_star_dconv_rows` through the autograd forms of the same kernels, the input gradient accumulated in
+        integers (`ordered`: a train step carries the same bits from run to run); `offs`: per level (B, h, w, 18)"""
+        from .autograd import deform_conv_autograd, deform_im2col_autograd, linear_autograd
+        C = self.feat_channels
+        outs = []
+        for xl, ol, (h, wd) in zip(torch.split(x, [B * h * wd for h, wd in sizes], 0), offs, sizes):
+            xl = xl.view(B, h, wd, C)
+            if x.dtype != torch.float32:
+                outs.append(deform_conv_autograd(xl, ol, m.weight, 1, 1, 1, False, True, True, True).reshape(B * h * wd, C))
+            else:
+                col = deform_im2col_autograd(xl, ol, 1, 1, 1, False, True)
+                outs.append(linear_autograd(col, m.weight.permute(0, 2, 3, 1).reshape(C, 9 * C), None, relu=True))
+        return torch.cat(outs, 0)
+
+    def forward_rows(self, feats):
+        """inference: list of (B,h,w,C) NHWC maps -> (A (rows, >= C) class logits, R1 (rows, >= 4) raw refinement logits, D0
+        (rows, 4) first distances), fp32 in every compute mode, level-major rows, and the level sizes"""
+        B = feats[0].shape[0]
+        sizes = [tuple(int(v) for v in f.shape[1:3]) for f in feats]
+        x0 = cat_rows(feats)
+        self._check_dcn_channels(x0)
+        c = self._vf_caches
+        xc = self._tower_rows(x0, self.cls_convs, self._tower_caches[0], B, sizes)
+        xr = self._tower_rows(x0, self.reg_convs, self._tower_caches[1], B, sizes)
+        xi = self._tower_rows(xr, [self.vfnet_reg_conv], [c['reg_conv']], B, sizes)
+        r0 = self._head_rows(xi, (self.vfnet_reg,), c['reg'], B, sizes)
+        d0, off = ops.vfnet_star_offsets(r0, self._scales_tensor(), B, sizes, self.strides, self._denoms(), self.gradient_mul)
+        r1 = self._head_rows(self._star_dconv_rows(xr, off, self.vfnet_reg_refine_dconv, c['refine_dconv'], B, sizes),
+                             (self.vfnet_reg_refine,), c['refine'], B, sizes)
+        a = self._head_rows(self._star_dconv_rows(xc, off, self.vfnet_cls_dconv, c['cls_dconv'], B, sizes),
+                            (self.vfnet_cls,), c['cls'], B, sizes)
+        return a, r1, d0, sizes
+
+    def forward_head_fused(self, feats):
+        """training forward over all levels, differentiable: (A, D0, D1, sizes); A fp32 with zero padding columns, D0 / D1
+        (rows, 4) distances in pixels"""
+        from . import train_ops
+        B = feats[0].shape[0]
+        sizes = tuple(tuple(int(v) for v in f.shape[1:3]) for f in feats)
+        x0 = cat_rows(feats)
+        self._check_dcn_channels(x0)
+        xc = self._tower_fused(x0, self.cls_convs, B, sizes)
+        xr = self._tower_fused(x0, self.reg_convs, B, sizes)
+        r0 = self._head_fused(self._tower_fused(xr, [self.vfnet_reg_conv], B, sizes), (self.vfnet_reg,), B, sizes)
+        scales = torch.stack([s.scale.float().reshape(()) for s in self.scales])
+        d0, offs = train_ops.vfnet_star_offsets(r0, scales, B, sizes, self.strides, self._denoms(), self.gradient_mul)
+        r1 = self._head_fused(self._star_dconv_fused(xr, offs, self.vfnet_reg_refine_dconv, B, sizes),
+                              (self.vfnet_reg_refine,), B, sizes)
+        a = self._head_fused(self._star_dconv_fused(xc, offs, self.vfnet_cls_dconv, B, sizes), (self.vfnet_cls,), B, sizes)
+        scales_refine = torch.stack([s.scale.float().reshape(()) for s in self.scales_refine])
+        d1 = train_ops.vfnet_refine(r1, scales_refine, d0, B, sizes)
+        return a, d0, d1, sizes
+
+    def forward_nhwc(self, feats):
+        """list of (B,h,w,C) -> (cls (B,h,w,C), bbox_pred (B,h,w,4), bbox_pred_refine (B,h,w,4)) lists, fp32"""
+        from .autograd import wants_grad
+        if not feats[0].is_cuda:
+            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
+            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
+        B = feats[0].shape[0]
+        if wants_grad(feats[0], self.vfnet_cls.weight, self.cls_convs[0].conv.weight):
+            a, d0, d1, sizes = self.forward_head_fused(list(feats))
+        else:
+            a, r1, d0, sizes = self.forward_rows(list(feats))
+            d1 = ops.vfnet_refine(r1, self._scales_refine_tensor(), B, sizes, d0)
+        cls, reg, ref, r = [], [], [], 0
+        for h, w in sizes:
+            n = B * h * w
+            cls.append(a[r:r + n].view(B, h, w, -1)[..., :self.cls_out_channels])
+            reg.append(d0[r:r + n].view(B, h, w, 4))
+            ref.append(d1[r:r + n].view(B, h, w, 4))
+            r += n
+        return cls, reg, ref
+
+    def star_dcn_offset(self, bbox_pred, gradient_mul, stride):
+        """vfnet_head.py:274-313 on torch ops (the host mirror): (N, 4, H, W) distances -> (N, 18, H, W) offsets"""
+        g = ((1 - gradient_mul) * bbox_pred.detach() + gradient_mul * bbox_pred) / stride
+        x1, y1, x2, y2 = g[:, 0], g[:, 1], g[:, 2], g[:, 3]
+        z = torch.zeros_like(x1)
+        ent = [-1.0 * y1, -1.0 * x1, -1.0 * y1, z, -1.0 * y1, x2, z, -1.0 * x1, z, z, z, x2, y2, -1.0 * x1, y2, z, y2, x2]
+        base = [float(v) for t in range(9) for v in (t // 3 - 1, t % 3 - 1)]
+        return torch.stack(ent, 1) - bbox_pred.new_tensor(base).view(1, 18, 1, 1)
+
+    def forward(self, feats):
+        """reference signature (vfnet_head.py:194-272): list of (N,C,h,w) -> lists of (N,C,h,w) class logits, (N,4,h,w)
+        distances and (N,4,h,w) refined distances"""
+        if not feats[0].is_cuda:        # host mirror on torch ops
+            import torch.nn.functional as F
+            cls, reg, ref = [], [], []
+            m = self.vfnet_reg_conv
+            for x, sc, scr, stride, denom in zip(feats, self.scales, self.scales_refine, self.strides, self._denoms()):
+                c, r = self._towers_host(x)
+                ri = F.relu(F.group_norm(F.conv2d(r, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
+                                         m.norm.bias, m.norm.eps))
+                d0 = (F.conv2d(ri, self.vfnet_reg.weight, self.vfnet_reg.bias, padding=1) * sc.scale).float().exp() * denom
+                off = self.star_dcn_offset(d0, self.gradient_mul, stride).to(r.dtype)
+                r2 = F.relu(deform_conv2d_host(r, off, self.vfnet_reg_refine_dconv.weight))
+                d1 = (F.conv2d(r2, self.vfnet_reg_refine.weight, self.vfnet_reg_refine.bias, padding=1) *
+                      scr.scale).float().exp() * d0.detach()
+                c2 = F.relu(deform_conv2d_host(c, off, self.vfnet_cls_dconv.weight))
+                cls.append(F.conv2d(c2, self.vfnet_cls.weight, self.vfnet_cls.bias, padding=1))
+                reg.append(d0)
+                ref.append(d1)
+            return cls, reg, ref
+        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
+        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
+
+    def get_points(self, featmap_sizes, dtype, device):
+        """vfnet_head.py:597-618 with use_atss: (x * s, y * s) + s * center_offset, the centres of the anchors"""
+        pts = []
+        for (h, w), s in zip(featmap_sizes, self.strides):
+            y, x = torch.meshgrid(torch.arange(0, h * s, s, dtype=dtype, device=device),
+                                  torch.arange(0, w * s, s, dtype=dtype, device=device), indexing='ij')
+            pts.append(torch.stack((x.reshape(-1), y.reshape(-1)), dim=-1) + s * self.anchor_center_offset)
+        return pts
+
+    # ------------------------------------------------------------------ test
+    def _score_rows(self, a, r, layout):
+        return ops.vfnet_score(a, layout)
+
+    def _layout(self, a, r, d0=None):
+        lay = ops.VfnetLayout(a, r, self.cls_out_channels)
+        lay.d0 = d0
+        return lay
+
+    def _decode_candidates(self, picked, a, r, layout, scales, sizes, max_shape, sf, cfg):
+        return ops.vfnet_decode_levels(picked, a, r, layout.d0, layout, scales, sizes, self.strides, self._base_table(),
+                                       max_shape, sf, cfg.score_thr)
+
+    def simple_test_padded(self, feats_nhwc, img_metas, rescale=False):
+        a, r1, d0, sizes = self.forward_rows(list(feats_nhwc))
+        return self.get_bboxes_rows(a, r1, self._layout(a, r1, d0), self._scales_refine_tensor(), sizes, img_metas,
+                                    rescale=rescale)
+
+    def _get_bboxes_device(self, outs, img_metas, cfg, rescale):
+        """the reference-signature tensors on the kernels' rows: the refined distances as D0 under zero refinement logits
+        (exp(0) = 1 exactly)"""
+        cls_scores, _, refine = outs
+        sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
+        rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float().contiguous()  # noqa: E731
+        a, d1 = rows(cls_scores), rows(refine)
+        r = torch.zeros_like(d1)
+        return self.get_bboxes_rows(a, r, self._layout(a, r, d1), a.new_ones(len(sizes)), sizes, img_metas, cfg, rescale)
+
+    def get_bboxes(self, cls_scores, bbox_preds, bbox_preds_refine, img_metas, cfg=None, rescale=False, with_nms=True,
+                   batched_nms=None):
+        """reference signature (vfnet_head.py:463-595): per-level (N,C,h,w) / (N,4,h,w) / (N,4,h,w) -> per image (dets (k,5),
+        labels (k,)).  Device tensors take `get_bboxes_rows`; CPU tensors the reference's chain on torch ops, with the
+        caller's `batched_nms` (this package's NMS is a device kernel)."""
+        return self._get_bboxes((cls_scores, bbox_preds, bbox_preds_refine), img_metas, cfg, rescale, with_nms, batched_nms)
+
+    def _get_bboxes_host(self, cls_scores, bbox_preds, bbox_preds_refine, img_metas, cfg, rescale, batched_nms):
+        B, C = cls_scores[0].shape[0], self.cls_out_channels
+        points_l = self.get_points([c.shape[-2:] for c in cls_scores], bbox_preds[0].dtype, bbox_preds[0].device)
+        nms_pre = cfg.get('nms_pre', -1)
+        out = []
+        for b in range(B):
+            boxes_l, scores_l = [], []
+            h, w = img_metas[b]['img_shape'][:2]
+            for cls, reg, points in zip(cls_scores, bbox_preds_refine, points_l):
+                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
+                d = reg[b].detach().permute(1, 2, 0).reshape(-1, 4)
+                if 0 < nms_pre < s.shape[0]:
+                    _, idx = s.max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
+                    idx = idx[:nms_pre]
+                    points, d, s = points[idx], d[idx], s[idx]
+                box = distance2bbox(points, d)
+                boxes_l.append(torch.stack([box[:, 0].clamp(0, w), box[:, 1].clamp(0, h), box[:, 2].clamp(0, w),
+                                            box[:, 3].clamp(0, h)], -1))
+                scores_l.append(s)
+            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), None, img_metas[b], cfg, rescale, batched_nms))
+        return out
+
+    # ------------------------------------------------------------------ train
+    def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
+        """the device-resident train step of the head; no host read"""
+        self._refuse_ignore(gt_bboxes_ignore)
+        a, d0, d1, sizes = self.forward_head_fused(list(feats_nhwc))
+        return self.loss_fused(a, d0, d1, sizes, gt_bboxes, gt_labels, img_metas)
+
+    def loss_fused(self, a, d0, d1, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
+        """VFNetHead.loss on the row tensors of all levels: ATSS's whole-batch adaptive assignment, then the loss kernels --
+        targets, IoU weights and the three normalisers are formed on the device (averaged over ranks there when
+        distributed), nothing is read back.  `self.last_targets` keeps (gt_inds, coef3, norm3)."""
+        from . import train_ops
+        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
+        gts, labels = gts.to(a.device), labels.to(a.device)
+        B = len(img_metas)
+        sizes = [tuple(int(v) for v in s) for s in sizes]
+        base = self._base_table()
+        gt_inds = train_ops.atss_assign(gts, offs, B, sizes, self.strides, base, self.assigner.topk,
+                                        valid_cells(self.anchor_generator, sizes, img_metas, a))
+        meta = train_ops.VfnetLossMeta(B, sizes, self.strides, base, self.cls_out_channels, offs, self.loss_cls.alpha,
+                                       self.loss_cls.gamma, self.loss_cls.iou_weighted, self.loss_bbox.eps,
+                                       self.loss_cls.loss_weight, self.loss_bbox.loss_weight, self.loss_bbox_refine.loss_weight)
+        losses, coef, norm3 = train_ops.vfnet_loss(a, d0, d1, gt_inds, gts, labels, meta, 0, self._norm_hook())
+        self.last_targets = (gt_inds, coef, norm3)
+        return dict(loss_cls=losses[0], loss_bbox=losses[1], loss_bbox_rf=losses[2])
+
+    def get_targets(self, cls_scores, mlvl_points, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore):
+        """vfnet_head.py:620-761 with use_atss, on torch ops (the host mirror): (labels per level, label weights, (l, t, r,
+        b) targets per level, box weights)"""
+        featmap_sizes = [tuple(int(v) for v in f.size()[-2:]) for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=cls_scores[0].device)
+        self._all_valid = None
+        res = self._atss_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore, gt_labels,
+                                 self.cls_out_channels, True, encode=False)
+        if res is None:
+            return None
+        _, labels_list, lw_list, bt_list, bw_list, _, _ = res
+        num_imgs = len(img_metas)
+        targets = [bbox2distance(p.repeat(num_imgs, 1), t.reshape(-1, 4)) for p, t in zip(mlvl_points, bt_list)]
+        return ([l.reshape(-1) for l in labels_list], torch.cat([w.reshape(-1) for w in lw_list]), targets,
+                torch.cat([w.reshape(-1) for w in bw_list]))
+
+    def loss(self, cls_scores, bbox_preds, bbox_preds_refine, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        """vfnet_head.py:315-461.  Device tensors go to the HIP kernels (`loss_fused` on the distances as they are); CPU
+        tensors take the reference's chain in torch (the host mirror)."""
+        assert len(cls_scores) == len(bbox_preds) == len(bbox_preds_refine)
+        featmap_sizes = [tuple(int(v) for v in f.size()[-2:]) for f in cls_scores]
+        C = self.cls_out_channels
+        rows = lambda lst, n: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, n) for t in lst])        # noqa: E731
+        flat_cls, flat_d0, flat_d1 = rows(cls_scores, C), rows(bbox_preds, 4), rows(bbox_preds_refine, 4)
+        if cls_scores[0].is_cuda:
+            self._refuse_ignore(gt_bboxes_ignore)
+            return self.loss_fused(flat_cls.float().contiguous(), flat_d0.float().contiguous(), flat_d1.float().contiguous(),
+                                   featmap_sizes, gt_bboxes, gt_labels, img_metas)
+        points = self.get_points(featmap_sizes, bbox_preds[0].dtype, bbox_preds[0].device)
+        labels, _, bbox_targets, _ = self.get_targets(cls_scores, points, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
+        num_imgs = cls_scores[0].size(0)
+        flat_labels, flat_targets = torch.cat(labels), torch.cat(bbox_targets)
+        flat_points = torch.cat([p.repeat(num_imgs, 1) for p in points])
+        pos = ((flat_labels >= 0) & (flat_labels < self.num_classes)).nonzero().reshape(-1)
+        num_pos = len(pos)
+        num_pos_avg = max(reduce_mean(flat_cls.new_tensor(float(num_pos))).item(), 1.0)
+        pos_points = flat_points[pos]
+        target_boxes = distance2bbox(pos_points, flat_targets[pos]).detach()
+        boxes0, boxes1 = distance2bbox(pos_points, flat_d0[pos]), distance2bbox(pos_points, flat_d1[pos])
+        w_ini = bbox_overlaps(boxes0, target_boxes, is_aligned=True).clamp(min=1e-6).detach()
+        w_rf = bbox_overlaps(boxes1, target_boxes, is_aligned=True).clamp(min=1e-6).detach()
+        avg_ini = reduce_mean(w_ini.sum()).clamp_(min=1).item()
+        avg_rf = reduce_mean(w_rf.sum()).clamp_(min=1).item()
+        cls_iou_targets = torch.zeros_like(flat_cls)
+        if num_pos > 0:
+            loss_bbox = self.loss_bbox(boxes0, target_boxes, weight=w_ini, avg_factor=avg_ini)
+            loss_bbox_refine = self.loss_bbox_refine(boxes1, target_boxes, weight=w_rf, avg_factor=avg_rf)
+            cls_iou_targets[pos, flat_labels[pos]] = w_rf
+        else:
+            loss_bbox, loss_bbox_refine = flat_d0[pos].sum() * 0, flat_d1[pos].sum() * 0
+        loss_cls = self.loss_cls(flat_cls, cls_iou_targets, avg_factor=num_pos_avg)
+        return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_bbox_rf=loss_bbox_refine)

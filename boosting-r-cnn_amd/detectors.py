@@ -618,3 +618,11 @@ class GFL(SingleStageDetector):
 
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)
+
+
+@DETECTORS.register_module()
+class VFNet(SingleStageDetector):
+    """mmdet/models/detectors/vfnet.py:6-18"""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg)

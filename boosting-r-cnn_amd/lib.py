@@ -136,6 +136,8 @@ SIGNATURES = {
     'brcnn_deform_conv_nhwc': (c_int, [c_ptr] * 6 + [c_int] * 10 + [c_ptr]),
     'brcnn_deform_im2col_nhwc_g': (c_int, [c_ptr] * 3 + [c_int] * 14 + [c_ptr]),
     'brcnn_deform_col2im_nhwc_g': (c_int, [c_ptr] * 5 + [c_int] * 14 + [c_ptr]),
+    'brcnn_deform_col2im_ordered_workspace_bytes': (ctypes.c_size_t, [c_int] * 4),
+    'brcnn_deform_col2im_nhwc_ordered': (c_int, [c_ptr] * 5 + [c_int] * 14 + [c_ptr, ctypes.c_size_t, c_ptr]),
     'brcnn_deform_conv_nhwc_g': (c_int, [c_ptr] * 6 + [c_int] * 12 + [c_ptr]),
     'brcnn_deform_conv_route': (c_int, [c_int] * 9),
     'brcnn_pack_conv_weights': (c_int, [c_ptr] * 3 + [c_int] * 5 + [c_ptr]),
@@ -223,6 +225,22 @@ SIGNATURES = {
     'brcnn_gfl_loss_finalize': (c_int, [c_ptr, c_size, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int] + [c_ptr] * 4),
     'brcnn_gfl_loss_backward': (c_int, [c_ptr] * 4 + [c_int, c_int] + [c_ptr] * 4 + [c_int, c_int] + [c_ptr] * 8 +
                                 [c_size] + [c_ptr] * 4),
+    'brcnn_vfnet_rows_workspace_bytes': (c_size, [c_int, c_int, c_ptr, c_ptr]),
+    'brcnn_vfnet_star_offsets': (c_int, [c_ptr, c_int, c_int, c_ptr, c_int, c_int] + [c_ptr] * 4 + [c_f32, c_f32] +
+                                 [c_ptr] * 3),
+    'brcnn_vfnet_star_offsets_backward': (c_int, [c_ptr, c_int, c_int, c_ptr, c_int, c_int] + [c_ptr] * 3 + [c_f32] +
+                                          [c_ptr] * 4 + [c_size] + [c_ptr] * 3),
+    'brcnn_vfnet_refine': (c_int, [c_ptr, c_int, c_int, c_ptr, c_int, c_int] + [c_ptr] * 5),
+    'brcnn_vfnet_refine_backward': (c_int, [c_ptr, c_int, c_int, c_ptr, c_int, c_int] + [c_ptr] * 5 + [c_size] +
+                                    [c_ptr] * 3),
+    'brcnn_vfnet_decode_levels': (c_int, [c_ptr] * 6 + [c_int, c_int] + [c_ptr] * 5 + [c_int, c_ptr, c_ptr, c_f32] +
+                                  [c_ptr] * 6),
+    'brcnn_vfnet_loss_workspace_bytes': (c_size, [c_int, c_int, c_ptr, c_ptr, c_int]),
+    'brcnn_vfnet_loss_forward': (c_int, [c_ptr, c_int, c_int, c_ptr, c_ptr, c_int, c_int] + [c_ptr] * 4 + [c_int] +
+                                 [c_ptr] * 6 + [c_size, c_ptr, c_ptr]),
+    'brcnn_vfnet_loss_finalize': (c_int, [c_ptr, c_size, c_ptr, c_int, c_int, c_ptr, c_ptr, c_int] + [c_ptr] * 4),
+    'brcnn_vfnet_loss_backward': (c_int, [c_ptr, c_int, c_int, c_ptr, c_ptr, c_int, c_int] + [c_ptr] * 4 + [c_int] +
+                                  [c_ptr] * 11),
     'brcnn_coco_order_workspace_bytes': (c_size, [c_i64]),
     'brcnn_coco_match': (c_int, [c_ptr] * 6 + [c_int, c_int, c_ptr, c_int, c_ptr, c_int, c_int] + [c_ptr] * 7),
     'brcnn_coco_order': (c_int, [c_ptr, c_i64, c_int, c_ptr, c_ptr, c_size, c_ptr]),

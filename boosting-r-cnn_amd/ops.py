@@ -1442,6 +1442,96 @@ def gfl_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, base_a
     return d.outs
 
 
+# --------------------------------------------------------------------------- VFNet head, test time
+class VfnetLayout:
+    """where the VFNet kernels find the head outputs: A (rows, stride_a) with the C class logits at `cls_off`, R (rows,
+    stride_r) with the 4 raw distance logits at `reg_off` (include/brcnn_hip.h: layout4_host)"""
+
+    def __init__(self, a, r, num_classes, cls_off=0, reg_off=0):
+        import ctypes
+        _require_gpu(a, r)
+        for t in (a, r):
+            assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous()
+        assert a.shape[0] == r.shape[0]
+        c = int(num_classes)
+        assert 0 <= cls_off and cls_off + c <= a.shape[1] and 0 <= reg_off and reg_off + 4 <= r.shape[1]
+        self.C, self.rows = c, int(a.shape[0])
+        self.values = (int(a.shape[1]), int(cls_off), int(r.shape[1]), int(reg_off))
+        self.arr = (ctypes.c_int * 4)(*self.values)
+
+
+def _vfnet_rows(r, batch, sizes, reg_off):
+    """the checks the VFNet row entries share: R (rows, >= reg_off + 4) fp32 dense, level-major rows"""
+    import ctypes
+    _require_gpu(r)
+    assert r.dim() == 2 and r.dtype == torch.float32 and r.is_contiguous() and 0 <= reg_off and reg_off + 4 <= r.shape[1]
+    L = len(sizes)
+    if L > 8:
+        raise ValueError(f'vfnet: {L} pyramid levels, at most 8 are supported')
+    if batch > 64:      # BRCNN_MAX_IMAGES
+        raise ValueError(f'vfnet: batch {batch} exceeds 64 images per call')
+    assert r.shape[0] == sum(batch * h * w for h, w in sizes)
+    ints = ctypes.c_int * L
+    return L, ints(*[int(h) for h, _ in sizes]), ints(*[int(w) for _, w in sizes])
+
+
+def vfnet_star_offsets(r0, scales, batch, sizes, strides, denoms, gradient_mul, reg_off=0):
+    """brcnn_vfnet_star_offsets, one launch over all levels and images: r0 (rows, >= 4) the raw output of `vfnet_reg`, scales
+    (L,) on the device -> (D0 (rows, 4) = exp(scale_l * raw) * denoms[l] in (l, t, r, b) order, offsets (rows, 18) of the
+    star-shaped deformable conv, row layout of brcnn_deform_im2col_nhwc_g)"""
+    import ctypes
+    L, hs, ws = _vfnet_rows(r0, batch, sizes, reg_off)
+    _require_gpu(scales)
+    assert scales.dtype == torch.float32 and scales.shape == (L,) and scales.is_contiguous()
+    assert len(strides) == L and len(denoms) == L
+    d0 = torch.empty((r0.shape[0], 4), dtype=torch.float32, device=r0.device)
+    off = torch.empty((r0.shape[0], 18), dtype=torch.float32, device=r0.device)
+    f0, f1 = ctypes.c_float(1.0 - gradient_mul).value, ctypes.c_float(gradient_mul).value
+    st = _L.load().brcnn_vfnet_star_offsets(_ptr(r0), int(r0.shape[1]), int(reg_off), _ptr(scales), int(batch), L, hs, ws,
+                                            (ctypes.c_int * L)(*[int(s) for s in strides]),
+                                            (ctypes.c_float * L)(*[float(d) for d in denoms]), f0, f1, _ptr(d0), _ptr(off),
+                                            _stream())
+    _L.check(st, 'brcnn_vfnet_star_offsets')
+    return d0, off
+
+
+def vfnet_refine(r1, scales_refine, batch, sizes, d0, reg_off=0):
+    """brcnn_vfnet_refine: D1 (rows, 4) = exp(scale_refine_l * raw1) * D0"""
+    L, hs, ws = _vfnet_rows(r1, batch, sizes, reg_off)
+    _require_gpu(scales_refine, d0)
+    assert scales_refine.dtype == torch.float32 and scales_refine.shape == (L,) and scales_refine.is_contiguous()
+    assert d0.dtype == torch.float32 and d0.shape == (r1.shape[0], 4) and d0.is_contiguous()
+    d1 = torch.empty_like(d0)
+    st = _L.load().brcnn_vfnet_refine(_ptr(r1), int(r1.shape[1]), int(reg_off), _ptr(scales_refine), int(batch), L, hs, ws,
+                                      _ptr(d0), _ptr(d1), _stream())
+    _L.check(st, 'brcnn_vfnet_refine')
+    return d1
+
+
+def vfnet_score(a, layout):
+    """max_c sigmoid(cls_c) per row of A: `dense_score` with one anchor per cell on the class columns in place"""
+    off = layout.values[1]
+    return dense_score(a[:, off:off + layout.C], 1, layout.C).view(-1)
+
+
+def vfnet_decode_levels(topk_inds, a, r1, d0, layout, scales_refine, feat_hws, strides, base_anchors, max_shape, scale_factor,
+                        score_thr):
+    """The candidates of multiclass_nms for all levels and images in one launch (brcnn_vfnet_decode_levels): D1 =
+    exp(scale_refine_l * raw1) * D0 of the picked rows, laid from the point of the picked cell (the centre of its anchor);
+    clipped to max_shape (B, 2), divided by scale_factor (B, 4) unless None.  base_anchors: `atss_base_anchors`.  Returns
+    boxes (B,T*C,4), scores (B,T*C) = class sigmoid, labels (B,T*C) int64, valid (B,T*C) bool = score > score_thr, n_valid
+    (B,) int32; (level, pick, class) order."""
+    d = _DecodeLevels(topk_inds, layout.C, max_shape, scale_factor, a.device)
+    assert len(base_anchors) == 4 * d.L
+    _require_gpu(d0)
+    assert d0.dtype == torch.float32 and d0.shape == (layout.rows, 4) and d0.is_contiguous()
+    st = _L.load().brcnn_vfnet_decode_levels(
+        *d.rows_head(a, r1, layout, scales_refine, feat_hws, strides), base_anchors, _ptr(d0), d.c, _ptr(max_shape),
+        _ptr(scale_factor), float(score_thr), *d.out_ptrs, _stream())
+    _L.check(st, 'brcnn_vfnet_decode_levels')
+    return d.outs
+
+
 # --------------------------------------------------------------------------- Cascade R-CNN, test time
 def _rows_in_place(t):
     """a fp32 (rows, cols) device tensor the cascade kernels read with a row stride: the two column blocks of the heads'
@@ -1742,14 +1832,26 @@ def deform_im2col_nhwc(x, offset_mask, kernel=3, stride=1, pad=1, dilation=1, ch
     return col, (ho, wo)
 
 
-def deform_col2im_nhwc(x, offset_mask, dcol, stride=1, pad=1, deform_groups=1, modulated=True):
+def deform_col2im_nhwc(x, offset_mask, dcol, stride=1, pad=1, deform_groups=1, modulated=True, ordered=False):
     """backward of the 3x3 deformable im2col: dcol (N*Ho*Wo, 9*C) fp32 -> (dx fp32 (N,H,W,C), d_offset_mask like offset_mask);
-    x fp32 / bf16 / fp16, offset_mask (N,Ho,Wo,(3 | 2) * 9 * G) exactly the layout (every entry of its gradient is written)"""
+    x fp32 / bf16 / fp16, offset_mask (N,Ho,Wo,(3 | 2) * 9 * G) exactly the layout (every entry of its gradient is written).
+    `ordered`: dx accumulated in integers on a grid scaled to max |dcol| (brcnn_deform_col2im_nhwc_ordered; its precision is
+    stated in include/brcnn_hip.h): the same bits from run to run"""
     _require_gpu(x, offset_mask, dcol)
     assert x.is_contiguous() and offset_mask.is_contiguous() and dcol.is_contiguous() and dcol.dtype == torch.float32
     n, h, w, c = x.shape
-    dx = torch.zeros((n, h, w, c), dtype=torch.float32, device=x.device)
     dom = torch.empty_like(offset_mask)
+    if ordered:
+        lib = _L.load()
+        dx = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+        nb = lib.brcnn_deform_col2im_ordered_workspace_bytes(n, h, w, c)
+        ws = torch.empty((nb // 8,), dtype=torch.int64, device=x.device)
+        st = lib.brcnn_deform_col2im_nhwc_ordered(_ptr(x), _ptr(offset_mask), _ptr(dcol), _ptr(dx), _ptr(dom), n, h, w, c, 3, 3,
+                                                  int(stride), int(pad), 1, offset_mask.shape[3], c, int(deform_groups),
+                                                  int(bool(modulated)), _dt(x), _ptr(ws), nb, _stream())
+        _L.check(st, 'brcnn_deform_col2im_nhwc_ordered')
+        return dx, dom
+    dx = torch.zeros((n, h, w, c), dtype=torch.float32, device=x.device)
     st = _L.load().brcnn_deform_col2im_nhwc_g(_ptr(x), _ptr(offset_mask), _ptr(dcol), _ptr(dx), _ptr(dom), n, h, w, c, 3, 3,
                                               int(stride), int(pad), 1, offset_mask.shape[3], c, int(deform_groups),
                                               int(bool(modulated)), _dt(x), _stream())

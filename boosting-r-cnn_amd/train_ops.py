@@ -704,6 +704,164 @@ def gfl_loss(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook=None
     return CenternessLossFunction.apply(a, r, scales, gt_inds, gts, gt_labels, layout, meta, norm_hook)
 
 
+# ----------------------------------------------------------------------------- VFNet head: distances, star offsets, loss
+def _vfnet_rows_workspace(lib, batch, sizes, device):
+    L = len(sizes)
+    hs, ws = _ints([h for h, _ in sizes]), _ints([w for _, w in sizes])
+    nb = lib.brcnn_vfnet_rows_workspace_bytes(int(batch), L, hs, ws)
+    return torch.empty((nb + 3) // 4, dtype=torch.float32, device=device), nb, L, hs, ws
+
+
+class VfnetStarOffsetsFunction(Function):
+    """(D0 (rows, 4), offsets of level 0, ..., offsets of level L - 1) from the raw output of `vfnet_reg` and the per-level
+    scales (brcnn_vfnet_star_offsets): the offsets of a level are a (B, h, w, 18) view of one tensor, the input both star
+    deformable convs of the level read.  Backward takes dD0 and the offset gradients of all levels (each possibly absent)
+    and leaves d raw0 (every element written) and dscale (L,)"""
+
+    @staticmethod
+    def forward(ctx, r0, scales, batch, sizes, strides, denoms, gradient_mul, reg_off):
+        from . import ops
+        scales = scales.detach().float().contiguous()
+        d0, off = ops.vfnet_star_offsets(r0, scales, batch, sizes, strides, denoms, gradient_mul, reg_off)
+        ctx.save_for_backward(r0, scales, d0)
+        ctx.cfg = (int(batch), [tuple(int(v) for v in s) for s in sizes], [int(s) for s in strides], float(gradient_mul),
+                   int(reg_off))
+        outs, r = [], 0
+        for h, w in ctx.cfg[1]:
+            n = batch * h * w
+            outs.append(off[r:r + n].view(batch, h, w, 18))
+            r += n
+        return (d0,) + tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dd0, *doffs):
+        r0, scales, d0 = ctx.saved_tensors
+        batch, sizes, strides, gm, reg_off = ctx.cfg
+        doff = None
+        if any(g is not None for g in doffs):
+            doff = torch.cat([(g.float().reshape(-1, 18) if g is not None else r0.new_zeros((batch * h * w, 18)))
+                              for g, (h, w) in zip(doffs, sizes)], 0).contiguous()
+        dd0 = dd0.float().contiguous() if dd0 is not None else None
+        lib = _L.load()
+        ws, nb, L, hs, wds = _vfnet_rows_workspace(lib, batch, sizes, r0.device)
+        dr0, dscale = torch.empty_like(r0), torch.empty_like(scales)
+        st = lib.brcnn_vfnet_star_offsets_backward(_ptr(r0), int(r0.shape[1]), reg_off, _ptr(scales), batch, L, hs, wds,
+                                                   _ints(strides), ctypes.c_float(gm).value, _ptr(d0), _ptr(dd0), _ptr(doff),
+                                                   _ptr(ws), nb, _ptr(dr0), _ptr(dscale), _stream())
+        _L.check(st, 'brcnn_vfnet_star_offsets_backward')
+        return dr0, dscale, None, None, None, None, None, None
+
+
+def vfnet_star_offsets(r0, scales, batch, sizes, strides, denoms, gradient_mul, reg_off=0):
+    """(D0, [offsets per level]), differentiable w.r.t. r0 and scales"""
+    out = VfnetStarOffsetsFunction.apply(r0, scales, batch, sizes, strides, denoms, gradient_mul, reg_off)
+    return out[0], list(out[1:])
+
+
+class VfnetRefineFunction(Function):
+    """D1 = exp(scale_refine_l * raw1) * D0 with D0 a constant (brcnn_vfnet_refine), differentiable w.r.t. raw1 and the
+    scales"""
+
+    @staticmethod
+    def forward(ctx, r1, scales_refine, d0, batch, sizes, reg_off):
+        from . import ops
+        scales_refine = scales_refine.detach().float().contiguous()
+        d1 = ops.vfnet_refine(r1, scales_refine, batch, sizes, d0, reg_off)
+        ctx.save_for_backward(r1, scales_refine, d1)
+        ctx.cfg = (int(batch), [tuple(int(v) for v in s) for s in sizes], int(reg_off))
+        return d1
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dd1):
+        r1, scales, d1 = ctx.saved_tensors
+        batch, sizes, reg_off = ctx.cfg
+        lib = _L.load()
+        ws, nb, L, hs, wds = _vfnet_rows_workspace(lib, batch, sizes, r1.device)
+        dd1 = dd1.float().contiguous()
+        dr1, dscale = torch.empty_like(r1), torch.empty_like(scales)
+        st = lib.brcnn_vfnet_refine_backward(_ptr(r1), int(r1.shape[1]), reg_off, _ptr(scales), batch, L, hs, wds, _ptr(d1),
+                                             _ptr(dd1), _ptr(ws), nb, _ptr(dr1), _ptr(dscale), _stream())
+        _L.check(st, 'brcnn_vfnet_refine_backward')
+        return dr1, dscale, None, None, None, None
+
+
+def vfnet_refine(r1, scales_refine, d0, batch, sizes, reg_off=0):
+    return VfnetRefineFunction.apply(r1, scales_refine, d0.detach(), batch, sizes, reg_off)
+
+
+class VfnetLossMeta(CenternessLossMeta):
+    """the VFNet loss call: the base anchors of the pyramid (their centres are the points); scalar losses [loss_cls,
+    loss_bbox, loss_bbox_rf] (include/brcnn_hip.h: cfg7_host).  The assignment is `atss_assign`."""
+
+    kind = 'vfnet'
+
+    def __init__(self, batch, sizes, strides, base_anchors, num_classes, gt_offsets, alpha, gamma, iou_weighted, eps, lw_cls,
+                 lw_bbox, lw_refine):
+        super().__init__(batch, sizes, strides, num_classes, gt_offsets,
+                         [alpha, gamma, 1.0 if iou_weighted else 0.0, eps, lw_cls, lw_bbox, lw_refine])
+        assert len(base_anchors) == 4 * self.L
+        self.base = base_anchors
+
+
+class VfnetLossFunction(Function):
+    """losses (3,) = [loss_cls, loss_bbox, loss_bbox_rf] from A (rows, stride_a) and the distances D0, D1 (rows, 4),
+    differentiable w.r.t. all three (brcnn_vfnet_loss_*); also coef3 and norm3 = [n_pos, sum w_ini, sum w_rf]"""
+
+    @staticmethod
+    def forward(ctx, a, d0, d1, gt_inds, gts, gt_labels, cls_off, meta, norm_hook):
+        _require_gpu(a, d0, d1, gt_inds, gts, gt_labels)
+        assert a.dim() == 2 and a.dtype == torch.float32 and a.is_contiguous() and a.shape[0] == meta.rows
+        assert 0 <= cls_off and cls_off + meta.C <= a.shape[1]
+        d0, d1 = d0.detach().float().contiguous(), d1.detach().float().contiguous()
+        assert d0.shape == (meta.rows, 4) and d1.shape == (meta.rows, 4)
+        assert gt_inds.dtype == torch.int32 and gt_inds.shape == (meta.batch, meta.per_image) and gt_inds.is_contiguous()
+        if meta.total_gt:
+            assert gts.dtype == torch.float32 and gts.shape == (meta.total_gt, 4) and gts.is_contiguous()
+            assert gt_labels.dtype == torch.int64 and gt_labels.shape == (meta.total_gt,) and gt_labels.is_contiguous()
+        lib = _L.load()
+        ws, nb = meta.workspace(lib, a.device)
+        out = torch.empty((9,), dtype=torch.float32, device=a.device)
+        norm3, losses, coef = out[:3], out[3:6], out[6:]
+        st = lib.brcnn_vfnet_loss_forward(*VfnetLossFunction._args(a, cls_off, d0, d1, gt_inds, gts, gt_labels, meta), _ptr(ws),
+                                          nb, _ptr(norm3), _stream())
+        _L.check(st, 'brcnn_vfnet_loss_forward')
+        if norm_hook is not None:
+            norm_hook(norm3)
+        st = lib.brcnn_vfnet_loss_finalize(_ptr(ws), nb, _ptr(norm3), meta.batch, meta.L, meta.hs, meta.ws, meta.C, meta.cfg,
+                                           _ptr(losses), _ptr(coef), _stream())
+        _L.check(st, 'brcnn_vfnet_loss_finalize')
+        ctx.save_for_backward(a, d0, d1, gt_inds, gts, gt_labels, coef)
+        ctx.cls_off, ctx.meta = int(cls_off), meta
+        ctx.mark_non_differentiable(coef, norm3)
+        return losses, coef, norm3
+
+    @staticmethod
+    def _args(a, cls_off, d0, d1, gt_inds, gts, gt_labels, meta):
+        gp, lp = (_ptr(gts), _ptr(gt_labels)) if meta.total_gt else (None, None)
+        return (_ptr(a), int(a.shape[1]), int(cls_off), _ptr(d0), _ptr(d1), meta.batch, meta.L, meta.hs, meta.ws, meta.strides,
+                meta.base, meta.C, _ptr(gt_inds), gp, lp, meta.gt_offsets, meta.cfg)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g3, _gc, _gn):
+        a, d0, d1, gt_inds, gts, gt_labels, coef = ctx.saved_tensors
+        meta = ctx.meta
+        da, dd0, dd1 = torch.empty_like(a), torch.empty_like(d0), torch.empty_like(d1)
+        g3 = g3.float().contiguous()
+        st = _L.load().brcnn_vfnet_loss_backward(*VfnetLossFunction._args(a, ctx.cls_off, d0, d1, gt_inds, gts, gt_labels, meta),
+                                                 _ptr(g3), _ptr(coef), _ptr(da), _ptr(dd0), _ptr(dd1), _stream())
+        _L.check(st, 'brcnn_vfnet_loss_backward')
+        return da, dd0, dd1, None, None, None, None, None, None
+
+
+def vfnet_loss(a, d0, d1, gt_inds, gts, gt_labels, meta, cls_off=0, norm_hook=None):
+    """(losses (3,), coef3, norm3); `norm_hook(norm3)` may change norm3 in place between the sums and the division (the mean
+    over ranks)"""
+    return VfnetLossFunction.apply(a, d0, d1, gt_inds, gts, gt_labels, cls_off, meta, norm_hook)
+
+
 # ----------------------------------------------------------------------------- boosting loss
 class BoostLossFunction(Function):
     """out3 = [loss_cls, loss_bbox, acc] of the boosting-reweighted R-CNN loss

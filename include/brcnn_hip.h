@@ -736,6 +736,22 @@ int brcnn_deform_col2im_nhwc_g(const void *x, const float *offset_mask, const fl
                                float *d_offset_mask, int batch, int height, int width, int channels, int kh, int kw,
                                int stride, int pad, int dilation, int om_stride, int channels_padded, int deform_groups,
                                int modulated, int dtype, void *stream);
+/* brcnn_deform_col2im_nhwc_g whose dx carries the same bits from run to run: the contributions are added as 64-bit integers
+ * (integer addition does not depend on the order the waves arrive in; fp32 atomics do) and converted once.  The grid comes
+ * from the data of the call: a pre-pass takes m = max |dcol| and its binary exponent ex (m < 2^ex); a contribution (dcol *
+ * mask * corner weight, at most m in magnitude) is scaled by 2^(S - ex), S = 62 - ceil(log2(Ho * Wo * kh * kw * 4)), so that
+ * even every sample of an image on one pixel sums below 2^62: no overflow at any finite input.  Precision: a contribution is
+ * rounded to a multiple of 2^(ex - S), an absolute error of at most m * 2^-S each (S = 41 for a 100 x 168 map, 50 for
+ * 6 x 7); one of at least m * 2^(24 - S) keeps all 24 bits of fp32, one below m * 2^(-S - 1) is dropped -- where the fp32
+ * atomics of the other entry keep the relative precision of every partial sum instead.  A dcol or a contribution that is
+ * not finite makes every element of dx NaN.  d_offset_mask is the other entry's, bit for bit.  workspace:
+ * brcnn_deform_col2im_ordered_workspace_bytes (8 bytes per element of dx + 8).  The star deformable convs of VFNetHead train
+ * through this entry. */
+size_t brcnn_deform_col2im_ordered_workspace_bytes(int batch, int height, int width, int channels);
+int brcnn_deform_col2im_nhwc_ordered(const void *x, const float *offset_mask, const float *dcol, float *dx,
+                                     float *d_offset_mask, int batch, int height, int width, int channels, int kh, int kw,
+                                     int stride, int pad, int dilation, int om_stride, int channels_padded, int deform_groups,
+                                     int modulated, int dtype, void *workspace, size_t workspace_bytes, void *stream);
 /* The fused 16-bit deformable 3x3 conv with deform groups, modulated or not, any cout % 64 == 0 (output-channel blocks in
  * the grid).  Requires (channels / deform_groups) % 64 == 0 (a K step -- one tap x 64 channels -- then lies inside one
  * group) and om_stride >= (modulated ? 27 : 18) * deform_groups; anything else is refused with BRCNN_EINVAL and the
@@ -1409,6 +1425,74 @@ int brcnn_gfl_loss_backward(const float *a, const float *r, const int *layout4_h
                             const float *gts, const int64_t *gt_labels, const int *gt_offsets_host, const float *cfg5_host,
                             const float *grad_losses, const float *coef3, void *workspace, size_t workspace_bytes, float *da,
                             float *dr, float *dscale, void *stream);
+
+/* ------------------------------------------------------------------------------
+ * The VFNet head: VFNetHead with VarifocalLoss (models/dense_heads/vfnet_head.py, models/losses/varifocal_loss.py),
+ * csrc/vfnet_head.hip.  ONE anchor per cell as for the ATSS head (base_anchors_host (L, 4)); only its centre is used: it is
+ * the reference's point (x * s, y * s) + s * center_offset.  Row tensors over all levels, level-major rows, fp32, read in
+ * place: A (rows, stride_a) with the C class logits at cls_off; R0 / R1 (rows, stride_r) with the 4 RAW distance logits
+ * (l, t, r, b) at reg_off; D0 / D1 dense (rows, 4) distances in pixels.  scales / scales_refine: (L) floats ON THE DEVICE.
+ * layout4_host = [stride_a, cls_off, stride_r, reg_off].
+ *   brcnn_vfnet_star_offsets: D0 = exp(scale_l * raw0) * denoms_host[l], and offsets (rows, 18) in the row layout of
+ *     brcnn_deform_im2col_nhwc_g ([2t] = dy, [2t + 1] = dx of tap t) in star_dcn_offset's order: q = (f0 * D0 + f1 * D0) /
+ *     stride_l, the signed entries (taps 0..8 sample top-left, top, top-right, left, centre, right, bottom-left, bottom,
+ *     bottom-right of the box), minus the base offset (ty - 1, tx - 1).  f0 = (float)(1 - gradient_mul), f1 =
+ *     (float)gradient_mul.  The offsets are not clamped: the deformable kernels compare a sample coordinate with (-1, H) x
+ *     (-1, W) in fp32 before any conversion to int, so a huge or non-finite offset samples zero.
+ *   brcnn_vfnet_star_offsets_backward: dD0 (rows, 4) and d_offsets (rows, 18), each may be NULL (zeros) -> g = dD0 + f1 *
+ *     (signed sums of the three entries per side / stride_l); d raw0 = g * D0 * scale_l written to every element of dr0
+ *     (rows, stride_r), zeros outside the 4 columns; dscale (L) from block partials summed in a fixed order.
+ *   brcnn_vfnet_refine / _backward: D1 = exp(scale_refine_l * raw1) * D0 with D0 a constant; d raw1 = dD1 * D1 *
+ *     scale_refine_l, dscale (L) likewise.  workspace of both backward entries: brcnn_vfnet_rows_workspace_bytes.
+ *   brcnn_vfnet_decode_levels: everything between the top-k and multiclass_nms (vfnet_head.py:463-595): D1 of the picked row,
+ *     box = (px - l, py - t, px + r, py + b) clipped to max_shape, divided by scale_factor; score = sigmoid(cls_c), valid =
+ *     score > score_thr; (level, pick, class) order.  The ranking score is brcnn_dense_score on A in place.
+ *   brcnn_vfnet_loss_forward / _finalize / _backward: VFNetHead.loss (vfnet_head.py:315-461) on gt_inds (brcnn_atss_assign's
+ *     convention; <= 0 and invalid cells are background: the reference passes no weight to loss_cls).  Per positive: target =
+ *     bbox2distance(point, gt), gt' = distance2bbox(point, target), the boxes of D0 and D1, w_ini = max(aligned
+ *     bbox_overlaps(box0, gt'), 1e-6), w_rf likewise (constants); sums of w_ini * (1 - giou0) and w_rf * (1 - giou1).  Class
+ *     term over every (row, class): at a positive's label q = w_rf, q * BCE(x, q) (iou_weighted) or BCE(x, q); elsewhere
+ *     alpha * sigmoid(x)^gamma * softplus(x); gamma >= 1.  forward leaves block partials and norm3 = [n_pos of the batch, sum
+ *     w_ini, sum w_rf] on the device (the caller may average norm3 over ranks); finalize clamps each to >= 1 (N, S0, S1) and
+ *     leaves losses (3) = [lw_cls * vfl / N, lw_bbox * box0 / S0, lw_rf * box1 / S1] and coef3 = [lw_cls / N, lw_bbox / S0,
+ *     lw_rf / S1]; backward takes grad_losses (3) and writes every element of dA (rows, stride_a), dD0 and dD1 (rows, 4),
+ *     padding columns and non-positive rows of dD0 / dD1 exactly 0.  Fixed summation order, no float atomics.
+ * cfg7_host = [VFL alpha, VFL gamma, iou_weighted, giou eps, loss_weight_cls, loss_weight_bbox, loss_weight_bbox_refine].
+ * At most BRCNN_MAX_LEVELS levels and BRCNN_MAX_IMAGES images.
+ * -------------------------------------------------------------------------- */
+size_t brcnn_vfnet_rows_workspace_bytes(int batch, int num_levels, const int *heights, const int *widths);
+int brcnn_vfnet_star_offsets(const float *r0, int stride_r, int reg_off, const float *scales, int batch, int num_levels,
+                             const int *heights, const int *widths, const int *strides, const float *denoms_host, float f0,
+                             float f1, float *d0, float *offsets, void *stream);
+int brcnn_vfnet_star_offsets_backward(const float *r0, int stride_r, int reg_off, const float *scales, int batch,
+                                      int num_levels, const int *heights, const int *widths, const int *strides, float f1,
+                                      const float *d0, const float *dd0, const float *doffsets, void *workspace,
+                                      size_t workspace_bytes, float *dr0, float *dscale, void *stream);
+int brcnn_vfnet_refine(const float *r1, int stride_r, int reg_off, const float *scales_refine, int batch, int num_levels,
+                       const int *heights, const int *widths, const float *d0, float *d1, void *stream);
+int brcnn_vfnet_refine_backward(const float *r1, int stride_r, int reg_off, const float *scales_refine, int batch,
+                                int num_levels, const int *heights, const int *widths, const float *d1, const float *dd1,
+                                void *workspace, size_t workspace_bytes, float *dr1, float *dscale, void *stream);
+int brcnn_vfnet_decode_levels(const int64_t *const *topk_inds, const int *counts, const float *a, const float *r1,
+                              const int *layout4_host, const float *scales_refine, int batch, int num_levels,
+                              const int *heights, const int *widths, const int *strides, const float *base_anchors_host,
+                              const float *d0, int num_classes, const float *max_shape, const float *scale_factor,
+                              float score_thr, float *boxes, float *scores, int64_t *labels, uint8_t *valid, int32_t *n_valid,
+                              void *stream);
+size_t brcnn_vfnet_loss_workspace_bytes(int batch, int num_levels, const int *heights, const int *widths, int num_classes);
+int brcnn_vfnet_loss_forward(const float *a, int stride_a, int cls_off, const float *d0, const float *d1, int batch,
+                             int num_levels, const int *heights, const int *widths, const int *strides,
+                             const float *base_anchors_host, int num_classes, const int32_t *gt_inds, const float *gts,
+                             const int64_t *gt_labels, const int *gt_offsets_host, const float *cfg7_host, void *workspace,
+                             size_t workspace_bytes, float *norm3, void *stream);
+int brcnn_vfnet_loss_finalize(const void *workspace, size_t workspace_bytes, const float *norm3, int batch, int num_levels,
+                              const int *heights, const int *widths, int num_classes, const float *cfg7_host, float *losses,
+                              float *coef3, void *stream);
+int brcnn_vfnet_loss_backward(const float *a, int stride_a, int cls_off, const float *d0, const float *d1, int batch,
+                              int num_levels, const int *heights, const int *widths, const int *strides,
+                              const float *base_anchors_host, int num_classes, const int32_t *gt_inds, const float *gts,
+                              const int64_t *gt_labels, const int *gt_offsets_host, const float *cfg7_host,
+                              const float *grad_losses, const float *coef3, float *da, float *dd0, float *dd1, void *stream);
 
 /* ------------------------------------------------------------------------------
  * Optimizer step of the train loop: SGD with momentum and weight decay after clipping the global gradient

@@ -11,7 +11,7 @@ B = int(os.environ.get('B', '8'))
 DTYPE = os.environ.get('BRCNN_DTYPE', 'f32')
 out = {}
 FILES = [(d, f) for d in ('configs/boosting_rcnn', 'configs/dcn', 'configs/faster_rcnn', 'configs/cascade_rcnn', 'configs/retinanet',
-                              'configs/fcos', 'configs/atss', 'configs/gfl') for f in sorted(os.listdir(d))]
+                              'configs/fcos', 'configs/atss', 'configs/gfl', 'configs/vfnet') for f in sorted(os.listdir(d))]
 for d, f in FILES:
     if not f.endswith('.py'):
         continue
