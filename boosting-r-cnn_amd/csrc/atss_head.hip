@@ -10,24 +10,24 @@
 //                        cell index.  The (L * topk) candidates stay in LDS; thread 0 forms mean + std in (level, rank)
 //                        order; every positive candidate claims its anchor with an integer atomic max on
 //                        (IoU bits << 32 | ~gt index).  A second launch turns the keys into gt_inds / max_overlaps.
-//   atss_decode_levels : fcos_decode_levels_kernel with the anchor decode of dense_decode_levels_kernel.
+//   atss_decode_levels : rows_decode_levels_kernel with the anchor decode of dense_decode_levels_kernel.
 //   atss_loss_*        : ATSSHead.loss, the block-partial scheme of fcos_loss_* (fixed order within a thread, LDS tree, one
 //                        finalize workgroup): no float atomics, the same bits from run to run.
 //
-// The layout, the geometry, the decode kernel and the loss kernels are centerness_head.h's, instantiated with AtssTraits.
+// The layout, the geometry, the decode kernel and the loss kernels are row_head.h's, instantiated with AtssTraits.
 #include "box_iou.h"
-#include "centerness_head.h"
+#include "row_head.h"
 
 namespace {
 
 constexpr int AT_MAX_TOPK = 16;
 
-struct AtssGeom : CenternessGeom {
+struct AtssGeom : RowGeom {
     float base[BRCNN_MAX_LEVELS][4];
     float eps, mean[4], std[4], max_ratio;
 };
 
-struct AtssDecode : CenternessDecode {
+struct AtssDecode : RowDecode {
     float base[BRCNN_MAX_LEVELS][4];
     float mean[4], std[4], max_ratio;
 };
@@ -182,7 +182,7 @@ struct AnchorCell {
     float ctr_t;
 };
 
-struct AtssTraits {
+struct AtssTraits : CenternessTraits<AtssTraits> {
     using Geom = AtssGeom;
     using Decode = AtssDecode;
     using Cell = AnchorCell;
@@ -192,8 +192,8 @@ struct AtssTraits {
     static __device__ __forceinline__ int grad(const AtssGeom& g, int term, int l) { return term * g.L + l; }     // gl (3, L)
 
     // delta2bbox of the cell's anchor, after the Scale
-    static __device__ __forceinline__ float4 decode_box(const AtssDecode& lv, int l, int cell, const float* __restrict__ raw,
-                                                        float sc) {
+    static __device__ __forceinline__ float4 decode_box(const AtssDecode& lv, int l, int cell, size_t,
+                                                        const float* __restrict__ raw, float sc) {
         const float4 an = anchor_of(lv.base[l], lv.width[l], lv.stride[l], cell);
         const float d[4] = {sc * raw[0], sc * raw[1], sc * raw[2], sc * raw[3]};
         return decode_anchor<false>(an, d, lv.mean, lv.std, lv.max_ratio, nullptr);
@@ -317,10 +317,7 @@ BRCNN_API int brcnn_atss_assign(const float* gts, const int* gt_offsets_host, in
         hipLaunchKernelGGL(atss_assign_kernel, dim3(total_gt), dim3(CH_THREADS), 0, (hipStream_t)stream, g, as, gts, keys);
         BRCNN_LAUNCH_CHECK();
     }
-    const long long total = (long long)batch * g.n;
-    long long grid = (total + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(atss_assign_write_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, g, as, keys, gt_inds,
+    hipLaunchKernelGGL(atss_assign_write_kernel, dim3(rows_grid((long long)batch * g.n)), dim3(256), 0, (hipStream_t)stream, g, as, keys, gt_inds,
                        max_overlaps);
     BRCNN_LAUNCH_CHECK();
     return 0;
@@ -338,8 +335,7 @@ BRCNN_API int brcnn_atss_decode_levels(const int64_t* const* topk_inds, const in
     const int st = fill_decode_common(lv, topk_inds, counts, a, r, layout8_host, scales, batch, num_levels, heights, widths,
                                       strides, num_classes, max_shape, score_thr, boxes, scores, labels, valid, n_valid);
     if (st) return st;
-    for (int l = 0; l < num_levels; l++)
-        for (int k = 0; k < 4; k++) lv.base[l][k] = base_anchors_host[4 * l + k];
+    fill_decode_base(lv, base_anchors_host, num_levels);
     for (int k = 0; k < 4; k++) { lv.mean[k] = means4_host[k]; lv.std[k] = stds4_host[k]; }
     lv.max_ratio = (float)fabs(log(wh_ratio_clip));
     return launch_decode_levels<AtssTraits>(lv, batch, a, r, scales, max_shape, scale_factor, boxes, scores, labels, valid,
@@ -349,9 +345,7 @@ BRCNN_API int brcnn_atss_decode_levels(const int64_t* const* topk_inds, const in
 BRCNN_API size_t brcnn_atss_loss_workspace_bytes(int batch, int num_levels, const int* heights, const int* widths,
                                                  int num_classes) {
     AtssGeom g;
-    int ones[BRCNN_MAX_LEVELS];
-    for (int l = 0; l < BRCNN_MAX_LEVELS; l++) ones[l] = 1;
-    if (fill_geom(g, batch, num_levels, heights, widths, ones, nullptr, num_classes, nullptr, nullptr, nullptr)) return 0;
+    if (fill_geom(g, batch, num_levels, heights, widths, UnitStrides().v, nullptr, num_classes, nullptr, nullptr, nullptr)) return 0;
     return loss_workspace_bytes<AtssTraits>(g);
 }
 
@@ -370,9 +364,8 @@ BRCNN_API int brcnn_atss_loss_forward(const float* a, const float* r, const int*
         workspace_bytes < loss_workspace_bytes<AtssTraits>(g))
         return BRCNN_EINVAL;
     float* partials = (float*)workspace;
-    hipLaunchKernelGGL(centerness_loss_forward_kernel<AtssTraits>, dim3(g.blk0[CH_SEGS]), dim3(CH_THREADS), 0,
-                       (hipStream_t)stream, g, a, r, scales, gt_inds, gts, gt_labels, partials);
-    BRCNN_LAUNCH_CHECK();
+    const int fs = launch_loss_forward<AtssTraits>(g, ScaledRows{a, r, scales}, gt_inds, gts, gt_labels, partials, stream);
+    if (fs) return fs;
     hipLaunchKernelGGL(anchor_loss_norm_kernel<AtssTraits>, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, gt_inds, partials, norm2);
     BRCNN_LAUNCH_CHECK();
     return 0;
@@ -382,10 +375,9 @@ BRCNN_API int brcnn_atss_loss_finalize(const void* workspace, size_t workspace_b
                                        int num_levels, const int* heights, const int* widths, int num_classes,
                                        const float* cfg15_host, float* losses, float* coef3, void* stream) {
     AtssGeom g;
-    int ones[BRCNN_MAX_LEVELS];
-    for (int l = 0; l < BRCNN_MAX_LEVELS; l++) ones[l] = 1;
     if (!cfg15_host) return BRCNN_EINVAL;
-    const int st = fill_geom(g, batch, num_levels, heights, widths, ones, nullptr, num_classes, nullptr, nullptr, cfg15_host);
+    const int st = fill_geom(g, batch, num_levels, heights, widths, UnitStrides().v, nullptr, num_classes, nullptr, nullptr,
+                             cfg15_host);
     if (st) return st;
     if (!workspace || !norm2 || !losses || !coef3 || workspace_bytes < loss_workspace_bytes<AtssTraits>(g)) return BRCNN_EINVAL;
     hipLaunchKernelGGL(atss_loss_finalize_kernel, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g,

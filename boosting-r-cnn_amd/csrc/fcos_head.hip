@@ -22,20 +22,20 @@
 //                        formed in the kernel.  Block partials (fixed order within a thread, LDS tree) -> one workgroup
 //                        (strided sums, LDS tree): no float atomics, the same bits from run to run.
 //
-// The layout, the geometry, the decode kernel and the loss kernels are centerness_head.h's, instantiated with FcosTraits.
-#include "centerness_head.h"
+// The layout, the geometry, the decode kernel and the loss kernels are row_head.h's, instantiated with FcosTraits.
+#include "row_head.h"
 
 namespace {
 
 constexpr float FC_INF = 1e8f;
 
-struct FcosGeom : CenternessGeom {
+struct FcosGeom : RowGeom {
     float eps_overlap, eps_loss;
 };
 
 // ------------------------------------------------------------------------------------------------------------ test time
 __global__ __launch_bounds__(256) void fcos_score_kernel(const float* __restrict__ a, const float* __restrict__ r,
-                                                        const CenternessLayout lay, int C, long long rows,
+                                                        const RowLayout lay, int C, long long rows,
                                                         float* __restrict__ score) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (long long)gridDim.x * blockDim.x) {
         const float* x = a + (size_t)i * lay.sa + lay.cls_off;
@@ -101,9 +101,9 @@ struct Point {
     float px, py, t[4], ctr_t;
 };
 
-struct FcosTraits {
+struct FcosTraits : CenternessTraits<FcosTraits> {
     using Geom = FcosGeom;
-    using Decode = CenternessDecode;
+    using Decode = RowDecode;
     using Cell = Point;
     static constexpr int PARTIALS = 4;              // the fourth: the number of positives
     static constexpr bool HAS_INVALID = false;
@@ -111,7 +111,7 @@ struct FcosTraits {
     static __device__ __forceinline__ int grad(const FcosGeom&, int term, int) { return term; }      // g3 (3,)
 
     // distance2bbox around the cell centre (core/bbox/transforms.py), after the Scale and the exp | relu * stride
-    static __device__ __forceinline__ float4 decode_box(const CenternessDecode& lv, int l, int cell,
+    static __device__ __forceinline__ float4 decode_box(const RowDecode& lv, int l, int cell, size_t,
                                                         const float* __restrict__ raw, float sc) {
         const int st = lv.stride[l];
         const float px = (float)((cell % lv.width[l]) * st + st / 2);
@@ -177,14 +177,6 @@ struct FcosTraits {
     }
 };  // FcosTraits
 
-// the sum of partials[which] over the workgroups of term `term` (0 class, 1 points) of every level, level by level
-__device__ __forceinline__ float term_sum(const FcosGeom& g, const float* __restrict__ partials, int which, int term,
-                                          float* red, int tid) {
-    float total = 0.f;
-    for (int l = 0; l < g.L; l++) total += level_sum(g, partials, which, l, term, red, tid);
-    return total;
-}
-
 // norm2 = [number of positives of the batch, sum of their centerness targets]
 __global__ __launch_bounds__(256) void fcos_loss_norm_kernel(const FcosGeom g, const float* __restrict__ partials,
                                                             float* __restrict__ norm2) {
@@ -249,7 +241,7 @@ BRCNN_API int brcnn_fcos_decode_levels(const int64_t* const* topk_inds, const in
                                        const int* heights, const int* widths, const int* strides, int num_classes,
                                        const float* max_shape, const float* scale_factor, float score_thr, float* boxes,
                                        float* scores, int64_t* labels, uint8_t* valid, int32_t* n_valid, void* stream) {
-    CenternessDecode lv = {};
+    RowDecode lv = {};
     const int st = fill_decode_common(lv, topk_inds, counts, a, r, layout8_host, scales, batch, num_levels, heights, widths,
                                       strides, num_classes, max_shape, score_thr, boxes, scores, labels, valid, n_valid);
     if (st) return st;
@@ -271,10 +263,7 @@ BRCNN_API int brcnn_fcos_assign(const float* gts, const int* gt_offsets_host, in
         as.lo[l] = ranges_host[2 * l]; as.hi[l] = ranges_host[2 * l + 1];
         as.rad[l] = (float)((double)strides[l] * center_sample_radius);    // `strides[lvl] * radius` stored into a fp32 tensor
     }
-    const long long total = (long long)batch * g.n;
-    long long grid = (total + 255) / 256;
-    if (grid > 8192) grid = 8192;
-    hipLaunchKernelGGL(fcos_assign_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, g, as, gts, gt_inds);
+    hipLaunchKernelGGL(fcos_assign_kernel, dim3(rows_grid((long long)batch * g.n)), dim3(256), 0, (hipStream_t)stream, g, as, gts, gt_inds);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }
@@ -282,9 +271,7 @@ BRCNN_API int brcnn_fcos_assign(const float* gts, const int* gt_offsets_host, in
 BRCNN_API size_t brcnn_fcos_loss_workspace_bytes(int batch, int num_levels, const int* heights, const int* widths,
                                                  int num_classes) {
     FcosGeom g;
-    int ones[BRCNN_MAX_LEVELS];
-    for (int l = 0; l < BRCNN_MAX_LEVELS; l++) ones[l] = 1;
-    if (fill_geom(g, batch, num_levels, heights, widths, ones, num_classes, nullptr, nullptr, nullptr)) return 0;
+    if (fill_geom(g, batch, num_levels, heights, widths, UnitStrides().v, num_classes, nullptr, nullptr, nullptr)) return 0;
     return loss_workspace_bytes<FcosTraits>(g);
 }
 
@@ -302,9 +289,8 @@ BRCNN_API int brcnn_fcos_loss_forward(const float* a, const float* r, const int*
         workspace_bytes < loss_workspace_bytes<FcosTraits>(g))
         return BRCNN_EINVAL;
     float* partials = (float*)workspace;
-    hipLaunchKernelGGL(centerness_loss_forward_kernel<FcosTraits>, dim3(g.blk0[CH_SEGS]), dim3(CH_THREADS), 0,
-                       (hipStream_t)stream, g, a, r, scales, gt_inds, gts, gt_labels, partials);
-    BRCNN_LAUNCH_CHECK();
+    const int fs = launch_loss_forward<FcosTraits>(g, ScaledRows{a, r, scales}, gt_inds, gts, gt_labels, partials, stream);
+    if (fs) return fs;
     hipLaunchKernelGGL(fcos_loss_norm_kernel, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, partials, norm2);
     BRCNN_LAUNCH_CHECK();
     return 0;
@@ -314,10 +300,8 @@ BRCNN_API int brcnn_fcos_loss_finalize(const void* workspace, size_t workspace_b
                                        int num_levels, const int* heights, const int* widths, int num_classes,
                                        const float* cfg7_host, float* losses3, float* coef3, void* stream) {
     FcosGeom g;
-    int ones[BRCNN_MAX_LEVELS];
-    for (int l = 0; l < BRCNN_MAX_LEVELS; l++) ones[l] = 1;
     if (!cfg7_host) return BRCNN_EINVAL;
-    const int st = fill_geom(g, batch, num_levels, heights, widths, ones, num_classes, nullptr, nullptr, cfg7_host);
+    const int st = fill_geom(g, batch, num_levels, heights, widths, UnitStrides().v, num_classes, nullptr, nullptr, cfg7_host);
     if (st) return st;
     if (!workspace || !norm2 || !losses3 || !coef3 || workspace_bytes < loss_workspace_bytes<FcosTraits>(g))
         return BRCNN_EINVAL;

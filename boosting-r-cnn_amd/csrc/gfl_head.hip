@@ -1,40 +1,35 @@
 // The GFL head: GFLHead (mmdet/models/dense_heads/gfl_head.py) with QualityFocalLoss / DistributionFocalLoss
 // (models/losses/gfocal_loss.py), trained on brcnn_atss_assign's gt_inds.
 //
-// One anchor per cell, regenerated where it is needed (centerness_head.h: anchor_of); only its centre is used.  The head's
+// One anchor per cell, regenerated where it is needed (row_head.h: anchor_of); only its centre is used.  The head's
 // outputs are two fp32 row tensors: A with the C class logits, R with the 4 * (reg_max + 1) RAW box logits, side-major
 // [left | top | right | bottom]; logit = scale_l * raw is formed here.  A side's distance is the expectation of the
 // max-subtracted softmax over its reg_max + 1 logits, exp sum and expectation accumulated in bin order.
 //
 //   gfl_decode_levels : one thread per (image, pick, class) slot; distance * stride from the anchor centre, then
 //                       decode_tail.h's store_candidate.  score = sigmoid(cls_c): GFL has no centerness.
-//   gfl_loss_*        : GFLHead.loss in the block-partial scheme of centerness_head.h (its geometry, block_sum, level_sum,
-//                       the norm and dscale kernels): fixed order within a thread, LDS tree, one finalize workgroup; no
-//                       float atomics, the same bits from run to run.  The forward / backward kernels are this file's own:
-//                       the class term reads a per-row quality (the IoU of the row's decoded box, recomputed by the one
-//                       thread that needs it), and a box row is 4 * (reg_max + 1) wide with two loss terms on it.
+//   gfl_loss_*        : GFLHead.loss in the block-partial scheme of row_head.h: fixed order within a thread, LDS tree, one
+//                       finalize workgroup; no float atomics, the same bits from run to run.  The class term reads a per-row
+//                       quality (the IoU of the row's decoded box, recomputed by the one thread that needs it).  The dR
+//                       kernel is this file's own: a box row is 4 * (reg_max + 1) wide with two loss terms on it.
+//
+// The layout, the geometry, the decode kernel, the loss forward and the dA kernels are row_head.h's, instantiated with GflTraits.
 #include "box_iou.h"
-#include "centerness_head.h"
+#include "row_head.h"
 
 namespace {
 
 constexpr int GFL_MAX_REG = 16;
 
-struct GflGeom : CenternessGeom {
+struct GflGeom : RowGeom {
     float base[BRCNN_MAX_LEVELS][4];
     int reg_max;
     float beta, eps, lw_dfl;
 };
 
-struct GflDecode : CenternessDecode {
+struct GflDecode : RowDecode {
     float base[BRCNN_MAX_LEVELS][4];
     int reg_max;
-};
-
-// only what the shared norm / dscale kernels and the workspace size ask of a traits type
-struct GflTraits {
-    using Geom = GflGeom;
-    static constexpr int PARTIALS = 3;
 };
 
 // the integral of one side: logits x_i = sc * raw[i], i = 0 .. n.  Returns the expectation sum p_i * i; *mx the maximum,
@@ -49,45 +44,6 @@ __device__ __forceinline__ float side_integral(const float* __restrict__ raw, fl
     *mx = m;
     *z = zs;
     return d;
-}
-
-// -------------------------------------------------------------------------------------------------------------- test time
-__global__ __launch_bounds__(256) void gfl_decode_levels_kernel(const GflDecode lv, int batch, const float* __restrict__ a,
-                                                               const float* __restrict__ r,
-                                                               const float* __restrict__ scales,
-                                                               const float* __restrict__ max_shape,
-                                                               const float* __restrict__ scale_factor,
-                                                               float* __restrict__ boxes, float* __restrict__ scores,
-                                                               int64_t* __restrict__ labels, uint8_t* __restrict__ valid,
-                                                               int* __restrict__ n_valid) {
-    const long long per_image = (long long)lv.T * lv.C;
-    const long long total = (long long)batch * per_image;
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(t / per_image);
-        const long long q = t - (long long)b * per_image;
-        const int col = (int)(q / lv.C), c = (int)(q - (long long)col * lv.C);
-        int l = 0;
-#pragma unroll
-        for (int i = 1; i < BRCNN_MAX_LEVELS; i++)
-            if (i < lv.num && col >= lv.col0[i]) l = i;
-        const int count = lv.col0[l + 1] - lv.col0[l];
-        long long cell = lv.inds[l][(size_t)b * count + (col - lv.col0[l])];
-        cell = cell < 0 ? 0 : (cell >= lv.hw[l] ? lv.hw[l] - 1 : cell);     // (a picked index is a cell of the level)
-        const size_t row = (size_t)(lv.row0[l] + (long long)b * lv.hw[l] + cell);
-        const float s = sigmoidf_(a[row * lv.lay.sa + lv.lay.cls_off + c]);
-        const float4 an = anchor_of(lv.base[l], lv.width[l], lv.stride[l], (int)cell);
-        const float cx = (an.z + an.x) / 2.f, cy = (an.w + an.y) / 2.f;
-        const float* raw = r + row * lv.lay.sr + lv.lay.reg_off;
-        const float sc = scales[l], st = (float)lv.stride[l];
-        const int w = lv.reg_max + 1;
-        float m, z;
-        const float d0 = side_integral(raw, sc, lv.reg_max, &m, &z) * st;
-        const float d1 = side_integral(raw + w, sc, lv.reg_max, &m, &z) * st;
-        const float d2 = side_integral(raw + 2 * w, sc, lv.reg_max, &m, &z) * st;
-        const float d3 = side_integral(raw + 3 * w, sc, lv.reg_max, &m, &z) * st;
-        store_candidate(t, b, c, cx - d0, cy - d1, cx + d2, cy + d3, s, s > lv.score_thr, max_shape, scale_factor, boxes, scores,
-                        labels, valid, n_valid);
-    }
 }
 
 // ------------------------------------------------------------------------------------------------------------------ loss
@@ -152,10 +108,6 @@ __device__ __forceinline__ float gfl_target_side(const GflGeom& g, const GflCell
     return fminf(fmaxf(t, 0.f), hi);
 }
 
-// BCE(x, 0) = softplus(x).  Not head_loss.h's bce_logits(x, 0.f): its x - (min(x, 0) - log1p(..)) cancels for x < 0 and
-// leaves an error of eps * |x| on a value of exp(x) -- this term runs over every (anchor, class), most of them far below 0
-__device__ __forceinline__ float softplusf_(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-
 // quality_focal_loss of one (row, class) element.  Off the label: BCE(x, 0) * sigmoid(x)^beta; at a positive's label (hit):
 // BCE(x, q) * |q - sigmoid(x)|^beta.  With BWD the derivative w.r.t. x (q is a constant; abs passes sign(0) = 0)
 template <bool BWD>
@@ -174,70 +126,72 @@ __device__ __forceinline__ float qfl_elem(float x, bool hit, float q, float beta
 
 // partials: 3 arrays of `nblk` floats.  A class workgroup writes [QFL sum, 0, 0]; a point workgroup [weighted GIoU sum,
 // weighted DFL sum, sum of the weights]
-__global__ __launch_bounds__(256) void gfl_loss_forward_kernel(const GflGeom g, const float* __restrict__ a,
-                                                              const float* __restrict__ r, const float* __restrict__ scales,
-                                                              const int* __restrict__ gt_inds, const float* __restrict__ gts,
-                                                              const int64_t* __restrict__ gt_labels,
-                                                              float* __restrict__ partials) {
-    __shared__ float red[CH_THREADS];
-    const int blk = blockIdx.x, tid = threadIdx.x, nblk = g.blk0[CH_SEGS];
-    int seg = 0;
+struct GflTraits {
+    using Geom = GflGeom;
+    using Decode = GflDecode;
+    using Rows = ScaledRows;
+    using Cell = GflCell;
+    static constexpr int PARTIALS = 3;
+    static constexpr bool HAS_INVALID = true;
+    static constexpr bool HAS_CENTERNESS = false;
+    static constexpr bool HAS_QUALITY = true;
+
+    static __device__ __forceinline__ int grad(const GflGeom& g, int term, int l) { return term * g.L + l; }      // gl (3, L)
+
+    // the four integrals * stride around the anchor centre
+    static __device__ __forceinline__ float4 decode_box(const GflDecode& lv, int l, int cell, size_t,
+                                                        const float* __restrict__ raw, float sc) {
+        const float4 an = anchor_of(lv.base[l], lv.width[l], lv.stride[l], cell);
+        const float cx = (an.z + an.x) / 2.f, cy = (an.w + an.y) / 2.f;
+        const float st = (float)lv.stride[l];
+        const int w = lv.reg_max + 1;
+        float m, z;
+        const float d0 = side_integral(raw, sc, lv.reg_max, &m, &z) * st;
+        const float d1 = side_integral(raw + w, sc, lv.reg_max, &m, &z) * st;
+        const float d2 = side_integral(raw + 2 * w, sc, lv.reg_max, &m, &z) * st;
+        const float d3 = side_integral(raw + 3 * w, sc, lv.reg_max, &m, &z) * st;
+        return make_float4(cx - d0, cy - d1, cx + d2, cy + d3);
+    }
+
+    static __device__ __forceinline__ GflCell locate(const GflGeom& g, const int* __restrict__ gt_inds,
+                                                     const float* __restrict__ gts, int l, long long r, bool want_targets) {
+        return gfl_locate(g, gt_inds, gts, l, r, want_targets);
+    }
+
+    static __device__ __forceinline__ float quality(const GflGeom& g, const ScaledRows& in, const int* __restrict__ gt_inds,
+                                                    const float* __restrict__ gts, int l, long long r, size_t row) {
+        const GflCell o = gfl_locate(g, gt_inds, gts, l, r, true);
+        return gfl_quality(gfl_box(g, o, in.r + row * g.lay.sr + g.lay.reg_off, in.scales[l]), o);
+    }
+
+    template <bool BWD>
+    static __device__ __forceinline__ float cls_elem(const GflGeom& g, float x, bool hit, float q) {
+        return qfl_elem<BWD>(x, hit, q, g.beta);
+    }
+
+    static __device__ __forceinline__ void point_terms(const GflGeom& g, const ScaledRows& in, const GflCell& o, int l,
+                                                       size_t row, float* acc) {
+        const float sc = in.scales[l];
+        const float* raw = in.r + row * g.lay.sr + g.lay.reg_off;
+        const GflBox x = gfl_box(g, o, raw, sc);
+        const float wt = gfl_weight(g, in.a, row);
+        acc[0] += corner_box_loss<false>(true, g.eps, g.eps, x.p.x, x.p.y, x.p.z, x.p.w, o.gt.x, o.gt.y, o.gt.z, o.gt.w,
+                                         nullptr) * wt;
+        float dfl = 0.f;
 #pragma unroll
-    for (int i = 1; i < CH_SEGS; i++)
-        if (i < 2 * g.L && blk >= g.blk0[i]) seg = i;
-    const int l = seg >> 1;
-    const bool points = seg & 1;
-    const long long rows = (long long)g.B * g.h[l] * g.w[l];
-    const long long total = points ? rows : rows * g.C;
-    const long long e0 = (long long)(blk - g.blk0[seg]) * CH_CHUNK;
-    const float sc = scales[l];
-    float acc[3] = {0.f, 0.f, 0.f};
-    for (int j = 0; j < CH_PER_THREAD; j++) {
-        const long long e = e0 + (long long)j * CH_THREADS + tid;
-        if (e >= total) break;
-        if (!points) {
-            const long long rr = e / g.C;
-            const int c = (int)(e - rr * g.C);
-            GflCell o = gfl_locate(g, gt_inds, gts, l, rr, false);
-            if (o.gi == -2) continue;
-            const size_t row = (size_t)(g.row0[l] + rr);
-            const bool hit = o.gi >= 0 && gt_labels[o.gi] == c;
-            float q = 0.f;
-            if (hit) {
-                o = gfl_locate(g, gt_inds, gts, l, rr, true);
-                q = gfl_quality(gfl_box(g, o, r + row * g.lay.sr + g.lay.reg_off, sc), o);
-            }
-            acc[0] += qfl_elem<false>(a[row * g.lay.sa + g.lay.cls_off + c], hit, q, g.beta);
-        } else {
-            const GflCell o = gfl_locate(g, gt_inds, gts, l, e, true);
-            if (o.gi < 0) continue;
-            const size_t row = (size_t)(g.row0[l] + e);
-            const float* raw = r + row * g.lay.sr + g.lay.reg_off;
-            const GflBox x = gfl_box(g, o, raw, sc);
-            const float wt = gfl_weight(g, a, row);
-            acc[0] += corner_box_loss<false>(true, g.eps, g.eps, x.p.x, x.p.y, x.p.z, x.p.w, o.gt.x, o.gt.y, o.gt.z, o.gt.w,
-                                             nullptr) * wt;
-            float dfl = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float t = gfl_target_side(g, o, k);
-                const int left = (int)t;                                     // t >= 0: the truncation is the floor
-                const float wl = (float)(left + 1) - t, wr = t - (float)left;
-                const float* rk = raw + k * (g.reg_max + 1);
-                const float lz = logf(x.z[k]);
-                const float ce_l = -((sc * rk[left] - x.m[k]) - lz), ce_r = -((sc * rk[left + 1] - x.m[k]) - lz);
-                dfl += ce_l * wl + ce_r * wr;
-            }
-            acc[1] += dfl * wt * 0.25f;
-            acc[2] += wt;
+        for (int k = 0; k < 4; k++) {
+            const float t = gfl_target_side(g, o, k);
+            const int left = (int)t;                                     // t >= 0: the truncation is the floor
+            const float wl = (float)(left + 1) - t, wr = t - (float)left;
+            const float* rk = raw + k * (g.reg_max + 1);
+            const float lz = logf(x.z[k]);
+            const float ce_l = -((sc * rk[left] - x.m[k]) - lz), ce_r = -((sc * rk[left + 1] - x.m[k]) - lz);
+            dfl += ce_l * wl + ce_r * wr;
         }
+        acc[1] += dfl * wt * 0.25f;
+        acc[2] += wt;
     }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float s = block_sum(acc[k], red, tid);
-        if (tid == 0) partials[k * nblk + blk] = s;
-    }
-}
+};  // GflTraits
 
 // losses (3, L) = [loss_cls | loss_bbox | loss_dfl] per level; coef3 = [lw_cls / N, lw_bbox / S, lw_dfl / S]
 __global__ __launch_bounds__(256) void gfl_loss_finalize_kernel(const GflGeom g, const float* __restrict__ partials,
@@ -259,37 +213,6 @@ __global__ __launch_bounds__(256) void gfl_loss_finalize_kernel(const GflGeom g,
         coef3[0] = g.lw_cls / N;
         coef3[1] = g.lw_bbox / S;
         coef3[2] = g.lw_dfl / S;
-    }
-}
-
-// one thread per element of dA (rows, stride_a), padding columns included: every element is written
-__global__ __launch_bounds__(256) void gfl_loss_backward_a_kernel(const GflGeom g, const float* __restrict__ a,
-                                                                 const float* __restrict__ r,
-                                                                 const float* __restrict__ scales,
-                                                                 const int* __restrict__ gt_inds,
-                                                                 const float* __restrict__ gts,
-                                                                 const int64_t* __restrict__ gt_labels,
-                                                                 const float* __restrict__ gl,
-                                                                 const float* __restrict__ coef3, float* __restrict__ da) {
-    const long long total = g.row0[g.L] * g.lay.sa;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-        const long long row = e / g.lay.sa;
-        const int c = (int)(e - row * g.lay.sa) - g.lay.cls_off;
-        float v = 0.f;
-        if (c >= 0 && c < g.C) {
-            const int l = level_of_row(g, row);
-            GflCell o = gfl_locate(g, gt_inds, gts, l, row - g.row0[l], false);
-            if (o.gi != -2) {
-                const bool hit = o.gi >= 0 && gt_labels[o.gi] == c;
-                float q = 0.f;
-                if (hit) {
-                    o = gfl_locate(g, gt_inds, gts, l, row - g.row0[l], true);
-                    q = gfl_quality(gfl_box(g, o, r + (size_t)row * g.lay.sr + g.lay.reg_off, scales[l]), o);
-                }
-                v = gl[l] * coef3[0] * qfl_elem<true>(a[e], hit, q, g.beta);
-            }
-        }
-        da[e] = v;
     }
 }
 
@@ -356,16 +279,9 @@ __global__ __launch_bounds__(256) void gfl_loss_backward_r_kernel(const GflGeom 
 }
 
 // --------------------------------------------------------------------------------------------------------------- host
-// layout4_host = [stride_a, cls_off, stride_r, reg_off]
+// layout4 (row_head.h) with 4 * (reg_max + 1) box columns
 bool gfl_layout_ok(const int* v, int C, int reg_max) {
-    if (!v || reg_max < 1 || reg_max > GFL_MAX_REG) return false;
-    return v[0] > 0 && v[2] > 0 && v[1] >= 0 && v[3] >= 0 && v[1] + C <= v[0] && v[3] + 4 * (reg_max + 1) <= v[2];
-}
-
-CenternessLayout gfl_layout(const int* v) {
-    CenternessLayout y = {};
-    y.sa = v[0]; y.cls_off = v[1]; y.sr = v[2]; y.reg_off = v[3];
-    return y;
+    return reg_max >= 1 && reg_max <= GFL_MAX_REG && layout4_ok(v, C, 4 * (reg_max + 1));
 }
 
 // cfg5_host: [QFL beta, eps of the GIoU, loss_weight_cls, loss_weight_bbox, loss_weight_dfl]
@@ -377,7 +293,7 @@ int fill_geom(GflGeom& g, int batch, int num_levels, const int* heights, const i
     g.reg_max = reg_max;
     if (layout4) {
         if (!gfl_layout_ok(layout4, C, reg_max)) return BRCNN_EINVAL;
-        g.lay = gfl_layout(layout4);
+        g.lay = make_layout4(layout4);
     }
     for (int l = 0; l < BRCNN_MAX_LEVELS; l++)
         for (int k = 0; k < 4; k++) g.base[l][k] = (base && l < num_levels) ? base[4 * l + k] : 0.f;
@@ -403,27 +319,18 @@ BRCNN_API int brcnn_gfl_decode_levels(const int64_t* const* topk_inds, const int
     GflDecode lv = {};
     const int st = fill_decode_picks(lv, topk_inds, counts, batch, num_levels, heights, widths, strides, num_classes, score_thr);
     if (st) return st;
-    lv.lay = gfl_layout(layout4_host);
+    lv.lay = make_layout4(layout4_host);
     lv.reg_max = reg_max;
-    for (int l = 0; l < num_levels; l++)
-        for (int k = 0; k < 4; k++) lv.base[l][k] = base_anchors_host[4 * l + k];
-    if (batch == 0) return 0;
-    BRCNN_HIP_CHECK(hipMemsetAsync(n_valid, 0, sizeof(int32_t) * batch, (hipStream_t)stream));
-    const long long total = (long long)batch * lv.T * lv.C;
-    long long grid = (total + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(gfl_decode_levels_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, lv, batch, a, r, scales,
-                       max_shape, scale_factor, boxes, scores, labels, valid, n_valid);
-    BRCNN_LAUNCH_CHECK();
-    return 0;
+    fill_decode_base(lv, base_anchors_host, num_levels);
+    return launch_decode_levels<GflTraits>(lv, batch, a, r, scales, max_shape, scale_factor, boxes, scores, labels, valid,
+                                           n_valid, stream);
 }
 
 BRCNN_API size_t brcnn_gfl_loss_workspace_bytes(int batch, int num_levels, const int* heights, const int* widths,
                                                 int num_classes) {
     GflGeom g;
-    int ones[BRCNN_MAX_LEVELS];
-    for (int l = 0; l < BRCNN_MAX_LEVELS; l++) ones[l] = 1;
-    if (fill_geom(g, batch, num_levels, heights, widths, ones, nullptr, 1, num_classes, nullptr, nullptr, nullptr)) return 0;
+    if (fill_geom(g, batch, num_levels, heights, widths, UnitStrides().v, nullptr, 1, num_classes, nullptr, nullptr, nullptr))
+        return 0;
     return loss_workspace_bytes<GflTraits>(g);
 }
 
@@ -442,9 +349,8 @@ BRCNN_API int brcnn_gfl_loss_forward(const float* a, const float* r, const int* 
         workspace_bytes < loss_workspace_bytes<GflTraits>(g))
         return BRCNN_EINVAL;
     float* partials = (float*)workspace;
-    hipLaunchKernelGGL(gfl_loss_forward_kernel, dim3(g.blk0[CH_SEGS]), dim3(CH_THREADS), 0, (hipStream_t)stream, g, a, r,
-                       scales, gt_inds, gts, gt_labels, partials);
-    BRCNN_LAUNCH_CHECK();
+    const int fs = launch_loss_forward<GflTraits>(g, ScaledRows{a, r, scales}, gt_inds, gts, gt_labels, partials, stream);
+    if (fs) return fs;
     hipLaunchKernelGGL(anchor_loss_norm_kernel<GflTraits>, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, gt_inds,
                        partials, norm2);
     BRCNN_LAUNCH_CHECK();
@@ -455,10 +361,9 @@ BRCNN_API int brcnn_gfl_loss_finalize(const void* workspace, size_t workspace_by
                                       int num_levels, const int* heights, const int* widths, int num_classes,
                                       const float* cfg5_host, float* losses, float* coef3, void* stream) {
     GflGeom g;
-    int ones[BRCNN_MAX_LEVELS];
-    for (int l = 0; l < BRCNN_MAX_LEVELS; l++) ones[l] = 1;
     if (!cfg5_host) return BRCNN_EINVAL;
-    const int st = fill_geom(g, batch, num_levels, heights, widths, ones, nullptr, 1, num_classes, nullptr, nullptr, cfg5_host);
+    const int st = fill_geom(g, batch, num_levels, heights, widths, UnitStrides().v, nullptr, 1, num_classes, nullptr, nullptr,
+                             cfg5_host);
     if (st) return st;
     if (!workspace || !norm2 || !losses || !coef3 || workspace_bytes < loss_workspace_bytes<GflTraits>(g)) return BRCNN_EINVAL;
     hipLaunchKernelGGL(gfl_loss_finalize_kernel, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, (const float*)workspace,
@@ -478,19 +383,17 @@ BRCNN_API int brcnn_gfl_loss_backward(const float* a, const float* r, const int*
     const int st = fill_geom(g, batch, num_levels, heights, widths, strides, base_anchors_host, reg_max, num_classes,
                              gt_offsets_host, layout4_host, cfg5_host);
     if (st) return st;
-    if (!a || !r || !scales || !gt_inds || !grad_losses || !coef3 || !workspace || !da || !dr || !dscale ||
-        ((!gts || !gt_labels) && g.gt_off[batch] > 0) || workspace_bytes < loss_workspace_bytes<GflTraits>(g))
+    if (!loss_backward_args_ok<GflTraits>(g, a, r, scales, gt_inds, gts, gt_labels, grad_losses, coef3, workspace,
+                                          workspace_bytes, da, dr, dscale))
         return BRCNN_EINVAL;
-    long long ga = (g.row0[g.L] * g.lay.sa + 255) / 256;
-    if (ga > 8192) ga = 8192;
-    hipLaunchKernelGGL(gfl_loss_backward_a_kernel, dim3((int)ga), dim3(256), 0, (hipStream_t)stream, g, a, r, scales, gt_inds,
-                       gts, gt_labels, grad_losses, coef3, da);
-    BRCNN_LAUNCH_CHECK();
+    const int as = launch_loss_backward_a<GflTraits>(g, ScaledRows{a, r, scales}, gt_inds, gts, gt_labels, grad_losses, coef3, da,
+                                                     stream);
+    if (as) return as;
     float* dsp = (float*)workspace;
     hipLaunchKernelGGL(gfl_loss_backward_r_kernel, dim3(g.pblk0[g.L]), dim3(CH_THREADS), 0, (hipStream_t)stream, g, a, r, scales,
                        gt_inds, gts, grad_losses, coef3, dr, dsp);
     BRCNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(centerness_dscale_kernel<GflTraits>, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, dsp, dscale);
+    hipLaunchKernelGGL(rows_dscale_kernel<GflTraits>, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, dsp, dscale);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }

@@ -1,5 +1,5 @@
-// Loss elements shared by the dense heads with a centerness branch (fcos_head.hip, atss_head.hip): one definition, so that
-// both heads evaluate the same fp32 expressions in the same order.
+// Loss elements shared by the dense heads on row tensors (fcos_head.hip, atss_head.hip, gfl_head.hip, vfnet_head.hip): one
+// definition, so that every head evaluates the same fp32 expressions in the same order.
 #pragma once
 #include "common.h"
 #include <float.h>
@@ -26,6 +26,10 @@ __device__ __forceinline__ float focal_elem(float x, bool is_pos, float gamma, f
 __device__ __forceinline__ float bce_logits(float x, float t) {
     return (1.f - t) * x - (fminf(x, 0.f) - log1pf(expf(-fabsf(x))));
 }
+
+// BCE(x, 0) = softplus(x).  Not bce_logits(x, 0.f): its x - (min(x, 0) - log1p(..)) cancels for x < 0 and leaves an error
+// of eps * |x| on a value of exp(x) -- this term runs over every (anchor, class), most of them far below 0
+__device__ __forceinline__ float softplusf_(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
 // The box loss of one (predicted, target) pair of corner boxes: aligned bbox_overlaps (iou2d_calculator.py:192-261), then
 // -log(max(iou, eps_loss)) (iou_loss.py:14-50) or, with giou, 1 - giou (:102-117).  With BWD, gp = d loss / d (p1x, p1y,

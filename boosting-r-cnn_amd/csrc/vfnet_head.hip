@@ -1,7 +1,7 @@
 // The VFNet head: VFNetHead (mmdet/models/dense_heads/vfnet_head.py) with VarifocalLoss (models/losses/varifocal_loss.py),
 // trained on brcnn_atss_assign's gt_inds.
 //
-// One anchor per cell, regenerated where it is needed (centerness_head.h: anchor_of); only its centre is used: it is the
+// One anchor per cell, regenerated where it is needed (row_head.h: anchor_of); only its centre is used: it is the
 // reference's point (x * s, y * s) + s * center_offset.  The head leaves fp32 row tensors over all levels, level-major rows:
 // R0 / R1 with 4 RAW distance logits in (l, t, r, b) order, A with the C class logits; D0 / D1 are dense (rows, 4) distances
 // in pixels.
@@ -12,33 +12,36 @@
 //   vfnet_refine        : D1 = exp(scale_refine_l * raw1) * D0 (D0 a constant) and its backward: the same two kernels.
 //   vfnet_decode_levels : one thread per (image, pick, class) slot; D1 of the picked row, distance2bbox from the point, then
 //                         decode_tail.h's store_candidate.  score = sigmoid(cls_c).
-//   vfnet_loss_*        : VFNetHead.loss in the block-partial scheme of centerness_head.h (its geometry, block_sum, level_sum
-//                         and the dscale kernel): fixed order within a thread, LDS tree, one norm and one finalize workgroup;
-//                         no float atomics, the same bits from run to run.
+//   vfnet_loss_*        : VFNetHead.loss in the block-partial scheme of row_head.h: fixed order within a thread, LDS tree,
+//                         one norm and one finalize workgroup; no float atomics, the same bits from run to run.  The dD
+//                         kernel is this file's own.
+//
+// The geometry, the decode kernel, the loss forward and the dA kernels are row_head.h's, instantiated with VfTraits.
 //
 // The deformable kernels (deform.hip, deform_common.h) compare a sample coordinate with (-1, H) x (-1, W) in fp32 BEFORE any
 // conversion to int, so a huge, infinite or NaN offset samples zero and indexes nothing: the offsets are not clamped here.
 #include "box_iou.h"
-#include "centerness_head.h"
+#include "row_head.h"
 
 namespace {
 
-struct VfGeom : CenternessGeom {
+struct VfGeom : RowGeom {
     float base[BRCNN_MAX_LEVELS][4];
     float denom[BRCNN_MAX_LEVELS];
     float eps;
     int iou_weighted;
 };
 
-struct VfDecode : CenternessDecode {
+struct VfDecode : RowDecode {
     float base[BRCNN_MAX_LEVELS][4];
+    const float* d0;                        // (rows, 4), device
 };
 
-// what the shared dscale kernel and the workspace size ask of a traits type.  Partial arrays of the loss forward:
-// [VFL sum (class workgroups) | sum w_ini (1 - giou0) (point workgroups), sum w_rf (1 - giou1), sum w_ini, sum w_rf, n_pos]
-struct VfTraits {
-    using Geom = VfGeom;
-    static constexpr int PARTIALS = 5;
+// the device pointers the loss kernels read
+struct VfRows {
+    const float* __restrict__ a;
+    const float* __restrict__ d0;
+    const float* __restrict__ d1;
 };
 
 // -------------------------------------------------------------------------------------------- distances and star offsets
@@ -129,42 +132,6 @@ __global__ __launch_bounds__(256) void vfnet_dist_backward_kernel(const VfGeom g
     if (tid == 0) dscale_partials[blk] = s;
 }
 
-// -------------------------------------------------------------------------------------------------------------- test time
-__global__ __launch_bounds__(256) void vfnet_decode_levels_kernel(const VfDecode lv, int batch, const float* __restrict__ a,
-                                                                 const float* __restrict__ r1, const float* __restrict__ d0,
-                                                                 const float* __restrict__ scales_refine,
-                                                                 const float* __restrict__ max_shape,
-                                                                 const float* __restrict__ scale_factor,
-                                                                 float* __restrict__ boxes, float* __restrict__ scores,
-                                                                 int64_t* __restrict__ labels, uint8_t* __restrict__ valid,
-                                                                 int* __restrict__ n_valid) {
-    const long long per_image = (long long)lv.T * lv.C;
-    const long long total = (long long)batch * per_image;
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-        const int b = (int)(t / per_image);
-        const long long q = t - (long long)b * per_image;
-        const int col = (int)(q / lv.C), c = (int)(q - (long long)col * lv.C);
-        int l = 0;
-#pragma unroll
-        for (int i = 1; i < BRCNN_MAX_LEVELS; i++)
-            if (i < lv.num && col >= lv.col0[i]) l = i;
-        const int count = lv.col0[l + 1] - lv.col0[l];
-        long long cell = lv.inds[l][(size_t)b * count + (col - lv.col0[l])];
-        cell = cell < 0 ? 0 : (cell >= lv.hw[l] ? lv.hw[l] - 1 : cell);     // (a picked index is a cell of the level)
-        const size_t row = (size_t)(lv.row0[l] + (long long)b * lv.hw[l] + cell);
-        const float s = sigmoidf_(a[row * lv.lay.sa + lv.lay.cls_off + c]);
-        const float4 an = anchor_of(lv.base[l], lv.width[l], lv.stride[l], (int)cell);
-        const float px = (an.z + an.x) / 2.f, py = (an.w + an.y) / 2.f;
-        const float* raw = r1 + row * lv.lay.sr + lv.lay.reg_off;
-        const float sc = scales_refine[l];
-        float d[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) d[k] = expf(raw[k] * sc) * d0[row * 4 + k];
-        store_candidate(t, b, c, px - d[0], py - d[1], px + d[2], py + d[3], s, s > lv.score_thr, max_shape, scale_factor, boxes,
-                        scores, labels, valid, n_valid);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------------ loss
 // what one row is: its image, its state and, for a positive, the point and the target box after the reference's round trip
 // gt -> bbox2distance -> distance2bbox (not the identity in fp32)
@@ -202,9 +169,6 @@ __device__ __forceinline__ float vf_weight(const float4 p, const VfCell& o) {
     return fmaxf(pair_iou(p, (p.z - p.x) * (p.w - p.y), o.gt, (o.gt.z - o.gt.x) * (o.gt.w - o.gt.y)), 1e-6f);
 }
 
-// softplus(x) = BCE(x, 0) without the cancellation of bce_logits(x, 0.f) for x < 0
-__device__ __forceinline__ float vf_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
-
 // varifocal_loss of one (row, class) element.  At a positive's label (hit, q > 0): BCE(x, q) * q (iou_weighted) or BCE(x, q);
 // elsewhere BCE(x, 0) * (alpha * sigmoid(x)^gamma).  With BWD the derivative w.r.t. x (q is a constant)
 template <bool BWD>
@@ -214,72 +178,65 @@ __device__ __forceinline__ float vfl_elem(float x, bool hit, float q, float alph
         if (!BWD) return iou_weighted ? bce_logits(x, q) * q : bce_logits(x, q);
         return iou_weighted ? (p - q) * q : p - q;
     }
-    const float ce = vf_softplus(x), mod = alpha * powf(p, gamma);
+    const float ce = softplusf_(x), mod = alpha * powf(p, gamma);
     if (!BWD) return ce * mod;
     return p * mod + ce * (gamma * mod * (1.f - p));
 }
 
-__global__ __launch_bounds__(256) void vfnet_loss_forward_kernel(const VfGeom g, const float* __restrict__ a,
-                                                                const float* __restrict__ d0, const float* __restrict__ d1,
-                                                                const int* __restrict__ gt_inds, const float* __restrict__ gts,
-                                                                const int64_t* __restrict__ gt_labels,
-                                                                float* __restrict__ partials) {
-    __shared__ float red[CH_THREADS];
-    const int blk = blockIdx.x, tid = threadIdx.x, nblk = g.blk0[CH_SEGS];
-    int seg = 0;
-#pragma unroll
-    for (int i = 1; i < CH_SEGS; i++)
-        if (i < 2 * g.L && blk >= g.blk0[i]) seg = i;
-    const int l = seg >> 1;
-    const bool points = seg & 1;
-    const long long rows = (long long)g.B * g.h[l] * g.w[l];
-    const long long total = points ? rows : rows * g.C;
-    const long long e0 = (long long)(blk - g.blk0[seg]) * CH_CHUNK;
-    float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < CH_PER_THREAD; j++) {
-        const long long e = e0 + (long long)j * CH_THREADS + tid;
-        if (e >= total) break;
-        if (!points) {
-            const long long rr = e / g.C;
-            const int c = (int)(e - rr * g.C);
-            VfCell o = vf_locate(g, gt_inds, gts, l, rr, false);
-            const size_t row = (size_t)(g.row0[l] + rr);
-            const bool hit = o.gi >= 0 && gt_labels[o.gi] == c;
-            float q = 0.f;
-            if (hit) {
-                o = vf_locate(g, gt_inds, gts, l, rr, true);
-                q = vf_weight(vf_box(o, d1 + row * 4), o);
-            }
-            acc[0] += vfl_elem<false>(a[row * g.lay.sa + g.lay.cls_off + c], hit, q, g.alpha, g.gamma, g.iou_weighted != 0);
-        } else {
-            const VfCell o = vf_locate(g, gt_inds, gts, l, e, true);
-            if (o.gi < 0) continue;
-            const size_t row = (size_t)(g.row0[l] + e);
-            const float4 p0 = vf_box(o, d0 + row * 4), p1 = vf_box(o, d1 + row * 4);
-            const float w0 = vf_weight(p0, o), w1 = vf_weight(p1, o);
-            acc[0] += corner_box_loss<false>(true, g.eps, g.eps, p0.x, p0.y, p0.z, p0.w, o.gt.x, o.gt.y, o.gt.z, o.gt.w,
-                                             nullptr) * w0;
-            acc[1] += corner_box_loss<false>(true, g.eps, g.eps, p1.x, p1.y, p1.z, p1.w, o.gt.x, o.gt.y, o.gt.z, o.gt.w,
-                                             nullptr) * w1;
-            acc[2] += w0;
-            acc[3] += w1;
-            acc[4] += 1.f;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        const float s = block_sum(acc[k], red, tid);
-        if (tid == 0) partials[k * nblk + blk] = s;
-    }
-}
+// Partial arrays of the loss forward: [VFL sum (class workgroups) | sum w_ini (1 - giou0) (point workgroups),
+// sum w_rf (1 - giou1), sum w_ini, sum w_rf, n_pos]
+struct VfTraits {
+    using Geom = VfGeom;
+    using Decode = VfDecode;
+    using Rows = VfRows;
+    using Cell = VfCell;
+    static constexpr int PARTIALS = 5;
+    static constexpr bool HAS_INVALID = false;      // an invalid cell counts as background
+    static constexpr bool HAS_CENTERNESS = false;
+    static constexpr bool HAS_QUALITY = true;
 
-// the sum of partials[which] of (term) over all levels, level by level
-__device__ __forceinline__ float vf_total(const VfGeom& g, const float* __restrict__ partials, int which, int term, float* red,
-                                          int tid) {
-    float s = 0.f;
-    for (int l = 0; l < g.L; l++) s += level_sum(g, partials, which, l, term, red, tid);
-    return s;
-}
+    static __device__ __forceinline__ int grad(const VfGeom&, int term, int) { return term; }        // g3 (3,)
+
+    // distance2bbox from the point with D1 = exp(scale_refine * raw1) * D0 of the picked row
+    static __device__ __forceinline__ float4 decode_box(const VfDecode& lv, int l, int cell, size_t row,
+                                                        const float* __restrict__ raw, float sc) {
+        const float4 an = anchor_of(lv.base[l], lv.width[l], lv.stride[l], cell);
+        const float px = (an.z + an.x) / 2.f, py = (an.w + an.y) / 2.f;
+        float d[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) d[k] = expf(raw[k] * sc) * lv.d0[row * 4 + k];
+        return make_float4(px - d[0], py - d[1], px + d[2], py + d[3]);
+    }
+
+    static __device__ __forceinline__ VfCell locate(const VfGeom& g, const int* __restrict__ gt_inds,
+                                                    const float* __restrict__ gts, int l, long long r, bool want_targets) {
+        return vf_locate(g, gt_inds, gts, l, r, want_targets);
+    }
+
+    static __device__ __forceinline__ float quality(const VfGeom& g, const VfRows& in, const int* __restrict__ gt_inds,
+                                                    const float* __restrict__ gts, int l, long long r, size_t row) {
+        const VfCell o = vf_locate(g, gt_inds, gts, l, r, true);
+        return vf_weight(vf_box(o, in.d1 + row * 4), o);
+    }
+
+    template <bool BWD>
+    static __device__ __forceinline__ float cls_elem(const VfGeom& g, float x, bool hit, float q) {
+        return vfl_elem<BWD>(x, hit, q, g.alpha, g.gamma, g.iou_weighted != 0);
+    }
+
+    static __device__ __forceinline__ void point_terms(const VfGeom& g, const VfRows& in, const VfCell& o, int, size_t row,
+                                                       float* acc) {
+        const float4 p0 = vf_box(o, in.d0 + row * 4), p1 = vf_box(o, in.d1 + row * 4);
+        const float w0 = vf_weight(p0, o), w1 = vf_weight(p1, o);
+        acc[0] += corner_box_loss<false>(true, g.eps, g.eps, p0.x, p0.y, p0.z, p0.w, o.gt.x, o.gt.y, o.gt.z, o.gt.w,
+                                         nullptr) * w0;
+        acc[1] += corner_box_loss<false>(true, g.eps, g.eps, p1.x, p1.y, p1.z, p1.w, o.gt.x, o.gt.y, o.gt.z, o.gt.w,
+                                         nullptr) * w1;
+        acc[2] += w0;
+        acc[3] += w1;
+        acc[4] += 1.f;
+    }
+};  // VfTraits
 
 // norm3 = [number of positives of the batch, sum w_ini, sum w_rf], not clamped (the caller may average them over ranks);
 // a count is an integer below 2^24, exact in fp32
@@ -287,8 +244,8 @@ __global__ __launch_bounds__(256) void vfnet_loss_norm_kernel(const VfGeom g, co
                                                              float* __restrict__ norm3) {
     __shared__ float red[CH_THREADS];
     const int tid = threadIdx.x;
-    const float n = vf_total(g, partials, 4, 1, red, tid), s0 = vf_total(g, partials, 2, 1, red, tid),
-                s1 = vf_total(g, partials, 3, 1, red, tid);
+    const float n = term_sum(g, partials, 4, 1, red, tid), s0 = term_sum(g, partials, 2, 1, red, tid),
+                s1 = term_sum(g, partials, 3, 1, red, tid);
     if (tid == 0) { norm3[0] = n; norm3[1] = s0; norm3[2] = s1; }
 }
 
@@ -299,8 +256,8 @@ __global__ __launch_bounds__(256) void vfnet_loss_finalize_kernel(const VfGeom g
     __shared__ float red[CH_THREADS];
     const int tid = threadIdx.x;
     const float N = fmaxf(norm3[0], 1.f), S0 = fmaxf(norm3[1], 1.f), S1 = fmaxf(norm3[2], 1.f);
-    const float cls = vf_total(g, partials, 0, 0, red, tid), b0 = vf_total(g, partials, 0, 1, red, tid),
-                b1 = vf_total(g, partials, 1, 1, red, tid);
+    const float cls = term_sum(g, partials, 0, 0, red, tid), b0 = term_sum(g, partials, 0, 1, red, tid),
+                b1 = term_sum(g, partials, 1, 1, red, tid);
     if (tid == 0) {
         losses[0] = g.lw_cls * (cls / N);
         losses[1] = g.lw_bbox * (b0 / S0);
@@ -308,34 +265,6 @@ __global__ __launch_bounds__(256) void vfnet_loss_finalize_kernel(const VfGeom g
         coef3[0] = g.lw_cls / N;
         coef3[1] = g.lw_bbox / S0;
         coef3[2] = g.lw_ctr / S1;
-    }
-}
-
-// one thread per element of dA (rows, stride_a), padding columns included: every element is written
-__global__ __launch_bounds__(256) void vfnet_loss_backward_a_kernel(const VfGeom g, const float* __restrict__ a,
-                                                                   const float* __restrict__ d1,
-                                                                   const int* __restrict__ gt_inds,
-                                                                   const float* __restrict__ gts,
-                                                                   const int64_t* __restrict__ gt_labels,
-                                                                   const float* __restrict__ gl,
-                                                                   const float* __restrict__ coef3, float* __restrict__ da) {
-    const long long total = g.row0[g.L] * g.lay.sa;
-    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
-        const long long row = e / g.lay.sa;
-        const int c = (int)(e - row * g.lay.sa) - g.lay.cls_off;
-        float v = 0.f;
-        if (c >= 0 && c < g.C) {
-            const int l = level_of_row(g, row);
-            VfCell o = vf_locate(g, gt_inds, gts, l, row - g.row0[l], false);
-            const bool hit = o.gi >= 0 && gt_labels[o.gi] == c;
-            float q = 0.f;
-            if (hit) {
-                o = vf_locate(g, gt_inds, gts, l, row - g.row0[l], true);
-                q = vf_weight(vf_box(o, d1 + (size_t)row * 4), o);
-            }
-            v = gl[0] * coef3[0] * vfl_elem<true>(a[e], hit, q, g.alpha, g.gamma, g.iou_weighted != 0);
-        }
-        da[e] = v;
     }
 }
 
@@ -367,23 +296,11 @@ __global__ __launch_bounds__(256) void vfnet_loss_backward_d_kernel(const VfGeom
 }
 
 // --------------------------------------------------------------------------------------------------------------- host
-// layout4_host = [stride_a, cls_off, stride_r, reg_off]
-bool vf_layout_ok(const int* v, int C) {
-    return v && v[0] > 0 && v[2] > 0 && v[1] >= 0 && v[3] >= 0 && v[1] + C <= v[0] && v[3] + 4 <= v[2];
-}
-
-CenternessLayout vf_layout(const int* v) {
-    CenternessLayout y = {};
-    y.sa = v[0]; y.cls_off = v[1]; y.sr = v[2]; y.reg_off = v[3];
-    return y;
-}
-
 // cfg7_host: [VFL alpha, VFL gamma, iou_weighted, eps of the GIoU, loss_weight_cls, loss_weight_bbox, loss_weight_refine]
 int fill_geom(VfGeom& g, int batch, int num_levels, const int* heights, const int* widths, const int* strides, const float* base,
               const float* denoms, int C, const int* gt_offsets_host, const float* cfg7) {
-    int ones[BRCNN_MAX_LEVELS];
-    for (int l = 0; l < BRCNN_MAX_LEVELS; l++) ones[l] = 1;
-    const int st = fill_geom_common(g, batch, num_levels, heights, widths, strides ? strides : ones, C, gt_offsets_host, nullptr);
+    const UnitStrides ones;
+    const int st = fill_geom_common(g, batch, num_levels, heights, widths, strides ? strides : ones.v, C, gt_offsets_host, nullptr);
     if (st) return st;
     for (int l = 0; l < BRCNN_MAX_LEVELS; l++) {
         for (int k = 0; k < 4; k++) g.base[l][k] = (base && l < num_levels) ? base[4 * l + k] : 0.f;
@@ -399,11 +316,6 @@ int fill_geom(VfGeom& g, int batch, int num_levels, const int* heights, const in
     return 0;
 }
 
-int rows_grid(long long n) {
-    long long grid = (n + 255) / 256;
-    return (int)(grid > 8192 ? 8192 : (grid < 1 ? 1 : grid));
-}
-
 template <bool STAR>
 int launch_dist_backward(const VfGeom& g, const float* raw, int sr, int off, const float* scales, const float* d, const float* dd,
                          const float* doff, float f1, void* workspace, size_t workspace_bytes, float* draw, float* dscale,
@@ -415,7 +327,7 @@ int launch_dist_backward(const VfGeom& g, const float* raw, int sr, int off, con
     hipLaunchKernelGGL(vfnet_dist_backward_kernel<STAR>, dim3(g.pblk0[g.L]), dim3(CH_THREADS), 0, (hipStream_t)stream, g, raw,
                        sr, off, scales, d, dd, doff, f1, draw, dsp);
     BRCNN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(centerness_dscale_kernel<VfTraits>, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, dsp, dscale);
+    hipLaunchKernelGGL(rows_dscale_kernel<VfTraits>, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, dsp, dscale);
     BRCNN_LAUNCH_CHECK();
     return 0;
 }
@@ -486,23 +398,16 @@ BRCNN_API int brcnn_vfnet_decode_levels(const int64_t* const* topk_inds, const i
                                         const float* max_shape, const float* scale_factor, float score_thr, float* boxes,
                                         float* scores, int64_t* labels, uint8_t* valid, int32_t* n_valid, void* stream) {
     if (!a || !r1 || !d0 || !scales_refine || !base_anchors_host || !max_shape || !boxes || !scores || !labels || !valid ||
-        !n_valid || num_classes <= 0 || !vf_layout_ok(layout4_host, num_classes))
+        !n_valid || num_classes <= 0 || !layout4_ok(layout4_host, num_classes, 4))
         return BRCNN_EINVAL;
     VfDecode lv = {};
     const int st = fill_decode_picks(lv, topk_inds, counts, batch, num_levels, heights, widths, strides, num_classes, score_thr);
     if (st) return st;
-    lv.lay = vf_layout(layout4_host);
-    for (int l = 0; l < num_levels; l++)
-        for (int k = 0; k < 4; k++) lv.base[l][k] = base_anchors_host[4 * l + k];
-    if (batch == 0) return 0;
-    BRCNN_HIP_CHECK(hipMemsetAsync(n_valid, 0, sizeof(int32_t) * batch, (hipStream_t)stream));
-    const long long total = (long long)batch * lv.T * lv.C;
-    long long grid = (total + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    hipLaunchKernelGGL(vfnet_decode_levels_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, lv, batch, a, r1, d0,
-                       scales_refine, max_shape, scale_factor, boxes, scores, labels, valid, n_valid);
-    BRCNN_LAUNCH_CHECK();
-    return 0;
+    lv.lay = make_layout4(layout4_host);
+    lv.d0 = d0;
+    fill_decode_base(lv, base_anchors_host, num_levels);
+    return launch_decode_levels<VfTraits>(lv, batch, a, r1, scales_refine, max_shape, scale_factor, boxes, scores, labels, valid,
+                                          n_valid, stream);
 }
 
 BRCNN_API size_t brcnn_vfnet_loss_workspace_bytes(int batch, int num_levels, const int* heights, const int* widths,
@@ -528,9 +433,8 @@ BRCNN_API int brcnn_vfnet_loss_forward(const float* a, int stride_a, int cls_off
         return BRCNN_EINVAL;
     g.lay.sa = stride_a; g.lay.cls_off = cls_off;
     float* partials = (float*)workspace;
-    hipLaunchKernelGGL(vfnet_loss_forward_kernel, dim3(g.blk0[CH_SEGS]), dim3(CH_THREADS), 0, (hipStream_t)stream, g, a, d0, d1,
-                       gt_inds, gts, gt_labels, partials);
-    BRCNN_LAUNCH_CHECK();
+    const int fs = launch_loss_forward<VfTraits>(g, VfRows{a, d0, d1}, gt_inds, gts, gt_labels, partials, stream);
+    if (fs) return fs;
     hipLaunchKernelGGL(vfnet_loss_norm_kernel, dim3(1), dim3(CH_THREADS), 0, (hipStream_t)stream, g, partials, norm3);
     BRCNN_LAUNCH_CHECK();
     return 0;
@@ -565,9 +469,8 @@ BRCNN_API int brcnn_vfnet_loss_backward(const float* a, int stride_a, int cls_of
         ((!gts || !gt_labels) && g.gt_off[batch] > 0) || stride_a <= 0 || cls_off < 0 || cls_off + num_classes > stride_a)
         return BRCNN_EINVAL;
     g.lay.sa = stride_a; g.lay.cls_off = cls_off;
-    hipLaunchKernelGGL(vfnet_loss_backward_a_kernel, dim3(rows_grid(g.row0[g.L] * g.lay.sa)), dim3(256), 0, (hipStream_t)stream, g,
-                       a, d1, gt_inds, gts, gt_labels, grad_losses, coef3, da);
-    BRCNN_LAUNCH_CHECK();
+    const int as = launch_loss_backward_a<VfTraits>(g, VfRows{a, d0, d1}, gt_inds, gts, gt_labels, grad_losses, coef3, da, stream);
+    if (as) return as;
     hipLaunchKernelGGL(vfnet_loss_backward_d_kernel, dim3(rows_grid(g.row0[g.L])), dim3(256), 0, (hipStream_t)stream, g, d0, d1,
                        gt_inds, gts, grad_losses, coef3, dd0, dd1);
     BRCNN_LAUNCH_CHECK();

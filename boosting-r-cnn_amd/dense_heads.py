@@ -34,6 +34,11 @@ def cat_rows(feats):
     return _cr(list(feats))
 
 
+def _nchw_rows(lst):
+    """per-level (N,C,h,w) maps -> (rows, C) fp32, level-major rows, the row order of the kernels"""
+    return torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float()
+
+
 def reduce_mean(tensor):
     """mean over ranks (mmdet/core/utils/dist_utils.py:67-73); identity when not distributed"""
     if not (dist.is_available() and dist.is_initialized()):
@@ -240,6 +245,18 @@ class AnchorHead(nn.Module):
         if '_base_host' not in self.__dict__:
             self.__dict__['_base_host'] = ops.atss_base_anchors(self.anchor_generator.base_anchors)
         return self.__dict__['_base_host']
+
+    def _assign_atss_device(self, a, sizes, gt_bboxes, gt_labels, img_metas, gt_flat):
+        """what the `loss_fused` of the heads on ATSS's assignment starts from: the packed ground truth on the device of `a`
+        and brcnn_atss_assign over the valid cells -> (gts, labels, offs, sizes, base, gt_inds)"""
+        from . import train_ops
+        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
+        gts, labels = gts.to(a.device), labels.to(a.device)
+        sizes = [tuple(int(v) for v in s) for s in sizes]
+        base = self._base_table()
+        gt_inds = train_ops.atss_assign(gts, offs, len(img_metas), sizes, self.strides, base, self.assigner.topk,
+                                        valid_cells(self.anchor_generator, sizes, img_metas, a))
+        return gts, labels, offs, sizes, base, gt_inds
 
     def _atss_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
                       gt_labels_list=None, label_channels=1, unmap_outputs=True, encode=True):
@@ -1196,7 +1213,8 @@ class DenseDetHead:
     test-cfg and limit checks, the Normal(0.01) / bias_prob initialisation, the class-aware NMS of the device path's
     candidate slots, the `get_bboxes` skeleton (device or host dispatch, the one host sync) with the tail of the host
     mirror, and the reference's simple_test / forward_train drivers.  A head supplies `_get_bboxes_device(outs, img_metas,
-    cfg, rescale)` -> padded (dets, labels, num) and `_get_bboxes_host(*outs, img_metas, cfg, rescale, batched_nms)`."""
+    cfg, rescale)` -> padded (dets, labels, num) and the three hooks of `_get_bboxes_host` (RetinaHead, with several
+    anchors per cell, keeps a `_get_bboxes_host` of its own)."""
 
     supports_tta = False
     # nms_pre / level limits of the device path (include/brcnn_hip.h: brcnn_rpn_topk)
@@ -1271,6 +1289,34 @@ class DenseDetHead:
         self._check_test_cfg(cfg)
         return self._get_bboxes_host(*outs, img_metas, cfg, rescale, ops.batched_nms if batched_nms is None else batched_nms)
 
+    def _get_bboxes_host(self, *args):
+        """the host mirror of `get_bboxes` on torch ops, `args` = (*outs, img_metas, cfg, rescale, batched_nms): per image and
+        level the nms_pre best candidates (stable descending sort: ties by ascending index), the head's decode and clip,
+        then `_host_nms`.  A head supplies `_priors_host(sizes, outs)` -> per level the anchors or points, `_level_host(l,
+        *maps)` -> (box values (n, ..), centerness sigmoid (n,) or None) from the level's (h,w,C) maps after the class map,
+        and `_decode_host(priors, d, (h_img, w_img))` -> clipped boxes"""
+        *outs, img_metas, cfg, rescale, batched_nms = args
+        B, C = outs[0][0].shape[0], self.cls_out_channels
+        priors_l = self._priors_host([c.shape[-2:] for c in outs[0]], outs)
+        nms_pre = cfg.get('nms_pre', -1)
+        out = []
+        for b in range(B):
+            boxes_l, scores_l, ctr_l = [], [], []
+            for l, (priors, cls, *maps) in enumerate(zip(priors_l, *outs)):
+                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
+                d, ct = self._level_host(l, *[m[b].detach().permute(1, 2, 0) for m in maps])
+                if 0 < nms_pre < s.shape[0]:
+                    rank = s if ct is None else s * ct[:, None]
+                    _, idx = rank.max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
+                    idx = idx[:nms_pre]
+                    priors, d, s, ct = priors[idx], d[idx], s[idx], (None if ct is None else ct[idx])
+                boxes_l.append(self._decode_host(priors, d, img_metas[b]['img_shape'][:2]))
+                scores_l.append(s)
+                ctr_l.append(ct)
+            factor = None if ctr_l[0] is None else torch.cat(ctr_l)
+            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), factor, img_metas[b], cfg, rescale, batched_nms))
+        return out
+
     def _host_nms(self, boxes, scores, factor, img_meta, cfg, rescale, batched_nms):
         """the tail of the host mirror for one image: rescale, score threshold on the class score (before the optional
         per-box `factor`, bbox_nms.py:48-58), fan-out to classes, class-aware NMS, max_per_img -> (dets (k,5), labels (k,))"""
@@ -1309,8 +1355,9 @@ class GNTowerHead(DenseDetHead):
     """What FCOSHead, ATSSHead and GFLHead share on top of DenseDetHead: two towers of `stacked_convs` 3x3 conv + GroupNorm
     + ReLU (`cls_convs`, `reg_convs`), each ending in ONE fused fp32 head conv whose columns `_head_groups()` names, one
     `Scale` per level, and the (A, R) row tensors the kernels of csrc/fcos_head.hip, csrc/atss_head.hip and csrc/gfl_head.hip
-    read in place.  A head supplies `_head_groups`, `_layout`, `_rows_from_reference`, `_decode_candidates` and `loss_fused`,
-    and `_score_rows` when it does not rank by the centerness product."""
+    read in place.  A head supplies `_head_groups`, `_cls_conv`, `_split_rows`, `_heads_host`, `_layout`,
+    `_rows_from_reference`, `_decode_candidates` and `loss_fused`, and `_score_rows` when it does not rank by the centerness
+    product."""
 
     def _init_towers(self):
         self.cls_convs, self.reg_convs = nn.ModuleList(), nn.ModuleList()
@@ -1398,6 +1445,28 @@ class GNTowerHead(DenseDetHead):
         from .autograd import ConvNHWCFunction, fused_head_weights
         w, b = fused_head_weights(heads, 32 if x.dtype == torch.float32 else 64)
         return ConvNHWCFunction.apply(x, w, b, B, sizes, 1, 1, False, False, True)
+
+    def forward_nhwc(self, feats):
+        """list of (B,h,w,C) NHWC maps -> the head's outputs as per-level (B,h,w,.) lists, fp32 (`_split_rows`)"""
+        from .autograd import wants_grad
+        if not feats[0].is_cuda:
+            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
+            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
+        *rows, sizes = self._rows(list(feats), wants_grad(feats[0], self._cls_conv().weight, self.cls_convs[0].conv.weight))
+        return self._split_rows(*rows, sizes, feats[0].shape[0])
+
+    def _rows(self, feats, grad):
+        """the row tensors `_split_rows` takes, and the level sizes: the training forward when a gradient is wanted"""
+        return self.forward_head_fused(feats) if grad else self.forward_rows(feats)
+
+    def forward(self, feats):
+        """the reference signature: list of (N,C,h,w) -> the head's outputs as lists of (N,.,h,w).  CPU tensors take the
+        host mirror on torch ops: the towers, then the head's `_heads_host(c, r, level)`"""
+        if not feats[0].is_cuda:
+            outs = [self._heads_host(*self._towers_host(x), l) for l, x in enumerate(feats)]
+            return tuple(list(o) for o in zip(*outs))
+        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
+        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
 
     def _towers_host(self, x):
         """the host mirror of the two towers on torch ops: one (N,C,h,w) map -> (class tower, box tower) outputs"""
@@ -1711,7 +1780,7 @@ class RetinaHead(DenseDetHead, AnchorHead):
         if device.type == 'cuda':
             self._refuse_ignore(gt_bboxes_ignore)
             sizes = tuple(tuple(int(v) for v in s_) for s_ in featmap_sizes)
-            rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float().contiguous()   # noqa: E731
+            rows = lambda lst: _nchw_rows(lst).contiguous()   # noqa: E731
             return self.loss_fused(rows(cls_scores), rows(bbox_preds), sizes, gt_bboxes, gt_labels, img_metas)
         num_imgs = len(img_metas)
         anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
@@ -1757,6 +1826,11 @@ class RetinaHead(DenseDetHead, AnchorHead):
 
 
 INF = 1e8
+
+
+def _clamped(box, h, w):
+    """(n, 4) corner boxes clamped to an (h, w) image"""
+    return torch.stack([box[:, 0].clamp(0, w), box[:, 1].clamp(0, h), box[:, 2].clamp(0, w), box[:, 3].clamp(0, h)], -1)
 
 
 def distance2bbox(points, distance):
@@ -1858,7 +1932,10 @@ class FCOSHead(GNTowerHead, nn.Module):
         return ops.FcosLayout(a, r, C, 0, 0, self.centerness_on_reg, 4 if self.centerness_on_reg else C,
                               self.norm_on_bbox, type(self.loss_bbox).__name__ == 'GIoULoss')
 
-    def _decode_rows(self, a, r, sizes, B, training):
+    def _cls_conv(self):
+        return self.conv_cls
+
+    def _split_rows(self, a, r, sizes, B):
         """(A, R) rows -> the reference's per-level NHWC (cls, bbox_pred AFTER scale / exp | relu [* stride], centerness)"""
         C, co = self.cls_out_channels, (4 if self.centerness_on_reg else self.cls_out_channels)
         cls, reg, ctr = [], [], []
@@ -1866,7 +1943,7 @@ class FCOSHead(GNTowerHead, nn.Module):
             d = vr[..., :4] * self.scales[l].scale
             if self.norm_on_bbox:
                 d = d.relu()
-                d = d if training else d * self.strides[l]
+                d = d if self.training else d * self.strides[l]
             else:
                 d = d.exp()
             cls.append(va[..., :C])
@@ -1874,40 +1951,19 @@ class FCOSHead(GNTowerHead, nn.Module):
             ctr.append((vr if self.centerness_on_reg else va)[..., co:co + 1])
         return cls, reg, ctr
 
-    def forward_nhwc(self, feats):
-        """list of (B,h,w,C) -> (cls (B,h,w,C), bbox_pred (B,h,w,4) decoded distances, centerness (B,h,w,1)) lists, fp32"""
-        from .autograd import wants_grad
-        if not feats[0].is_cuda:
-            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
-            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
-        B = feats[0].shape[0]
-        if wants_grad(feats[0], self.conv_cls.weight, self.cls_convs[0].conv.weight):
-            a, r, sizes = self.forward_head_fused(list(feats))
+    def _heads_host(self, c, r, l):
+        """fcos_head.py:111-161 on the tower outputs of level l: (N,C,h,w) class logits, (N,4,h,w) distances after Scale and
+        exp / relu, (N,1,h,w) centerness logits"""
+        import torch.nn.functional as F
+        cls = F.conv2d(c, self.conv_cls.weight, self.conv_cls.bias, padding=1)
+        ctr = F.conv2d(r if self.centerness_on_reg else c, self.conv_centerness.weight, self.conv_centerness.bias, padding=1)
+        d = (F.conv2d(r, self.conv_reg.weight, self.conv_reg.bias, padding=1) * self.scales[l].scale).float()
+        if self.norm_on_bbox:
+            d = F.relu(d)
+            d = d if self.training else d * self.strides[l]
         else:
-            a, r, sizes = self.forward_rows(list(feats))
-        return self._decode_rows(a, r, sizes, B, self.training)
-
-    def forward(self, feats):
-        """reference signature (fcos_head.py:111-161): list of (N,C,h,w) -> lists of (N,C,h,w) class logits, (N,4,h,w)
-        distances after Scale and exp / relu, (N,1,h,w) centerness logits"""
-        if not feats[0].is_cuda:        # host mirror on torch ops
-            import torch.nn.functional as F
-            cls, reg, ctr = [], [], []
-            for x, scale, stride in zip(feats, self.scales, self.strides):
-                c, r = self._towers_host(x)
-                cls.append(F.conv2d(c, self.conv_cls.weight, self.conv_cls.bias, padding=1))
-                ctr.append(F.conv2d(r if self.centerness_on_reg else c, self.conv_centerness.weight,
-                                    self.conv_centerness.bias, padding=1))
-                d = (F.conv2d(r, self.conv_reg.weight, self.conv_reg.bias, padding=1) * scale.scale).float()
-                if self.norm_on_bbox:
-                    d = F.relu(d)
-                    d = d if self.training else d * stride
-                else:
-                    d = d.exp()
-                reg.append(d)
-            return cls, reg, ctr
-        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
-        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
+            d = d.exp()
+        return cls, d, ctr
 
     # ------------------------------------------------------------------ test
     def get_points(self, featmap_sizes, dtype, device):
@@ -1926,12 +1982,11 @@ class FCOSHead(GNTowerHead, nn.Module):
         """the reference-signature tensors (decoded distances) as the kernels' (A, R) rows with unit scales: the raw value
         is log(d), or under norm_on_bbox d itself (test time: d / stride, exact for power-of-two strides; a distance
         the relu left at exactly 0 takes no gradient, as through the relu)"""
-        rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float()   # noqa: E731
         if self.norm_on_bbox:
             raw = bbox_preds if training else [d / s for d, s in zip(bbox_preds, self.strides)]
         else:
             raw = [d.log() for d in bbox_preds]
-        cls, reg, ctr = rows(cls_scores), rows(raw), rows(centernesses)
+        cls, reg, ctr = _nchw_rows(cls_scores), _nchw_rows(raw), _nchw_rows(centernesses)
         if self.centerness_on_reg:
             return cls.contiguous(), torch.cat([reg, ctr], 1).contiguous()
         return torch.cat([cls, ctr], 1).contiguous(), reg.contiguous()
@@ -1943,32 +1998,19 @@ class FCOSHead(GNTowerHead, nn.Module):
         caller's `batched_nms` (this package's NMS is a device kernel)."""
         return self._get_bboxes((cls_scores, bbox_preds, centernesses), img_metas, cfg, rescale, with_nms, batched_nms)
 
-    def _get_bboxes_host(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms):
-        B, C = cls_scores[0].shape[0], self.cls_out_channels
-        points_l = self.get_points([c.shape[-2:] for c in cls_scores], bbox_preds[0].dtype, bbox_preds[0].device)
-        nms_pre = cfg.get('nms_pre', -1)
-        out = []
-        for b in range(B):
-            boxes_l, scores_l, ctr_l = [], [], []
-            h_img, w_img = img_metas[b]['img_shape'][:2]
-            for cls, reg, ctr, pts in zip(cls_scores, bbox_preds, centernesses, points_l):
-                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
-                ct = ctr[b].detach().permute(1, 2, 0).reshape(-1).sigmoid()
-                d = reg[b].detach().permute(1, 2, 0).reshape(-1, 4)
-                if 0 < nms_pre < s.shape[0]:
-                    _, idx = (s * ct[:, None]).max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
-                    idx = idx[:nms_pre]
-                    pts, d, s, ct = pts[idx], d[idx], s[idx], ct[idx]
-                bx = torch.stack([pts[:, 0] - d[:, 0], pts[:, 1] - d[:, 1], pts[:, 0] + d[:, 2], pts[:, 1] + d[:, 3]], -1)
-                hi = bx.new_tensor([w_img, h_img, w_img, h_img])
-                bx = torch.where(bx < 0, bx.new_zeros(()), bx)
-                bx = torch.where(bx > hi, hi, bx)
-                boxes_l.append(bx)
-                scores_l.append(s)
-                ctr_l.append(ct)
-            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), torch.cat(ctr_l), img_metas[b], cfg, rescale,
-                                      batched_nms))
-        return out
+    def _priors_host(self, sizes, outs):
+        return self.get_points(sizes, outs[1][0].dtype, outs[1][0].device)
+
+    @staticmethod
+    def _level_host(l, reg, ctr):
+        return reg.reshape(-1, 4), ctr.reshape(-1).sigmoid()
+
+    @staticmethod
+    def _decode_host(pts, d, img_hw):
+        bx = torch.stack([pts[:, 0] - d[:, 0], pts[:, 1] - d[:, 1], pts[:, 0] + d[:, 2], pts[:, 1] + d[:, 3]], -1)
+        hi = bx.new_tensor([img_hw[1], img_hw[0], img_hw[1], img_hw[0]])
+        bx = torch.where(bx < 0, bx.new_zeros(()), bx)
+        return torch.where(bx > hi, hi, bx)
 
     # ------------------------------------------------------------------ train
     def loss_fused(self, a, r, scales, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
@@ -2148,6 +2190,9 @@ class ATSSHead(GNTowerHead, AnchorHead):
     def _layout(self, a, r):
         return ops.FcosLayout(a, r, self.cls_out_channels, 0, 0, True, 4, False, True)
 
+    def _cls_conv(self):
+        return self.atss_cls
+
     def _split_rows(self, a, r, sizes, B):
         """(A, R) rows -> the reference's per-level NHWC (cls, bbox_pred AFTER the Scale, centerness)"""
         C = self.cls_out_channels
@@ -2158,33 +2203,13 @@ class ATSSHead(GNTowerHead, AnchorHead):
             ctr.append(vr[..., 4:5])
         return cls, reg, ctr
 
-    def forward_nhwc(self, feats):
-        """list of (B,h,w,C) -> (cls (B,h,w,C), bbox_pred (B,h,w,4) scaled deltas, centerness (B,h,w,1)) lists, fp32"""
-        from .autograd import wants_grad
-        if not feats[0].is_cuda:
-            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
-            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
-        B = feats[0].shape[0]
-        if wants_grad(feats[0], self.atss_cls.weight, self.cls_convs[0].conv.weight):
-            a, r, sizes = self.forward_head_fused(list(feats))
-        else:
-            a, r, sizes = self.forward_rows(list(feats))
-        return self._split_rows(a, r, sizes, B)
-
-    def forward(self, feats):
-        """reference signature (atss_head.py:96-141): list of (N,C,h,w) -> lists of (N,C,h,w) class logits, (N,4,h,w) deltas
-        after the Scale, (N,1,h,w) centerness logits"""
-        if not feats[0].is_cuda:        # host mirror on torch ops
-            import torch.nn.functional as F
-            cls, reg, ctr = [], [], []
-            for x, scale in zip(feats, self.scales):
-                c, r = self._towers_host(x)
-                cls.append(F.conv2d(c, self.atss_cls.weight, self.atss_cls.bias, padding=1))
-                reg.append((F.conv2d(r, self.atss_reg.weight, self.atss_reg.bias, padding=1) * scale.scale).float())
-                ctr.append(F.conv2d(r, self.atss_centerness.weight, self.atss_centerness.bias, padding=1))
-            return cls, reg, ctr
-        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
-        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
+    def _heads_host(self, c, r, l):
+        """atss_head.py:96-141 on the tower outputs of level l: (N,C,h,w) class logits, (N,4,h,w) deltas after the Scale,
+        (N,1,h,w) centerness logits"""
+        import torch.nn.functional as F
+        return (F.conv2d(c, self.atss_cls.weight, self.atss_cls.bias, padding=1),
+                (F.conv2d(r, self.atss_reg.weight, self.atss_reg.bias, padding=1) * self.scales[l].scale).float(),
+                F.conv2d(r, self.atss_centerness.weight, self.atss_centerness.bias, padding=1))
 
     # ------------------------------------------------------------------ test
     def _decode_candidates(self, picked, a, r, layout, scales, sizes, max_shape, sf, cfg):
@@ -2194,8 +2219,8 @@ class ATSSHead(GNTowerHead, AnchorHead):
     @staticmethod
     def _rows_from_reference(cls_scores, bbox_preds, centernesses):
         """the reference-signature tensors (deltas after the Scale) as the kernels' (A, R) rows, to be read with unit scales"""
-        rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float()   # noqa: E731
-        return rows(cls_scores).contiguous(), torch.cat([rows(bbox_preds), rows(centernesses)], 1).contiguous()
+        return (_nchw_rows(cls_scores).contiguous(),
+                torch.cat([_nchw_rows(bbox_preds), _nchw_rows(centernesses)], 1).contiguous())
 
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg=None, rescale=False, with_nms=True,
                    batched_nms=None):
@@ -2204,29 +2229,16 @@ class ATSSHead(GNTowerHead, AnchorHead):
         caller's `batched_nms` (this package's NMS is a device kernel)."""
         return self._get_bboxes((cls_scores, bbox_preds, centernesses), img_metas, cfg, rescale, with_nms, batched_nms)
 
-    def _get_bboxes_host(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, batched_nms):
+    def _priors_host(self, sizes, outs):
+        return self.anchor_generator.grid_anchors(sizes, outs[0][0].device)
+
+    @staticmethod
+    def _level_host(l, reg, ctr):
+        return reg.reshape(-1, 4), ctr.reshape(-1).sigmoid()
+
+    def _decode_host(self, anchors, d, img_hw):
         from .core import delta2bbox
-        B, C = cls_scores[0].shape[0], self.cls_out_channels
-        anchors_l = self.anchor_generator.grid_anchors([c.shape[-2:] for c in cls_scores], cls_scores[0].device)
-        nms_pre = cfg.get('nms_pre', -1)
-        out = []
-        for b in range(B):
-            boxes_l, scores_l, ctr_l = [], [], []
-            for cls, reg, ctr, anchors in zip(cls_scores, bbox_preds, centernesses, anchors_l):
-                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
-                ct = ctr[b].detach().permute(1, 2, 0).reshape(-1).sigmoid()
-                d = reg[b].detach().permute(1, 2, 0).reshape(-1, 4)
-                if 0 < nms_pre < s.shape[0]:
-                    _, idx = (s * ct[:, None]).max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
-                    idx = idx[:nms_pre]
-                    anchors, d, s, ct = anchors[idx], d[idx], s[idx], ct[idx]
-                boxes_l.append(delta2bbox(anchors, d, self.bbox_coder.means, self.bbox_coder.stds,
-                                          max_shape=tuple(img_metas[b]['img_shape'][:2])))
-                scores_l.append(s)
-                ctr_l.append(ct)
-            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), torch.cat(ctr_l), img_metas[b], cfg, rescale,
-                                      batched_nms))
-        return out
+        return delta2bbox(anchors, d, self.bbox_coder.means, self.bbox_coder.stds, max_shape=tuple(img_hw))
 
     # ------------------------------------------------------------------ train
     def loss_fused(self, a, r, scales, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
@@ -2234,13 +2246,8 @@ class ATSSHead(GNTowerHead, AnchorHead):
         targets and both normalisers are formed on the device (averaged over ranks there when distributed), nothing is
         read back.  Returns the reference's per-level lists; `self.last_targets` keeps (gt_inds, coef3, norm2)."""
         from . import train_ops
-        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
-        gts, labels = gts.to(a.device), labels.to(a.device)
+        gts, labels, offs, sizes, base, gt_inds = self._assign_atss_device(a, sizes, gt_bboxes, gt_labels, img_metas, gt_flat)
         B = len(img_metas)
-        sizes = [tuple(int(v) for v in s) for s in sizes]
-        base = self._base_table()
-        gt_inds = train_ops.atss_assign(gts, offs, B, sizes, self.strides, base, self.assigner.topk,
-                                        valid_cells(self.anchor_generator, sizes, img_metas, a))
         meta = train_ops.AtssLossMeta(B, sizes, self.strides, base, self.cls_out_channels, offs, self.loss_cls.gamma,
                                       self.loss_cls.alpha, self.loss_bbox.eps, self.loss_cls.loss_weight,
                                       self.loss_bbox.loss_weight, self.loss_centerness.loss_weight, self.bbox_coder.means,
@@ -2411,17 +2418,11 @@ class GFLHead(GNTowerHead, AnchorHead):
         """GFL has no centerness: the top-k ranks by max_c sigmoid(cls_c)"""
         return ops.gfl_score(a, layout)
 
-    def forward_nhwc(self, feats):
-        """list of (B,h,w,C) -> (cls (B,h,w,C), bbox_pred (B,h,w,4 * (reg_max + 1)) scaled logits) lists, fp32"""
-        from .autograd import wants_grad
-        if not feats[0].is_cuda:
-            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
-            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
-        B = feats[0].shape[0]
-        if wants_grad(feats[0], self.gfl_cls.weight, self.cls_convs[0].conv.weight):
-            a, r, sizes = self.forward_head_fused(list(feats))
-        else:
-            a, r, sizes = self.forward_rows(list(feats))
+    def _cls_conv(self):
+        return self.gfl_cls
+
+    def _split_rows(self, a, r, sizes, B):
+        """(A, R) rows -> the reference's per-level NHWC (cls, bbox_pred (B,h,w,4 * (reg_max + 1)) AFTER the Scale)"""
         C, W = self.cls_out_channels, 4 * (self.reg_max + 1)
         cls, reg = [], []
         for l, (va, vr) in enumerate(self._level_views(a, r, sizes, B)):
@@ -2429,19 +2430,12 @@ class GFLHead(GNTowerHead, AnchorHead):
             reg.append(vr[..., :W] * self.scales[l].scale)
         return cls, reg
 
-    def forward(self, feats):
-        """reference signature (gfl_head.py:154-196): list of (N,C,h,w) -> lists of (N,C,h,w) class logits and
-        (N,4 * (reg_max + 1),h,w) box logits after the Scale"""
-        if not feats[0].is_cuda:        # host mirror on torch ops
-            import torch.nn.functional as F
-            cls, reg = [], []
-            for x, scale in zip(feats, self.scales):
-                c, r = self._towers_host(x)
-                cls.append(F.conv2d(c, self.gfl_cls.weight, self.gfl_cls.bias, padding=1))
-                reg.append((F.conv2d(r, self.gfl_reg.weight, self.gfl_reg.bias, padding=1) * scale.scale).float())
-            return cls, reg
-        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
-        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
+    def _heads_host(self, c, r, l):
+        """gfl_head.py:154-196 on the tower outputs of level l: (N,C,h,w) class logits and (N,4 * (reg_max + 1),h,w) box
+        logits after the Scale"""
+        import torch.nn.functional as F
+        return (F.conv2d(c, self.gfl_cls.weight, self.gfl_cls.bias, padding=1),
+                (F.conv2d(r, self.gfl_reg.weight, self.gfl_reg.bias, padding=1) * self.scales[l].scale).float())
 
     @staticmethod
     def anchor_center(anchors):
@@ -2457,8 +2451,7 @@ class GFLHead(GNTowerHead, AnchorHead):
     def _rows_from_reference(cls_scores, bbox_preds):
         """the reference-signature tensors (box logits after the Scale) as the kernels' (A, R) rows, to be read with unit
         scales"""
-        rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float()   # noqa: E731
-        return rows(cls_scores).contiguous(), rows(bbox_preds).contiguous()
+        return _nchw_rows(cls_scores).contiguous(), _nchw_rows(bbox_preds).contiguous()
 
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False, with_nms=True, batched_nms=None):
         """reference signature (base_dense_head / gfl_head.py:373-472): per-level (N,C,h,w) / (N,4 * (reg_max + 1),h,w) ->
@@ -2466,27 +2459,14 @@ class GFLHead(GNTowerHead, AnchorHead):
         torch ops, with the caller's `batched_nms` (this package's NMS is a device kernel)."""
         return self._get_bboxes((cls_scores, bbox_preds), img_metas, cfg, rescale, with_nms, batched_nms)
 
-    def _get_bboxes_host(self, cls_scores, bbox_preds, img_metas, cfg, rescale, batched_nms):
-        B, C = cls_scores[0].shape[0], self.cls_out_channels
-        anchors_l = self.anchor_generator.grid_anchors([c.shape[-2:] for c in cls_scores], cls_scores[0].device)
-        nms_pre = cfg.get('nms_pre', -1)
-        out = []
-        for b in range(B):
-            boxes_l, scores_l = [], []
-            h, w = img_metas[b]['img_shape'][:2]
-            for cls, reg, stride, anchors in zip(cls_scores, bbox_preds, self.strides, anchors_l):
-                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
-                d = self.integral(reg[b].detach().permute(1, 2, 0)) * stride
-                if 0 < nms_pre < s.shape[0]:
-                    _, idx = s.max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
-                    idx = idx[:nms_pre]
-                    anchors, d, s = anchors[idx], d[idx], s[idx]
-                box = distance2bbox(self.anchor_center(anchors), d)
-                boxes_l.append(torch.stack([box[:, 0].clamp(0, w), box[:, 1].clamp(0, h), box[:, 2].clamp(0, w),
-                                            box[:, 3].clamp(0, h)], -1))
-                scores_l.append(s)
-            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), None, img_metas[b], cfg, rescale, batched_nms))
-        return out
+    def _priors_host(self, sizes, outs):
+        return self.anchor_generator.grid_anchors(sizes, outs[0][0].device)
+
+    def _level_host(self, l, reg):
+        return self.integral(reg) * self.strides[l], None
+
+    def _decode_host(self, anchors, d, img_hw):
+        return _clamped(distance2bbox(self.anchor_center(anchors), d), *img_hw)
 
     # ------------------------------------------------------------------ train
     def loss_fused(self, a, r, scales, sizes, gt_bboxes, gt_labels, img_metas, gt_flat=None):
@@ -2495,13 +2475,8 @@ class GFLHead(GNTowerHead, AnchorHead):
         when distributed), nothing is read back.  Returns the reference's per-level lists; `self.last_targets` keeps
         (gt_inds, coef3, norm2)."""
         from . import train_ops
-        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
-        gts, labels = gts.to(a.device), labels.to(a.device)
+        gts, labels, offs, sizes, base, gt_inds = self._assign_atss_device(a, sizes, gt_bboxes, gt_labels, img_metas, gt_flat)
         B = len(img_metas)
-        sizes = [tuple(int(v) for v in s) for s in sizes]
-        base = self._base_table()
-        gt_inds = train_ops.atss_assign(gts, offs, B, sizes, self.strides, base, self.assigner.topk,
-                                        valid_cells(self.anchor_generator, sizes, img_metas, a))
         meta = train_ops.GflLossMeta(B, sizes, self.strides, base, self.reg_max, self.cls_out_channels, offs,
                                      self.loss_cls.beta, self.loss_bbox.eps, self.loss_cls.loss_weight,
                                      self.loss_bbox.loss_weight, self.loss_dfl.loss_weight)
@@ -2793,18 +2768,18 @@ class VFNetHead(GNTowerHead, AnchorHead):
         d1 = train_ops.vfnet_refine(r1, scales_refine, d0, B, sizes)
         return a, d0, d1, sizes
 
-    def forward_nhwc(self, feats):
-        """list of (B,h,w,C) -> (cls (B,h,w,C), bbox_pred (B,h,w,4), bbox_pred_refine (B,h,w,4)) lists, fp32"""
-        from .autograd import wants_grad
-        if not feats[0].is_cuda:
-            outs = self.forward([f.permute(0, 3, 1, 2) for f in feats])
-            return tuple([t.permute(0, 2, 3, 1) for t in lst] for lst in outs)
-        B = feats[0].shape[0]
-        if wants_grad(feats[0], self.vfnet_cls.weight, self.cls_convs[0].conv.weight):
-            a, d0, d1, sizes = self.forward_head_fused(list(feats))
-        else:
-            a, r1, d0, sizes = self.forward_rows(list(feats))
-            d1 = ops.vfnet_refine(r1, self._scales_refine_tensor(), B, sizes, d0)
+    def _cls_conv(self):
+        return self.vfnet_cls
+
+    def _rows(self, feats, grad):
+        """(A, D0, D1, sizes): the inference rows end in the refinement kernel"""
+        if grad:
+            return self.forward_head_fused(feats)
+        a, r1, d0, sizes = self.forward_rows(feats)
+        return a, d0, ops.vfnet_refine(r1, self._scales_refine_tensor(), feats[0].shape[0], sizes, d0), sizes
+
+    def _split_rows(self, a, d0, d1, sizes, B):
+        """(A, D0, D1) rows -> the reference's per-level NHWC (cls (B,h,w,C), bbox_pred (B,h,w,4), bbox_pred_refine)"""
         cls, reg, ref, r = [], [], [], 0
         for h, w in sizes:
             n = B * h * w
@@ -2823,29 +2798,21 @@ class VFNetHead(GNTowerHead, AnchorHead):
         base = [float(v) for t in range(9) for v in (t // 3 - 1, t % 3 - 1)]
         return torch.stack(ent, 1) - bbox_pred.new_tensor(base).view(1, 18, 1, 1)
 
-    def forward(self, feats):
-        """reference signature (vfnet_head.py:194-272): list of (N,C,h,w) -> lists of (N,C,h,w) class logits, (N,4,h,w)
-        distances and (N,4,h,w) refined distances"""
-        if not feats[0].is_cuda:        # host mirror on torch ops
-            import torch.nn.functional as F
-            cls, reg, ref = [], [], []
-            m = self.vfnet_reg_conv
-            for x, sc, scr, stride, denom in zip(feats, self.scales, self.scales_refine, self.strides, self._denoms()):
-                c, r = self._towers_host(x)
-                ri = F.relu(F.group_norm(F.conv2d(r, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight,
-                                         m.norm.bias, m.norm.eps))
-                d0 = (F.conv2d(ri, self.vfnet_reg.weight, self.vfnet_reg.bias, padding=1) * sc.scale).float().exp() * denom
-                off = self.star_dcn_offset(d0, self.gradient_mul, stride).to(r.dtype)
-                r2 = F.relu(deform_conv2d_host(r, off, self.vfnet_reg_refine_dconv.weight))
-                d1 = (F.conv2d(r2, self.vfnet_reg_refine.weight, self.vfnet_reg_refine.bias, padding=1) *
-                      scr.scale).float().exp() * d0.detach()
-                c2 = F.relu(deform_conv2d_host(c, off, self.vfnet_cls_dconv.weight))
-                cls.append(F.conv2d(c2, self.vfnet_cls.weight, self.vfnet_cls.bias, padding=1))
-                reg.append(d0)
-                ref.append(d1)
-            return cls, reg, ref
-        outs = self.forward_nhwc([to_nhwc(f) for f in feats])
-        return tuple([t.permute(0, 3, 1, 2) for t in lst] for lst in outs)
+    def _heads_host(self, c, r, l):
+        """vfnet_head.py:194-272 on the tower outputs of level l: (N,C,h,w) class logits, (N,4,h,w) distances and (N,4,h,w)
+        refined distances"""
+        import torch.nn.functional as F
+        m = self.vfnet_reg_conv
+        ri = F.relu(F.group_norm(F.conv2d(r, m.conv.weight, None, padding=1), m.norm.num_groups, m.norm.weight, m.norm.bias,
+                                 m.norm.eps))
+        d0 = (F.conv2d(ri, self.vfnet_reg.weight, self.vfnet_reg.bias, padding=1) *
+              self.scales[l].scale).float().exp() * self._denoms()[l]
+        off = self.star_dcn_offset(d0, self.gradient_mul, self.strides[l]).to(r.dtype)
+        r2 = F.relu(deform_conv2d_host(r, off, self.vfnet_reg_refine_dconv.weight))
+        d1 = (F.conv2d(r2, self.vfnet_reg_refine.weight, self.vfnet_reg_refine.bias, padding=1) *
+              self.scales_refine[l].scale).float().exp() * d0.detach()
+        c2 = F.relu(deform_conv2d_host(c, off, self.vfnet_cls_dconv.weight))
+        return F.conv2d(c2, self.vfnet_cls.weight, self.vfnet_cls.bias, padding=1), d0, d1
 
     def get_points(self, featmap_sizes, dtype, device):
         """vfnet_head.py:597-618 with use_atss: (x * s, y * s) + s * center_offset, the centres of the anchors"""
@@ -2879,8 +2846,7 @@ class VFNetHead(GNTowerHead, AnchorHead):
         (exp(0) = 1 exactly)"""
         cls_scores, _, refine = outs
         sizes = [tuple(int(v) for v in c.shape[-2:]) for c in cls_scores]
-        rows = lambda lst: torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in lst], 0).float().contiguous()  # noqa: E731
-        a, d1 = rows(cls_scores), rows(refine)
+        a, d1 = _nchw_rows(cls_scores).contiguous(), _nchw_rows(refine).contiguous()
         r = torch.zeros_like(d1)
         return self.get_bboxes_rows(a, r, self._layout(a, r, d1), a.new_ones(len(sizes)), sizes, img_metas, cfg, rescale)
 
@@ -2891,27 +2857,16 @@ class VFNetHead(GNTowerHead, AnchorHead):
         caller's `batched_nms` (this package's NMS is a device kernel)."""
         return self._get_bboxes((cls_scores, bbox_preds, bbox_preds_refine), img_metas, cfg, rescale, with_nms, batched_nms)
 
-    def _get_bboxes_host(self, cls_scores, bbox_preds, bbox_preds_refine, img_metas, cfg, rescale, batched_nms):
-        B, C = cls_scores[0].shape[0], self.cls_out_channels
-        points_l = self.get_points([c.shape[-2:] for c in cls_scores], bbox_preds[0].dtype, bbox_preds[0].device)
-        nms_pre = cfg.get('nms_pre', -1)
-        out = []
-        for b in range(B):
-            boxes_l, scores_l = [], []
-            h, w = img_metas[b]['img_shape'][:2]
-            for cls, reg, points in zip(cls_scores, bbox_preds_refine, points_l):
-                s = cls[b].detach().permute(1, 2, 0).reshape(-1, C).sigmoid()
-                d = reg[b].detach().permute(1, 2, 0).reshape(-1, 4)
-                if 0 < nms_pre < s.shape[0]:
-                    _, idx = s.max(-1)[0].sort(descending=True, stable=True)   # ties by ascending index
-                    idx = idx[:nms_pre]
-                    points, d, s = points[idx], d[idx], s[idx]
-                box = distance2bbox(points, d)
-                boxes_l.append(torch.stack([box[:, 0].clamp(0, w), box[:, 1].clamp(0, h), box[:, 2].clamp(0, w),
-                                            box[:, 3].clamp(0, h)], -1))
-                scores_l.append(s)
-            out.append(self._host_nms(torch.cat(boxes_l), torch.cat(scores_l), None, img_metas[b], cfg, rescale, batched_nms))
-        return out
+    def _priors_host(self, sizes, outs):
+        return self.get_points(sizes, outs[1][0].dtype, outs[1][0].device)
+
+    @staticmethod
+    def _level_host(l, reg, refine):
+        return refine.reshape(-1, 4), None
+
+    @staticmethod
+    def _decode_host(points, d, img_hw):
+        return _clamped(distance2bbox(points, d), *img_hw)
 
     # ------------------------------------------------------------------ train
     def forward_train_nhwc(self, feats_nhwc, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
@@ -2925,13 +2880,8 @@ class VFNetHead(GNTowerHead, AnchorHead):
         targets, IoU weights and the three normalisers are formed on the device (averaged over ranks there when
         distributed), nothing is read back.  `self.last_targets` keeps (gt_inds, coef3, norm3)."""
         from . import train_ops
-        gts, labels, offs = gt_flat if gt_flat is not None else train_ops.flatten_gts(gt_bboxes, gt_labels)
-        gts, labels = gts.to(a.device), labels.to(a.device)
+        gts, labels, offs, sizes, base, gt_inds = self._assign_atss_device(a, sizes, gt_bboxes, gt_labels, img_metas, gt_flat)
         B = len(img_metas)
-        sizes = [tuple(int(v) for v in s) for s in sizes]
-        base = self._base_table()
-        gt_inds = train_ops.atss_assign(gts, offs, B, sizes, self.strides, base, self.assigner.topk,
-                                        valid_cells(self.anchor_generator, sizes, img_metas, a))
         meta = train_ops.VfnetLossMeta(B, sizes, self.strides, base, self.cls_out_channels, offs, self.loss_cls.alpha,
                                        self.loss_cls.gamma, self.loss_cls.iou_weighted, self.loss_bbox.eps,
                                        self.loss_cls.loss_weight, self.loss_bbox.loss_weight, self.loss_bbox_refine.loss_weight)

@@ -1401,30 +1401,42 @@ def atss_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, base_
 GFL_MAX_REG = 16
 
 
-class GflLayout:
-    """where the GFL kernels find the head outputs: A (rows, stride_a) with the C class logits at `cls_off`, R (rows,
-    stride_r) with the 4 * (reg_max + 1) raw box logits at `reg_off` (include/brcnn_hip.h: layout4_host)"""
+class Layout4:
+    """where the kernels of a head without a centerness find its outputs: A (rows, stride_a) with the C class logits at
+    `cls_off`, R (rows, stride_r) with `box_width` raw box columns at `reg_off` (include/brcnn_hip.h: layout4_host)"""
 
-    def __init__(self, a, r, num_classes, reg_max, cls_off=0, reg_off=0):
+    def __init__(self, a, r, num_classes, box_width, cls_off=0, reg_off=0):
         import ctypes
         _require_gpu(a, r)
         for t in (a, r):
             assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous()
         assert a.shape[0] == r.shape[0]
-        c, n = int(num_classes), int(reg_max)
-        if not 1 <= n <= GFL_MAX_REG:
-            raise ValueError(f'gfl: reg_max={reg_max} outside [1, {GFL_MAX_REG}]')
-        assert 0 <= cls_off and cls_off + c <= a.shape[1] and 0 <= reg_off and reg_off + 4 * (n + 1) <= r.shape[1]
-        self.C, self.reg_max, self.rows = c, n, int(a.shape[0])
+        c = int(num_classes)
+        assert 0 <= cls_off and cls_off + c <= a.shape[1] and 0 <= reg_off and reg_off + box_width <= r.shape[1]
+        self.C, self.rows = c, int(a.shape[0])
         self.values = (int(a.shape[1]), int(cls_off), int(r.shape[1]), int(reg_off))
         self.arr = (ctypes.c_int * 4)(*self.values)
 
 
-def gfl_score(a, layout):
-    """max_c sigmoid(cls_c) per row of A -- GFL ranks by the class score alone --: `dense_score` with one anchor per cell,
-    reading the class columns of A in place.  (rows,) dense fp32, the input of `rpn_topk` once split by level"""
+def class_score(a, layout):
+    """max_c sigmoid(cls_c) per row of A -- GFL and VFNet rank by the class score alone --: `dense_score` with one anchor per
+    cell, reading the class columns of A in place.  (rows,) dense fp32, the input of `rpn_topk` once split by level"""
     off = layout.values[1]
     return dense_score(a[:, off:off + layout.C], 1, layout.C).view(-1)
+
+
+class GflLayout(Layout4):
+    """the 4 * (reg_max + 1) raw box logits of GFL at `reg_off` of R"""
+
+    def __init__(self, a, r, num_classes, reg_max, cls_off=0, reg_off=0):
+        n = int(reg_max)
+        if not 1 <= n <= GFL_MAX_REG:
+            raise ValueError(f'gfl: reg_max={reg_max} outside [1, {GFL_MAX_REG}]')
+        super().__init__(a, r, num_classes, 4 * (n + 1), cls_off, reg_off)
+        self.reg_max = n
+
+
+gfl_score = class_score
 
 
 def gfl_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, base_anchors, max_shape, scale_factor, score_thr):
@@ -1443,21 +1455,14 @@ def gfl_decode_levels(topk_inds, a, r, layout, scales, feat_hws, strides, base_a
 
 
 # --------------------------------------------------------------------------- VFNet head, test time
-class VfnetLayout:
-    """where the VFNet kernels find the head outputs: A (rows, stride_a) with the C class logits at `cls_off`, R (rows,
-    stride_r) with the 4 raw distance logits at `reg_off` (include/brcnn_hip.h: layout4_host)"""
+class VfnetLayout(Layout4):
+    """the 4 raw distance logits of VFNet at `reg_off` of R"""
 
     def __init__(self, a, r, num_classes, cls_off=0, reg_off=0):
-        import ctypes
-        _require_gpu(a, r)
-        for t in (a, r):
-            assert t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous()
-        assert a.shape[0] == r.shape[0]
-        c = int(num_classes)
-        assert 0 <= cls_off and cls_off + c <= a.shape[1] and 0 <= reg_off and reg_off + 4 <= r.shape[1]
-        self.C, self.rows = c, int(a.shape[0])
-        self.values = (int(a.shape[1]), int(cls_off), int(r.shape[1]), int(reg_off))
-        self.arr = (ctypes.c_int * 4)(*self.values)
+        super().__init__(a, r, num_classes, 4, cls_off, reg_off)
+
+
+vfnet_score = class_score
 
 
 def _vfnet_rows(r, batch, sizes, reg_off):
@@ -1506,12 +1511,6 @@ def vfnet_refine(r1, scales_refine, batch, sizes, d0, reg_off=0):
                                       _ptr(d0), _ptr(d1), _stream())
     _L.check(st, 'brcnn_vfnet_refine')
     return d1
-
-
-def vfnet_score(a, layout):
-    """max_c sigmoid(cls_c) per row of A: `dense_score` with one anchor per cell on the class columns in place"""
-    off = layout.values[1]
-    return dense_score(a[:, off:off + layout.C], 1, layout.C).view(-1)
 
 
 def vfnet_decode_levels(topk_inds, a, r1, d0, layout, scales_refine, feat_hws, strides, base_anchors, max_shape, scale_factor,
